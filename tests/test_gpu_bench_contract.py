@@ -5,15 +5,17 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.gpu
-def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
+def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline(tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "c1", "--genome-len", "3000000",
-           "--reads", "1500", "--read-bases", "60000000", "--insertions", "30", "--cpu-sample-reads", "40", "--default-aligner-parity-reads", "40"]
+           "--reads", "1500", "--read-bases", "60000000", "--insertions", "30", "--cpu-sample-reads", "40", "--default-aligner-parity-reads", "40",
+           "--dump-outputs", str(tmp_path / "dump")]
     p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
@@ -51,6 +53,12 @@ def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
     # measured with every step's reads packed and uploaded underneath the previous step; two steps of 25 ms each: a relation between two
     # noisy numbers, only there to catch a wrong unit
     assert 0 < d["value_streaming_incl_h2d"] <= 2.0 * d["value"]
+    # --dump-outputs: the last timed step's records and CIGAR words of the sampled reads, float64, within 64 MB
+    x = d["dump_outputs"]
+    arrs = {f: np.load(str(tmp_path / "dump" / f)) for f in x["files"]}
+    assert "cigars.npy" in arrs and "alns_qid.npy" in arrs and all(v.dtype == np.float64 for v in arrs.values())
+    assert x["bytes"] == sum(v.nbytes for v in arrs.values()) <= 64 << 20 and 0 < x["reads"] <= 1500 and x["records"] > 0
+    assert int(arrs["alns_n_cigar.npy"].sum()) == len(arrs["cigars.npy"]) == x["cigar_words"]
 
 
 @pytest.mark.gpu
