@@ -55,6 +55,8 @@ def lib():
         L.tor_ext.restype = i32
         L.tor_ext.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(MapOpt), vp, C.POINTER(i32), i32,
                               C.POINTER(i32), C.POINTER(i32)]
+        L.tor_debug_dp.restype = i32
+        L.tor_debug_dp.argtypes = [vp, vp, vp, vp, C.POINTER(MapOpt), vp, i32, vp, vp, i64]
         L.tor_depth_medians.argtypes = [vp, i64, vp, i32, vp, i32, vp, vp, vp, vp]
         L.tor_consensus.restype = i64; L.tor_consensus.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, vp, i64, vp, vp]
         L.tor_poa.restype = i64; L.tor_poa.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, vp, i64, vp, vp]
@@ -176,3 +178,23 @@ def consensus(alns, cigars, queries, targets, min_depth=3, poa=False):
                             int(min_depth), out.ctypes.data, cap, ooff.ctypes.data, olen.ctypes.data)
     assert n <= cap
     return [bytes(out[ooff[i]:ooff[i] + olen[i]]).decode() for i in range(len(tl))]
+
+
+def debug_dp(queries, targets, mo, probs):
+    """the oracle's DP of each problem of a telr_debug_dp list (band_dp / longgap_fill / band_dp_fallback).
+    queries, targets: lists of ASCII sequences; probs: (np, 12) int32 rows as Engine.debug_dp takes them.
+    -> dict of per-problem arrays score, bi, bj, touched, and cigars (a list of uint32 arrays, start to end)"""
+    qb, qo, _ = concat(queries)
+    tb, to, _ = concat(targets)
+    P = np.ascontiguousarray(probs, dtype=np.int32).reshape(-1, 12)
+    npb = len(P)
+    res = np.zeros((npb, 6), np.int32)
+    cap = int((6 * (P[:, 4].astype(np.int64) + P[:, 5]) + 16).sum()) + 16
+    cig = np.zeros(cap, np.uint32)
+    rc = lib().tor_debug_dp(qb.ctypes.data, qo.ctypes.data, tb.ctypes.data, to.ctypes.data, C.byref(mo), P.ctypes.data, npb,
+                            res.ctypes.data, cig.ctypes.data, cap)
+    if rc != 0:
+        raise ValueError("tor_debug_dp: bad problem list")
+    out = {k: res[:, i].copy() for i, k in enumerate(("score", "bi", "bj", "touched"))}
+    out["cigars"] = [cig[res[x, 5]:res[x, 5] + res[x, 4]].copy() for x in range(npb)]
+    return out

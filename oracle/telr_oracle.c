@@ -1052,6 +1052,44 @@ int32_t tor_ext(const char *q, int m, const char *t, int n, const telr_map_opt *
     return r.score;
 }
 
+/* debug entry: a list of DP problems as the engine's test tap takes them (telr_debug_dp).  probs: np x 12 int32
+ * {qid, q_off, tid, t_off, m, n, dlo, dhi, kind, qstep, tstep, qcomp} over two ASCII sequence sets; kinds 0 (band_dp),
+ * 1 / 2 (band_dp with z-drop), 3 (band_dp_fallback; convex cost: its closing gap at the convex price, as align_chain does),
+ * 5 (longgap_fill).  res: np x 6 {score, bi, bj, touched, CIGAR ops, first op in cig}; CIGARs start to end.
+ * Returns 0, or -1 on a bad kind or when cig_cap is too small. */
+int32_t tor_debug_dp(const char *qascii, const int64_t *qoff, const char *tascii, const int64_t *toff, const telr_map_opt *mo,
+                     const int32_t *probs, int32_t np, int32_t *res, uint32_t *cig, int64_t cig_cap)
+{
+    convex_t CX; const int cx = (mo->cx_scale > 0 || (mo->flags & MFX_CONVEX)) && convex_of(mo, &CX);
+    u32v_t rc = {0, 0, 0};
+    int64_t w = 0;
+    for (int32_t x = 0; x < np; ++x) {
+        const int32_t *p = probs + (size_t)x * 12;
+        const int m = p[4], n = p[5], kind = p[8];
+        const int qlo = p[9] > 0 ? p[1] : p[1] - m + 1, tlo = p[10] > 0 ? p[3] : p[3] - n + 1;
+        uint8_t *qq = (uint8_t*)malloc(m + 1), *tt = (uint8_t*)malloc(n + 1);
+        for (int i = 0; i < m; ++i) qq[i] = NT4[(uint8_t)qascii[qoff[p[0]] + qlo + i]];
+        for (int i = 0; i < n; ++i) tt[i] = NT4[(uint8_t)tascii[toff[p[2]] + tlo + i]];
+        dp_seq_t s = { qq, tt, p[1] - qlo, p[3] - tlo, p[9], p[10], p[11], m, n };
+        dp_res_t r = { 0, 0, 0, 0, 0 };
+        rc.n = 0;
+        if (kind == 0 || kind == 1 || kind == 2) r = band_dp(&s, p[6], p[7], kind != 0, mo, &rc);
+        else if (kind == 5) r = longgap_fill(&s, mo, &rc);
+        else if (kind == 3) {
+            int fb_mlen;
+            r = band_dp_fallback(&s, mo, &rc, &fb_mlen);
+            if (cx) { int g = m > n ? m - n : n - m, c1 = mo->q + g * mo->e, c2 = mo->q2 + g * mo->e2; r.score = (r.score + (g ? (c1 < c2 ? c1 : c2) : 0)) * CX.S - (g ? (int)cx_cost(&CX, g) : 0); }
+        }
+        free(qq); free(tt);
+        if ((kind != 0 && kind != 1 && kind != 2 && kind != 3 && kind != 5) || w + rc.n > cig_cap) { free(rc.a); return -1; }
+        int32_t *o = res + (size_t)x * 6;
+        o[0] = r.score; o[1] = r.bi; o[2] = r.bj; o[3] = r.touched; o[4] = (int32_t)rc.n; o[5] = (int32_t)w;
+        for (int64_t z = rc.n - 1; z >= 0; --z) cig[w++] = rc.a[z];
+    }
+    free(rc.a);
+    return 0;
+}
+
 /* align one chain; fills the alignment fields of `al` and appends the CIGAR */
 static void align_chain(const tor_index *ix, const uint8_t *q, int qlen, const chain_t *c, const uint64_t *ca,
                         const telr_map_opt *mo, telr_aln *al, u32v_t *cigars, telr_counters *ctr)

@@ -117,5 +117,7 @@ def lib():
     L.telr_debug_index.restype = C.c_int; L.telr_debug_index.argtypes = [vp, vp, vp, vp, vp]
     L.telr_debug_pack.restype = C.c_int; L.telr_debug_pack.argtypes = [cp, i32, C.c_int, vp, vp]
     L.telr_debug_mid_occ.restype = i32; L.telr_debug_mid_occ.argtypes = [vp, C.POINTER(MapOpt)]
+    L.telr_debug_dp_limits.restype = C.c_int; L.telr_debug_dp_limits.argtypes = [C.POINTER(MapOpt), vp]
+    L.telr_debug_dp.restype = C.c_int; L.telr_debug_dp.argtypes = [vp, vp, vp, C.POINTER(MapOpt), vp, i32, vp, vp, vp, i64]
     _lib = L
     return L

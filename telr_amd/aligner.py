@@ -86,6 +86,35 @@ class Engine:
         self.L.telr_last_dp_classes(self.h, a.ctypes.data)
         return a.reshape(N_DPCLS, 4)
 
+    # the eight host bounds of the packed int16 DP classes for `mo` (telr_engine.hip: pk_steps_limit ... tag8_steps)
+    DP_LIMITS = ("pk_steps_limit", "pk_wide_limit", "pk_wide_maxd", "pk_ext_limit", "pk_ext_maxd", "tb4_mask", "tb4_steps", "tag8_steps")
+
+    @staticmethod
+    def dp_limits(mo):
+        """-> {name: value} of DP_LIMITS (no device needed)"""
+        a = np.zeros(8, np.int32)
+        rc = _lib.lib().telr_debug_dp_limits(C.byref(mo), a.ctypes.data)
+        if rc != 0:
+            raise _lib.TelrError("telr_debug_dp_limits: %d" % rc, rc)
+        return dict(zip(Engine.DP_LIMITS, (int(v) for v in a)))
+
+    def debug_dp(self, queries, targets, mo, probs):
+        """one DP pass (the map path's dp_pass) over a list of problems -- test tap.  probs: (np, 12) int32 rows
+        {qid, q_off, tid, t_off, m, n, dlo, dhi, kind, qstep, tstep, qcomp}; queries / targets: SeqSet.
+        -> dict of per-problem arrays cls, retry, score, bi, bj, mlen, tb_off, and cigars (a list of uint32 arrays, start to end)"""
+        P = np.ascontiguousarray(probs, dtype=np.int32).reshape(-1, 12)
+        npb = len(P)
+        res = np.zeros((npb, 8), np.int32); tb = np.zeros(npb, np.int64)
+        steps = P[:, 4].astype(np.int64) + P[:, 5]
+        cap = int((6 * steps + 16).sum()) + 16
+        cig = np.zeros(cap, np.uint32)
+        self._chk(self.L.telr_debug_dp(self.h, queries.h, targets.h, C.byref(mo), P.ctypes.data, npb, res.ctypes.data,
+                                       tb.ctypes.data, cig.ctypes.data, cap), "telr_debug_dp")
+        out = {k: res[:, i].copy() for i, k in enumerate(("cls", "retry", "score", "bi", "bj", "mlen"))}
+        out["tb_off"] = tb
+        out["cigars"] = [cig[res[x, 7]:res[x, 7] + res[x, 6]].copy() for x in range(npb)]
+        return out
+
     def release_scratch(self):
         """give the context's grow-only scratch back to the device (the next call allocates what it needs again)"""
         self._chk(self.L.telr_release_scratch(self.h), "telr_release_scratch")
@@ -435,6 +464,11 @@ class Index:
 
     def debug_mid_occ(self, mo):
         return int(self.eng.L.telr_debug_mid_occ(self.h, C.byref(mo)))
+
+    def debug_dp(self, queries, mo, probs):
+        """Engine.debug_dp against this index's targets"""
+        q = queries if isinstance(queries, SeqSet) else SeqSet(self.eng, queries)
+        return self.eng.debug_dp(q, self.targets, mo, probs)
 
     def debug_last_batch(self, nq):
         L = self.eng.L

@@ -2184,6 +2184,8 @@ __global__ void k_prob_sizes(DpProb *__restrict__ probs, int32_t np, int fill_ma
         if (hasn) cls = d_dp_class(P.kind, D, P.m + P.n, 0, 0, 0);
     }
     if (d_tb4(cls, tb4) && P.m + P.n > tb4_steps) cls = 14;        // the nibble cell keeps scores times four: longer fills take the two-lane class
+    // every size below is a multiple of 64 bytes, so every problem's piece (and every interleaved wave's) starts on a 64-byte
+    // line: the tiled walk reads the rows above a cell inside the cell's own line (d_traceback_lane: w - 16 / 32 / 48)
     int64_t tb;
     if (P.kind == 5) {       // both halves: H of every band cell (int32) + its trace-back byte, anti-diagonal major
         const int S = P.m < P.n ? P.m : P.n, lm = P.m < S + P.dhi ? P.m : S + P.dhi, ln = P.n < S + P.dhi ? P.n : S + P.dhi;
@@ -3573,8 +3575,8 @@ __device__ __forceinline__ void d_traceback_lane(const DpProb *__restrict__ prob
         // tiled: the cells one to three steps up the diagonal are the same byte column of the rows above, 16 bytes apart in this
         // very line while the row is not the tile's first -- read with the current cell, a run of diagonal moves is one trip
         const int mij = i < j ? i : j, kr = tiled ? (a >> 1) & 3 : 0;
-        const bool v1 = kr >= 1 && mij > 1, v2 = kr >= 2 && mij > 2, v3 = kr >= 3 && mij > 3;
-        const uint32_t t1 = v1 ? st8[((w - 16) >> 2) * 256 + (w & 3)] : 0xffu, t2 = v2 ? st8[((w - 32) >> 2) * 256 + (w & 3)] : 0xffu, t3 = v3 ? st8[((w - 48) >> 2) * 256 + (w & 3)] : 0xffu;
+        const bool up1 = kr >= 1 && mij > 1, up2 = kr >= 2 && mij > 2, up3 = kr >= 3 && mij > 3;
+        const uint32_t t1 = up1 ? st8[((w - 16) >> 2) * 256 + (w & 3)] : 0xffu, t2 = up2 ? st8[((w - 32) >> 2) * 256 + (w & 3)] : 0xffu, t3 = up3 ? st8[((w - 48) >> 2) * 256 + (w & 3)] : 0xffu;
         const uint32_t nd = (uint32_t)((t1 & 7u) != 0u) << 1 | (uint32_t)((t2 & 7u) != 0u) << 2 | (uint32_t)((t3 & 7u) != 0u) << 3;
         const uint32_t mb = (t >> 7) | ((t1 >> 7) & 1u) << 1 | ((t2 >> 7) & 1u) << 2 | ((t3 >> 7) & 1u) << 3;
         touched |= (j - i - dlo <= mg) | (dhi_ - (j - i) <= mg);       // within mg diagonals of a band edge

@@ -2288,10 +2288,9 @@ static int map_range(telr_ctx *ctx, const telr_index *ix, const telr_seqset *que
     return rr;
 }
 
-extern "C" int telr_map(telr_ctx *ctx, const telr_index *ix, const telr_seqset *queries, const int32_t *qtarget, const telr_map_opt *mo, telr_result **out)
+// the option checks of telr_map (telr_debug_dp applies the same ones)
+static int check_map_opt(telr_ctx *ctx, const telr_map_opt *mo)
 {
-    (void)hipGetLastError();          // a failed allocation of an EARLIER call leaves its error with the thread: not this call's
-    if (!ctx || !ix || !queries || !mo || !out) return TELR_E_ARG;
     if (mo->chain_lookback != 64 && mo->chain_lookback != 128 && mo->chain_lookback != 256) { ctx->err = "chain_lookback must be 64, 128 or 256"; return TELR_E_ARG; }
     if (mo->e < mo->e2 || mo->q > mo->q2) { ctx->err = "two-piece gap cost needs e >= e2 and q <= q2"; return TELR_E_ARG; }
     if (mo->fill_margin < 0 || mo->fill_margin > 64) { ctx->err = "fill_margin must be 0..64"; return TELR_E_ARG; }
@@ -2304,6 +2303,14 @@ extern "C" int telr_map(telr_ctx *ctx, const telr_index *ix, const telr_seqset *
     if (mo->max_gap >= TELR_TPAD || mo->ext_band * 2 + 1 > DP_DMAX || mo->ext_band < 1 || mo->ext_max < 1) return TELR_E_ARG;
     if (mo->bw_long > mo->bw && mo->ext_band > 31) {       // the two halves of a long-gap fill (spec 3.11) are bands of the extension width, held in 64 diagonals of LDS
         ctx->err = "long join (bw_long) needs ext_band <= 31"; return TELR_E_ARG; }
+    return TELR_OK;
+}
+
+extern "C" int telr_map(telr_ctx *ctx, const telr_index *ix, const telr_seqset *queries, const int32_t *qtarget, const telr_map_opt *mo, telr_result **out)
+{
+    (void)hipGetLastError();          // a failed allocation of an EARLIER call leaves its error with the thread: not this call's
+    if (!ctx || !ix || !queries || !mo || !out) return TELR_E_ARG;
+    TRY(check_map_opt(ctx, mo));
     if (queries->max_len >= (1 << 24)) return TELR_E_RANGE;
     HIPCHK(hipSetDevice(ctx->device));
     memset(ctx->stage_ms, 0, sizeof(ctx->stage_ms));
@@ -2570,6 +2577,83 @@ extern "C" int telr_debug_index(telr_ctx *ctx, const telr_index *ix, uint64_t *e
     return TELR_OK;
 }
 extern "C" int32_t telr_debug_mid_occ(const telr_index *ix, const telr_map_opt *mo) { return ix && mo ? index_mid_occ(ix, mo) : -1; }
+// The host's int16 bounds of the DP classes for `mo` (tests aim their problems at them): pk_steps_limit, pk_wide_limit,
+// pk_wide_maxd, pk_ext_limit, pk_ext_maxd, tb4_mask, tb4_steps, tag8_steps.  No device needed.
+extern "C" int telr_debug_dp_limits(const telr_map_opt *mo, int32_t *out)
+{
+    if (!mo || !out) return TELR_E_ARG;
+    out[0] = pk_steps_limit(mo); out[1] = pk_wide_limit(mo); out[2] = pk_wide_maxd(mo); out[3] = pk_ext_limit(mo);
+    out[4] = pk_ext_maxd(mo); out[5] = tb4_mask(mo); out[6] = tb4_steps(mo); out[7] = tag8_steps(mo);
+    return TELR_OK;
+}
+// One DP pass over a caller's list of problems (test tap: every class of dp_pass against the oracle, problem by problem).
+// probs: np x 12 int32 {qid, q_off, tid, t_off, m, n, dlo, dhi, kind, qstep, tstep, qcomp}, q_off / t_off = the sequence offset
+// of DP base 0 (a window runs down from it when its step is -1); kinds 0 (fill), 1 / 2 (left / right z-drop extension),
+// 3 (diagonal fall-back), 5 (long-gap fill), with the bands the map path builds (k_segments_w).  Out, per problem: res np x 8
+// {class, retry flag, score, bi, bj, mlen, CIGAR ops, first op in cig}, tb_off[np], and the CIGARs (len << 4 | op, start to end)
+// packed into cig[cig_cap].
+extern "C" int telr_debug_dp(telr_ctx *ctx, const telr_seqset *qs, const telr_seqset *tg, const telr_map_opt *mo, const int32_t *probs, int32_t np,
+                             int32_t *res, int64_t *tb_off, uint32_t *cig, int64_t cig_cap)
+{
+    (void)hipGetLastError();
+    if (!ctx || !qs || !tg || !mo || (np > 0 && (!probs || !res || !tb_off || !cig)) || np < 0 || np > (1 << 20)) return TELR_E_ARG;
+    TRY(check_map_opt(ctx, mo));
+    if (np == 0) return TELR_OK;
+    const auto even_lo = [](int lo) { return lo - (lo & 1); };
+    std::vector<DpProb> hp((size_t)np);
+    for (int x = 0; x < np; ++x) {
+        const int32_t *p = probs + (size_t)x * 12;
+        const int qid = p[0], q_off = p[1], tid = p[2], t_off = p[3], m = p[4], n = p[5], dlo = p[6], dhi = p[7], kind = p[8], qstep = p[9], tstep = p[10], qcomp = p[11];
+        auto bad = [&](const char *why) { ctx->err = "telr_debug_dp: problem " + std::to_string(x) + ": " + why; return TELR_E_ARG; };
+        if (qid < 0 || qid >= qs->n || tid < 0 || tid >= tg->n) return bad("sequence id");
+        if (m < 1 || n < 1 || (qstep != 1 && qstep != -1) || (tstep != 1 && tstep != -1) || (qcomp != 0 && qcomp != 1)) return bad("lengths or steps");
+        const int64_t qlo = qstep > 0 ? q_off : (int64_t)q_off - m + 1, tlo = tstep > 0 ? t_off : (int64_t)t_off - n + 1;
+        if (qlo < 0 || qlo + m > qs->len[qid] || tlo < 0 || tlo + n > tg->len[tid]) return bad("window outside its sequence");
+        if (dlo & 1) return bad("dlo must be even");
+        const int D = dhi - dlo + 1, dl = n - m;
+        if (kind == 0 || kind == 3) {        // fill: W diagonals of slack on either side of the corner-to-corner range
+            const int W = dhi - (dl > 0 ? dl : 0);
+            if (W < 0 || dlo != even_lo((dl < 0 ? dl : 0) - W)) return bad("fill band");
+            if (kind == 0 ? D > DP_DMAX : D <= DP_DMAX) return bad("fill band width (kind 3 = wider than DP_DMAX)");
+        } else if (kind == 1 || kind == 2 || kind == 5) {      // the extension band
+            if (dlo != even_lo(-mo->ext_band) || dhi != mo->ext_band) return bad("extension band");
+            if (kind == 5 && !(mo->bw_long > mo->bw && (dl > mo->bw || -dl > mo->bw))) return bad("long-gap fill needs bw_long > bw and |n - m| > bw");
+            if (kind != 5 && (m > mo->ext_max || n > m + mo->ext_band)) return bad("extension window");
+        } else return bad("kind");
+        DpProb &P = hp[(size_t)x];
+        P.qi0 = qs->boff[qid] + q_off; P.ti0 = tg->boff[tid] + t_off; P.tb_off = P.cig_off = 0;
+        P.m = m; P.n = n; P.dlo = dlo; P.dhi = dhi; P.qstep = (int8_t)qstep; P.tstep = (int8_t)tstep; P.qcomp = (int8_t)qcomp; P.kind = (int8_t)kind;
+        P.chain = x; P.pad[0] = P.pad[1] = 0;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DpProb *d_probs; DpRes *d_res; int32_t *d_retry; uint32_t *d_rawcig = nullptr;
+    TRY(ctx_buf_t(ctx, "dbg_probs", (size_t)np, &d_probs));
+    TRY(ctx_buf_t(ctx, "dbg_res", (size_t)np, &d_res));
+    TRY(ctx_buf_t(ctx, "dbg_retry", (size_t)np + 1, &d_retry));
+    HIPCHK(hipMemcpyAsync(d_probs, hp.data(), (size_t)np * sizeof(DpProb), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_retry, 0, ((size_t)np + 1) * 4, st));
+    TRY(dp_pass(ctx, qs, tg, mo, d_probs, np, d_res, &d_rawcig, d_retry, "", true));
+    std::vector<DpRes> hr((size_t)np); std::vector<int32_t> hretry((size_t)np);
+    HIPCHK(hipMemcpyAsync(hp.data(), d_probs, (size_t)np * sizeof(DpProb), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hr.data(), d_res, (size_t)np * sizeof(DpRes), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hretry.data(), d_retry, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int64_t raw_n = 0, tot = 0;
+    for (int x = 0; x < np; ++x) { raw_n = std::max(raw_n, hp[x].cig_off + hr[x].nops); tot += hr[x].nops; }
+    if (tot > cig_cap) { ctx->err = "telr_debug_dp: cig_cap too small"; return TELR_E_RANGE; }
+    std::vector<uint32_t> raw((size_t)raw_n);
+    if (raw_n) { HIPCHK(hipMemcpyAsync(raw.data(), d_rawcig, (size_t)raw_n * 4, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); }
+    int64_t w = 0;
+    for (int x = 0; x < np; ++x) {
+        const DpProb &P = hp[x]; const DpRes &R = hr[x];
+        int32_t *o = res + (size_t)x * 8;
+        o[0] = P.pad[0] & 0xff; o[1] = hretry[x]; o[2] = R.score; o[3] = R.bi; o[4] = R.bj; o[5] = R.mlen; o[6] = R.nops; o[7] = (int32_t)w;
+        tb_off[x] = P.tb_off;
+        for (int k = R.nops - 1; k >= 0; --k) cig[w++] = raw[(size_t)P.cig_off + k];        // the trace-back writes end -> start
+    }
+    return TELR_OK;
+}
 
 // ---------------------------------------------------------------------------------------
 // depth medians
