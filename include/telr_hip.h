@@ -352,6 +352,12 @@ int  telr_consensus_build(telr_ctx *ctx, const telr_result *r, const telr_seqset
  * the heaviest-bundle path.  Unlike the pile-up vote it re-phases columns: it does not trust the pairwise CIGARs inside a window. */
 int  telr_poa_build(telr_ctx *ctx, const telr_result *r, const telr_seqset *queries, const telr_index *idx, int32_t min_depth,
                     telr_consensus **out);
+/* Both builds check every record of r before anything reaches the device and return TELR_E_ARG if one fails: 0 <= ts <= te <=
+ * the target's length, 0 <= qs <= qe <= qlen == the query's length, CIGAR ops only M / I / D, M + D = te - ts, M + I = qe - qs
+ * (a record without CIGAR ops votes nothing and passes).  Host-only debug entry of the same check on caller-held arrays:
+ * TELR_OK, or TELR_E_ARG with *first_bad = the index of the first record that fails. */
+int  telr_debug_check_records(const telr_aln *alns, int64_t n, const uint32_t *cigars, int64_t n_cigar, const int32_t *qlens, int32_t n_queries,
+                              const int32_t *tlens, int32_t n_targets, int64_t *first_bad);
 int32_t telr_consensus_count(const telr_consensus *c);              /* = number of targets */
 const char *telr_consensus_seq(const telr_consensus *c);             /* concatenated consensus sequences (A C G T N) */
 const int64_t *telr_consensus_off(const telr_consensus *c);

@@ -60,6 +60,7 @@ def lib():
         L.tor_depth_medians.argtypes = [vp, i64, vp, i32, vp, i32, vp, vp, vp, vp]
         L.tor_consensus.restype = i64; L.tor_consensus.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, vp, i64, vp, vp]
         L.tor_poa.restype = i64; L.tor_poa.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, vp, i64, vp, vp]
+        L.tor_poa_stats.restype = i64; L.tor_poa_stats.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -163,9 +164,14 @@ for _i, _c in enumerate("ACGT"):
 _NT4[ord("U")] = 3; _NT4[ord("u")] = 3
 
 
-def consensus(alns, cigars, queries, targets, min_depth=3, poa=False):
+POA_STATS = ("offered", "voting", "merged", "capped", "nodes", "max_in", "dropped_in", "far_rows", "kind0", "kind1", "kind2", "kind3",
+             "diag_run", "diag_k1", "best_min", "best_max", "ran", "L", "seg_max", "seg_min")
+
+
+def consensus(alns, cigars, queries, targets, min_depth=3, poa=False, stats=False):
     """pile-up consensus of the targets from the primary records (spec 3.12), or -- poa=True -- the window partial-order
-    consensus (spec 3.13) -> list of str"""
+    consensus (spec 3.13) -> list of str.  stats=True (poa only, tor_poa_stats): -> (strings, per-window list of dicts of
+    POA_STATS, each with "nbefore": the graph's node count before each voting piece)"""
     from telr_amd.fasta import concat
     alns = np.ascontiguousarray(alns); cigars = np.ascontiguousarray(cigars, dtype=np.uint32)
     qb, qo, ql = queries if isinstance(queries, tuple) else concat(queries)
@@ -174,10 +180,25 @@ def consensus(alns, cigars, queries, targets, min_depth=3, poa=False):
     tb = np.ascontiguousarray(tb, np.uint8); to = np.ascontiguousarray(to, np.int64); tl = np.ascontiguousarray(tl, np.int32)
     cap = int(tl.sum()) * (1 + 8) + 16
     out = np.zeros(cap, np.uint8); ooff = np.zeros(len(tl), np.int64); olen = np.zeros(len(tl), np.int32)
-    n = (lib().tor_poa if poa else lib().tor_consensus)(alns.ctypes.data, len(alns), cigars.ctypes.data, q4.ctypes.data, qo.ctypes.data, len(tl), tb.ctypes.data, to.ctypes.data, tl.ctypes.data,
-                            int(min_depth), out.ctypes.data, cap, ooff.ctypes.data, olen.ctypes.data)
-    assert n <= cap
-    return [bytes(out[ooff[i]:ooff[i] + olen[i]]).decode() for i in range(len(tl))]
+    args = (alns.ctypes.data, len(alns), cigars.ctypes.data, q4.ctypes.data, qo.ctypes.data, len(tl), tb.ctypes.data, to.ctypes.data, tl.ctypes.data,
+            int(min_depth), out.ctypes.data, cap, ooff.ctypes.data, olen.ctypes.data)
+    if stats:
+        assert poa
+        nwin = int(((tl.astype(np.int64) + 199) // 200).sum())
+        wst = np.zeros((max(nwin, 1), len(POA_STATS)), np.int32); nb = np.zeros((max(nwin, 1), 64), np.int32)
+        n = lib().tor_poa_stats(*args, wst.ctypes.data, nb.ctypes.data)
+    else:
+        n = (lib().tor_poa if poa else lib().tor_consensus)(*args)
+    assert 0 <= n <= cap
+    strs = [bytes(out[ooff[i]:ooff[i] + olen[i]]).decode() for i in range(len(tl))]
+    if not stats:
+        return strs
+    ws = []
+    for k in range(nwin):
+        d = {f: int(v) for f, v in zip(POA_STATS, wst[k])}
+        d["nbefore"] = [int(x) for x in nb[k] if x >= 0]
+        ws.append(d)
+    return strs, ws
 
 
 def debug_dp(queries, targets, mo, probs):

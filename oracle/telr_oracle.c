@@ -1523,17 +1523,26 @@ typedef struct {
     int16_t col[POA_MAXNODE];                /* the window column the node belongs to (a new node: that of the node it is aligned to / put behind) */
     int L;                                   /* columns of the window */
 } poa_t;
-static void poa_add_edge(poa_t *g, int u, int v)
+/* tor_poa_stats: what one window reached (TOR_POA_NSTAT int32 per window, tests/consensus_edges.py names them) */
+#define POA_RING    16      /* the kernel's LDS ring of rows (poa.hip.h): a predecessor further back is read from its slot */
+#define TOR_POA_NSTAT 20
+enum { PS_OFFERED, PS_VOTING, PS_MERGED, PS_CAPPED, PS_NODES, PS_MAXIN, PS_DROPPED, PS_FAR, PS_KIND0, PS_KIND1, PS_KIND2, PS_KIND3,
+       PS_DIAGRUN, PS_DIAGK1, PS_BESTMIN, PS_BESTMAX, PS_RAN, PS_L, PS_SEGMAX, PS_SEGMIN };
+static void poa_add_edge(poa_t *g, int u, int v, int32_t *st)
 {
     for (int k = 0; k < g->nin[v]; ++k) if (g->in[v][k] == u) { ++g->inw[v][k]; return; }
-    if (g->nin[v] >= POA_MAXIN) return;
+    if (g->nin[v] >= POA_MAXIN) { if (st) ++st[PS_DROPPED]; return; }
     g->in[v][g->nin[v]] = (int16_t)u; g->inw[v][g->nin[v]] = 1; ++g->nin[v]; ++g->nout[u];
 }
 /* align seq[0..n) to the graph and merge it in; H is scratch of (nodes + 1) x (n + 1) */
 /* The score matrix is BANDED: the row of a node holds POA_BAND cells, the piece's positions [lo, lo + POA_BAND) with
  * lo = clamp((col + 1) * n / L - POA_BAND / 2, 0, max(0, n + 1 - POA_BAND)) -- around where the node's column falls on the piece
  * when piece and window are stretched onto each other (a 200-base window of a 10 %-error read drifts by a few bases, never 32);
- * every cell outside a row's band counts as -32000.  Row 0 (the virtual start) is j * gap and not stored. */
+ * every cell outside a row's band counts as -32000.  Row 0 (the virtual start) is j * gap and not stored.
+ * Dead cells: every stored cell is floored at -32000 (`best` starts there), as the kernel floors a cell's candidate before its
+ * row's gap chain -- the two recurrences are the same, so both sides hold the same value in every cell of a band, and a chain
+ * of dead cells stays at -32000 instead of losing 4 per row towards the int16 wrap.  Live scores lie within
+ * [-4 (2048 + 400), 3 * 400]; every stored value is checked to fit. */
 static inline int poa_lo(int col, int n, int L) { int lo = (col + 1) * n / L - POA_BAND / 2, hi = n + 1 - POA_BAND; if (lo > hi) lo = hi; return lo < 0 ? 0 : lo; }
 static inline int poa_cell(const int16_t *H, const int16_t *lo, int row, int j, int n)
 {
@@ -1541,12 +1550,24 @@ static inline int poa_cell(const int16_t *H, const int16_t *lo, int row, int j, 
     const int jj = j - lo[row - 1];
     return (jj < 0 || jj >= POA_BAND || j > n) ? -32000 : H[(size_t)(row - 1) * POA_BAND + jj];
 }
-static void poa_add_seq(poa_t *g, const uint8_t *seq, int n, int16_t *H, int16_t *rank)
+static void poa_add_seq(poa_t *g, const uint8_t *seq, int n, int16_t *H, int16_t *rank, int32_t *st)
 {
     static __thread int16_t lo[POA_MAXNODE];
     for (int r = 0; r < g->n; ++r) { rank[g->order[r]] = (int16_t)(r + 1); lo[r] = (int16_t)poa_lo(g->col[g->order[r]], n, g->L); }
     for (int r = 0; r < g->n; ++r) {
         const int v = g->order[r];
+        if (st) {                          /* the kind of row the kernel's sweep meets (poa.hip.h), by its own formula */
+            const int c = g->nin[v], np = c ? c : 1, dl = r ? lo[r] - lo[r - 1] : 9;
+            int ring = 1, far = 0, pr0 = 0;
+            for (int k = 0; k < np; ++k) {
+                const int pr = c ? rank[g->in[v][k]] : 0;
+                far |= pr && r - (pr - 1) > POA_RING;
+                ring &= pr && r - (pr - 1) <= POA_RING;
+                if (k == 0) pr0 = pr;
+            }
+            const int kind = np == 1 && pr0 == r && (unsigned)dl <= 1u ? dl : np <= 2 && ring ? 2 : 3;
+            ++st[PS_KIND0 + kind]; st[PS_FAR] += far;
+        }
         int16_t *row = H + (size_t)r * POA_BAND;
         const int j0 = lo[r], j1 = j0 + POA_BAND - 1 < n ? j0 + POA_BAND - 1 : n;
         for (int j = j0; j <= j1; ++j) {
@@ -1559,6 +1580,8 @@ static void poa_add_seq(poa_t *g, const uint8_t *seq, int n, int16_t *H, int16_t
                 if (j > 0) { c = poa_cell(H, lo, pr, j - 1, n) + (seq[j - 1] == g->base[v] && seq[j - 1] < 4 ? POA_M : POA_X); if (c > best) best = c; }
             }
             if (j > j0) { const int c = row[j - 1 - j0] + POA_G; if (c > best) best = c; }  /* the base is inserted */
+            if (best < -32000 || best > INT16_MAX) { fprintf(stderr, "tor_poa: cell %d outside int16\n", best); abort(); }
+            if (st) { if (best < st[PS_BESTMIN]) st[PS_BESTMIN] = best; if (best > st[PS_BESTMAX]) st[PS_BESTMAX] = best; }
             row[j - j0] = (int16_t)best;
         }
     }
@@ -1567,7 +1590,7 @@ static void poa_add_seq(poa_t *g, const uint8_t *seq, int n, int16_t *H, int16_t
     for (int v = 0; v < g->n; ++v) if (!g->nout[v]) { const int sc = poa_cell(H, lo, rank[v], n, n); if (sc > endsc) endsc = sc, endv = v; }
     /* walk back: diagonal from the first pred that explains the cell, else skip-node from the first pred, else inserted base */
     static __thread int16_t pn[POA_MAXNODE + POA_SEGMAX + 2], pj[POA_MAXNODE + POA_SEGMAX + 2];
-    int np = 0, v = endv, j = n;
+    int np = 0, v = endv, j = n, run = 0;                                /* run: diagonal steps from the first predecessor in a row */
     while (v >= 0 || j > 0) {
         if (v < 0) { pn[np] = -1; pj[np] = (int16_t)(j - 1); ++np; --j; continue; }          /* bases before the graph's start */
         const int cur = poa_cell(H, lo, rank[v], j, n), npred = g->nin[v] ? g->nin[v] : 1;
@@ -1576,9 +1599,13 @@ static void poa_add_seq(poa_t *g, const uint8_t *seq, int n, int16_t *H, int16_t
             const int sc = seq[j - 1] == g->base[v] && seq[j - 1] < 4 ? POA_M : POA_X;
             for (int k = 0; k < npred && !moved; ++k) {
                 const int p = g->nin[v] ? g->in[v][k] : -1;
-                if (poa_cell(H, lo, p >= 0 ? rank[p] : 0, j - 1, n) + sc == cur) { pn[np] = (int16_t)v; pj[np] = (int16_t)(j - 1); ++np; v = p; --j; moved = 1; }
+                if (poa_cell(H, lo, p >= 0 ? rank[p] : 0, j - 1, n) + sc == cur) {
+                    pn[np] = (int16_t)v; pj[np] = (int16_t)(j - 1); ++np; v = p; --j; moved = 1;
+                    if (st) { run = k == 0 ? run + 1 : 0; if (run > st[PS_DIAGRUN]) st[PS_DIAGRUN] = run; st[PS_DIAGK1] += k > 0; }
+                }
             }
         }
+        if (!moved) run = 0;
         for (int k = 0; k < npred && !moved; ++k) {
             const int p = g->nin[v] ? g->in[v][k] : -1;
             if (poa_cell(H, lo, p >= 0 ? rank[p] : 0, j, n) + POA_G == cur) { v = p; moved = 1; }      /* node skipped: nothing to merge */
@@ -1613,7 +1640,7 @@ static void poa_add_seq(poa_t *g, const uint8_t *seq, int n, int16_t *H, int16_t
             for (int s_ = g->ring[x]; s_ != x; s_ = g->ring[s_]) if (s_ < n_old && rank[s_] - 1 > m) m = rank[s_] - 1;
             behind = m;
         }
-        if (prev >= 0) poa_add_edge(g, prev, u); else ++g->startc[u];
+        if (prev >= 0) poa_add_edge(g, prev, u, st); else ++g->startc[u];
         prev = u;
     }
     if (prev >= 0) ++g->endc[prev];
@@ -1656,10 +1683,11 @@ static int poa_consensus(const poa_t *g, char *out)
     for (int i = 0; i < n; ++i) out[i] = tmp[n - 1 - i];
     return n;
 }
-/* same interface as tor_consensus */
-int64_t tor_poa(const telr_aln *alns, int64_t n_aln, const uint32_t *cigars, const uint8_t *q_nt4, const int64_t *qoff,
-                int32_t n_targets, const char *t_ascii, const int64_t *toff, const int32_t *tlen, int32_t min_depth,
-                char *out, int64_t cap, int64_t *out_off, int32_t *out_len)
+/* tor_poa and tor_poa_stats; wst / nbefore: NULL, or TOR_POA_NSTAT / POA_MAXSEG int32 per window (targets in order, their
+ * windows in order) -- what the window reached, and the node count of the graph before each voting piece (-1: none) */
+static int64_t poa_run(const telr_aln *alns, int64_t n_aln, const uint32_t *cigars, const uint8_t *q_nt4, const int64_t *qoff,
+                       int32_t n_targets, const char *t_ascii, const int64_t *toff, const int32_t *tlen, int32_t min_depth,
+                       char *out, int64_t cap, int64_t *out_off, int32_t *out_len, int32_t *wst, int32_t *nbefore)
 {
     poa_t *g = (poa_t*)malloc(sizeof(poa_t));
     int16_t *H = (int16_t*)malloc(sizeof(int16_t) * (size_t)POA_MAXNODE * POA_BAND), *rank = (int16_t*)malloc(2 * POA_MAXNODE);
@@ -1678,6 +1706,12 @@ int64_t tor_poa(const telr_aln *alns, int64_t n_aln, const uint32_t *cigars, con
         const char *ts = t_ascii + toff[t];
         for (int32_t w0 = 0; w0 < tlen[t]; w0 += POA_W) {
             const int32_t w1 = w0 + POA_W < tlen[t] ? w0 + POA_W : tlen[t];
+            int32_t *st = wst, *nb = nbefore;
+            if (st) {
+                memset(st, 0, 4 * TOR_POA_NSTAT); st[PS_BESTMIN] = INT32_MAX; st[PS_BESTMAX] = INT32_MIN; st[PS_L] = w1 - w0; st[PS_SEGMIN] = -1;
+                for (int s = 0; s < POA_MAXSEG; ++s) nb[s] = -1;
+                wst += TOR_POA_NSTAT; nbefore += POA_MAXSEG;
+            }
             int nseg = 0;
             for (int64_t z = first[t]; z < first[t + 1] && nseg < POA_MAXSEG; ++z) {
                 const telr_aln *r = &alns[idx[z]];
@@ -1702,6 +1736,7 @@ int64_t tor_poa(const telr_aln *alns, int64_t n_aln, const uint32_t *cigars, con
                 if (big) continue;
                 const int len = qb - qa;
                 if (qa < 0 || len < (w1 - w0) / 2 || len > POA_SEGMAX) continue;     /* (a piece shorter than half the window: the read lacks what the draft has here) */
+                if (st) ++st[PS_OFFERED];
                 int ok = 1;
                 for (int x = 0; x < len; ++x) {
                     int b = rev ? q[r->qlen - 1 - (qa + x)] : q[qa + x];
@@ -1710,8 +1745,10 @@ int64_t tor_poa(const telr_aln *alns, int64_t n_aln, const uint32_t *cigars, con
                     seg[(size_t)nseg * POA_SEGMAX + x] = (uint8_t)b;
                 }
                 if (!ok) continue;
+                if (st) { if (len > st[PS_SEGMAX]) st[PS_SEGMAX] = len; if (st[PS_SEGMIN] < 0 || len < st[PS_SEGMIN]) st[PS_SEGMIN] = len; }
                 seglen[nseg++] = len;
             }
+            if (st) st[PS_VOTING] = nseg;
             if (nseg < min_depth) { for (int32_t p = w0; p < w1; ++p) { if (w < cap) out[w] = "ACGTN"[NT4[(uint8_t)ts[p]]]; ++w; } continue; }
             /* the graph starts as the draft's window */
             g->n = g->L = w1 - w0;
@@ -1721,8 +1758,14 @@ int64_t tor_poa(const telr_aln *alns, int64_t n_aln, const uint32_t *cigars, con
                 if (v) { g->in[v][0] = (int16_t)(v - 1); g->inw[v][0] = 1; g->nin[v] = 1; g->nout[v - 1] = 1; }
             }
             for (int s = 0; s < nseg; ++s) {
-                if (g->n + seglen[s] > POA_MAXNODE) continue;                 /* the graph could outgrow its arrays: the piece is left out */
-                poa_add_seq(g, seg + (size_t)s * POA_SEGMAX, seglen[s], H, rank);
+                if (st) nb[s] = g->n;
+                if (g->n + seglen[s] > POA_MAXNODE) { if (st) ++st[PS_CAPPED]; continue; }       /* the graph could outgrow its arrays: the piece is left out */
+                poa_add_seq(g, seg + (size_t)s * POA_SEGMAX, seglen[s], H, rank, st);
+                if (st) ++st[PS_MERGED];
+            }
+            if (st) {
+                st[PS_RAN] = 1; st[PS_NODES] = g->n;
+                for (int v = 0; v < g->n; ++v) if (g->nin[v] > st[PS_MAXIN]) st[PS_MAXIN] = g->nin[v];
             }
             const int cl = poa_consensus(g, wout);
             for (int x = 0; x < cl; ++x) { if (w < cap) out[w] = wout[x]; ++w; }
@@ -1731,4 +1774,20 @@ int64_t tor_poa(const telr_aln *alns, int64_t n_aln, const uint32_t *cigars, con
     }
     free(g); free(H); free(rank); free(seg); free(wout); free(first); free(idx);
     return w;
+}
+/* same interface as tor_consensus */
+int64_t tor_poa(const telr_aln *alns, int64_t n_aln, const uint32_t *cigars, const uint8_t *q_nt4, const int64_t *qoff,
+                int32_t n_targets, const char *t_ascii, const int64_t *toff, const int32_t *tlen, int32_t min_depth,
+                char *out, int64_t cap, int64_t *out_off, int32_t *out_len)
+{
+    return poa_run(alns, n_aln, cigars, q_nt4, qoff, n_targets, t_ascii, toff, tlen, min_depth, out, cap, out_off, out_len, NULL, NULL);
+}
+/* the same strings, and what every window reached (tests/consensus_edges.py): wst[TOR_POA_NSTAT] and nbefore[POA_MAXSEG] per
+ * window, the windows of the targets in order (ceil(tlen / 200) per target) */
+int64_t tor_poa_stats(const telr_aln *alns, int64_t n_aln, const uint32_t *cigars, const uint8_t *q_nt4, const int64_t *qoff,
+                      int32_t n_targets, const char *t_ascii, const int64_t *toff, const int32_t *tlen, int32_t min_depth,
+                      char *out, int64_t cap, int64_t *out_off, int32_t *out_len, int32_t *wst, int32_t *nbefore)
+{
+    if (!wst || !nbefore) return -1;
+    return poa_run(alns, n_aln, cigars, q_nt4, qoff, n_targets, t_ascii, toff, tlen, min_depth, out, cap, out_off, out_len, wst, nbefore);
 }

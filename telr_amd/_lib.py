@@ -102,6 +102,7 @@ def lib():
     L.telr_debug_bam_sink_ms.restype = C.c_int; L.telr_debug_bam_sink_ms.argtypes = [vp]
     L.telr_debug_bam_ms.restype = C.c_int; L.telr_debug_bam_ms.argtypes = [vp]
     L.telr_debug_huff.restype = C.c_int; L.telr_debug_huff.argtypes = [vp, i32, i32, vp]
+    L.telr_debug_check_records.restype = C.c_int; L.telr_debug_check_records.argtypes = [vp, i64, vp, i64, vp, i32, vp, i32, C.POINTER(i64)]
     L.telr_debug_deflate_host.restype = C.c_int; L.telr_debug_deflate_host.argtypes = [vp, i32, vp, i32, vp]
     L.telr_stage_ms.restype = C.c_int; L.telr_stage_ms.argtypes = [vp, vp]
     L.telr_stage_name.restype = cp; L.telr_stage_name.argtypes = [C.c_int]

@@ -110,6 +110,51 @@ __global__ void __launch_bounds__(256) k_pick_i64(const int64_t *__restrict__ in
     if (i < n) out[i] = in[at[i]];
 }
 
+// The records both consensus builds hand to their kernels, checked on the host before anything is launched: k_pile_count adds
+// to the cells of [ts, te) of the record's target and reads [qs, qe) of its query, and the POA host cut reads the same, so a
+// record mapped elsewhere (telr_result_from_arrays, an all-to-all) must stay inside both.  For every record: 0 <= tid < nt,
+// 0 <= qid < nq, 0 <= ts <= te <= tlen[tid], 0 <= qs <= qe <= qlen == qlens[qid], its CIGAR inside the array, only M / I / D
+// ops, M + D = te - ts and M + I = qe - qs.  A record without CIGAR ops votes nothing and passes.  -> index of the first
+// record that fails, or -1.
+static int64_t cons_first_bad_record(const telr_aln *alns, int64_t n, const uint32_t *cig, int64_t ncig, const int32_t *qlens, int32_t nq,
+                                     const int32_t *tlens, int32_t nt)
+{
+    auto bad = [&](const telr_aln &a) {
+        if (a.qid < 0 || a.qid >= nq || a.tid < 0 || a.tid >= nt) return true;
+        if (a.ts < 0 || a.ts > a.te || a.te > tlens[a.tid]) return true;
+        if (a.qlen != qlens[a.qid] || a.qs < 0 || a.qs > a.qe || a.qe > a.qlen) return true;
+        if (a.n_cigar < 0 || a.cigar_off < 0 || a.cigar_off + a.n_cigar > ncig || (a.n_cigar > 0 && !cig)) return true;
+        int64_t tl = 0, ql = 0;
+        for (int32_t z = 0; z < a.n_cigar; ++z) {
+            const uint32_t c = cig[a.cigar_off + z]; const int op = (int)(c & 0xfu); const int64_t l = (int64_t)(c >> 4);
+            if (op == 0) { tl += l; ql += l; } else if (op == 1) ql += l; else if (op == 2) tl += l; else return true;
+        }
+        return a.n_cigar > 0 && (tl != (int64_t)a.te - a.ts || ql != (int64_t)a.qe - a.qs);
+    };
+    // (the records are walked by the host's worker threads: every CIGAR op is read once)
+    const int NTH = n < 4096 ? 1 : std::max(1, std::min(host_threads(), 16));
+    std::vector<int64_t> first((size_t)NTH, -1);
+    auto part = [&](int t) {
+        for (int64_t i = n * t / NTH, e = n * (t + 1) / NTH; i < e; ++i) if (bad(alns[i])) { first[(size_t)t] = i; return; }
+    };
+    if (NTH == 1) part(0); else HostPool::get().run(NTH, part);
+    for (int64_t f : first) if (f >= 0) return f;
+    return -1;
+}
+static int64_t cons_first_bad_record(const telr_result *r, const telr_seqset *queries, const telr_seqset *tg)
+{
+    return cons_first_bad_record(r->alns.data(), (int64_t)r->alns.size(), r->cig, (int64_t)r->ncig, queries->len.data(), queries->n, tg->len.data(), tg->n);
+}
+// host-only debug entry: the same check on caller-held arrays -> TELR_OK, or TELR_E_ARG with *first_bad = the failing record
+extern "C" int telr_debug_check_records(const telr_aln *alns, int64_t n, const uint32_t *cig, int64_t ncig, const int32_t *qlens, int32_t nq,
+                                        const int32_t *tlens, int32_t nt, int64_t *first_bad)
+{
+    if ((n > 0 && !alns) || n < 0 || ncig < 0 || nq < 0 || nt < 0 || (nq > 0 && !qlens) || (nt > 0 && !tlens)) return TELR_E_ARG;
+    const int64_t f = cons_first_bad_record(alns, n, cig, ncig, qlens, nq, tlens, nt);
+    if (first_bad) *first_bad = f;
+    return f < 0 ? TELR_OK : TELR_E_ARG;
+}
+
 struct telr_consensus { std::string seq; std::vector<int64_t> off; std::vector<int32_t> len; };
 extern "C" void telr_consensus_free(telr_consensus *c) { delete c; }
 extern "C" int32_t telr_consensus_count(const telr_consensus *c) { return c ? (int32_t)c->len.size() : 0; }
@@ -143,7 +188,7 @@ static int consensus_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset
     const telr_seqset *tg = idx->targets;
     const int32_t nt = tg->n;
     const size_t n = r->alns.size();
-    for (const telr_aln &a : r->alns) if (a.qid < 0 || a.qid >= queries->n || a.tid < 0 || a.tid >= nt) return TELR_E_ARG;
+    if (cons_first_bad_record(r, queries, tg) >= 0) { ctx->err = "telr_consensus_build: a record outside its query / target or with an op other than M, I, D"; return TELR_E_ARG; }
     std::vector<int64_t> tbase((size_t)nt + 1, 0);
     for (int t = 0; t < nt; ++t) tbase[t + 1] = tbase[t] + tg->len[t];
     const int64_t total = tbase[nt];

@@ -568,7 +568,7 @@ static int poa_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *quer
     hipStream_t st = ctx->stream;
     const telr_seqset *tg = idx->targets;
     const int32_t nt = tg->n;
-    for (const telr_aln &a : r->alns) if (a.qid < 0 || a.qid >= queries->n || a.tid < 0 || a.tid >= nt) return TELR_E_ARG;
+    if (cons_first_bad_record(r, queries, tg) >= 0) { ctx->err = "telr_poa_build: a record outside its query / target or with an op other than M, I, D"; return TELR_E_ARG; }
     // windows
     std::vector<int64_t> wbase((size_t)nt + 1, 0);
     for (int t = 0; t < nt; ++t) wbase[t + 1] = wbase[t] + (tg->len[t] + POA_W - 1) / POA_W;
