@@ -123,6 +123,13 @@ typedef struct telr_map_opt {
 #define TELR_MF_KEEP_CIGARS 0x8  /* engine only (the oracle ignores it): the result keeps its CIGAR array on the device as well
                                     (same offsets; ~1.2 bytes per query base reserved), so that telr_write_bam_dev on the same
                                     context need not upload it again.  Records and CIGARs on the host are what they are without it. */
+#define TELR_MF_CHAIN_SKIP 0x1000 /* minimap2's chaining scan (lchain.c: mg_lchain_dp, max_chain_iter 5000 / max_chain_skip 25):
+                                    the predecessors of an anchor are scanned from the nearest down to the first one on its strand
+                                    within max_gap reference bases, at most 5,000 back; a predecessor is taken only on a strictly
+                                    larger score, and the scan stops once more than 25 predecessors that already lie on a chain
+                                    through the anchor failed to improve it (the oracle's 0x1000: same f, p, chains and records).
+                                    Overrides chain_lookback (which must still be valid).  Applies to every preset and to the
+                                    per-target and per-query-target calls alike.  Off: the fixed look-back of the spec. */
 
 /* ---- one alignment (PAF line / SAM record worth of numbers), 88 bytes ---- */
 typedef struct telr_aln {

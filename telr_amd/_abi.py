@@ -45,6 +45,7 @@ class Counters(C.Structure):
 TELR_OK, TELR_E_NODEVICE, TELR_E_HIP, TELR_E_ARG, TELR_E_RANGE, TELR_E_NOMEM, TELR_E_IO = 0, -1, -2, -3, -4, -5, -6
 F_PRIMARY, F_SECONDARY, F_SUPPL, F_REV = 1, 2, 4, 8
 MF_CIGAR, MF_PER_TARGET, MF_FAITHFUL, MF_KEEP_CIGARS = 1, 2, 4, 8
+MF_CHAIN_SKIP = 0x1000          # minimap2's chaining scan (max_chain_iter 5000, max_chain_skip 25); overrides chain_lookback
 N_STAGES = 16
 N_DPCLS = 25
 

@@ -120,5 +120,6 @@ def lib():
     L.telr_debug_mid_occ.restype = i32; L.telr_debug_mid_occ.argtypes = [vp, C.POINTER(MapOpt)]
     L.telr_debug_dp_limits.restype = C.c_int; L.telr_debug_dp_limits.argtypes = [C.POINTER(MapOpt), vp]
     L.telr_debug_dp.restype = C.c_int; L.telr_debug_dp.argtypes = [vp, vp, vp, C.POINTER(MapOpt), vp, i32, vp, vp, vp, i64]
+    L.telr_debug_chain.restype = C.c_int; L.telr_debug_chain.argtypes = [vp, i32, vp, vp, C.POINTER(MapOpt), vp, vp]
     _lib = L
     return L

@@ -115,6 +115,19 @@ class Engine:
         out["cigars"] = [cig[res[x, 7]:res[x, 7] + res[x, 6]].copy() for x in range(npb)]
         return out
 
+    def debug_chain(self, keys, q_aoff, mo):
+        """the chaining stage of map() on sorted anchor lists -- test tap.  keys: uint64 anchors in the engine's layout (strand << 63 |
+        global reference position << 32 | query position << 8 | span), query q's at [q_aoff[q], q_aoff[q + 1]), ascending.
+        -> (f, p) int32 arrays (p relative to the query's first anchor, -1 for none)"""
+        K = np.ascontiguousarray(keys, dtype=np.uint64)
+        O = np.ascontiguousarray(q_aoff, dtype=np.int32)
+        if len(O) < 1 or int(O[-1]) != len(K):
+            raise ValueError("q_aoff must hold nq + 1 offsets ending at len(keys)")
+        f = np.zeros(len(K), np.int32); p = np.zeros(len(K), np.int32)
+        self._chk(self.L.telr_debug_chain(self.h, len(O) - 1, K.ctypes.data, O.ctypes.data, C.byref(mo), f.ctypes.data, p.ctypes.data),
+                  "telr_debug_chain")
+        return f, p
+
     def release_scratch(self):
         """give the context's grow-only scratch back to the device (the next call allocates what it needs again)"""
         self._chk(self.L.telr_release_scratch(self.h), "telr_release_scratch")

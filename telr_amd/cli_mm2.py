@@ -9,20 +9,25 @@ them with the HIP engine, writing SAM / PAF to stdout exactly where the referenc
   S6  minimap2 -a -x P -v 0 SUBJ QRY                                                           (TELR_te.py:504-506)
   S7  minimap2 -cx asm10 -v 0 -N 10 REF FLANK                                                  (TELR_liftover.py:253-266)
 
+minimap2's --max-chain-skip 25 and/or --max-chain-iter 5000 (its defaults, spelled out) select the engine's minimap2 chaining scan
+(TELR_MF_CHAIN_SKIP) instead of its fixed look-back; other values are refused (only 25 / 5000 is held to the oracle).
+
 usage:  python -m telr_amd.cli_mm2 minimap2 <args...>   |   python -m telr_amd.cli_mm2 ngmlr <args...>
 Exit code 0 and empty stdout when nothing maps (the reference treats an empty PAF as "locus not passed").
 """
 import sys
 
+_CHAIN_SCAN = {"--max-chain-skip": 25, "--max-chain-iter": 5000}        # the only values the engine's chaining scan runs
+
 
 def parse_argv(argv):
-    """-> dict(tool, preset, sam, cigar, md, cs, softclip, secondary, best_n, bw, target, query, rg, threads)"""
+    """-> dict(tool, preset, sam, cigar, md, cs, softclip, secondary, best_n, bw, target, query, rg, threads, chain_skip)"""
     if not argv:
         raise SystemExit(__doc__)
     tool = argv[0].split("/")[-1]
     a = argv[1:]
     o = dict(tool=tool, preset=None, sam=False, cigar=False, md=False, cs=False, softclip=False, secondary=True, best_n=None,
-             bw=None, target=None, query=None, rg=None, threads=None)
+             bw=None, target=None, query=None, rg=None, threads=None, chain_skip=False)
     if tool == "ngmlr":
         rg = {"id": None, "sm": None, "lb": None}
         i = 0
@@ -87,6 +92,13 @@ def parse_argv(argv):
             elif f == "-r":
                 v = a[i + 1].lower()
                 o["bw"] = int(float(v[:-1]) * 1000) if v.endswith("k") else int(v); i += 2
+            elif f.split("=", 1)[0] in _CHAIN_SCAN:
+                name, v = f.split("=", 1) if "=" in f else (f, a[i + 1] if i + 1 < len(a) else None)
+                i += 1 if "=" in f else 2
+                if v is None or v.strip() != str(_CHAIN_SCAN[name]):
+                    raise SystemExit("%s: only %d is supported (minimap2's default, the engine's chaining scan); got %r"
+                                     % (name, _CHAIN_SCAN[name], v))
+                o["chain_skip"] = True
             elif f.startswith("-"):
                 raise SystemExit("unsupported minimap2 option %r" % f)
             else:
@@ -107,7 +119,7 @@ def run(argv, out_path="/dev/stdout", engine=None):
     from .aligner import Engine
     from .presets import preset
     from .fasta import read_fasta
-    io, mo = preset(o["preset"])
+    io, mo = preset(o["preset"], chain_skip=o["chain_skip"])
     if not o["secondary"]:
         mo.secondary = 0
     if o["best_n"] is not None:

@@ -1311,9 +1311,10 @@ __device__ __forceinline__ uint64_t d_readlane64(uint64_t v, int lane)
 //  * the running maximum is kept as B = 2 best + (1 while no predecessor was taken), which turns "larger, or equal and the
 //    current best already has a predecessor" (ascending j, the largest j wins ties) into the single compare 2 v >= B.
 // With chain_skip_q8 == 0 (every preset) the oracle's "dd || dg > span" condition is moot (the penalty is 0 when dd == 0).
+// d_chain_link: the link alone -> 2 (f_j + sc(j, i)) and whether the link is allowed; d_chain_push adds the max/tie rule.
 template <bool SKIP>
-__device__ __forceinline__ void d_chain_push(uint32_t gi, uint32_t qi, uint32_t sp1, uint32_t gj1, uint32_t qj1, int32_t fj2p2, int32_t j,
-                                             uint32_t max_gap, uint32_t ddc, uint32_t gap_q8, uint32_t skip_q8, int32_t &B, int32_t &bp)
+__device__ __forceinline__ int32_t d_chain_link(uint32_t gi, uint32_t qi, uint32_t sp1, uint32_t gj1, uint32_t qj1, int32_t fj2p2,
+                                                uint32_t max_gap, uint32_t ddc, uint32_t gap_q8, uint32_t skip_q8, bool &ok)
 {
     const uint32_t dr1 = gi - gj1, dq1 = qi - qj1;
     uint32_t dd;
@@ -1321,14 +1322,21 @@ __device__ __forceinline__ void d_chain_push(uint32_t gi, uint32_t qi, uint32_t 
     const uint32_t dgm = dr1 < dq1 ? dr1 : dq1;
     const uint32_t vm = sp1 < dgm ? sp1 : dgm;                                  // min(span, dg) - 1
     uint32_t t = dr1 > dq1 ? dr1 : dq1; const uint32_t u = dd + ddc; t = t > u ? t : u;
-    const bool ok = t < max_gap;
+    ok = t < max_gap;
     const uint32_t l2h = __float_as_uint((float)(dd + 1u)) >> 16;              // ilog2_q8(dd+1)/2 + 16256
     int32_t pen = (int32_t)(__umul24(gap_q8, dd) + l2h) - 16256;
     if (SKIP) {
         pen += (int32_t)__umul24(skip_q8, dgm + 1u);
         if (dd == 0u && dgm <= sp1) pen = 0;
     }
-    const int32_t v2 = (((int32_t)vm - (pen >> 8)) << 1) + fj2p2;
+    return (((int32_t)vm - (pen >> 8)) << 1) + fj2p2;
+}
+template <bool SKIP>
+__device__ __forceinline__ void d_chain_push(uint32_t gi, uint32_t qi, uint32_t sp1, uint32_t gj1, uint32_t qj1, int32_t fj2p2, int32_t j,
+                                             uint32_t max_gap, uint32_t ddc, uint32_t gap_q8, uint32_t skip_q8, int32_t &B, int32_t &bp)
+{
+    bool ok;
+    const int32_t v2 = d_chain_link<SKIP>(gi, qi, sp1, gj1, qj1, fj2p2, max_gap, ddc, gap_q8, skip_q8, ok);
     if (ok && v2 >= B) { B = v2; bp = j; }
 }
 
@@ -1669,6 +1677,145 @@ __global__ void __launch_bounds__(64) k_chain_isl(const uint64_t *__restrict__ k
         d_chain_any<R, SKIP, MODE>(keys, isl_off[s], isl_off[s + 1] - isl_off[s], isl_pd[s], o, f, p, false);
 }
 
+// MINIMAP2'S PREDECESSOR SCAN (TELR_MF_CHAIN_SKIP; lchain.c: mg_lchain_dp, the oracle's chain_dp under 0x1000).  For anchor i the
+// predecessors j = i-1, i-2, ... down to st are scanned IN ORDER, where st = max(i - 5000, the first anchor on i's strand within
+// max_gap reference bases); j is taken only on a strictly larger score; every new maximum takes one from n_skip (not below 0),
+// every predecessor that does not improve and already lies on a chain through i (t[j] == i: the parent of a predecessor scanned
+// before it) adds one, and the scan stops when n_skip exceeds 25; every scanned j with a valid link marks t[p[j]] = i.
+// The early exit depends on the data of each anchor, so the anchors of a run are taken IN ORDER by one wave, and the 64 lanes take
+// 64 predecessors at a time (lane l: j = i - 1 - 64 c - l, chunk c).  A chunk is resolved with wave operations:
+//   * a prefix maximum of the scores above the running best decides where the new maxima lie;
+//   * marks inside the chunk come from lanes before the marked one (t[p[j']] with j' > j), set in a 64-byte LDS map;
+//   * the clamped +-1 walk of n_skip, x_l = T_l + max(0, -min_{k <= l} T_k) with T = n_skip + the prefix sum of the steps, gives the
+//     first lane where it exceeds 25: the break (that lane marks nothing).
+// Marks for predecessors below the chunk go to a stamp per anchor in device memory (`mark`, value = the absolute index of i: stale
+// stamps of other anchors never compare equal, and an anchor's own stamp is set to -1 when it is final, before any scan can read it).
+// The nearest 64 predecessors (key words, 2 f + 2, p) are kept in registers, shifted by one lane per anchor; the chunks below them
+// are read from f / p / keys, which are written 64 anchors at a time (every j <= i - 65 is written by the time the scan of i reads it).
+#define CHAIN_SCAN_H    5000        // minimap2's max_chain_iter
+#define CHAIN_SCAN_SKIP 25          // minimap2's max_chain_skip
+// inclusive prefix maximum of non-negative values over the 64 lanes (the DPP pattern of d_wave_scan_add; lanes without a source read 0)
+__device__ __forceinline__ uint32_t d_wave_scan_max0(uint32_t v)
+{
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, true));
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, true));
+    return v;
+}
+template <bool SKIP>
+__device__ __forceinline__ void d_chain_run_scan(const uint64_t *__restrict__ keys, const int64_t base, const int n, const int pdelta,
+                                                 const ChainOpt &o, int32_t *__restrict__ f, int32_t *__restrict__ p, int32_t *__restrict__ mark,
+                                                 uint8_t *__restrict__ fl)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t *a = keys + base;
+    const uint32_t max_gap = (uint32_t)o.max_gap, ddc = o.bw < o.max_gap ? (uint32_t)(o.max_gap - 1 - o.bw) : 0u;
+    const uint32_t gap_q8 = (uint32_t)o.chain_gap_q8, skip_q8 = (uint32_t)o.chain_skip_q8;
+    // the nearest 64 predecessors of the anchor whose turn it is: lane l holds i - 1 - l (reference word, query position, 2 f + 2, p
+    // inside the run); lanes l >= i hold nothing and fail the index test
+    uint32_t wg = 0, wq = 0; int32_t wf = 0, wp = -1;
+    uint64_t kb = lane < n ? a[lane] : 0;            // lane l: anchor i0 + l of the batch being chained
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const uint64_t kn = i0 + 64 + lane < n ? a[i0 + 64 + lane] : 0;
+        const int m = n - i0 < 64 ? n - i0 : 64;
+        int32_t of = 0, op = -1;                     // lane l: f and p of anchor i0 + l once it is final
+        for (int ii = 0; ii < m; ++ii) {
+            const int i = i0 + ii;
+            const uint32_t gi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(kb >> 32), ii);
+            const uint32_t klo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)kb, ii);
+            const uint32_t qi = (klo >> 8) & 0xffffffu, sp = klo & 0xffu;
+            const int32_t gpos = (int32_t)(gi & 0x7fffffffu);
+            const int lo = i - CHAIN_SCAN_H > 0 ? i - CHAIN_SCAN_H : 0;
+            int32_t best = (int32_t)sp, bp = -1, nskip = 0;
+            for (int c = 0; ; ++c) {
+                const int jt = i - 1 - 64 * c, j = jt - lane;       // (jt: the predecessor of lane 0)
+                if (jt < lo) break;
+                uint32_t g = wg, q = wq; int32_t fj2p2 = wf, pj = wp; bool mk = false;
+                if (c > 0 && j >= lo) {
+                    const uint64_t k = a[j];
+                    g = (uint32_t)(k >> 32); q = (uint32_t)A_Q(k);
+                    fj2p2 = 2 * f[base + j] + 2;
+                    const int32_t pa = p[base + j];
+                    pj = pa >= 0 ? pa - pdelta : -1;
+                    mk = mark[base + j] == (int32_t)(base + i);
+                }
+                // the window [st, i): same strand, at most max_gap reference bases behind i (monotone in j: a prefix of the lanes)
+                const bool inw = j >= lo && ((g ^ gi) >> 31) == 0u && gpos - (int32_t)(g & 0x7fffffffu) <= (int32_t)max_gap;
+                bool ok;
+                const int32_t v2 = d_chain_link<SKIP>(gi, qi, sp - 1u, g + 1u, q + 1u, fj2p2, max_gap, ddc, gap_q8, skip_q8, ok);
+                const bool valid = inw && ok;
+                const int32_t v = v2 >> 1;
+                // new maxima: above the running best and above every valid lane before
+                const uint32_t u = valid && v > best ? (uint32_t)(v - best) : 0u;
+                const uint32_t pre = d_wave_scan_max0(u);
+                const uint32_t ex = (uint32_t)__shfl_up((int)pre, 1);
+                const bool imp = u > (lane ? ex : 0u);
+                // marks inside the chunk: lane l' (j' = jt - l') with a valid link marks its parent when that lies in the chunk
+                fl[lane] = 0;
+                const int tl = jt - pj;
+                if (valid && pj >= 0 && tl < 64) fl[tl] = 1;
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");         // (LDS operations of a wave complete in order)
+                mk = mk || fl[lane] != 0;
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                // the n_skip walk and its break
+                const int32_t s = valid ? (imp ? -1 : (mk ? 1 : 0)) : 0;
+                const int32_t T = nskip + (int32_t)d_wave_scan_add((uint32_t)s);
+                const int32_t x = T + (int32_t)d_wave_scan_max0(T < 0 ? (uint32_t)(-T) : 0u);
+                const uint64_t brk = __ballot(x > CHAIN_SCAN_SKIP);
+                const int b = brk ? __ffsll((unsigned long long)brk) - 1 : 64;
+                const uint64_t scanned = b == 64 ? ~0ULL : ((1ULL << b) - 1);
+                const uint64_t im = __ballot(imp) & scanned;
+                if (im) {
+                    const int hl = 63 - __clzll((long long)im);
+                    best += (int32_t)__builtin_amdgcn_readlane((int)u, hl);
+                    bp = jt - hl;
+                }
+                const uint64_t win = __ballot(inw);
+                const bool more = b == 64 && win == ~0ULL && jt - 64 >= lo;
+                if (!more) break;
+                // marks below the chunk, for the chunks still to come (written before they are read)
+                if (valid && pj >= 0 && tl >= 64) mark[base + pj] = (int32_t)(base + i);
+                nskip = __builtin_amdgcn_readlane(x, 63);
+                __threadfence_block();
+            }
+            of = lane == ii ? best : of; op = lane == ii ? bp : op;
+            // anchor i enters the register window as its lane 0
+            wg = (uint32_t)__shfl_up((int)wg, 1); wq = (uint32_t)__shfl_up((int)wq, 1); wf = __shfl_up(wf, 1); wp = __shfl_up(wp, 1);
+            if (lane == 0) { wg = gi; wq = qi; wf = 2 * best + 2; wp = bp; }
+        }
+        if (lane < m) {
+            f[base + i0 + lane] = of; p[base + i0 + lane] = op >= 0 ? op + pdelta : -1;
+            mark[base + i0 + lane] = -1;
+        }
+        __threadfence_block();
+        kb = kn;
+    }
+}
+// one wave per query (q_order: longest first), or per island (the grid-stride loop of k_chain_isl); `mark`: one stamp per anchor
+template <bool SKIP>
+__global__ void __launch_bounds__(64) k_chain_scan(const uint64_t *__restrict__ keys, const int32_t *__restrict__ q_aoff, int32_t nq,
+                                                   ChainOpt o, int32_t *__restrict__ f, int32_t *__restrict__ p, int32_t *__restrict__ mark,
+                                                   const int32_t *__restrict__ q_order)
+{
+    __shared__ uint8_t fl[64];
+    if ((int)blockIdx.x >= nq) return;
+    const int q = q_order ? q_order[blockIdx.x] : blockIdx.x;
+    d_chain_run_scan<SKIP>(keys, q_aoff[q], q_aoff[q + 1] - q_aoff[q], 0, o, f, p, mark, fl);
+}
+template <bool SKIP>
+__global__ void __launch_bounds__(64) k_chain_scan_isl(const uint64_t *__restrict__ keys, const int32_t *__restrict__ isl_off, const int32_t *__restrict__ isl_pd,
+                                                       const int32_t *__restrict__ nisl, ChainOpt o, int32_t *__restrict__ f, int32_t *__restrict__ p,
+                                                       int32_t *__restrict__ mark)
+{
+    __shared__ uint8_t fl[64];
+    const int n_isl = *nisl;
+    for (int s = blockIdx.x; s < n_isl; s += gridDim.x)
+        d_chain_run_scan<SKIP>(keys, isl_off[s], isl_off[s + 1] - isl_off[s], isl_pd[s], o, f, p, mark, fl);
+}
+
 // peaks: anchors with no successor of larger f
 __global__ void k_nonpeak(const int32_t *__restrict__ q_aoff, const int32_t *__restrict__ f, const int32_t *__restrict__ p, uint8_t *__restrict__ nonpeak)
 {
@@ -1713,16 +1860,18 @@ struct ChainRec { int32_t score, cnt, a_off, pad; uint64_t a0, a1; };   // 32 B
 // latency per anchor.  One wave per query whatever its size (no LDS tiers, no lists).
 #define BT_INF 0xffffffffu
 #define BT_RING 512                 // >= look-back (<= 256) + 2 x 64
+#define BT_RING_SCAN 8192           // the same for the links of TELR_MF_CHAIN_SKIP (i - p[i] <= CHAIN_SCAN_H = 5000)
 __global__ void k_bt_rank(const int32_t *__restrict__ q_aoff, const uint64_t *__restrict__ pk, const int32_t *__restrict__ n_peaks, uint32_t *__restrict__ owner)
 {
     const int q = blockIdx.x;
     const int64_t base = q_aoff[q]; const int np = n_peaks[q];
     for (int t = threadIdx.x; t < np; t += blockDim.x) owner[base + (uint32_t)(pk[base + t] & 0xffffffffu)] = (uint32_t)t;
 }
+template <int RING>
 __global__ void __launch_bounds__(64) k_bt_owner(const int32_t *__restrict__ q_aoff, int32_t nq, const int32_t *__restrict__ p, int32_t lookback,
                                                  uint32_t *__restrict__ owner, const int32_t *__restrict__ q_order)
 {
-    __shared__ uint32_t W[BT_RING];
+    __shared__ uint32_t W[RING];
     __shared__ int32_t UP[64];
     const int q = q_order ? q_order[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
     const int64_t base = q_aoff[q]; const int n = q_aoff[q + 1] - q_aoff[q];
@@ -1731,30 +1880,31 @@ __global__ void __launch_bounds__(64) k_bt_owner(const int32_t *__restrict__ q_a
     for (int blk = nblk - 1; blk >= 0; --blk) {
         const int b0 = blk << 6;
         // ring entries that enter the window [b0 - lookback, b0 + 64): all of it for the first block handled, the lowest 64 afterwards
-        if (blk == nblk - 1) { for (int x = b0 - lookback + lane; x < b0 + 64; x += 64) if (x >= 0 && x < n) W[x & (BT_RING - 1)] = owner[base + x]; }
-        else { const int x = b0 - lookback + lane; if (x >= 0) W[x & (BT_RING - 1)] = owner[base + x]; }
+        if (blk == nblk - 1) { for (int x = b0 - lookback + lane; x < b0 + 64; x += 64) if (x >= 0 && x < n) W[x & (RING - 1)] = owner[base + x]; }
+        else { const int x = b0 - lookback + lane; if (x >= 0) W[x & (RING - 1)] = owner[base + x]; }
         const int i = b0 + lane; const bool valid = i < n;
         const int pi = valid ? p[base + i] : -1;
         int up = pi >= b0 ? pi - b0 : -1;
         UP[lane] = up;
         for (int k = 0; k < 6; ++k) {
             if (__ballot(up >= 0) == 0) break;
-            if (up >= 0) atomicMin(&W[(b0 + up) & (BT_RING - 1)], W[i & (BT_RING - 1)]);
+            if (up >= 0) atomicMin(&W[(b0 + up) & (RING - 1)], W[i & (RING - 1)]);
             const int nup = up >= 0 ? UP[up] : -1;
             UP[lane] = nup; up = nup;
         }
         if (valid) {
-            const uint32_t v = W[i & (BT_RING - 1)];
+            const uint32_t v = W[i & (RING - 1)];
             owner[base + i] = v;
-            if (pi >= 0 && pi < b0) atomicMin(&W[pi & (BT_RING - 1)], v);
+            if (pi >= 0 && pi < b0) atomicMin(&W[pi & (RING - 1)], v);
         }
     }
 }
+template <int RING>
 __global__ void __launch_bounds__(64) k_bt_depth(const int32_t *__restrict__ q_aoff, int32_t nq, const int32_t *__restrict__ p, const uint32_t *__restrict__ owner,
                                                  int32_t *__restrict__ depth, int32_t *__restrict__ ch_top, const int32_t *__restrict__ q_order)
 {
-    __shared__ uint32_t OWN[BT_RING];
-    __shared__ int32_t DEP[BT_RING];
+    __shared__ uint32_t OWN[RING];
+    __shared__ int32_t DEP[RING];
     __shared__ int32_t UP[64], VAL[64];
     const int q = q_order ? q_order[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
     const int64_t base = q_aoff[q]; const int n = q_aoff[q + 1] - q_aoff[q];
@@ -1763,11 +1913,11 @@ __global__ void __launch_bounds__(64) k_bt_depth(const int32_t *__restrict__ q_a
         const int b0 = blk << 6, i = b0 + lane; const bool valid = i < n;
         const uint32_t o = valid ? owner[base + i] : BT_INF;
         const int pi = valid ? p[base + i] : -1;
-        OWN[i & (BT_RING - 1)] = o;
-        const uint32_t po = pi >= 0 ? OWN[pi & (BT_RING - 1)] : BT_INF;
+        OWN[i & (RING - 1)] = o;
+        const uint32_t po = pi >= 0 ? OWN[pi & (RING - 1)] : BT_INF;
         const bool conn = o != BT_INF && pi >= 0 && po == o;           // the parent is on the same chain
         int up = -1, val = 0;
-        if (conn) { if (pi >= b0) { up = pi - b0; val = 1; } else val = DEP[pi & (BT_RING - 1)] + 1; }
+        if (conn) { if (pi >= b0) { up = pi - b0; val = 1; } else val = DEP[pi & (RING - 1)] + 1; }
         UP[lane] = up; VAL[lane] = val;
         for (int k = 0; k < 6; ++k) {
             if (__ballot(up >= 0) == 0) break;
@@ -1775,7 +1925,7 @@ __global__ void __launch_bounds__(64) k_bt_depth(const int32_t *__restrict__ q_a
             val += add;
             VAL[lane] = val; UP[lane] = nup; up = nup;
         }
-        DEP[i & (BT_RING - 1)] = val;
+        DEP[i & (RING - 1)] = val;
         if (valid) {
             depth[base + i] = val;
             if (o != BT_INF && !conn) ch_top[base + o] = i;            // exactly one top anchor per chain

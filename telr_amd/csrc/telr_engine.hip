@@ -1681,6 +1681,99 @@ struct HostTrace {
 // ---------------------------------------------------------------------------------------
 // one batch of queries [q0, q1)
 struct OccCut { int32_t mid_occ; const int32_t *d_tmid; };      // pooled cut-off; per-target cut-offs (nullable)
+// ---- chaining of sorted anchor lists: f / p of every anchor (map_batch; telr_debug_chain runs the same dispatch on a caller's lists).
+// n_over / d_overlist: the queries with more than SEGSORT_CAP anchors; d_qorder: the order of the one-wave-per-query launches (or null)
+static int chain_dispatch(telr_ctx *ctx, hipStream_t st, const telr_map_opt *mo, const uint64_t *d_skeys, const int32_t *d_qaoff, int nq, int32_t na,
+                          int32_t n_over, const int32_t *d_overlist, const int32_t *d_qorder, int32_t *d_f, int32_t *d_p)
+{
+    // long join: anchors are chained within max(bw, bw_long) diagonals
+    ChainOpt co; co.max_gap = mo->max_gap; co.bw = mo->bw_long > mo->bw ? mo->bw_long : mo->bw; co.min_cnt = mo->min_cnt; co.min_chain_score = mo->min_chain_score;
+    co.chain_gap_q8 = mo->chain_gap_q8; co.chain_skip_q8 = mo->chain_skip_q8;
+    // which loop: chosen per run of anchors (kernels.hip.h: WHICH LOOP); A/B: chain_push = the full push loop (every one of the H links scored)
+    // everywhere, chain_lazy = the lazy far look-back everywhere, chain_no_mw = no second kernel for the long dense runs.
+    // TELR_CHAIN_DENSE=n,span,mw_n moves the choices (tests, experiments).
+    static const bool chain_push = ab_on("chain_push"), chain_lazy = ab_on("chain_lazy"), chain_no_mw = ab_on("chain_no_mw");
+    static int dense_v[3] = {2048, 48, 1 << 19};
+    static const bool dense_env = [] { if (const char *e = getenv("TELR_CHAIN_DENSE")) sscanf(e, "%d%*[,:]%d%*[,:]%d", &dense_v[0], &dense_v[1], &dense_v[2]); return true; }();
+    (void)dense_env;
+    const int Rr = mo->chain_lookback / 64;
+    const bool mw_all = dense_v[2] <= SEGSORT_CAP;            // (small thresholds: every query is looked at, not only the over-size list)
+    static const bool no_islands = ab_on("no_islands");       // A/B: one wave per query whatever the call's shape
+    const bool islands = nq <= CHAIN_ISL_NQ && na > 0 && !no_islands;
+    const bool mw = !(mo->flags & TELR_MF_CHAIN_SKIP) && !chain_push && !chain_lazy && !chain_no_mw && Rr >= 2 && na > 0 && !islands && dense_v[2] > 0 && (mw_all || n_over > 0);
+    co.dense_n = dense_v[0]; co.dense_span = dense_v[1]; co.mw_n = mw ? dense_v[2] : 0;
+#define CHAIN_LAUNCH(RR, SK) do { if (chain_push) hipLaunchKernelGGL((k_chain<RR, SK, 0>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, 0); \
+                                  else if (chain_lazy) hipLaunchKernelGGL((k_chain<RR, SK, 1>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, 0); \
+                                  else hipLaunchKernelGGL((k_chain<RR, SK, 2>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, mw ? 1 : 0); } while (0)
+#define CHAIN_MW(RR, SK) hipLaunchKernelGGL((k_chain_mw<RR, SK>), dim3(mw_all ? nq : n_over), dim3(64 * RR), 0, ctx->side[0], d_skeys, d_qaoff, mw_all ? nq : n_over, mw_all ? (const int32_t*)nullptr : (const int32_t*)d_overlist, co, d_f, d_p)
+    const bool skip = co.chain_skip_q8 != 0;
+    if (mo->flags & TELR_MF_CHAIN_SKIP) {
+        // minimap2's order-dependent predecessor scan (kernels.hip.h: MINIMAP2'S PREDECESSOR SCAN): one wave per query, or per island
+        // for calls with few queries; never the push / lazy / multi-wave loops.  `chain_mark`: one stamp per anchor, set by the kernel.
+        int32_t *d_mark;
+        TRY(ctx_buf_t(ctx, "chain_mark", (size_t)na + 1, &d_mark));
+        if (islands) {
+            int32_t *d_head, *d_rank, *d_ioff, *d_ipd;
+            TRY(ctx_buf_t(ctx, "isl_head", (size_t)na + 1, &d_head));
+            TRY(ctx_buf_t(ctx, "isl_rank", (size_t)na + 1, &d_rank));
+            TRY(ctx_buf_t(ctx, "isl_off", (size_t)na + 2, &d_ioff));
+            TRY(ctx_buf_t(ctx, "isl_pd", (size_t)na + 1, &d_ipd));
+            HIPCHK(hipMemsetAsync(d_head + na, 0, 4, st));
+            hipLaunchKernelGGL(k_isl_heads, dim3(nq), dim3(256), 0, st, d_skeys, d_qaoff, nq, (uint32_t)co.max_gap, d_head);
+            HIPCHK(hipGetLastError());
+            TRY((dev_exclusive_scan<int32_t, int32_t>(ctx, d_head, d_rank, (size_t)na + 1)));
+            hipLaunchKernelGGL(k_isl_fill, dim3(nq), dim3(256), 0, st, d_qaoff, nq, d_head, d_rank, (int32_t)na, d_ioff, d_ipd);
+            const unsigned grid = (unsigned)std::min<int64_t>((int64_t)na, 256 * 32);
+            if (skip) hipLaunchKernelGGL(k_chain_scan_isl<true>, dim3(grid), dim3(64), 0, st, d_skeys, d_ioff, d_ipd, d_rank + na, co, d_f, d_p, d_mark);
+            else hipLaunchKernelGGL(k_chain_scan_isl<false>, dim3(grid), dim3(64), 0, st, d_skeys, d_ioff, d_ipd, d_rank + na, co, d_f, d_p, d_mark);
+        } else if (nq > 0) {
+            if (skip) hipLaunchKernelGGL(k_chain_scan<true>, dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_mark, d_qorder);
+            else hipLaunchKernelGGL(k_chain_scan<false>, dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_mark, d_qorder);
+        }
+        HIPCHK(hipGetLastError());
+        return TELR_OK;
+    }
+    if (islands) {
+        // few queries: chain island by island (kernels.hip.h: ISLANDS) -- same f and p, thousands of waves instead of nq
+        int32_t *d_head, *d_rank, *d_ioff, *d_ipd;
+        TRY(ctx_buf_t(ctx, "isl_head", (size_t)na + 1, &d_head));
+        TRY(ctx_buf_t(ctx, "isl_rank", (size_t)na + 1, &d_rank));
+        TRY(ctx_buf_t(ctx, "isl_off", (size_t)na + 2, &d_ioff));
+        TRY(ctx_buf_t(ctx, "isl_pd", (size_t)na + 1, &d_ipd));
+        HIPCHK(hipMemsetAsync(d_head + na, 0, 4, st));
+        hipLaunchKernelGGL(k_isl_heads, dim3(nq), dim3(256), 0, st, d_skeys, d_qaoff, nq, (uint32_t)co.max_gap, d_head);
+        HIPCHK(hipGetLastError());
+        TRY((dev_exclusive_scan<int32_t, int32_t>(ctx, d_head, d_rank, (size_t)na + 1)));
+        hipLaunchKernelGGL(k_isl_fill, dim3(nq), dim3(256), 0, st, d_qaoff, nq, d_head, d_rank, (int32_t)na, d_ioff, d_ipd);
+        const unsigned grid = (unsigned)std::min<int64_t>((int64_t)na, 256 * 32);
+#define CHAIN_ISL(RR, SK) do { if (chain_push) hipLaunchKernelGGL((k_chain_isl<RR, SK, 0>), dim3(grid), dim3(64), 0, st, d_skeys, d_ioff, d_ipd, d_rank + na, co, d_f, d_p); \
+                               else if (chain_lazy) hipLaunchKernelGGL((k_chain_isl<RR, SK, 1>), dim3(grid), dim3(64), 0, st, d_skeys, d_ioff, d_ipd, d_rank + na, co, d_f, d_p); \
+                               else hipLaunchKernelGGL((k_chain_isl<RR, SK, 2>), dim3(grid), dim3(64), 0, st, d_skeys, d_ioff, d_ipd, d_rank + na, co, d_f, d_p); } while (0)
+        if (Rr == 1) { if (skip) CHAIN_ISL(1, true); else CHAIN_ISL(1, false); }
+        else if (Rr == 2) { if (skip) CHAIN_ISL(2, true); else CHAIN_ISL(2, false); }
+        else { if (skip) CHAIN_ISL(4, true); else CHAIN_ISL(4, false); }
+#undef CHAIN_ISL
+    }
+    else {
+        if (mw) {
+            // the long dense runs beside the others: forked here, joined behind k_chain
+            HIPCHK(hipEventRecord(ctx->ev_side[0], st));
+            HIPCHK(hipStreamWaitEvent(ctx->side[0], ctx->ev_side[0], 0));
+            if (Rr == 2) { if (skip) CHAIN_MW(2, true); else CHAIN_MW(2, false); }
+            else { if (skip) CHAIN_MW(4, true); else CHAIN_MW(4, false); }
+            HIPCHK(hipEventRecord(ctx->ev_side[0], ctx->side[0]));
+        }
+        if (Rr == 1) { if (skip) CHAIN_LAUNCH(1, true); else CHAIN_LAUNCH(1, false); }
+        else if (Rr == 2) { if (skip) CHAIN_LAUNCH(2, true); else CHAIN_LAUNCH(2, false); }
+        else { if (skip) CHAIN_LAUNCH(4, true); else CHAIN_LAUNCH(4, false); }
+        if (mw) HIPCHK(hipStreamWaitEvent(st, ctx->ev_side[0], 0));
+    }
+#undef CHAIN_LAUNCH
+#undef CHAIN_MW
+    HIPCHK(hipGetLastError());
+    return TELR_OK;
+}
+
 static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs, const int32_t *d_qtarget, int32_t q0, int32_t q1,
                      const telr_map_opt *mo, OccCut occ, telr_result *R, RangeTurn *gate = nullptr)
 {
@@ -1846,64 +1939,7 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
     int32_t *d_f, *d_p;
     TRY(ctx_buf_t(ctx, "chain_f", (size_t)na, &d_f));
     TRY(ctx_buf_t(ctx, "chain_p", (size_t)na, &d_p));
-    // long join: anchors are chained within max(bw, bw_long) diagonals
-    ChainOpt co; co.max_gap = mo->max_gap; co.bw = mo->bw_long > mo->bw ? mo->bw_long : mo->bw; co.min_cnt = mo->min_cnt; co.min_chain_score = mo->min_chain_score;
-    co.chain_gap_q8 = mo->chain_gap_q8; co.chain_skip_q8 = mo->chain_skip_q8;
-    // which loop: chosen per run of anchors (kernels.hip.h: WHICH LOOP); A/B: chain_push = the full push loop (every one of the H links scored)
-    // everywhere, chain_lazy = the lazy far look-back everywhere, chain_no_mw = no second kernel for the long dense runs.
-    // TELR_CHAIN_DENSE=n,span,mw_n moves the choices (tests, experiments).
-    static const bool chain_push = ab_on("chain_push"), chain_lazy = ab_on("chain_lazy"), chain_no_mw = ab_on("chain_no_mw");
-    static int dense_v[3] = {2048, 48, 1 << 19};
-    static const bool dense_env = [] { if (const char *e = getenv("TELR_CHAIN_DENSE")) sscanf(e, "%d%*[,:]%d%*[,:]%d", &dense_v[0], &dense_v[1], &dense_v[2]); return true; }();
-    (void)dense_env;
-    const int Rr = mo->chain_lookback / 64;
-    const bool mw_all = dense_v[2] <= SEGSORT_CAP;            // (small thresholds: every query is looked at, not only the over-size list)
-    static const bool no_islands = ab_on("no_islands");       // A/B: one wave per query whatever the call's shape
-    const bool islands = nq <= CHAIN_ISL_NQ && na > 0 && !no_islands;
-    const bool mw = !chain_push && !chain_lazy && !chain_no_mw && Rr >= 2 && na > 0 && !islands && dense_v[2] > 0 && (mw_all || n_over > 0);
-    co.dense_n = dense_v[0]; co.dense_span = dense_v[1]; co.mw_n = mw ? dense_v[2] : 0;
-#define CHAIN_LAUNCH(RR, SK) do { if (chain_push) hipLaunchKernelGGL((k_chain<RR, SK, 0>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, 0); \
-                                  else if (chain_lazy) hipLaunchKernelGGL((k_chain<RR, SK, 1>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, 0); \
-                                  else hipLaunchKernelGGL((k_chain<RR, SK, 2>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, mw ? 1 : 0); } while (0)
-#define CHAIN_MW(RR, SK) hipLaunchKernelGGL((k_chain_mw<RR, SK>), dim3(mw_all ? nq : n_over), dim3(64 * RR), 0, ctx->side[0], d_skeys, d_qaoff, mw_all ? nq : n_over, mw_all ? (const int32_t*)nullptr : (const int32_t*)d_overlist, co, d_f, d_p)
-    const bool skip = co.chain_skip_q8 != 0;
-    if (islands) {
-        // few queries: chain island by island (kernels.hip.h: ISLANDS) -- same f and p, thousands of waves instead of nq
-        int32_t *d_head, *d_rank, *d_ioff, *d_ipd;
-        TRY(ctx_buf_t(ctx, "isl_head", (size_t)na + 1, &d_head));
-        TRY(ctx_buf_t(ctx, "isl_rank", (size_t)na + 1, &d_rank));
-        TRY(ctx_buf_t(ctx, "isl_off", (size_t)na + 2, &d_ioff));
-        TRY(ctx_buf_t(ctx, "isl_pd", (size_t)na + 1, &d_ipd));
-        HIPCHK(hipMemsetAsync(d_head + na, 0, 4, st));
-        hipLaunchKernelGGL(k_isl_heads, dim3(nq), dim3(256), 0, st, d_skeys, d_qaoff, nq, (uint32_t)co.max_gap, d_head);
-        HIPCHK(hipGetLastError());
-        TRY((dev_exclusive_scan<int32_t, int32_t>(ctx, d_head, d_rank, (size_t)na + 1)));
-        hipLaunchKernelGGL(k_isl_fill, dim3(nq), dim3(256), 0, st, d_qaoff, nq, d_head, d_rank, (int32_t)na, d_ioff, d_ipd);
-        const unsigned grid = (unsigned)std::min<int64_t>((int64_t)na, 256 * 32);
-#define CHAIN_ISL(RR, SK) do { if (chain_push) hipLaunchKernelGGL((k_chain_isl<RR, SK, 0>), dim3(grid), dim3(64), 0, st, d_skeys, d_ioff, d_ipd, d_rank + na, co, d_f, d_p); \
-                               else if (chain_lazy) hipLaunchKernelGGL((k_chain_isl<RR, SK, 1>), dim3(grid), dim3(64), 0, st, d_skeys, d_ioff, d_ipd, d_rank + na, co, d_f, d_p); \
-                               else hipLaunchKernelGGL((k_chain_isl<RR, SK, 2>), dim3(grid), dim3(64), 0, st, d_skeys, d_ioff, d_ipd, d_rank + na, co, d_f, d_p); } while (0)
-        if (Rr == 1) { if (skip) CHAIN_ISL(1, true); else CHAIN_ISL(1, false); }
-        else if (Rr == 2) { if (skip) CHAIN_ISL(2, true); else CHAIN_ISL(2, false); }
-        else { if (skip) CHAIN_ISL(4, true); else CHAIN_ISL(4, false); }
-#undef CHAIN_ISL
-    }
-    else {
-        if (mw) {
-            // the long dense runs beside the others: forked here, joined behind k_chain
-            HIPCHK(hipEventRecord(ctx->ev_side[0], st));
-            HIPCHK(hipStreamWaitEvent(ctx->side[0], ctx->ev_side[0], 0));
-            if (Rr == 2) { if (skip) CHAIN_MW(2, true); else CHAIN_MW(2, false); }
-            else { if (skip) CHAIN_MW(4, true); else CHAIN_MW(4, false); }
-            HIPCHK(hipEventRecord(ctx->ev_side[0], ctx->side[0]));
-        }
-        if (Rr == 1) { if (skip) CHAIN_LAUNCH(1, true); else CHAIN_LAUNCH(1, false); }
-        else if (Rr == 2) { if (skip) CHAIN_LAUNCH(2, true); else CHAIN_LAUNCH(2, false); }
-        else { if (skip) CHAIN_LAUNCH(4, true); else CHAIN_LAUNCH(4, false); }
-        if (mw) HIPCHK(hipStreamWaitEvent(st, ctx->ev_side[0], 0));
-    }
-#undef CHAIN_LAUNCH
-#undef CHAIN_MW
+    TRY(chain_dispatch(ctx, st, mo, d_skeys, d_qaoff, nq, na, n_over, d_overlist, d_qorder, d_f, d_p));
     HIPCHK(hipGetLastError());
     t_ch.stop();
 
@@ -1940,8 +1976,13 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
         TRY(ctx_buf_t(ctx, "bt_chaoff", (size_t)na + 1, &d_chaoff));
         HIPCHK(hipMemsetAsync(d_owner, 0xff, ((size_t)na + 1) * 4, st));
         hipLaunchKernelGGL(k_bt_rank, dim3(nq), dim3(256), 0, st, d_qaoff, d_pk2, d_npk, d_owner);
-        hipLaunchKernelGGL(k_bt_owner, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, mo->chain_lookback, d_owner, d_qorder);
-        hipLaunchKernelGGL(k_bt_depth, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, d_owner, d_depth, d_chtop, d_qorder);
+        if (mo->flags & TELR_MF_CHAIN_SKIP) {      // links up to CHAIN_SCAN_H anchors back: the rings of BT_RING_SCAN entries
+            hipLaunchKernelGGL(k_bt_owner<BT_RING_SCAN>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, (int32_t)CHAIN_SCAN_H, d_owner, d_qorder);
+            hipLaunchKernelGGL(k_bt_depth<BT_RING_SCAN>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, d_owner, d_depth, d_chtop, d_qorder);
+        } else {
+            hipLaunchKernelGGL(k_bt_owner<BT_RING>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, mo->chain_lookback, d_owner, d_qorder);
+            hipLaunchKernelGGL(k_bt_depth<BT_RING>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, d_owner, d_depth, d_chtop, d_qorder);
+        }
         hipLaunchKernelGGL(k_bt_emit, dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, d_f, d_p, d_pk2, d_npk, d_choff, mo->min_chain_score, mo->min_cnt,
                            d_owner, d_depth, d_chtop, d_chaoff, d_rec, d_nch, d_qorder);
         hipLaunchKernelGGL(k_bt_scatter, dim3(nq), dim3(256), 0, st, d_skeys, d_qaoff, d_owner, d_depth, d_chaoff, d_canch, d_qorder);
@@ -2584,6 +2625,46 @@ extern "C" int telr_debug_dp_limits(const telr_map_opt *mo, int32_t *out)
     if (!mo || !out) return TELR_E_ARG;
     out[0] = pk_steps_limit(mo); out[1] = pk_wide_limit(mo); out[2] = pk_wide_maxd(mo); out[3] = pk_ext_limit(mo);
     out[4] = pk_ext_maxd(mo); out[5] = tb4_mask(mo); out[6] = tb4_steps(mo); out[7] = tag8_steps(mo);
+    return TELR_OK;
+}
+// The chaining stage of telr_map (chain_dispatch) on a caller's anchor lists (test tap: the scan's edges without seeding).
+// keys: q_aoff[nq] anchors in the engine's 64-bit layout (strand << 63 | global reference position << 32 | query position << 8 |
+// span), query q's list at [q_aoff[q], q_aoff[q + 1]) in ascending order.  Out: f and p of every anchor (p relative to the query's
+// first anchor, -1 for none), as telr_map computes them for `mo`.
+extern "C" int telr_debug_chain(telr_ctx *ctx, int32_t nq, const uint64_t *keys, const int32_t *q_aoff, const telr_map_opt *mo, int32_t *f, int32_t *p)
+{
+    (void)hipGetLastError();
+    if (!ctx || !mo || nq < 0 || nq > (1 << 24) || (nq > 0 && !q_aoff)) return TELR_E_ARG;
+    TRY(check_map_opt(ctx, mo));
+    if (nq == 0) return TELR_OK;
+    if (q_aoff[0] != 0) { ctx->err = "telr_debug_chain: q_aoff[0] must be 0"; return TELR_E_ARG; }
+    int32_t n_over = 0;
+    std::vector<int32_t> over;
+    for (int q = 0; q < nq; ++q) {
+        const int32_t a0 = q_aoff[q], a1 = q_aoff[q + 1];
+        if (a1 < a0 || a1 > (1 << 30)) { ctx->err = "telr_debug_chain: q_aoff must ascend (at most 2^30 anchors)"; return TELR_E_ARG; }
+        for (int32_t i = a0 + 1; i < a1; ++i)
+            if (keys[i] < keys[i - 1]) { ctx->err = "telr_debug_chain: the anchors of query " + std::to_string(q) + " are not sorted"; return TELR_E_ARG; }
+        if (a1 - a0 > SEGSORT_CAP) { over.push_back(q); ++n_over; }
+    }
+    const int32_t na = q_aoff[nq];
+    if (na > 0 && (!keys || !f || !p)) return TELR_E_ARG;
+    if (na == 0) return TELR_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    uint64_t *d_keys; int32_t *d_qaoff, *d_over, *d_f, *d_p;
+    TRY(ctx_buf_t(ctx, "dbg_ch_keys", (size_t)na, &d_keys));
+    TRY(ctx_buf_t(ctx, "dbg_ch_qaoff", (size_t)nq + 1, &d_qaoff));
+    TRY(ctx_buf_t(ctx, "dbg_ch_over", (size_t)n_over + 1, &d_over));
+    TRY(ctx_buf_t(ctx, "dbg_ch_f", (size_t)na, &d_f));
+    TRY(ctx_buf_t(ctx, "dbg_ch_p", (size_t)na, &d_p));
+    HIPCHK(hipMemcpyAsync(d_keys, keys, (size_t)na * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_qaoff, q_aoff, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, st));
+    if (n_over) HIPCHK(hipMemcpyAsync(d_over, over.data(), (size_t)n_over * 4, hipMemcpyHostToDevice, st));
+    TRY(chain_dispatch(ctx, st, mo, d_keys, d_qaoff, nq, na, n_over, d_over, nullptr, d_f, d_p));
+    HIPCHK(hipMemcpyAsync(f, d_f, (size_t)na * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(p, d_p, (size_t)na * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return TELR_OK;
 }
 // One DP pass over a caller's list of problems (test tap: every class of dp_pass against the oracle, problem by problem).

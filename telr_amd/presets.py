@@ -8,7 +8,7 @@ the same numbers (tests/test_abi.py keeps them in lock-step).
 """
 import threading
 
-from ._abi import IdxOpt, MapOpt, MF_CIGAR
+from ._abi import IdxOpt, MapOpt, MF_CIGAR, MF_CHAIN_SKIP
 
 
 def _gap_q8(k, scale=0.8):
@@ -40,7 +40,9 @@ class override:
         return False
 
 
-def preset(name):
+def preset(name, chain_skip=False):
+    """-> (IdxOpt, MapOpt) of a preset.  chain_skip: minimap2's order-dependent chaining scan (MF_CHAIN_SKIP: look-back 5,000,
+    stop after 25 predecessors already on a chain through the anchor) instead of the spec's fixed look-back; off by default."""
     io = IdxOpt(k=15, w=10, is_hpc=0, bucket_bits=0)
     mo = MapOpt(
         mid_occ_frac=2e-4, min_mid_occ=10, max_mid_occ=1000000,
@@ -113,4 +115,6 @@ def preset(name):
     mo.chain_gap_q8 = _gap_q8(io.k)
     for f, v in _OVERRIDES.items():          # (one reference read: see override)
         setattr(mo, f, v)
+    if chain_skip:
+        mo.flags |= MF_CHAIN_SKIP
     return io, mo
