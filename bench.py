@@ -22,11 +22,17 @@ replicated (built by every rank), no collective on the stage-1 data path; the lo
 travel to the owner in one all-to-all and the per-locus table is merged by ONE all-gather (RCCL).  `--scaling weak`:
 every rank maps its own 30x read set.
 
-Next to `value`, `roofline` and `cpu_baseline` the line carries: `stage1_to_sorted_bam` (reads resident -> telr_map -> coordinate-
-sorted BAM + .bai built on the device, the reference's real stage-1 hand-off; at N > 1 also `job_bam`: the ONE file of the job,
-written by rank 0 from the gathered records), `stage1_from_files` (--files-leg: FASTA files -> telr_alignment.alignment()),
-`value_streaming_incl_h2d`, `te_loci` (+ `polish_pileup`), and at N = 1 `expected_strong_scaling` (rank 0's shard of a 2 / 4 / 8-rank
-run mapped alone on this GPU).
+A plain run does what `value` needs and nothing else: it generates the data, builds the index, uploads the reads, runs the
+set-up, warm-up and timed steps, writes --dump-outputs and prints the line.  Besides the headline keys the line carries what the
+timed steps measured along the way (`roofline` of k_dp_pk, `stage_ms_per_step`, `dp_classes`, `counters`, ...).
+
+`--full` adds every other leg, after the timed steps: `value_incl_h2d` (a second pack + upload of the reads, before the timed steps),
+`cpu_baseline` (the CPU oracle on a read sample, with a record-by-record parity check), `value_reference_default_aligner`,
+`stage1_to_sorted_bam` (reads resident -> telr_map -> coordinate-sorted BAM + .bai built on the device, the reference's real
+stage-1 hand-off; at N > 1 also `job_bam`: the ONE file of the job, written by rank 0 from the gathered records),
+`stage1_from_files` (--files-leg: FASTA files -> telr_alignment.alignment()), `value_streaming_incl_h2d`, `te_loci` (+
+`polish_pileup`), `reference_cpu_path`, and at N = 1 `expected_strong_scaling` (rank 0's shard of a 2 / 4 / 8-rank run mapped alone
+on this GPU).  The `--no-*` options switch single legs of a --full run off.
 
 Prints ONE JSON line on rank 0.
 """
@@ -60,7 +66,7 @@ CONFIGS = {
 }
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
@@ -103,9 +109,19 @@ def parse():
     ap.add_argument("--no-bam-prepare", action="store_true", help="do not create / allocate / map the BAM file in the background while the reads are mapped")
     ap.add_argument("--dry-launch", action="store_true", help="launcher smoke test: ranks initialise torch.distributed, report and exit (no GPU work)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step returned (rank 0: the records and CIGAR words of a fixed, seeded sample of its reads) as DIR/<name>.npy, float64, at most 64 MB")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every leg besides the headline (CPU baseline and parity, default aligner, h2d and streaming rates, strong-scaling shards, BAM, TE loci, upstream tools); without it a run is set-up, warm-up, timed steps and the line")
+    a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:
+        extra = [o for o, on in (("--files-leg", a.files_leg), ("--flank-parity", a.flank_parity), ("--poa-parity", a.poa_parity > 0),
+                                 ("--bam-sha", a.bam_sha), ("--force-exchange", a.force_exchange)) if on]
+        if extra:
+            ap.error("%s shape legs of a --full run; add --full" % ", ".join(extra))
+        # the headline alone: every leg that has a switch of its own is off
+        a.no_cpu_baseline = a.no_default_aligner_leg = a.no_upstream_check = a.no_shard_leg = a.no_stream_leg = a.no_polish_leg = True
+        a.bam_leg = "none"
+        a.loci = 0
     return a
 
 
@@ -598,10 +614,11 @@ def main():
     t0 = time.time()
     qs = eng.seqset(D["reads"])           # 2-bit packing on the host + H2D of this rank's whole read set
     t_upload_first = time.time() - t0     # includes pinning the context's staging buffers (once per context)
-    t0 = time.time()
-    qs2 = eng.seqset(D["reads"])          # the steady state of a run that streams read batches: staging already pinned
-    t_upload = time.time() - t0
-    qs2.free()
+    if a.full:                            # (value_incl_h2d)
+        t0 = time.time()
+        qs2 = eng.seqset(D["reads"])      # the steady state of a run that streams read batches: staging already pinned
+        t_upload = time.time() - t0
+        qs2.free()
     n_bases = qs.bases()
 
     # Steps are streamed the way a stage-1 run over many read batches would be: telr_map returns when the alignment
@@ -683,14 +700,19 @@ def main():
     stage_tot, cls_tot, ctr_tot, launches, retries = T0["stage_tot"], T0["cls_tot"], T0["ctr_tot"], T0["launches"], T0["retries"]
     dt, dt_local, aligned, al, value = T0["dt"], T0["dt_local"], T0["aligned"], T0["al"], T0["value"]
     per_rank_ms = [dt_local / a.steps * 1e3]
+    t_upload_max = value_h2d = None
     if dist is not None:
         dev = device if device is not None else "cpu"
-        t = torch.tensor([t_upload], dtype=torch.float64, device=dev); dist.all_reduce(t, op=dist.ReduceOp.MAX); t_upload_max = float(t[0])
+        if a.full:
+            t = torch.tensor([t_upload], dtype=torch.float64, device=dev); dist.all_reduce(t, op=dist.ReduceOp.MAX); t_upload_max = float(t[0])
         s = torch.tensor([n_bases], dtype=torch.float64, device=dev); dist.all_reduce(s, op=dist.ReduceOp.SUM); job_bases = float(s[0])
         pr = torch.zeros(world, dtype=torch.float64, device=dev); pr[rank] = dt_local / a.steps * 1e3; dist.all_reduce(pr); per_rank_ms = [float(x) for x in pr.cpu()]
     else:
-        t_upload_max, job_bases = t_upload, float(n_bases)
-    value_h2d = aligned / (dt + a.steps * t_upload_max) / 1e9
+        job_bases = float(n_bases)
+        if a.full:
+            t_upload_max = t_upload
+    if a.full:
+        value_h2d = aligned / (dt + a.steps * t_upload_max) / 1e9
 
     # ---- the reference's DEFAULT stage-1 aligner on the same reads (TELR_input.py:176-177 `--aligner nglmr`, TELR_alignment.py:28-51):
     # the same measurement -- same read set resident, same warm-up, same a.steps timed steps, same synchronisation -- with the
@@ -1199,8 +1221,7 @@ def main():
     out = {
         "metric": "gbp_aligned_per_s", "value": value, "unit": "Gbp/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None,
-        "dtype": "int16", "data": "synthetic",
-        "value_incl_h2d": value_h2d, "value_streaming_incl_h2d": value_stream, "h2d_pack_upload_s": t_upload_max, "h2d_pack_upload_first_call_s": t_upload_first,
+        "dtype": "int16", "data": "synthetic", "full": a.full, "h2d_pack_upload_first_call_s": t_upload_first,
         "config": {"workload": "BASELINE %s: %s, preset %s, stage-1 reads->reference" % (cfg["label"], D["text"], pname + (" + experiment " + a.map_opt if a.map_opt else "")),
                    "reads_this_rank": int(len(D["reads"][2])), "read_bases_this_rank": n_bases, "read_bases_job": job_bases,
                    "parallelism": ("one fixed read set dealt to %d ranks in blocks by cumulative bases" % world if a.scaling == "strong" else "every rank maps its own read set (x%d)" % world)
@@ -1227,6 +1248,8 @@ def main():
         "frac_reads_mapped": frac_mapped, "index_build_s": t_index, "datagen_s": t_gen, "device": eng.device_name(),
         "counters": ctr, "dp_retries": retries // a.steps,
     }
+    if a.full:
+        out.update(value_incl_h2d=value_h2d, value_streaming_incl_h2d=value_stream, h2d_pack_upload_s=t_upload_max)
     if dump_out is not None:
         out["dump_outputs"] = dump_out
     if bam_out is not None:

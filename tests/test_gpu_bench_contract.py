@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline(tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "c1", "--genome-len", "3000000",
            "--reads", "1500", "--read-bases", "60000000", "--insertions", "30", "--cpu-sample-reads", "40", "--default-aligner-parity-reads", "40",
-           "--dump-outputs", str(tmp_path / "dump")]
+           "--dump-outputs", str(tmp_path / "dump"), "--full"]
     p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
@@ -62,12 +62,42 @@ def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline(tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_dumps_what_a_full_run_dumps(tmp_path):
+    """Without --full the line carries the headline and what the timed steps measured, no other leg; its dump equals the one a --full
+    run of the same command writes"""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "c1", "--genome-len", "3000000",
+            "--reads", "1500", "--read-bases", "60000000", "--insertions", "30"]
+    out = []
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-default-aligner-leg", "--no-upstream-check", "--loci", "0"])):
+        p = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / name)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1, lines[:5]
+        out.append(json.loads(lines[0]))
+    plain, full = out
+    assert plain["full"] is False and full["full"] is True
+    assert plain["metric"] == "gbp_aligned_per_s" and plain["unit"] == "Gbp/s" and plain["higher_is_better"] is True and plain["dtype"] == "int16"
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["value"] > 0.05 and plain["ms_per_step"] > 0
+    whole = plain["config"]["read_bases_this_rank"] / (plain["ms_per_step"] * 1e-3) / 1e9
+    assert 0.8 * whole <= plain["value"] <= 1.001 * whole
+    for k in ("cpu_baseline", "value_reference_default_aligner", "reference_cpu_path", "stage1_to_sorted_bam", "te_loci", "te_loci_per_s",
+              "expected_strong_scaling", "value_incl_h2d", "value_streaming_incl_h2d", "h2d_pack_upload_s"):
+        assert k not in plain, k
+    for k in ("stage1_to_sorted_bam", "value_incl_h2d", "value_streaming_incl_h2d"):           # (the shard leg needs 4,096 reads)
+        assert k in full, k
+    assert plain["roofline"]["kernel"] == "k_dp_pk" and plain["stage_ms_per_step"] and plain["counters"]["records"] > 0
+    assert plain["dump_outputs"]["files"] == full["dump_outputs"]["files"] and plain["dump_outputs"]["records"] > 0
+    for f in plain["dump_outputs"]["files"]:
+        assert np.array_equal(np.load(str(tmp_path / "plain" / f)), np.load(str(tmp_path / "full" / f))), f
+
+
+@pytest.mark.gpu
 def test_two_ranks_merge_to_the_one_rank_locus_table():
     """The N > 1 code path on the real engine (two ranks on device 0, gloo): reads dealt to the ranks, every rank maps its
     share, the window reads of a locus travel to the locus' owner (all-to-all), the per-locus rows are merged by ONE
     all-gather -- and the merged table is the table one rank computes alone."""
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--config", "c1", "--genome-len", "3000000", "--reads", "1500",
-            "--read-bases", "60000000", "--insertions", "30", "--no-cpu-baseline", "--no-stream-leg", "--bam-sha"]
+            "--read-bases", "60000000", "--insertions", "30", "--no-cpu-baseline", "--no-stream-leg", "--bam-sha", "--full"]
     out = []
     for extra in (["--gpus", "1"], ["--gpus", "2", "--one-gpu", "--backend", "gloo"]):
         env = dict(os.environ)
@@ -116,7 +146,7 @@ def test_collectives_of_the_n_rank_path_run_through_rccl_on_device_tensors():
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     args = ["--gpus", "1", "--steps", "1", "--warmup", "0", "--config", "c1", "--genome-len", "3000000", "--reads", "1500", "--read-bases", "60000000",
-            "--insertions", "30", "--no-cpu-baseline", "--no-stream-leg", "--bam-sha"]
+            "--insertions", "30", "--no-cpu-baseline", "--no-stream-leg", "--bam-sha", "--full"]
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     plain = json.loads([l for l in p.stdout.decode().splitlines() if l.strip()][-1])

@@ -5,7 +5,7 @@ set -u
 cfg=$1; shift; shift
 cd "$GRAFT_REPO_ROOT"
 cache=$(mktemp -d /tmp/telr_cache.XXXXXX)
-B="python3 bench.py --config $cfg --data-cache $cache --no-cpu-baseline --no-upstream-check --no-stream-leg --no-shard-leg --bam-leg none --no-default-aligner-leg --no-polish-leg --steps 2 --warmup 1"
+B="python3 bench.py --config $cfg --data-cache $cache --no-cpu-baseline --no-upstream-check --no-stream-leg --no-shard-leg --bam-leg none --no-default-aligner-leg --no-polish-leg --steps 2 --warmup 1 --full"
 $B > /dev/null 2>&1
 for rep in 1 2 3; do
   for name in default "$@"; do

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/prof; mkdir -p $out
 cache=$(mktemp -d /tmp/telr_cache.XXXXXX)
 X="--no-default-aligner-leg --no-upstream-check"
-timeout 1200 python3 bench.py --config $cfg --data-cache $cache --bam-leg none --loci 0 --no-stream-leg --no-shard-leg --cpu-sample-reads 12000 $X "$@" > $out/${tag}_bench.json 2>$out/${tag}_bench.err || { echo "plain bench run failed"; tail -5 $out/${tag}_bench.err; exit 1; }
+timeout 1200 python3 bench.py --config $cfg --data-cache $cache --bam-leg none --loci 0 --no-stream-leg --no-shard-leg --cpu-sample-reads 12000 --full $X "$@" > $out/${tag}_bench.json 2>$out/${tag}_bench.err || { echo "plain bench run failed"; tail -5 $out/${tag}_bench.err; exit 1; }
 B="python3 bench.py --config $cfg --data-cache $cache --require-cache --no-cpu-baseline --loci 0 --no-stream-leg --no-shard-leg --bam-leg none $X"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/kt -- $B --steps 3 --warmup 1 "$@" > $out/${tag}_bench_under_rocprof.json 2>/dev/null
 python3 tools/prof_summary.py gpurun_out/kt > $out/${tag}_kernel_trace_summary.txt

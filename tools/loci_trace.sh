@@ -6,7 +6,7 @@ tag=${1:-loci}; cfg=${2:-c2}
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/prof; mkdir -p $out
 cache=$(mktemp -d /tmp/telr_cache.XXXXXX)
-A="--config $cfg --data-cache $cache --bam-leg none --no-stream-leg --no-default-aligner-leg --no-shard-leg --no-cpu-baseline --no-upstream-check --steps 1 --warmup 0"
+A="--config $cfg --data-cache $cache --bam-leg none --no-stream-leg --no-default-aligner-leg --no-shard-leg --no-cpu-baseline --no-upstream-check --steps 1 --warmup 0 --full"
 TELR_TRACE=host timeout 900 python3 bench.py $A > $out/${tag}_bench_plain.json 2>$out/${tag}_bench_plain.err || { echo "plain run failed"; tail -5 $out/${tag}_bench_plain.err; exit 1; }
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/kt -- python3 bench.py $A --require-cache > $out/${tag}_bench_under_rocprof.json 2>/dev/null
 python3 tools/prof_summary.py gpurun_out/kt > $out/${tag}_kernel_trace_summary.txt
