@@ -1522,7 +1522,8 @@ static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *
         TRY(ctx_buf_t(ctx, "bam_rec0", nblk, &d_rec0)); TRY(ctx_buf_t(ctx, "bam_T", 1, &d_T)); TRY(ctx_buf_t(ctx, "bam_hist", (size_t)DEFL_NCLS * 288, &d_hist));
         TRY(ctx_buf_t(ctx, "bam_csize", nblk, &d_csize)); TRY(ctx_buf_t(ctx, "bam_cs64", nblk + 1, &d_cs64)); TRY(ctx_buf_t(ctx, "bam_coff", nblk + 1, &d_coff));
         TRY(ctx_buf_t(ctx, "bam_slots", nblk * (size_t)DEFL_SLOT, &d_slots));
-        hipLaunchKernelGGL(k_blk_first_rec, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, d_ust, (int32_t)nrec, (uint64_t)head.size(), (int32_t)nblk, d_rec0);
+        // (a slice without header, records and unmapped reads is an empty stream: no block, nothing to launch)
+        if (nblk) hipLaunchKernelGGL(k_blk_first_rec, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, d_ust, (int32_t)nrec, (uint64_t)head.size(), (int32_t)nblk, d_rec0);
         static DeflTabs T;                   // 8 KB: not on the stack of a ctypes caller's thread
         memset(&T, 0, sizeof(T)); defl_len_syms(T.len_sym);
         HIPCHK(hipMemcpyAsync(d_T, &T, sizeof(T), hipMemcpyHostToDevice, st));
@@ -1535,7 +1536,7 @@ static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *
         }
         const int32_t stride = (int32_t)std::max<size_t>(1, nb_first / 4096);
         const unsigned nsamp = (unsigned)((nb_first + stride - 1) / stride);
-        hipLaunchKernelGGL(k_bam_hist, dim3(nsamp), dim3(DEFL_THREADS), 0, st, d_u, utotal, (uint64_t)head.size(), d_ust, (int32_t)nrec, d_rec0, stride, d_T, d_hist);
+        if (nsamp) hipLaunchKernelGGL(k_bam_hist, dim3(nsamp), dim3(DEFL_THREADS), 0, st, d_u, utotal, (uint64_t)head.size(), d_ust, (int32_t)nrec, d_rec0, stride, d_T, d_hist);
         HIPCHK(hipGetLastError());
         std::vector<uint32_t> h_hist((size_t)DEFL_NCLS * 288);
         HIPCHK(hipMemcpyAsync(h_hist.data(), d_hist, h_hist.size() * 4, hipMemcpyDeviceToHost, st));
