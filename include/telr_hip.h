@@ -130,6 +130,21 @@ typedef struct telr_map_opt {
                                     through the anchor failed to improve it (the oracle's 0x1000: same f, p, chains and records).
                                     Overrides chain_lookback (which must still be valid).  Applies to every preset and to the
                                     per-target and per-query-target calls alike.  Off: the fixed look-back of the spec. */
+#define TELR_MF_SEED_RESCUE 0x2000 /* minimap2's high-occurrence seed rescue (seed.c: mm_seed_select, occ_dist 500, max_max_occ 4095): in a
+                                    maximal run of query minimizers with more than mid_occ occurrences (an absent minimizer ends a run
+                                    like a rare one), bounded by the query positions ps and pe of the minimizers around it (0 and the
+                                    query length at the ends), the (int)((pe - ps) / 500.0 + .499) least frequent ones with fewer than
+                                    4,095 occurrences are seeded after all, each with all its occurrences, the earlier one on a tie
+                                    (the oracle's 0x2000: same anchors, chains and records).  In the voting presets their hits vote
+                                    like any other.  Applies to queries mapped against the whole index with the pooled cut-off; on
+                                    a TELR_MF_PER_TARGET call and for a query with a target of its own (qtarget[i] >= 0) it is
+                                    accepted and changes nothing.  Record fields such as n_ambi and the counters' meaning are unaffected. */
+#define TELR_MF_MM2_MAPQ   0x20000 /* minimap2's MAPQ (map.c: mm_set_mapq) WITHOUT the second-best DP score (dp_max2 is not computed):
+                                    (int)(identity * min(pen_s1, pen_cm) * 40 * (1 - subsc / score) * ln(dp_score / a))
+                                    - (int)(4.343 * ln(n_sub + 1) + .499), clamped to 0..60, with identity = mlen / blen,
+                                    pen_s1 = min(1, score / 100), pen_cm = min(1, cnt / 10), subsc floored at min_chain_score
+                                    (the oracle's 0x20000: same mapq).  Every other field is what it is without it.  Applies to
+                                    every call.  Off: the formula of Li 2018. */
 
 /* ---- one alignment (PAF line / SAM record worth of numbers), 88 bytes ---- */
 typedef struct telr_aln {

@@ -46,6 +46,8 @@ TELR_OK, TELR_E_NODEVICE, TELR_E_HIP, TELR_E_ARG, TELR_E_RANGE, TELR_E_NOMEM, TE
 F_PRIMARY, F_SECONDARY, F_SUPPL, F_REV = 1, 2, 4, 8
 MF_CIGAR, MF_PER_TARGET, MF_FAITHFUL, MF_KEEP_CIGARS = 1, 2, 4, 8
 MF_CHAIN_SKIP = 0x1000          # minimap2's chaining scan (max_chain_iter 5000, max_chain_skip 25); overrides chain_lookback
+MF_SEED_RESCUE = 0x2000         # minimap2's high-occurrence seed rescue (mm_seed_select: one seed per 500 bases of a skipped stretch)
+MF_MM2_MAPQ = 0x20000           # minimap2's MAPQ (mm_set_mapq without the second-best DP score) instead of the Li-2018 formula
 N_STAGES = 16
 N_DPCLS = 25
 

@@ -11,6 +11,9 @@ them with the HIP engine, writing SAM / PAF to stdout exactly where the referenc
 
 minimap2's --max-chain-skip 25 and/or --max-chain-iter 5000 (its defaults, spelled out) select the engine's minimap2 chaining scan
 (TELR_MF_CHAIN_SKIP) instead of its fixed look-back; other values are refused (only 25 / 5000 is held to the oracle).
+minimap2's -e INT (the distance between rescued seeds, default 500) as `-e 500` / `-e500` selects minimap2's high-occurrence seed rescue
+(TELR_MF_SEED_RESCUE); other values are refused.  minimap2 has no option that names its MAPQ formula, so the shim has none either:
+TELR_MF_MM2_MAPQ is reached through presets.preset(..., mm2_mapq=True) or the option block.
 
 usage:  python -m telr_amd.cli_mm2 minimap2 <args...>   |   python -m telr_amd.cli_mm2 ngmlr <args...>
 Exit code 0 and empty stdout when nothing maps (the reference treats an empty PAF as "locus not passed").
@@ -18,10 +21,11 @@ Exit code 0 and empty stdout when nothing maps (the reference treats an empty PA
 import sys
 
 _CHAIN_SCAN = {"--max-chain-skip": 25, "--max-chain-iter": 5000}        # the only values the engine's chaining scan runs
+_RESCUE_DIST = 500                                                      # the only -e the engine's seed rescue runs
 
 
 def parse_argv(argv):
-    """-> dict(tool, preset, sam, cigar, md, cs, softclip, secondary, best_n, bw, target, query, rg, threads, chain_skip)"""
+    """-> dict(tool, preset, sam, cigar, md, cs, softclip, secondary, best_n, bw, target, query, rg, threads, chain_skip), plus seed_rescue=True only when -e 500 was given (the dict of the other shapes is unchanged)"""
     if not argv:
         raise SystemExit(__doc__)
     tool = argv[0].split("/")[-1]
@@ -99,6 +103,13 @@ def parse_argv(argv):
                     raise SystemExit("%s: only %d is supported (minimap2's default, the engine's chaining scan); got %r"
                                      % (name, _CHAIN_SCAN[name], v))
                 o["chain_skip"] = True
+            elif f.startswith("-e") and not f.startswith("--"):
+                v = f[2:] if len(f) > 2 else (a[i + 1] if i + 1 < len(a) else None)
+                i += 1 if len(f) > 2 else 2
+                if v is None or v.strip() != str(_RESCUE_DIST):
+                    raise SystemExit("%s: only %d is supported (minimap2's default, the engine's seed rescue); got %r"
+                                     % ("-e", _RESCUE_DIST, v))
+                o["seed_rescue"] = True
             elif f.startswith("-"):
                 raise SystemExit("unsupported minimap2 option %r" % f)
             else:
@@ -119,7 +130,7 @@ def run(argv, out_path="/dev/stdout", engine=None):
     from .aligner import Engine
     from .presets import preset
     from .fasta import read_fasta
-    io, mo = preset(o["preset"], chain_skip=o["chain_skip"])
+    io, mo = preset(o["preset"], chain_skip=o["chain_skip"], seed_rescue=o.get("seed_rescue", False))
     if not o["secondary"]:
         mo.secondary = 0
     if o["best_n"] is not None:

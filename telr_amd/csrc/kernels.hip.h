@@ -695,6 +695,7 @@ struct SeedArgs {
     const int32_t *tile_off, *q_tile0;
     // MODE 1 inside the LDS sort (segsort.hip.h: SeedProducer): anchor w of the query goes to lds_keys[w] instead of keys[q_aoff[q] + w]
     uint64_t *lds_keys;
+    int32_t rescue;              // TELR_MF_SEED_RESCUE on a call without TELR_MF_PER_TARGET: d_seed_rescue marks minimizers above the cut-off (queries with tf < 0)
 };
 
 __device__ __forceinline__ void d_put_key(const SeedArgs &A, int64_t w, uint64_t key)
@@ -715,6 +716,89 @@ __device__ __forceinline__ uint32_t d_occ_lower(const uint32_t *__restrict__ pos
     while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if ((pos[mid] >> 1) < g) lo = mid + 1; else hi = mid; }
     return lo;
 }
+// ---- high-occurrence seed rescue (TELR_MF_SEED_RESCUE; minimap2 seed.c: mm_seed_select, the oracle's 0x2000) -------------
+// A stretch is a maximal run of a query's minimizers with more than mid_occ occurrences (an absent minimizer, count 0, ends one
+// like a rare one).  With ps / pe the query positions of the minimizers around it (0 / qlen at the query's ends), the
+// k = (int)((pe - ps) / 500. + .499) least frequent minimizers of the stretch that have fewer than SEED_RESCUE_MAX_OCC occurrences are
+// seeded after all, the earlier one on a tie.
+#define SEED_RESCUE_DIST    500
+#define SEED_RESCUE_MAX_OCC 4095
+#define SEED_RESCUE_LIST    1024      /* threads of the largest block: a round finds at most one stretch start per thread */
+// (pe - ps) / 500. + .499 is never an integer for an integer pe - ps, so the truncation is a floor of exact integers
+// (tests/test_seed_rescue_cpu.py pins the identity over 0 .. 2^24)
+__host__ __device__ __forceinline__ int32_t seed_rescue_k(int32_t pe, int32_t ps)
+{
+    return (int32_t)((1000LL * (pe - ps) + 249500LL) / 500000LL);
+}
+// where minimizer g of query q lives in mz_x / mz_y: g itself, or its slot of the sketch kernel's staging tiles (a query's tiles
+// are consecutive; empty ones repeat their offset, so the last tile that starts at or before g holds it)
+__device__ __forceinline__ int64_t d_mz_slot(const SeedArgs &A, int q, int g)
+{
+    if (!A.tile_off) return g;
+    int lo = A.q_tile0[q], hi = A.q_tile0[q + 1] - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (A.tile_off[mid] <= g) lo = mid; else hi = mid - 1; }
+    return (int64_t)lo * SK_TILE + (g - A.tile_off[lo]);
+}
+__device__ __forceinline__ uint64_t d_wave_min_u64(uint64_t v)
+{
+    for (int o = 32; o >= 1; o >>= 1) {
+        const uint64_t u = (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)v, o) | (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o) << 32;
+        v = u < v ? u : v;
+    }
+    return v;
+}
+// The whole block calls this for query q, minimizers [m0, m1), behind a barrier that makes mz_n (every minimizer's occurrence count,
+// 0 = absent) visible.  OUT: mark[g] = mz_n[g] for every rescued minimizer; nothing else is written.  The caller's next barrier
+// makes the marks visible.  The block finds the stretch starts, nthr minimizers a round, and lists them in LDS; its waves take the
+// listed stretches in turn.  A wave picks the k minimizers by k wave-wide arg-mins over the stretch on the key (count << 32 | index
+// in the stretch): the keys are distinct, so round r takes the smallest key above round r - 1's and never reads a mark.
+__device__ __forceinline__ void d_seed_rescue(const SeedArgs &A, const int q, const int m0, const int m1, int32_t *__restrict__ mark, const int tid, const int nthr)
+{
+    __shared__ int32_t s_start[SEED_RESCUE_LIST];
+    __shared__ int32_t s_nstart;
+    const int32_t *__restrict__ occ = A.mz_n;
+    const int32_t cut = A.mid_occ;
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = nthr >> 6;      // (nthr is a multiple of 64: whole waves)
+    const int qlen = A.qlen[q];
+    for (int gb = m0; gb < m1; gb += nthr) {
+        if (tid == 0) s_nstart = 0;
+        __syncthreads();
+        const int g = gb + tid;
+        if (g < m1 && occ[g] > cut && (g == m0 || occ[g - 1] <= cut)) s_start[atomicAdd(&s_nstart, 1)] = g;
+        __syncthreads();
+        const int ns = s_nstart;
+        for (int si = wv; si < ns; si += nwv) {
+            const int s = s_start[si];
+            // the stretch's end: the first minimizer at or below the cut-off, or m1
+            int e = s + 1;
+            for (;;) {
+                const int j = e + lane;
+                const uint64_t stop = __ballot(j >= m1 || occ[j < m1 ? j : m1 - 1] <= cut);
+                if (stop) { e += __builtin_ctzll(stop); break; }
+                e += 64;
+            }
+            if (e > m1) e = m1;
+            const int32_t ps = s > m0 ? (int32_t)(A.mz_y[d_mz_slot(A, q, s - 1)] >> 1) : 0;
+            const int32_t pe = e < m1 ? (int32_t)(A.mz_y[d_mz_slot(A, q, e)] >> 1) : qlen;
+            const int32_t k = seed_rescue_k(pe, ps);
+            uint64_t last = 0; bool first = true;
+            for (int z = 0; z < k; ++z) {
+                uint64_t best = ~0ULL;
+                for (int j = s + lane; j < e; j += 64) {
+                    const int32_t c = occ[j];
+                    const uint64_t key = (uint64_t)(uint32_t)c << 32 | (uint32_t)(j - s);
+                    if (c < SEED_RESCUE_MAX_OCC && (first || key > last) && key < best) best = key;
+                }
+                best = d_wave_min_u64(best);
+                if (best == ~0ULL) break;          // fewer candidates than k
+                if (lane == 0) mark[s + (int32_t)(uint32_t)best] = (int32_t)(best >> 32);
+                last = best; first = false;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // A query restricted to one target (qtarget >= 0) and the per-target mode stand for the reference's separate runs of the
 // aligner against every contig (TELR_te.py:68-78,119-132,504-506; TELR_assembly.py:199-212): a minimizer's occurrences are
 // counted inside the target and compared with THAT target's cut-off (tmid), so a TE k-mer shared by hundreds of contigs
@@ -796,7 +880,8 @@ __device__ __forceinline__ void d_seed_query(const SeedArgs &A, const int q, con
                 else { a0 = d_occ_lower(A.I.pos, o0, o1, g0); a1 = d_occ_lower(A.I.pos, a0, o1, g1); }
             }
             cnt = (int32_t)(a1 - a0);
-            if (cnt > occ) cnt = 0;
+            // (seed rescue, MODE 1: a minimizer above the cut-off that still has its count was rescued by MODE 0)
+            if (cnt > occ && !(MODE == 1 && A.rescue && tf < 0)) cnt = 0;
         }
         cnt_out = cnt;
         if (MODE == 1 && cnt > 0) {
@@ -818,6 +903,8 @@ __device__ __forceinline__ void d_seed_query(const SeedArgs &A, const int q, con
         // rounds every round ended in a barrier and the block's waves could no longer hide each other's table misses: 8.1 -> 9.9 ms
         // per range): 256 counts a round, wave scan (DPP), the waves' totals through LDS
         __syncthreads();
+        // seed rescue: the rescued minimizers of the stretches above the cut-off get their counts back before the scan counts them
+        if constexpr (MODE == 0) { if (A.rescue && tf < 0) { d_seed_rescue(A, q, m0, m1, A.mz_cnt, tid, nthr); __syncthreads(); } }      // (never instantiated inside the LDS sort: its own LDS list)
         const int wv = tid >> 6, nwv = (nthr + 63) >> 6;
         for (int gb = m0; gb < m1; gb += nthr) {
             const int g = gb + tid;
@@ -880,14 +967,27 @@ __device__ __forceinline__ uint32_t d_vote_slot(uint32_t gp, uint32_t qadj, uint
 // FILTER = false: short k-mers (the ngmlr-* presets' 13-mers: 67 M possible, most of them in a 100-Mb genome) -- the filter
 // bitmap answers "maybe" for nearly every probe and only costs its own scattered line
 template <bool FILTER>
-__global__ void __launch_bounds__(256) k_vote_lookup(IndexView I, const uint64_t *__restrict__ mz_x, int32_t nmz, int32_t mid_occ, int32_t *__restrict__ mz_ent, int32_t *__restrict__ mz_n)
+__global__ void __launch_bounds__(256) k_vote_lookup(IndexView I, const uint64_t *__restrict__ mz_x, int32_t nmz, int32_t mid_occ, int32_t *__restrict__ mz_ent, int32_t *__restrict__ mz_n, int32_t rescue)
 {
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= nmz) return;
     uint32_t off = 0, n = 0;
     if (!d_ht_lookup<FILTER>(I, mz_x[g] >> 8, off, n)) n = 0;
-    if (n > (uint32_t)mid_occ) n = 0;
+    if (n > (uint32_t)mid_occ && !rescue) n = 0;          // (seed rescue: k_vote_rescue applies the cut-off)
     mz_ent[g] = (int32_t)off; mz_n[g] = (int32_t)n;
+}
+// seed rescue of the voting presets, one block per query between k_vote_lookup (which then keeps the counts above the cut-off) and
+// k_vote_qhits: a minimizer above the cut-off keeps its count if d_seed_rescue marks it and loses it otherwise, so everything
+// downstream sees the rescued minimizers as ordinary ones
+__global__ void __launch_bounds__(256) k_vote_rescue(SeedArgs A)
+{
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const int m0 = A.q_mzoff[q], m1 = A.q_mzoff[q + 1];
+    for (int g = m0 + tid; g < m1; g += 256) A.mz_cnt[g] = 0;
+    __syncthreads();
+    d_seed_rescue(A, q, m0, m1, A.mz_cnt, tid, 256);
+    __syncthreads();
+    for (int g = m0 + tid; g < m1; g += 256) if (A.mz_n[g] > A.mid_occ) A.mz_n[g] = A.mz_cnt[g];
 }
 __global__ void __launch_bounds__(64) k_vote_qhits(const int32_t *__restrict__ q_mzoff, const int32_t *__restrict__ mz_n, int32_t nq, int64_t *__restrict__ q_hits)
 {

@@ -993,6 +993,16 @@ static double index_density_bound(const telr_index *ix, int32_t mid_occ)
     return ix->dens_bound;
 }
 
+// ... of a call: with TELR_MF_SEED_RESCUE a query can hold one rescued minimizer per SEED_RESCUE_DIST bases on top of that, each
+// with fewer than SEED_RESCUE_MAX_OCC occurrences (a bound no read set comes near; a range that overflows its anchor budget all
+// the same is halved by map_range, and the density the call measures replaces the bound for the next one)
+static double call_density_bound(const telr_index *ix, int32_t mid_occ, const telr_map_opt *mo)
+{
+    double d = index_density_bound(ix, mid_occ);
+    if ((mo->flags & TELR_MF_SEED_RESCUE) && !(mo->flags & TELR_MF_PER_TARGET)) d += (double)(SEED_RESCUE_MAX_OCC - 1) / SEED_RESCUE_DIST;
+    return d;
+}
+
 static int index_per_target_occ(telr_ctx *ctx, const telr_index *ix, const telr_map_opt *mo, const int32_t **d_tmid)
 {
     const int n = ix->targets->n; const int64_t nmz = ix->n_mz;
@@ -1089,7 +1099,23 @@ static bool sel_less(const Sel &x, const Sel &y) { return x.key != y.key ? x.key
 
 static int32_t mapq_of(const telr_aln &r, const telr_map_opt *mo)
 {
+#pragma clang fp contract(off)      // every float expression here is evaluated operation by operation, as the oracle's are (-ffp-contract=off): no fused multiply-add
     if (!(r.flags & TELR_F_PRIMARY) && !(r.flags & TELR_F_SUPPL)) return 0;
+    if (mo->flags & TELR_MF_MM2_MAPQ) {
+        // mm_set_mapq of minimap2 2.22 without the second-best DP score (dp_max2 is not computed): identity, chain-score and
+        // anchor-count penalties, the sub-optimal chain, and the log of the number of sub-optimal chains
+        float pen_s1 = r.score > 100 ? 1.0f : 0.01f * (float)r.score;
+        float pen_cm = r.cnt > 10 ? 1.0f : 0.1f * (float)r.cnt;
+        if (pen_s1 < pen_cm) pen_cm = pen_s1;
+        float subsc = (float)(r.subsc > mo->min_chain_score ? r.subsc : mo->min_chain_score);
+        float identity = r.blen > 0 ? (float)r.mlen / (float)r.blen : 0.0f;
+        float x = subsc / (float)r.score;
+        int32_t mq = (int32_t)(identity * pen_cm * 40.0f * (1.0f - x) * logf((float)r.dp_score / (float)mo->a));
+        mq -= (int32_t)(4.343f * logf((float)r.n_sub + 1.0f) + .499f);
+        if (mq < 0) mq = 0;
+        if (mq > 60) mq = 60;
+        return mq;
+    }
     float f1 = (float)r.score, f2 = (float)(r.subsc > mo->min_chain_score ? r.subsc : mo->min_chain_score);
     float pen_cm = r.cnt > 10 ? 1.0f : 0.1f * (float)r.cnt;
     float x = f2 / f1; if (x > 1.0f) x = 1.0f;
@@ -1839,6 +1865,8 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
     SeedArgs S; S.I = I; S.mz_x = d_mx; S.mz_y = d_my; S.q_mzoff = d_qmz; S.qlen = qs->d_len + q0; S.qtarget = d_qtarget ? d_qtarget + q0 : nullptr;
     S.mid_occ = mid_occ; S.tmid = occ.d_tmid; S.per_target = (mo->flags & TELR_MF_PER_TARGET) ? 1 : 0; S.n_targets = tg->n; S.mz_cnt = d_mcnt; S.mz_ent = d_ment; S.mz_n = d_mn; S.mz_aoff = nullptr; S.q_cnt = nullptr; S.q_aoff = nullptr; S.lds_keys = nullptr; S.keys = nullptr; S.q_order = d_qorder;
     S.tile_off = mz_staged ? d_toff : nullptr; S.q_tile0 = mz_staged ? d_first : nullptr;
+    // TELR_MF_SEED_RESCUE applies to the calls the pooled cut-off applies to: not to TELR_MF_PER_TARGET, and not to a query with a target of its own
+    S.rescue = (mo->flags & TELR_MF_SEED_RESCUE) && !(mo->flags & TELR_MF_PER_TARGET) ? 1 : 0;
     VoteOpt VO; VO.len = mo->vote_len; VO.shift = mo->vote_bin_shift; VO.vmin = mo->vote_min; VO.frac_q8 = mo->vote_frac_q8;
     VoteArgs VA; memset(&VA, 0, sizeof(VA));
     // the per-query anchor counts: from the seeding kernel (which also leaves every minimizer's offset inside its query), or from the
@@ -1855,8 +1883,9 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
         TRY(ctx_buf_t(ctx, "vote_qhits", (size_t)nq + 2, &d_qhits)); TRY(ctx_buf_t(ctx, "vote_qsoff", (size_t)nq + 2, &d_qsoff));
         if (nmz) {
             static const bool always_filter = ab_on("vote_filter");
-            if (k <= 13 && !always_filter) hipLaunchKernelGGL(k_vote_lookup<false>, dim3((unsigned)((nmz + 255) / 256)), dim3(256), 0, st, I, d_mx, nmz, mid_occ, d_ment, d_mn);
-            else hipLaunchKernelGGL(k_vote_lookup<true>, dim3((unsigned)((nmz + 255) / 256)), dim3(256), 0, st, I, d_mx, nmz, mid_occ, d_ment, d_mn);
+            if (k <= 13 && !always_filter) hipLaunchKernelGGL(k_vote_lookup<false>, dim3((unsigned)((nmz + 255) / 256)), dim3(256), 0, st, I, d_mx, nmz, mid_occ, d_ment, d_mn, S.rescue);
+            else hipLaunchKernelGGL(k_vote_lookup<true>, dim3((unsigned)((nmz + 255) / 256)), dim3(256), 0, st, I, d_mx, nmz, mid_occ, d_ment, d_mn, S.rescue);
+            if (S.rescue) hipLaunchKernelGGL(k_vote_rescue, dim3(nq), dim3(256), 0, st, S);
         }
         hipLaunchKernelGGL(k_vote_qhits, dim3(nq + 1), dim3(64), 0, st, d_qmz, d_mn, nq, d_qhits);
         TRY((dev_qscan<int64_t, int64_t>(ctx, d_qhits, nq, d_qsoff, nullptr, 0, nullptr, nullptr)));
@@ -2413,7 +2442,7 @@ extern "C" int telr_map(telr_ctx *ctx, const telr_index *ix, const telr_seqset *
             // sub-read voting carries ~25 B per query base more (hits staged at 8 B each, compacted minimizers): two 1.4-Gbp
             // ranges in flight fill the device (2 x 152 GB measured at configs[3]) and leave the BAM writer nothing
             if (mo->vote_len > 0 && !qtarget && !(mo->flags & TELR_MF_PER_TARGET)) cap = 1100LL << 20;
-            const double per_base = ix->anchors_per_base > 0 ? ix->anchors_per_base : index_density_bound(ix, mid_occ.mid_occ);
+            const double per_base = ix->anchors_per_base > 0 ? ix->anchors_per_base : call_density_bound(ix, mid_occ.mid_occ, mo);
             if (per_base > 0) cap = std::min<int64_t>(cap, std::max<int64_t>(256LL << 20, (int64_t)(0.8e9 / per_base)));      // two in flight: half the anchor budget each
             // ... or that is large enough for two halves in flight to win: measured on configs[2] reads, two ranges against one:
             // 0.40 Gbp 30.7 / 27.4 ms, 0.51 Gbp 32.9 / 33.9, 0.81 Gbp 47.2 / 51.3, 1.01 Gbp 57.3 / 63.2 (the shard of a 4-rank run)
@@ -2514,7 +2543,7 @@ extern "C" int telr_map(telr_ctx *ctx, const telr_index *ix, const telr_seqset *
         } else {
             auto limit_for = [&](double per_base) { return std::min<int64_t>(batch_bases, std::max<int64_t>(256LL << 20, (int64_t)(1.6e9 / per_base))); };
             int64_t limit = batch_bases;
-            if (!fixed) { const double pb = ix->anchors_per_base > 0 ? ix->anchors_per_base : index_density_bound(ix, mid_occ.mid_occ); if (pb > 0) limit = limit_for(pb); }
+            if (!fixed) { const double pb = ix->anchors_per_base > 0 ? ix->anchors_per_base : call_density_bound(ix, mid_occ.mid_occ, mo); if (pb > 0) limit = limit_for(pb); }
             for (int32_t q0 = 0; q0 < nq; ) {
                 int32_t q1 = q0; int64_t b = 0;
                 while (q1 < nq && (q1 == q0 || b + queries->len[q1] <= limit)) { b += queries->len[q1]; ++q1; }

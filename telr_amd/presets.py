@@ -8,7 +8,7 @@ the same numbers (tests/test_abi.py keeps them in lock-step).
 """
 import threading
 
-from ._abi import IdxOpt, MapOpt, MF_CIGAR, MF_CHAIN_SKIP
+from ._abi import IdxOpt, MapOpt, MF_CIGAR, MF_CHAIN_SKIP, MF_SEED_RESCUE, MF_MM2_MAPQ
 
 
 def _gap_q8(k, scale=0.8):
@@ -40,9 +40,12 @@ class override:
         return False
 
 
-def preset(name, chain_skip=False):
+def preset(name, chain_skip=False, seed_rescue=False, mm2_mapq=False):
     """-> (IdxOpt, MapOpt) of a preset.  chain_skip: minimap2's order-dependent chaining scan (MF_CHAIN_SKIP: look-back 5,000,
-    stop after 25 predecessors already on a chain through the anchor) instead of the spec's fixed look-back; off by default."""
+    stop after 25 predecessors already on a chain through the anchor) instead of the spec's fixed look-back; off by default.
+    seed_rescue: minimap2's high-occurrence seed rescue (MF_SEED_RESCUE: in a stretch of minimizers above the occurrence cut-off the
+    least frequent ones, one per 500 query bases, are seeded after all); all-vs-all calls only; off by default.
+    mm2_mapq: minimap2's MAPQ (MF_MM2_MAPQ: mm_set_mapq without the second-best DP score) instead of the Li-2018 formula; off by default."""
     io = IdxOpt(k=15, w=10, is_hpc=0, bucket_bits=0)
     mo = MapOpt(
         mid_occ_frac=2e-4, min_mid_occ=10, max_mid_occ=1000000,
@@ -117,4 +120,8 @@ def preset(name, chain_skip=False):
         setattr(mo, f, v)
     if chain_skip:
         mo.flags |= MF_CHAIN_SKIP
+    if seed_rescue:
+        mo.flags |= MF_SEED_RESCUE
+    if mm2_mapq:
+        mo.flags |= MF_MM2_MAPQ
     return io, mo

@@ -40,8 +40,9 @@ def wait_release():
 atexit.register(wait_release)
 
 
-def alignment(bam, read, reference, out, sample_name, thread, method, presets, engine=None, chain_skip=False):
-    """chain_skip (minimap2 branch only): minimap2's own chaining scan (presets.preset(..., chain_skip=True)), not the fixed look-back"""
+def alignment(bam, read, reference, out, sample_name, thread, method, presets, engine=None, chain_skip=False, seed_rescue=False, mm2_mapq=False):
+    """chain_skip (minimap2 branch only): minimap2's own chaining scan (presets.preset(..., chain_skip=True)), not the fixed look-back.
+    seed_rescue, mm2_mapq (minimap2 branch only): minimap2's high-occurrence seed rescue and its own MAPQ (presets.preset)"""
     logging.info("Start alignment...")
     start_time = time.time()
     if presets not in ("ont", "pacbio"):
@@ -54,14 +55,16 @@ def alignment(bam, read, reference, out, sample_name, thread, method, presets, e
     elif method == "minimap2":
         name = "map-ont" if presets == "ont" else "map-pb"
         rg = None
-        cmd = "minimap2 --cs --MD -Y -L -ax %s%s %s %s" % (name, " --max-chain-skip 25" if chain_skip else "", reference, read)
+        cmd = "minimap2 --cs --MD -Y -L -ax %s%s%s %s %s" % (name, " --max-chain-skip 25" if chain_skip else "", " -e 500" if seed_rescue else "", reference, read)
     else:
         print("Alignment method not recognized, please provide ont or pacbio, exiting...")
         sys.exit(1)
     if chain_skip and method != "minimap2":
         raise ValueError("chain_skip is an option of the minimap2 branch")
+    if (seed_rescue or mm2_mapq) and method != "minimap2":
+        raise ValueError("seed_rescue and mm2_mapq are options of the minimap2 branch")
     eng = engine or Engine(0)
-    io, mo = preset(name, chain_skip=chain_skip)
+    io, mo = preset(name, chain_skip=chain_skip, seed_rescue=seed_rescue, mm2_mapq=mm2_mapq)
     tm = {}                                       # seconds per phase of the last call: alignment.last_timings
     t0 = time.time()
     tf, qf = load(reference), load(read)          # None for gzip: the Python reader
