@@ -228,6 +228,16 @@ int32_t telr_seqset_count(const telr_seqset *s);
 int  telr_seqset_packed(const telr_seqset *s, const void **d_seq2, const void **d_nmask, int64_t *nwords2, int64_t *nwordsn);
 int  telr_seqset_from_packed(telr_ctx *ctx, int32_t n, const int32_t *len, const void *d_seq2, int64_t nwords2,
                              const void *d_nmask, int64_t nwordsn, telr_seqset **out);
+/* Base qualities (FASTQ) for the QUAL field of the device BAM writer; optional.  qual_ascii[qual_off[i] .. qual_off[i] + len[i])
+ * are the quality characters of sequence i of `s`; what is kept on the device is one byte per base, the Phred value (character
+ * minus phred_offset; callers pass 33), in the set's own base layout: sequence i at byte B(i) of the array (see above).  Costs
+ * 1 byte of HBM per (padded) base -- about 4 GB for a 30x read set -- and the upload (32-MB chunks through pinned staging),
+ * taken only when called.  A character outside phred_offset .. phred_offset + 93 is TELR_E_ARG and leaves the set without
+ * qualities; attaching again replaces the values.  telr_seqset_free frees the array.  Sets made by telr_seqset_subset,
+ * telr_seqset_subset_rc and telr_seqset_from_packed carry NO qualities, whatever their source held (so the N-rank writer of
+ * telr_amd/shard.py, which moves packed reads between ranks, writes 0xff). */
+int  telr_seqset_attach_qual(telr_ctx *ctx, telr_seqset *s, const char *qual_ascii, const int64_t *qual_off, int32_t phred_offset);
+int  telr_seqset_has_qual(const telr_seqset *s);
 
 /* ---- FASTA / FASTQ text -> the arrays above (host code; plain files, not gzip).  Replaces handing the file names to
  *      ngmlr / minimap2 (src/telr/TELR_alignment.py:31-51, 69-82).  Names end at the first white space. */
@@ -242,6 +252,11 @@ const char *telr_fasta_seq(const telr_fasta *f);                 /* base buffer:
 const int64_t *telr_fasta_off(const telr_fasta *f);
 const int32_t *telr_fasta_len(const telr_fasta *f);
 const char *const *telr_fasta_names(const telr_fasta *f);
+/* FASTQ: the quality characters of record i are qual[qual_off[i] .. qual_off[i] + len[i]) -- in the mapped file itself when
+ * the bases are used in place, else copied next to the bases (CR dropped).  Both NULL for a FASTA file and for an empty file.
+ * A record whose quality line is not as long as its sequence line makes telr_fasta_load return TELR_E_ARG. */
+const char *telr_fasta_qual(const telr_fasta *f);
+const int64_t *telr_fasta_qual_off(const telr_fasta *f);
 void telr_fasta_free(telr_fasta *f);
 
 /* ---- index (replaces "minimap2 ... REF" re-indexing REF on every call) ----- */
@@ -304,6 +319,14 @@ int  telr_write_sam(const telr_result *r, int32_t n_queries, const char *const *
                     const int32_t *q_len, int32_t n_targets, const char *const *tnames, const char *t_ascii, const int64_t *t_off,
                     const int32_t *t_len, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb,
                     const char *pg_line, const char *path);
+/* The same with the reads' base qualities in column 11: q_qual[q_qual_off[q] .. + q_len[q]) are read q's quality characters,
+ * phred_offset what they are offset by (33 for FASTQ); printed as Phred + 33 for exactly the bases SEQ holds, in SEQ's
+ * orientation (reversed on the reverse strand, cut like SEQ by hard clips), `*` where SEQ is `*` or empty.  q_qual NULL =
+ * telr_write_sam.  A character outside phred_offset .. phred_offset + 93 is TELR_E_ARG (nothing is written). */
+int  telr_write_sam_qual(const telr_result *r, int32_t n_queries, const char *const *qnames, const char *q_ascii, const int64_t *q_off,
+                         const int32_t *q_len, int32_t n_targets, const char *const *tnames, const char *t_ascii, const int64_t *t_off,
+                         const int32_t *t_len, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb,
+                         const char *pg_line, const char *path, const char *q_qual, const int64_t *q_qual_off, int32_t phred_offset);
 
 /* Coordinate-sorted BAM (+ .bai when write_index != 0): replaces `samtools sort -o BAM SAM; samtools index BAM`
  * (src/telr/TELR_alignment.py:103-114).  Same arguments as telr_write_sam; level = zlib level (0 -> 1). */
@@ -311,6 +334,13 @@ int  telr_write_bam(const telr_result *r, int32_t n_queries, const char *const *
                     const int32_t *q_len, int32_t n_targets, const char *const *tnames, const char *t_ascii, const int64_t *t_off,
                     const int32_t *t_len, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb,
                     const char *pg_line, const char *bam_path, int32_t write_index, int32_t level);
+/* The same with QUAL = the Phred values of SEQ's bases (arguments as telr_write_sam_qual; q_qual NULL = telr_write_bam: 0xff).
+ * Its uncompressed stream equals the one telr_write_bam_dev writes for a read set with the same qualities attached. */
+int  telr_write_bam_qual(const telr_result *r, int32_t n_queries, const char *const *qnames, const char *q_ascii, const int64_t *q_off,
+                         const int32_t *q_len, int32_t n_targets, const char *const *tnames, const char *t_ascii, const int64_t *t_off,
+                         const int32_t *t_len, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb,
+                         const char *pg_line, const char *bam_path, int32_t write_index, int32_t level,
+                         const char *q_qual, const int64_t *q_qual_off, int32_t phred_offset);
 
 /* The same file made on the DEVICE from what is already resident there (the reads, the reference, the CIGARs): NM / MD / cs /
  * SA, the 4-bit SEQ, the coordinate sort (refID, position, forward before reverse strand, then query order) and the BGZF
@@ -318,9 +348,16 @@ int  telr_write_bam(const telr_result *r, int32_t n_queries, const char *const *
  * the .bai.  `queries` = the set the result was mapped from, `idx` = the index it was mapped against (its targets supply the
  * reference bases).  No ASCII sequences are needed.  level 0 = stored BGZF blocks; level >= 1 = deflate blocks coded on
  * the device (Huffman tables per BAM field class, run-length matches).  Bases print as the engine sees them: A C G T, anything
- * else N (telr_write_bam / telr_write_sam print the same, so the uncompressed streams of the two writers are equal). */
+ * else N (telr_write_bam / telr_write_sam print the same, so the uncompressed streams of the two writers are equal).
+ * QUAL is 0xff (absent) unless `queries` has qualities attached (telr_seqset_attach_qual): then every record holds the Phred
+ * values of the bases its SEQ holds, in SEQ's orientation -- reversed for a reverse-strand record, cut like SEQ on a
+ * hard-clipped supplementary record, none for a secondary (l_seq 0), the whole read forward for an unmapped read -- and the
+ * device deflate codes QUAL with a Huffman table of its own (a fourth field class).  telr_write_bam_slice honours attached
+ * qualities the same way.  A file written without qualities is byte for byte what it was before the option existed. */
 /* Optional, before telr_map: start creating `bam_path` in the background -- the file is created and mapped at once, then
- * est_bytes of it (a BAM with --cs --MD takes about 0.85 bytes per read base at level 1, 2.8 at level 0) are allocated and
+ * est_bytes of it (a BAM with --cs --MD takes about 0.85 bytes per read base at level 1, 2.8 at level 0; attached qualities add
+ * what their entropy asks for -- measured 0.81 -> 1.26 bytes per read base at level 1 with ONT-shaped qualities of 3.6 bits,
+ * tools/bam_qual_ab.py; up to 0.82 more for qualities spread evenly over 0..93) are allocated and
  * pre-faulted into the mapping block by block, front to back -- so that telr_write_bam_dev(... the same path ...) copies the
  * finished file image into pages that exist and are mapped (80+ GB/s instead of the 6-15 GB/s of a fresh page-cache page),
  * and cuts the file to size.  Without it, or past the estimate, the writer streams through a pinned ring and one pwrite

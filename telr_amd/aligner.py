@@ -18,6 +18,16 @@ def _np_from(ptr, n, dtype):
     return np.frombuffer(buf, dtype=dt, count=n).copy()
 
 
+def _qual_arrays(qual):
+    """base qualities as the C ABI takes them: a list of quality strings (str / bytes, Phred + 33, one per sequence) or the
+    (buffer, offsets) pair of fasta.FastaFile.qual -> (uint8 buffer, int64 offsets)"""
+    if isinstance(qual, tuple) and len(qual) == 2:
+        buf, off = qual
+    else:
+        buf, off, _ = concat([q.encode("latin-1") if isinstance(q, str) else q for q in qual])
+    return np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.int64)
+
+
 _DEFERRED = None          # list of (free function, handle) while deferred_frees() is active
 
 
@@ -64,8 +74,9 @@ class Engine:
         self.L.telr_device_name(self.h, b, 256)
         return b.value.decode()
 
-    def seqset(self, seqs):
-        return SeqSet(self, seqs)
+    def seqset(self, seqs, qual=None):
+        """qual: the sequences' base qualities (see SeqSet.attach_qual), kept on the device for the QUAL field of write_bam_device"""
+        return SeqSet(self, seqs, qual)
 
     def index(self, targets, io):
         return Index(self, targets, io)
@@ -173,7 +184,7 @@ class _DevWords:
 
 
 class SeqSet:
-    def __init__(self, eng, seqs):
+    def __init__(self, eng, seqs, qual=None):
         self.eng = eng
         if isinstance(seqs, tuple) and len(seqs) == 3:
             buf, off, ln = seqs
@@ -187,9 +198,27 @@ class SeqSet:
                                           C.byref(h)), "telr_seqset_create")
         self.h = h
         self.n = len(self.len)
+        if qual is not None:
+            self.attach_qual(qual)
 
     def bases(self):
         return int(self.eng.L.telr_seqset_bases(self.h))
+
+    def attach_qual(self, qual, phred_offset=33):
+        """one quality character per base: a list of strings (one per sequence) or a (buffer, offsets) pair such as
+        fasta.FastaFile.qual; 1 byte of device memory per base (telr_seqset_attach_qual).  Sets made by subset() / from_packed()
+        carry none.  A character outside phred_offset .. phred_offset + 93 raises and leaves the set without qualities."""
+        if not (isinstance(qual, tuple) and len(qual) == 2):
+            if len(qual) != self.n or any(len(q) != int(l) for q, l in zip(qual, self.len)):
+                raise ValueError("attach_qual: one quality character per base of every sequence")
+        buf, off = _qual_arrays(qual)
+        if len(off) != self.n:
+            raise ValueError("attach_qual: one offset per sequence")
+        self.eng._chk(self.eng.L.telr_seqset_attach_qual(self.eng.h, self.h, buf.ctypes.data, off.ctypes.data, int(phred_offset)), "telr_seqset_attach_qual")
+
+    @property
+    def has_qual(self):
+        return bool(self.eng.L.telr_seqset_has_qual(self.h))
 
     def subset(self, idx, eng=None, rc=None):
         """new set = copies of sequences idx (repeats allowed), gathered on the device from the packed form
@@ -380,8 +409,9 @@ class Index:
         self.eng._chk(self.eng.L.telr_write_paf(r, qa, ta, 1 if with_cigar else 0, path.encode(), 1 if append else 0), "telr_write_paf")
 
     def write_sam(self, r, qnames, queries, tnames, targets, path, md=True, cs=True, softclip=True, rg=None, cmdline="telr_map",
-                  primary_only=False, coordinate_sorted=False, header=True, unmapped=True):
+                  primary_only=False, coordinate_sorted=False, header=True, unmapped=True, qual=None):
         """queries / targets: lists of sequences (str) or (buf, off, len) triples as given to seqset().
+        qual: the queries' base qualities (a list of Phred + 33 strings or a (buffer, offsets) pair) for column 11; None: `*`.
         primary_only + coordinate_sorted + header=False = the text of `samtools view -F0x900 sorted.bam`
         (the polishing hand-off to wtpoa-cns, TELR_assembly.py:208,228)."""
         qb, qo, ql = queries if isinstance(queries, tuple) else concat(queries)
@@ -393,13 +423,19 @@ class Index:
         flags = (1 if md else 0) | (2 if cs else 0) | (4 if softclip else 0) | (0 if unmapped else 8) | (16 if primary_only else 0) | \
             (32 if coordinate_sorted else 0) | (0 if header else 64)
         rg_id, rg_sm, rg_lb = (None, None, None) if rg is None else tuple(x.encode() for x in rg)
-        self.eng._chk(self.eng.L.telr_write_sam(r, len(ql), qa, qb.ctypes.data, qo.ctypes.data, ql.ctypes.data, len(tl), ta,
-                                                tb.ctypes.data, to.ctypes.data, tl.ctypes.data, flags, rg_id, rg_sm, rg_lb,
-                                                cmdline.encode(), path.encode()), "telr_write_sam")
+        if qual is None:
+            self.eng._chk(self.eng.L.telr_write_sam(r, len(ql), qa, qb.ctypes.data, qo.ctypes.data, ql.ctypes.data, len(tl), ta,
+                                                    tb.ctypes.data, to.ctypes.data, tl.ctypes.data, flags, rg_id, rg_sm, rg_lb,
+                                                    cmdline.encode(), path.encode()), "telr_write_sam")
+        else:
+            qq, qqo = _qual_arrays(qual)
+            self.eng._chk(self.eng.L.telr_write_sam_qual(r, len(ql), qa, qb.ctypes.data, qo.ctypes.data, ql.ctypes.data, len(tl), ta,
+                                                         tb.ctypes.data, to.ctypes.data, tl.ctypes.data, flags, rg_id, rg_sm, rg_lb,
+                                                         cmdline.encode(), path.encode(), qq.ctypes.data, qqo.ctypes.data, 33), "telr_write_sam_qual")
 
     def write_bam(self, r, qnames, queries, tnames, targets, path, md=True, cs=True, softclip=True, rg=None, cmdline="telr_map",
-                  index=True, level=1):
-        """coordinate-sorted BAM + .bai (samtools sort + index, TELR_alignment.py:103-114)"""
+                  index=True, level=1, qual=None):
+        """coordinate-sorted BAM + .bai (samtools sort + index, TELR_alignment.py:103-114); qual as in write_sam (None: QUAL 0xff)"""
         qb, qo, ql = queries if isinstance(queries, tuple) else concat(queries)
         tb, to, tl = targets if isinstance(targets, tuple) else concat(targets)
         qb = np.ascontiguousarray(qb, np.uint8); tb = np.ascontiguousarray(tb, np.uint8)
@@ -408,14 +444,20 @@ class Index:
         qa, ta = self._cstr_array(qnames), self._cstr_array(tnames)
         flags = (1 if md else 0) | (2 if cs else 0) | (4 if softclip else 0)
         rg_id, rg_sm, rg_lb = (None, None, None) if rg is None else tuple(x.encode() for x in rg)
-        self.eng._chk(self.eng.L.telr_write_bam(r, len(ql), qa, qb.ctypes.data, qo.ctypes.data, ql.ctypes.data, len(tl), ta,
-                                                tb.ctypes.data, to.ctypes.data, tl.ctypes.data, flags, rg_id, rg_sm, rg_lb,
-                                                cmdline.encode(), path.encode(), 1 if index else 0, level), "telr_write_bam")
+        if qual is None:
+            self.eng._chk(self.eng.L.telr_write_bam(r, len(ql), qa, qb.ctypes.data, qo.ctypes.data, ql.ctypes.data, len(tl), ta,
+                                                    tb.ctypes.data, to.ctypes.data, tl.ctypes.data, flags, rg_id, rg_sm, rg_lb,
+                                                    cmdline.encode(), path.encode(), 1 if index else 0, level), "telr_write_bam")
+        else:
+            qq, qqo = _qual_arrays(qual)
+            self.eng._chk(self.eng.L.telr_write_bam_qual(r, len(ql), qa, qb.ctypes.data, qo.ctypes.data, ql.ctypes.data, len(tl), ta,
+                                                         tb.ctypes.data, to.ctypes.data, tl.ctypes.data, flags, rg_id, rg_sm, rg_lb,
+                                                         cmdline.encode(), path.encode(), 1 if index else 0, level, qq.ctypes.data, qqo.ctypes.data, 33), "telr_write_bam_qual")
 
     def write_bam_device(self, r, queries, qnames, tnames, path, md=True, cs=True, softclip=True, rg=None, cmdline="telr_map",
                          index=True, level=1, unmapped=True):
         """the same file built on the device from the resident reads / reference / CIGARs (telr_write_bam_dev);
-        queries = the SeqSet the result was mapped from"""
+        queries = the SeqSet the result was mapped from; its attached qualities, if any, become QUAL"""
         qa, ta = self._cstr_array(qnames), self._cstr_array(tnames)
         flags = (1 if md else 0) | (2 if cs else 0) | (4 if softclip else 0) | (0 if unmapped else 8)
         rg_id, rg_sm, rg_lb = (None, None, None) if rg is None else tuple(x.encode() for x in rg)

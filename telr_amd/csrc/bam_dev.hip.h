@@ -9,8 +9,9 @@
 //                -> NM, lengths of the MD and cs strings, inserted / deleted bases (for SA)
 //   k_bam_size   one thread per record: SA length, record size, sort key (refID, pos, strand)
 //   rocPRIM      stable radix sort of the keys, scan of the sizes in sorted order -> offset of every record
-//   k_bam_write  one wave per record: the whole BAM record (fixed part, name, CIGAR, 4-bit SEQ, QUAL 0xff, tags with
-//                MD / cs / SA text) at its place of the uncompressed stream
+//   k_bam_write  one wave per record: the whole BAM record (fixed part, name, CIGAR, 4-bit SEQ, QUAL 0xff -- or the Phred
+//                values of a read set with attached qualities, telr_seqset_attach_qual --, tags with MD / cs / SA text) at
+//                its place of the uncompressed stream
 //   k_bgzf_*     one workgroup per 65280-byte block of that stream: CRC-32 + framing (level 0: stored blocks;
 //                level >= 1: Huffman-coded deflate blocks, see below)
 //   host: DMA of the finished file image in chunks through a pinned ring into the file, .bai from the record offsets
@@ -38,11 +39,19 @@ struct BamArgs {
     BamInfo *info; uint32_t *rec_size; uint64_t *key; const uint64_t *rec_ustart; uint8_t *ubuf;
     const uint8_t *emit;                                // slice mode (nullable): record k is written iff emit[k]; the others are only there for the SA tags of their read
     const uint32_t *order; int32_t s0;                  // k_bam_write in pieces of the SORTED order: block x writes record order[s0 + x] (order null: record x)
+    const uint8_t *qqual;                               // nullable: one Phred value per read base, read q's at qqual[qboff[q] ..) (telr_seqset_attach_qual); null: QUAL is 0xff
 };
 
 typedef uint32_t __attribute__((aligned(1))) u32_unal;
 __device__ __forceinline__ void d_st32(uint8_t *p, uint32_t v) { *(u32_unal*)p = v; }
 __device__ __forceinline__ void d_st16(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); }
+// bytes x .. x + 3 of an array whose base is dword-aligned, as one dword (first byte low): the two aligned dwords around them,
+// funnel-shifted.  The second dword may lie up to 4 bytes behind byte x + 3: the array carries that slack.
+__device__ __forceinline__ uint32_t d_ld32_at(const uint8_t *__restrict__ base, int64_t x)
+{
+    const uint32_t *__restrict__ w = (const uint32_t*)base + (x >> 2);
+    return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)x & 3u);
+}
 __device__ __forceinline__ int d_ndig(uint32_t v)
 {
     return 1 + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u) + (v >= 100000000u) + (v >= 1000000000u);
@@ -420,12 +429,24 @@ __global__ void __launch_bounds__(64) k_bam_write(BamArgs A)
             }
         }
         const int head = (int)((4 - ((uintptr_t)p_qual & 3)) & 3), nh = head < Y.l_seq ? head : Y.l_seq;
-        if (lane < nh) p_qual[lane] = 0xff;
         const int body = (Y.l_seq - nh) >> 2;
         uint32_t *q4 = (uint32_t*)(p_qual + nh);
-        for (int i = lane; i < body; i += 64) q4[i] = 0xffffffffu;
         const int tail0 = nh + body * 4;
-        if (tail0 + lane < Y.l_seq && lane < 4) p_qual[tail0 + lane] = 0xff;
+        if (!A.qqual) {
+            if (lane < nh) p_qual[lane] = 0xff;
+            for (int i = lane; i < body; i += 64) q4[i] = 0xffffffffu;
+            if (tail0 + lane < Y.l_seq && lane < 4) p_qual[tail0 + lane] = 0xff;
+        } else {
+            // QUAL byte j is the quality of SEQ's base j: read base seq_lo + j, counted from the read's end on the reverse strand.
+            // The read's qualities start dword-aligned (qboff is a multiple of 64) but seq_lo + nh is anything: a stored dword is
+            // cut out of two loaded ones, and byte-swapped where the read runs backwards.
+            const uint8_t *__restrict__ qq = A.qqual + qb0;
+            const int last = a.qlen - 1 - Y.seq_lo;             // reverse: QUAL byte j <- read base last - j
+            if (lane < nh) p_qual[lane] = Y.rev ? qq[last - lane] : qq[Y.seq_lo + lane];
+            if (!Y.rev) for (int i = lane; i < body; i += 64) q4[i] = d_ld32_at(qq, (int64_t)Y.seq_lo + nh + 4 * i);
+            else for (int i = lane; i < body; i += 64) q4[i] = __builtin_bswap32(d_ld32_at(qq, (int64_t)last - nh - 4 * i - 3));
+            if (tail0 + lane < Y.l_seq && lane < 4) p_qual[tail0 + lane] = Y.rev ? qq[last - tail0 - lane] : qq[Y.seq_lo + tail0 + lane];
+        }
     }
     if (un) {
         if (A.rg_len && lane == 0) { uint8_t *t = p_tags; t[0] = 'R'; t[1] = 'G'; t[2] = 'Z'; t = d_put_str(t + 3, A.rg, A.rg_len); *t = 0; }
@@ -517,7 +538,11 @@ __global__ void __launch_bounds__(256) k_bgzf_store(const uint8_t *__restrict__ 
 // (k_bam_hist over a sample of the blocks, Huffman lengths on the host) and their headers are pasted as ready-made bit strings.
 // Matching is run-length only (distance 1): QUAL collapses, CIGAR zero bytes shorten; SEQ and the text have no long repeats
 // worth a hash table.  Field boundaries come from the records themselves (l_read_name, n_cigar_op, l_seq in the stream).
-#define DEFL_NCLS    3
+// A read set with attached qualities makes QUAL a kind of its own (class D, `qual` below): some forty values around the
+// platform's typical Phred, no runs -- under SEQ's 16-symbol table it would cost the ~12 bits of a rare literal per byte.  It
+// gets the fourth table and a switch candidate where SEQ ends.  Without qualities the fourth class does not exist: three
+// histograms, three tables, the same switches and the same bits as before there was one.
+#define DEFL_NCLS    4
 #define DEFL_THREADS 1024
 #define DEFL_PIECE   64             /* bytes per thread: BAM_BLK = 1020 pieces */
 #define DEFL_SEGCAP  256
@@ -533,7 +558,7 @@ struct DeflSeg { uint16_t start; uint16_t cls; };
 
 // segments of block [u0, u0 + n): where the table changes.  Executed by wave 0 of the workgroup; result in LDS (seg[0].start = 0).
 __device__ __forceinline__ int d_defl_segments(const uint8_t *__restrict__ ubuf, uint64_t u0, int n, uint64_t head, const uint64_t *__restrict__ ust, int32_t nrec,
-                                               int32_t rec0, DeflSeg *seg, int lane)
+                                               int32_t rec0, DeflSeg *seg, int lane, int qual)
 {
     // class at u0
     int nseg = 0;
@@ -543,26 +568,29 @@ __device__ __forceinline__ int d_defl_segments(const uint8_t *__restrict__ ubuf,
     bool first = rec0 >= 0;
     for (; r < nrec; r += 64) {
         const int k = r + lane;
-        uint64_t s = ~0ULL, p1 = 0, p2 = 0, e = 0;
+        uint64_t s = ~0ULL, p1 = 0, pq = 0, p2 = 0, e = 0;
         if (k < nrec) s = ust[k] + head;
         const bool in = k < nrec && s < uend;
         if (in) {
             e = ust[k + 1] + head;
             const uint8_t *h = ubuf + s;
             const uint32_t l_name = h[12], n_cig = (uint32_t)h[16] | (uint32_t)h[17] << 8, l_seq = (uint32_t)h[20] | (uint32_t)h[21] << 8 | (uint32_t)h[22] << 16 | (uint32_t)h[23] << 24;
-            p1 = s + 36 + l_name + 4ull * n_cig; p2 = p1 + (l_seq + 1) / 2 + l_seq;
+            p1 = s + 36 + l_name + 4ull * n_cig; pq = p1 + (l_seq + 1) / 2; p2 = pq + l_seq;
+            if (!qual) pq = p2;          // SEQ and its 0xff run are one field
         }
         if (first) {      // lane 0 holds the record around u0
-            if (lane == 0) { seg[0].start = 0; seg[0].cls = (uint16_t)(u0 < p1 ? 0 : (u0 < p2 ? 1 : 2)); }
+            if (lane == 0) { seg[0].start = 0; seg[0].cls = (uint16_t)(u0 < p1 ? 0 : (u0 < pq ? 1 : (u0 < p2 ? 3 : 2))); }
             nseg = 1; first = false;
         }
-        // candidate switches: (s, A), (p1, B), (p2, C) strictly inside the block, whose own field is long enough
-        bool k0 = in && s > u0 && s < uend && (p1 - s) >= DEFL_MINSEG, k1 = in && p1 > u0 && p1 < uend && (p2 - p1) >= DEFL_MINSEG, k2 = in && p2 > u0 && p2 < uend && (e - p2) >= DEFL_MINSEG;
-        const int cnt = (int)k0 + (int)k1 + (int)k2;
+        // candidate switches: (s, A), (p1, B), (pq, D: with qualities only), (p2, C) strictly inside the block, whose own field is long enough
+        bool k0 = in && s > u0 && s < uend && (p1 - s) >= DEFL_MINSEG, k1 = in && p1 > u0 && p1 < uend && (pq - p1) >= DEFL_MINSEG, k2 = in && p2 > u0 && p2 < uend && (e - p2) >= DEFL_MINSEG;
+        const bool kq = in && pq > u0 && pq < uend && (p2 - pq) >= DEFL_MINSEG;          // (no qualities: p2 - pq = 0)
+        const int cnt = (int)k0 + (int)k1 + (int)kq + (int)k2;
         const int inc = d_wave_incl(cnt, lane);
         int w = nseg + inc - cnt;
         if (k0 && w < DEFL_SEGCAP) { seg[w].start = (uint16_t)(s - u0); seg[w].cls = 0; ++w; }
         if (k1 && w < DEFL_SEGCAP) { seg[w].start = (uint16_t)(p1 - u0); seg[w].cls = 1; ++w; }
+        if (kq && w < DEFL_SEGCAP) { seg[w].start = (uint16_t)(pq - u0); seg[w].cls = 3; ++w; }
         if (k2 && w < DEFL_SEGCAP) { seg[w].start = (uint16_t)(p2 - u0); seg[w].cls = 2; ++w; }
         nseg += __shfl(inc, 63);
         if (nseg > DEFL_SEGCAP) nseg = DEFL_SEGCAP;
@@ -654,7 +682,7 @@ __device__ __forceinline__ uint32_t d_defl_piece(const uint8_t *in, int n, int t
 }
 
 __global__ void __launch_bounds__(DEFL_THREADS) k_bam_hist(const uint8_t *__restrict__ ubuf, uint64_t utotal, uint64_t head, const uint64_t *__restrict__ ust, int32_t nrec,
-                                                          const int32_t *__restrict__ rec0, int32_t stride, const DeflTabs *__restrict__ T, uint32_t *__restrict__ ghist)
+                                                          const int32_t *__restrict__ rec0, int32_t stride, const DeflTabs *__restrict__ T, uint32_t *__restrict__ ghist, int32_t qual)
 {
     __shared__ uint32_t in4[DEFL_IN4_WORDS];
     __shared__ DeflSeg seg[DEFL_SEGCAP];
@@ -668,7 +696,7 @@ __global__ void __launch_bounds__(DEFL_THREADS) k_bam_hist(const uint8_t *__rest
     const uint32_t *src4 = (const uint32_t*)(ubuf + u0);
     for (int i = t; i < (n + 3) >> 2; i += DEFL_THREADS) in4[i + (i >> 4)] = src4[i];
     for (int i = t; i < DEFL_NCLS * 288; i += DEFL_THREADS) hist[i] = 0;
-    if (t < 64) { const int ns = d_defl_segments(ubuf, u0, n, head, ust, nrec, rec0[b], seg, t); if (t == 0) s_nseg = ns; }
+    if (t < 64) { const int ns = d_defl_segments(ubuf, u0, n, head, ust, nrec, rec0[b], seg, t, qual); if (t == 0) s_nseg = ns; }
     __syncthreads();
     d_defl_piece<2>((const uint8_t*)in4, n, t, seg, s_nseg, T, nullptr, hist, nullptr, s_len);
     __syncthreads();
@@ -678,7 +706,7 @@ __global__ void __launch_bounds__(DEFL_THREADS) k_bam_hist(const uint8_t *__rest
 // one BGZF block: out slot b (DEFL_SLOT bytes), its size in csize[b]
 __global__ void __launch_bounds__(DEFL_THREADS) k_bgzf_deflate(const uint8_t *__restrict__ ubuf, uint64_t utotal, uint64_t head, const uint64_t *__restrict__ ust, int32_t nrec,
                                                               const int32_t *__restrict__ rec0, const DeflTabs *__restrict__ T, const CrcTabs *__restrict__ CT,
-                                                              uint8_t *__restrict__ slots, uint32_t *__restrict__ csize, uint32_t blk0)
+                                                              uint8_t *__restrict__ slots, uint32_t *__restrict__ csize, uint32_t blk0, int32_t qual)
 {
     __shared__ uint32_t in4[DEFL_IN4_WORDS];
     __shared__ uint32_t out4[BAM_BLK / 4 + 8];
@@ -696,7 +724,7 @@ __global__ void __launch_bounds__(DEFL_THREADS) k_bgzf_deflate(const uint8_t *__
     for (int i = t; i < (n + 3) >> 2; i += DEFL_THREADS) in4[i + (i >> 4)] = src4[i];
     for (int i = t; i < BAM_BLK / 4 + 8; i += DEFL_THREADS) out4[i] = 0;
     if (t < 256) tab[t] = CT->byte_tab[t];
-    if (t < 64) { const int ns = d_defl_segments(ubuf, u0, n, head, ust, nrec, rec0[b], seg, t); if (t == 0) s_nseg = ns; }
+    if (t < 64) { const int ns = d_defl_segments(ubuf, u0, n, head, ust, nrec, rec0[b], seg, t, qual); if (t == 0) s_nseg = ns; }
     __syncthreads();
     const uint8_t *in = (const uint8_t*)in4;
     const int nseg = s_nseg;
@@ -878,9 +906,10 @@ static void defl_len_syms(uint16_t *len_sym)
 }
 // histogram[class][288] -> tables.  Every literal, the end-of-block symbol and every length symbol keeps a code (count >= 1):
 // any byte may turn up in any class (fields shorter than DEFL_MINSEG ride on the table in force).
-static int defl_tables_from_hist(const uint32_t *hist, DeflTabs &T)
+// (ncls: 3 without qualities -- the fourth table stays empty and no segment names it --, DEFL_NCLS with them)
+static int defl_tables_from_hist(const uint32_t *hist, DeflTabs &T, int ncls)
 {
-    for (int c = 0; c < DEFL_NCLS; ++c) {
+    for (int c = 0; c < ncls; ++c) {
         uint32_t f[286];
         for (int i = 0; i < 286; ++i) f[i] = hist[c * 288 + i] + 1;
         uint8_t ll[286]; huff_lengths(f, 286, 15, ll);
@@ -922,7 +951,7 @@ extern "C" int telr_debug_deflate_host(const uint8_t *src, int32_t n, uint8_t *o
     walk([&](int b) { ++hist[b]; }, [&](int L) { ++hist[257 + (len_sym[L] & 31)]; });
     ++hist[256];
     DeflTabs T; memset(&T, 0, sizeof(T));
-    int rc = defl_tables_from_hist(hist.data(), T);
+    int rc = defl_tables_from_hist(hist.data(), T, 1);
     if (rc != TELR_OK) return rc;
     HostBits B;
     B.put(1u | 2u << 1, 3);
@@ -1431,6 +1460,8 @@ static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *
     A.q2 = queries->d_seq2; A.qn = queries->d_nmask; A.qboff = queries->d_boff; A.t2 = tg->d_seq2; A.tn = tg->d_nmask; A.tboff = tg->d_boff;
     A.qnames = d_qn; A.qname_off = d_qnoff; A.tnames = d_tn; A.tname_off = d_tnoff; A.rg = d_rg; A.rg_len = rg_len; A.flags = flags;
     A.info = d_info; A.rec_size = d_size; A.key = d_key; A.rec_ustart = d_rust; A.ubuf = nullptr;
+    A.qqual = queries->d_qual;
+    const int32_t has_qual = queries->d_qual ? 1 : 0;
     size_t n_ghost = 0;
     if (so && so->emit) {
         uint8_t *d_emit; TRY(ctx_buf_t(ctx, "bam_emit", nrec + 1, &d_emit));
@@ -1536,12 +1567,12 @@ static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *
         }
         const int32_t stride = (int32_t)std::max<size_t>(1, nb_first / 4096);
         const unsigned nsamp = (unsigned)((nb_first + stride - 1) / stride);
-        if (nsamp) hipLaunchKernelGGL(k_bam_hist, dim3(nsamp), dim3(DEFL_THREADS), 0, st, d_u, utotal, (uint64_t)head.size(), d_ust, (int32_t)nrec, d_rec0, stride, d_T, d_hist);
+        if (nsamp) hipLaunchKernelGGL(k_bam_hist, dim3(nsamp), dim3(DEFL_THREADS), 0, st, d_u, utotal, (uint64_t)head.size(), d_ust, (int32_t)nrec, d_rec0, stride, d_T, d_hist, has_qual);
         HIPCHK(hipGetLastError());
         std::vector<uint32_t> h_hist((size_t)DEFL_NCLS * 288);
         HIPCHK(hipMemcpyAsync(h_hist.data(), d_hist, h_hist.size() * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        TRY(defl_tables_from_hist(h_hist.data(), T));
+        TRY(defl_tables_from_hist(h_hist.data(), T, has_qual ? DEFL_NCLS : 3));
         HIPCHK(hipMemcpyAsync(d_T, &T, sizeof(T), hipMemcpyHostToDevice, st));
         // The blocks are coded in groups; a group's sizes come home, the host lays the group out behind the previous one and a
         // second stream moves it into the file image, whose finished prefix streams out to the file while the next groups are
@@ -1554,7 +1585,7 @@ static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *
             if (g && ev_piece[g]) HIPCHK(hipStreamWaitEvent(st, ev_piece[g], 0));
             const size_t b0 = b_done[g], nb = b_done[g + 1] - b_done[g];
             if (!nb) continue;
-            hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)nb), dim3(DEFL_THREADS), 0, st, d_u, utotal, (uint64_t)head.size(), d_ust, (int32_t)nrec, d_rec0, d_T, d_tabs, d_slots, d_csize, (uint32_t)b0);
+            hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)nb), dim3(DEFL_THREADS), 0, st, d_u, utotal, (uint64_t)head.size(), d_ust, (int32_t)nrec, d_rec0, d_T, d_tabs, d_slots, d_csize, (uint32_t)b0, has_qual);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(h_csize + b0, d_csize + b0, nb * 4, hipMemcpyDeviceToHost, st));
             hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); HIPCHK(hipEventRecord(e, st)); evg.push_back(e);

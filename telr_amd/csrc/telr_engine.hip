@@ -389,6 +389,7 @@ struct telr_seqset {
     uint32_t *d_seq2 = nullptr, *d_nmask = nullptr;
     int64_t *d_boff = nullptr; int32_t *d_len = nullptr;
     int32_t max_len = 0;
+    uint8_t *d_qual = nullptr;    // telr_seqset_attach_qual: one Phred value per base in the set's base layout (sequence i at boff[i]), else null
 };
 
 static inline uint8_t nt4_of(unsigned char c)
@@ -645,10 +646,12 @@ extern "C" void telr_seqset_free(telr_seqset *s)
 {
     if (!s) return;
     (void)hipFree(s->d_seq2); (void)hipFree(s->d_nmask); (void)hipFree(s->d_boff); (void)hipFree(s->d_len);
+    if (s->d_qual) (void)hipFree(s->d_qual);
     delete s;
 }
 extern "C" int64_t telr_seqset_bases(const telr_seqset *s) { return s ? s->total_bases : 0; }
 extern "C" int32_t telr_seqset_count(const telr_seqset *s) { return s ? s->n : 0; }
+extern "C" int telr_seqset_has_qual(const telr_seqset *s) { return s && s->d_qual ? 1 : 0; }
 
 // ---------------------------------------------------------------------------------------
 // rocPRIM plumbing (scans and sorts are library calls; the hot kernels are in kernels.hip.h)
@@ -2819,6 +2822,93 @@ extern "C" int telr_depth_medians(telr_ctx *ctx, const telr_result *r, int32_t n
 }
 
 // ---------------------------------------------------------------------------------------
+// Base qualities of a sequence set (FASTQ -> QUAL of the device BAM writer, bam_dev.hip.h).  One byte per base, the Phred
+// value, in the set's own base layout: sequence i at byte boff[i] (a multiple of 64), so the writer indexes it with the qboff
+// it has.  The ASCII goes up in chunks of 32 MB through two pinned staging buffers (checked on the host while it is staged);
+// a small kernel subtracts the offset and puts every read's piece at its padded place.
+#define QUAL_CHUNK ((size_t)32 << 20)
+struct EvBagQ { hipEvent_t v[2] = { nullptr, nullptr }; ~EvBagQ() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); } };
+// one workgroup per read that has bytes in the chunk [c0, c1) of the unpadded concatenation (coff: its offsets)
+__global__ void __launch_bounds__(256) k_qual_place(const uint8_t *__restrict__ stage, int64_t c0, int64_t c1, const int64_t *__restrict__ coff, const int64_t *__restrict__ boff,
+                                                    int32_t i0, uint32_t sub, uint8_t *__restrict__ qual)
+{
+    const int i = i0 + (int)blockIdx.x, t = threadIdx.x;
+    const int64_t r0 = coff[i], r1 = coff[i + 1];
+    const int64_t a = r0 > c0 ? r0 : c0, b = r1 < c1 ? r1 : c1;
+    if (a >= b) return;
+    const uint8_t *__restrict__ src = stage + (a - c0);
+    uint8_t *dst = qual + boff[i] + (a - r0);
+    const int64_t n = b - a;
+    // head bytes up to a dword of the destination, dwords, tail bytes (the source is a packed line: not aligned with it)
+    const int64_t head = (int64_t)((4 - ((uintptr_t)dst & 3)) & 3), nh = head < n ? head : n, body = (n - nh) >> 2;
+    if (t < nh) dst[t] = (uint8_t)(src[t] - sub);
+    uint32_t *d4 = (uint32_t*)(dst + nh);
+    for (int64_t k = t; k < body; k += 256) {
+        const uint8_t *q = src + nh + 4 * k;
+        d4[k] = ((uint32_t)q[0] - sub) | ((uint32_t)q[1] - sub) << 8 | ((uint32_t)q[2] - sub) << 16 | ((uint32_t)q[3] - sub) << 24;      // every byte >= sub (checked by the host)
+    }
+    const int64_t tail0 = nh + 4 * body;
+    if (t < 4 && tail0 + t < n) dst[tail0 + t] = (uint8_t)(src[tail0 + t] - sub);
+}
+extern "C" int telr_seqset_attach_qual(telr_ctx *ctx, telr_seqset *s, const char *qual_ascii, const int64_t *qual_off, int32_t phred_offset)
+{
+    (void)hipGetLastError();
+    if (!ctx || !s || phred_offset < 0 || phred_offset > 255 - 93 || (s->total_bases > 0 && (!qual_ascii || !qual_off))) return TELR_E_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (s->d_qual) { HIPCHK(hipFree(s->d_qual)); s->d_qual = nullptr; }      // attached again: the new values replace the old
+    const int32_t n = s->n;
+    std::vector<int64_t> coff((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) coff[i + 1] = coff[i] + s->len[i];
+    const int64_t tot = coff[n];
+    uint8_t *d_q = nullptr, *d_stage, *h_stage; int64_t *d_coff;
+    TRY(ctx_hbuf_t(ctx, "qual_stage", 2 * QUAL_CHUNK, &h_stage));
+    TRY(ctx_buf_t(ctx, "qual_dstage", 2 * QUAL_CHUNK, &d_stage));
+    TRY(ctx_buf_t(ctx, "qual_coff", (size_t)n + 1, &d_coff));
+    // (64 bytes behind the last sequence: the writer assembles a dword from the two aligned dwords around it)
+    { hipError_t e = hipMalloc(&d_q, (size_t)s->padded_bases + 64); if (e != hipSuccess) { ctx->err = std::string("seqset qualities: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? TELR_E_NOMEM : TELR_E_HIP; } }
+    EvBagQ ev;
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); (void)hipFree(d_q); return rc; };
+    auto hipfail = [&](hipError_t e) { ctx->err = std::string("seqset qualities: ") + hipGetErrorString(e); return fail(e == hipErrorOutOfMemory ? TELR_E_NOMEM : TELR_E_HIP); };
+    hipError_t e;
+    for (int k = 0; k < 2; ++k) if ((e = hipEventCreateWithFlags(&ev.v[k], hipEventDisableTiming)) != hipSuccess) return hipfail(e);
+    if ((e = hipMemsetAsync(d_q, 0, (size_t)s->padded_bases + 64, st)) != hipSuccess) return hipfail(e);
+    if ((e = hipMemcpyAsync(d_coff, coff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st)) != hipSuccess) return hipfail(e);
+    const unsigned char lo = (unsigned char)phred_offset, span = 93;
+    int chunk = 0;
+    for (int64_t c0 = 0; c0 < tot; c0 += (int64_t)QUAL_CHUNK, ++chunk) {
+        const int64_t c1 = std::min<int64_t>(tot, c0 + (int64_t)QUAL_CHUNK);
+        const int slot = chunk & 1;
+        if (chunk >= 2 && (e = hipEventSynchronize(ev.v[slot])) != hipSuccess) return hipfail(e);      // the kernel that read this slot last is done
+        // reads with bytes in [c0, c1): the last one starting at or before c0 .. the last one starting before c1
+        const int i0 = (int)(std::upper_bound(coff.begin(), coff.end(), c0) - coff.begin()) - 1;
+        const int i1 = (int)(std::lower_bound(coff.begin(), coff.end(), c1) - coff.begin());
+        uint8_t *h = h_stage + (size_t)slot * QUAL_CHUNK;
+        std::atomic<bool> bad{false};
+        parallel_ranges(host_threads(), i1 - i0, [&](int, int x0, int x1) {
+            bool b_ = false;
+            for (int i = i0 + x0; i < i0 + x1; ++i) {
+                const int64_t a = std::max(coff[i], c0), b = std::min(coff[i + 1], c1);
+                if (a >= b) continue;
+                const unsigned char *src = (const unsigned char*)qual_ascii + qual_off[i] + (a - coff[i]);
+                unsigned char *dst = h + (a - c0);
+                unsigned char over = 0;
+                for (int64_t x = 0; x < b - a; ++x) { const unsigned char c = src[x]; dst[x] = c; over |= (unsigned char)((unsigned char)(c - lo) > span); }
+                b_ |= over != 0;
+            }
+            if (b_) bad = true;
+        });
+        if (bad.load()) { ctx->err = "seqset qualities: a byte outside phred_offset .. phred_offset + 93"; return fail(TELR_E_ARG); }
+        if ((e = hipMemcpyAsync(d_stage + (size_t)slot * QUAL_CHUNK, h, (size_t)(c1 - c0), hipMemcpyHostToDevice, st)) != hipSuccess) return hipfail(e);
+        hipLaunchKernelGGL(k_qual_place, dim3((unsigned)(i1 - i0)), dim3(256), 0, st, d_stage + (size_t)slot * QUAL_CHUNK, c0, c1, d_coff, s->d_boff, (int32_t)i0, (uint32_t)lo, d_q);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev.v[slot], st)) != hipSuccess) return hipfail(e);
+    }
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hipfail(e);
+    s->d_qual = d_q;
+    return TELR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // PAF / SAM emitters (host).  The reference's call sites consume PAF columns 0,1,4,5,7,8,9,10,11
 // (TELR_liftover.py:215-240,356-380; TELR_te.py:89-95,136-142) and SAM records with NM/MD/AS/SA/cs
 // (hand-off H1: Sniffles, samtools depth, pysam; docs/02_Usage.md:76).
@@ -2868,12 +2958,24 @@ extern "C" int telr_write_paf(const telr_result *r, const char *const *qnames, c
     return TELR_OK;
 }
 
-extern "C" int telr_write_sam(const telr_result *r, int32_t n_queries, const char *const *qnames, const char *q_ascii, const int64_t *q_off,
-                              const int32_t *q_len, int32_t n_targets, const char *const *tnames, const char *t_ascii, const int64_t *t_off,
-                              const int32_t *t_len, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb,
-                              const char *pg_line, const char *path)
+// read q's quality characters as SAM prints them (Phred + 33), in the read's own direction; false: one of them is outside
+// phred_offset .. phred_offset + 93
+static bool qual_text(const char *q_qual, const int64_t *q_qual_off, int32_t phred_offset, int q, int ql, std::string &out)
+{
+    out.resize((size_t)ql);
+    const unsigned char *src = (const unsigned char*)q_qual + q_qual_off[q];
+    bool ok = true;
+    for (int x = 0; x < ql; ++x) { const int v = (int)src[x] - phred_offset; ok &= v >= 0 && v <= 93; out[x] = (char)(v + 33); }
+    return ok;
+}
+extern "C" int telr_write_sam_qual(const telr_result *r, int32_t n_queries, const char *const *qnames, const char *q_ascii, const int64_t *q_off,
+                                   const int32_t *q_len, int32_t n_targets, const char *const *tnames, const char *t_ascii, const int64_t *t_off,
+                                   const int32_t *t_len, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb,
+                                   const char *pg_line, const char *path, const char *q_qual, const int64_t *q_qual_off, int32_t phred_offset)
 {
     if (!r || !qnames || !q_ascii || !q_off || !q_len || !tnames || !t_ascii || !t_off || !t_len) return TELR_E_ARG;
+    if (q_qual && (!q_qual_off || phred_offset < 0 || phred_offset > 255 - 93)) return TELR_E_ARG;
+    if (q_qual) { std::string t; for (int q = 0; q < n_queries; ++q) if (!qual_text(q_qual, q_qual_off, phred_offset, q, q_len[q], t)) return TELR_E_ARG; }      // before the file is opened
     result_wait(r);
     FILE *f = path ? fopen(path, "w") : stdout;
     if (!f) return TELR_E_ARG;
@@ -2892,14 +2994,16 @@ extern "C" int telr_write_sam(const telr_result *r, int32_t n_queries, const cha
     // records are sorted by (qid, rank); group per query
     const size_t n = r->alns.size();
     size_t i = 0;
-    std::string seq, rc, line, md, cs, sa;
+    std::string seq, rc, line, md, cs, sa, qfw, qrv;
     for (int q = 0; q < n_queries; ++q) {
         size_t j = i;
         while (j < n && r->alns[j].qid == q) ++j;
         const char *qs = q_ascii + q_off[q]; const int ql = q_len[q];
+        if (q_qual) { qual_text(q_qual, q_qual_off, phred_offset, q, ql, qfw); qrv.assign(qfw.rbegin(), qfw.rend()); }
         if (j == i) {
             if (!(flags & TELR_SAM_NO_UNMAPPED)) {
-                line.clear(); line += qnames[q]; line += "\t4\t*\t0\t0\t*\t*\t0\t0\t"; line.append(qs, (size_t)ql); line += "\t*";
+                line.clear(); line += qnames[q]; line += "\t4\t*\t0\t0\t*\t*\t0\t0\t"; line.append(qs, (size_t)ql); line += '\t';
+                if (q_qual && ql > 0) line += qfw; else line += '*';
                 if (rg_id) { line += "\tRG:Z:"; line += rg_id; }
                 line += '\n';
                 emit(INT64_MAX, line);
@@ -2960,7 +3064,10 @@ extern "C" int telr_write_sam(const telr_result *r, int32_t n_queries, const cha
             if (sec) line += '*';
             else if (hard) line.append(qstr + clip5, (size_t)(ql - clip5 - clip3));
             else line.append(qstr, (size_t)ql);
-            line += "\t*";
+            // QUAL: the qualities of the bases SEQ holds, in its orientation; '*' where there is none
+            const int q_lo = hard ? clip5 : 0, q_n = sec ? 0 : (hard ? ql - clip5 - clip3 : ql);
+            line += '\t';
+            if (q_qual && q_n > 0) line.append((rev ? qrv : qfw).data() + q_lo, (size_t)q_n); else line += '*';
             snprintf(buf, sizeof(buf), "\tNM:i:%d\tAS:i:%d", nm, a.dp_score); line += buf;
             if (flags & TELR_SAM_MD) { line += "\tMD:Z:"; line += md; }
             if (flags & TELR_SAM_CS) { line += "\tcs:Z:"; line += cs; }
@@ -3000,6 +3107,13 @@ extern "C" int telr_write_sam(const telr_result *r, int32_t n_queries, const cha
     }
     if (path) fclose(f);
     return TELR_OK;
+}
+extern "C" int telr_write_sam(const telr_result *r, int32_t n_queries, const char *const *qnames, const char *q_ascii, const int64_t *q_off,
+                              const int32_t *q_len, int32_t n_targets, const char *const *tnames, const char *t_ascii, const int64_t *t_off,
+                              const int32_t *t_len, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb,
+                              const char *pg_line, const char *path)
+{
+    return telr_write_sam_qual(r, n_queries, qnames, q_ascii, q_off, q_len, n_targets, tnames, t_ascii, t_off, t_len, flags, rg_id, rg_sm, rg_lb, pg_line, path, nullptr, nullptr, 0);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3042,12 +3156,21 @@ static bool bgzf_block(const char *src, size_t n, int level, std::string &out)
     return true;
 }
 
-extern "C" int telr_write_bam(const telr_result *r, int32_t n_queries, const char *const *qnames, const char *q_ascii, const int64_t *q_off,
-                              const int32_t *q_len, int32_t n_targets, const char *const *tnames, const char *t_ascii, const int64_t *t_off,
-                              const int32_t *t_len, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb,
-                              const char *pg_line, const char *bam_path, int32_t write_index, int32_t level)
+extern "C" int telr_write_bam_qual(const telr_result *r, int32_t n_queries, const char *const *qnames, const char *q_ascii, const int64_t *q_off,
+                                   const int32_t *q_len, int32_t n_targets, const char *const *tnames, const char *t_ascii, const int64_t *t_off,
+                                   const int32_t *t_len, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb,
+                                   const char *pg_line, const char *bam_path, int32_t write_index, int32_t level,
+                                   const char *q_qual, const int64_t *q_qual_off, int32_t phred_offset)
 {
     if (!r || !qnames || !q_ascii || !q_off || !q_len || !tnames || !t_ascii || !t_off || !t_len || !bam_path) return TELR_E_ARG;
+    if (q_qual && (!q_qual_off || phred_offset < 0 || phred_offset > 255 - 93)) return TELR_E_ARG;
+    if (q_qual) { std::string t; for (int q = 0; q < n_queries; ++q) if (!qual_text(q_qual, q_qual_off, phred_offset, q, q_len[q], t)) return TELR_E_ARG; }
+    // QUAL of a record: Phred values (not + 33) of SEQ's bases in SEQ's orientation; 0xff without qualities
+    auto put_qual = [&](std::string &o, int q, int ql, bool rev, int seq_lo, int l_seq) {
+        if (!q_qual) { o.append((size_t)l_seq, (char)0xff); return; }
+        const unsigned char *src = (const unsigned char*)q_qual + q_qual_off[q];
+        for (int x = 0; x < l_seq; ++x) o += (char)(src[rev ? ql - 1 - (seq_lo + x) : seq_lo + x] - phred_offset);
+    };
     result_wait(r);
     const size_t n = r->alns.size();
     // --- 1. binary records (one per alignment + one per unmapped read), built in parallel over queries
@@ -3159,7 +3282,7 @@ extern "C" int telr_write_bam(const telr_result *r, int32_t n_queries, const cha
                 if (long_cigar) { put32(o, (uint32_t)l_seq << 4 | 4u); put32(o, (uint32_t)(a.te - a.ts) << 4 | 3u); }
                 else o.append((const char*)bc.data(), bc.size() * 4);
                 for (int x = 0; x < l_seq; x += 2) { uint8_t hi = nt16(qstr[seq_lo + x]), lo2 = x + 1 < l_seq ? nt16(qstr[seq_lo + x + 1]) : 0; o += (char)(hi << 4 | lo2); }
-                o.append((size_t)l_seq, (char)0xff);
+                put_qual(o, q, ql, rev, seq_lo, l_seq);
                 o += tagbuf;
                 uint32_t bs = (uint32_t)o.size() - 4; memcpy(&o[0], &bs, 4);
                 key[k] = ((int64_t)(a.tid + 1) << 33) | (int64_t)(uint32_t)a.ts << 1 | (rev ? 1 : 0);
@@ -3175,7 +3298,7 @@ extern "C" int telr_write_bam(const telr_result *r, int32_t n_queries, const cha
         put32(o, (uint32_t)ql); put32(o, (uint32_t)-1); put32(o, (uint32_t)-1); put32(o, 0);
         o.append(qnames[q], l_name);
         for (int x = 0; x < ql; x += 2) { uint8_t hi = nt16(qs[x]), lo2 = x + 1 < ql ? nt16(qs[x + 1]) : 0; o += (char)(hi << 4 | lo2); }
-        o.append((size_t)ql, (char)0xff);
+        put_qual(o, q, ql, false, 0, ql);
         if (rg_id) { o += "RGZ"; o += rg_id; o += '\0'; }
         uint32_t bs = (uint32_t)o.size() - 4; memcpy(&o[0], &bs, 4);
         key[n + u] = INT64_MAX;
@@ -3265,6 +3388,14 @@ extern "C" int telr_write_bam(const telr_result *r, int32_t n_queries, const cha
     fwrite(bai.data(), 1, bai.size(), f);
     fclose(f);
     return TELR_OK;
+}
+extern "C" int telr_write_bam(const telr_result *r, int32_t n_queries, const char *const *qnames, const char *q_ascii, const int64_t *q_off,
+                              const int32_t *q_len, int32_t n_targets, const char *const *tnames, const char *t_ascii, const int64_t *t_off,
+                              const int32_t *t_len, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb,
+                              const char *pg_line, const char *bam_path, int32_t write_index, int32_t level)
+{
+    return telr_write_bam_qual(r, n_queries, qnames, q_ascii, q_off, q_len, n_targets, tnames, t_ascii, t_off, t_len, flags, rg_id, rg_sm, rg_lb, pg_line, bam_path, write_index, level,
+                               nullptr, nullptr, 0);
 }
 
 #include "bam_dev.hip.h"

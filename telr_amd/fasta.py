@@ -7,24 +7,27 @@ def _open(path):
     return gzip.open(path, "rt") if str(path).endswith(".gz") else open(path, "r")
 
 
-def read_fasta(path):
-    """-> (names, seqs) ; FASTA or FASTQ, header truncated at first whitespace."""
-    names, seqs = [], []
+def read_fasta(path, with_qual=False):
+    """-> (names, seqs) ; FASTA or FASTQ, header truncated at first whitespace.
+    with_qual: -> (names, seqs, quals), quals = the quality lines of a FASTQ (str, as in the file), None for a FASTA."""
+    names, seqs, quals = [], [], None
     with _open(path) as fh:
         first = fh.read(1)
         if not first:
-            return names, seqs
+            return (names, seqs, quals) if with_qual else (names, seqs)
         fh.seek(0)
         if first == "@":
+            quals = []
             while True:
                 h = fh.readline()
                 if not h:
                     break
                 s = fh.readline().strip()
                 fh.readline()
-                fh.readline()
+                q = fh.readline()
                 names.append(h[1:].split()[0])
                 seqs.append(s)
+                quals.append(q.strip("\r\n"))
         else:
             cur = []
             for line in fh:
@@ -37,7 +40,7 @@ def read_fasta(path):
                     cur.append(line.strip())
             if names:
                 seqs.append("".join(cur))
-    return names, seqs
+    return (names, seqs, quals) if with_qual else (names, seqs)
 
 
 def concat(seqs):
@@ -63,7 +66,9 @@ def revcomp(s):
 class FastaFile:
     """A FASTA / FASTQ file parsed by the library (telr_fasta_load: worker threads over the mapped file) into the arrays the C
     ABI takes.  `.triple` = (base buffer, offsets, lengths) as numpy views of library memory (valid while this object lives),
-    `.names_c` = the C array of names for the writers, `.names` = the same as Python strings (built on first use)."""
+    `.names_c` = the C array of names for the writers, `.names` = the same as Python strings (built on first use),
+    `.qual` = (quality buffer, offsets) of a FASTQ -- record i's quality characters are buffer[offsets[i]:offsets[i] + len[i]],
+    views of the mapped file or of the library's copy -- or None for a FASTA (telr_fasta_qual)."""
 
     def __init__(self, path):
         import ctypes as C
@@ -85,6 +90,9 @@ class FastaFile:
         self.triple = (view(self.L.telr_fasta_seq(h), nb, np.uint8), view(self.L.telr_fasta_off(h), self.n, np.int64), view(self.L.telr_fasta_len(h), self.n, np.int32))
         self.names_c = C.cast(self.L.telr_fasta_names(h), C.POINTER(C.c_char_p * max(1, self.n))).contents if self.n else (C.c_char_p * 1)()
         self._names = None
+        qp = self.L.telr_fasta_qual(h)
+        # in place the qualities lie in the mapped file (`extent` bytes), else right behind the packed bases
+        self.qual = (view(qp, max(nb, self.bases), np.uint8), view(self.L.telr_fasta_qual_off(h), self.n, np.int64)) if qp else None
 
     @property
     def names(self):
@@ -96,9 +104,17 @@ class FastaFile:
         buf, off, ln = self.triple
         return [bytes(buf[off[i]:off[i] + ln[i]]).decode() for i in range(self.n)]
 
+    def quals(self):
+        """the quality lines as Python strings (None for a FASTA)"""
+        if self.qual is None:
+            return None
+        buf, off = self.qual
+        ln = self.triple[2]
+        return [bytes(buf[off[i]:off[i] + ln[i]]).decode("latin-1") for i in range(self.n)]
+
     def close(self):
         if getattr(self, "h", None):
-            self.triple = None; self.names_c = None
+            self.triple = None; self.names_c = None; self.qual = None
             self.L.telr_fasta_free(self.h); self.h = None
 
     def __del__(self):

@@ -40,8 +40,11 @@ def wait_release():
 atexit.register(wait_release)
 
 
-def alignment(bam, read, reference, out, sample_name, thread, method, presets, engine=None, chain_skip=False, seed_rescue=False, mm2_mapq=False):
-    """chain_skip (minimap2 branch only): minimap2's own chaining scan (presets.preset(..., chain_skip=True)), not the fixed look-back.
+def alignment(bam, read, reference, out, sample_name, thread, method, presets, engine=None, chain_skip=False, seed_rescue=False, mm2_mapq=False,
+              keep_qual=False):
+    """keep_qual: carry the base qualities of a FASTQ `read` file into QUAL of the BAM, as ngmlr and `minimap2 -a` do (1 byte of
+    device memory per read base, a level-1 BAM of about 1.55 times the size for ONT-shaped qualities: 0.81 -> 1.26 bytes per read base); a FASTA has none and gives the same file either way.  Default: QUAL 0xff.
+    chain_skip (minimap2 branch only): minimap2's own chaining scan (presets.preset(..., chain_skip=True)), not the fixed look-back.
     seed_rescue, mm2_mapq (minimap2 branch only): minimap2's high-occurrence seed rescue and its own MAPQ (presets.preset)"""
     logging.info("Start alignment...")
     start_time = time.time()
@@ -72,19 +75,24 @@ def alignment(bam, read, reference, out, sample_name, thread, method, presets, e
         tn, ts = tf.names_c, tf.triple
     else:
         tn, ts = read_fasta(reference)
+    qq = None
     if qf is not None:
         qn, qs, n_bases = qf.names_c, qf.triple, int(qf.triple[2].sum())
+        if keep_qual:
+            qq = qf.qual
     else:
-        qn, qs = read_fasta(read)
+        qn, qs, qq = read_fasta(read, with_qual=True)
         n_bases = sum(len(x) for x in qs)
+        if not keep_qual:
+            qq = None
     with_cs = method == "minimap2"
     tm["parse_files"] = time.time() - t0; t0 = time.time()
     ix = eng.index(ts, io)
     tm["pack_reference_build_index"] = time.time() - t0; t0 = time.time()
-    qset = eng.seqset(qs)
+    qset = eng.seqset(qs, qual=qq)
     tm["pack_upload_reads"] = time.time() - t0; t0 = time.time()
-    # about 0.85 bytes of BAM per read base with --cs --MD, 0.6 without cs, at level 1
-    ix.bam_prepare(bam, int((0.95 if with_cs else 0.7) * n_bases) + (64 << 20))
+    # about 0.85 bytes of BAM per read base with --cs --MD, 0.6 without cs, at level 1; qualities add their entropy (0.45 measured for ONT-shaped ones, at most 0.82: 6.55 bits)
+    ix.bam_prepare(bam, int(((0.95 if with_cs else 0.7) + (0.85 if qq is not None else 0)) * n_bases) + (64 << 20))
     mo.flags |= MF_KEEP_CIGARS                   # the CIGAR array stays on the device as well: the BAM writer reads it there
     r = None
     try:
