@@ -57,6 +57,8 @@ def lib():
                               C.POINTER(i32), C.POINTER(i32)]
         L.tor_debug_dp.restype = i32
         L.tor_debug_dp.argtypes = [vp, vp, vp, vp, C.POINTER(MapOpt), vp, i32, vp, vp, i64]
+        L.tor_debug_backtrack.restype = i32
+        L.tor_debug_backtrack.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(MapOpt), vp, vp, vp, vp, vp, vp, vp, i64, vp]
         L.tor_depth_medians.argtypes = [vp, i64, vp, i32, vp, i32, vp, vp, vp, vp]
         L.tor_consensus.restype = i64; L.tor_consensus.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, vp, i64, vp, vp]
         L.tor_poa.restype = i64; L.tor_poa.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, vp, i64, vp, vp]
@@ -219,3 +221,28 @@ def debug_dp(queries, targets, mo, probs):
     out = {k: res[:, i].copy() for i, k in enumerate(("score", "bi", "bj", "touched"))}
     out["cigars"] = [cig[res[x, 5]:res[x, 5] + res[x, 4]].copy() for x in range(npb)]
     return out
+
+
+def debug_backtrack(keys, q_aoff, f, p, qlen, goff, tlen, mo):
+    """the oracle's back-tracking (chain_backtrack), pass-1 selection (select_chains) and DP problem list (chain_problems, what
+    align_chain runs) on anchor lists with their chaining scores: same input and output as Engine.debug_backtrack"""
+    K = np.ascontiguousarray(keys, dtype=np.uint64)
+    O = np.ascontiguousarray(q_aoff, dtype=np.int32)
+    F = np.ascontiguousarray(f, dtype=np.int32); P = np.ascontiguousarray(p, dtype=np.int32)
+    QL = np.ascontiguousarray(qlen, dtype=np.int32)
+    G = np.ascontiguousarray(goff, dtype=np.uint32); TL = np.ascontiguousarray(tlen, dtype=np.int32)
+    nq, nt, na = len(O) - 1, len(TL), len(K)
+    if nq < 1 or int(O[0]) != 0 or int(O[-1]) != na or len(F) != na or len(P) != na or len(QL) != nq or len(G) != nt + 1:
+        raise ValueError("array lengths: q_aoff nq + 1 from 0 to len(keys), f / p one per key, qlen nq, goff n_targets + 1")
+    cap = 3 * na + 8
+    ch_off = np.zeros(nq + 1, np.int32); chains = np.zeros((na + 1, 9), np.int32); ch_aoff = np.zeros(na + 2, np.int32)
+    canch = np.zeros(na + 1, np.uint64); kept = np.zeros((na + 1, 10), np.int32); prob_off = np.zeros(na + 2, np.int32)
+    probs = np.zeros((cap, 12), np.int32); n_out = np.zeros(3, np.int64)
+    rc = lib().tor_debug_backtrack(nq, O.ctypes.data, K.ctypes.data, F.ctypes.data, P.ctypes.data, QL.ctypes.data, nt, G.ctypes.data,
+                                   TL.ctypes.data, C.byref(mo), ch_off.ctypes.data, chains.ctypes.data, ch_aoff.ctypes.data,
+                                   canch.ctypes.data, kept.ctypes.data, prob_off.ctypes.data, probs.ctypes.data, cap, n_out.ctypes.data)
+    if rc != 0:
+        raise ValueError("tor_debug_backtrack: the problem list does not fit")
+    nch, nk, npb = (int(v) for v in n_out)
+    return dict(chains=chains[:nch].copy(), ch_off=ch_off, ch_aoff=ch_aoff[:nch + 1].copy(), canch=canch[:int(ch_aoff[nch])].copy(),
+                kept=kept[:nk].copy(), prob_off=prob_off[:nk + 1].copy(), probs=probs[:npb].copy())

@@ -1090,69 +1090,104 @@ int32_t tor_debug_dp(const char *qascii, const int64_t *qoff, const char *tascii
     return 0;
 }
 
+/* The DP problems of one chain, in the order align_chain runs them (and tor_debug_backtrack reports them): the left extension
+ * (kind 1) when the chain starts inside both sequences, one fill per pair of consecutive breakpoints -- the greedy cuts: an
+ * anchor at least min_ksw_len past the last cut on BOTH axes, and always the last anchor -- as kind 0 (band_dp), 5 (long-gap
+ * fill: |n - m| > bw under bw_long > bw) or 3 (diagonal fall-back: a band wider than DP_DMAX), and the right extension (kind 2)
+ * when the chain ends inside both.  q_off / t_off: the sequence offset of DP base 0 (the window runs down from it when its step
+ * is -1); W / is_long: the first-pass band and whether the fill took the wide band at once (what the second pass looks at). */
+typedef struct { int32_t q_off, t_off, m, n, dlo, dhi, kind, qstep, tstep, W, is_long; } cprob_t;
+typedef VEC(cprob_t) cprobv_t;
+static void chain_problems(const chain_t *c, const uint64_t *ca, int32_t go, int qlen, int tlen, const telr_map_opt *mo, cprobv_t *out)
+{
+    /* TELR_MF_FAITHFUL (oracle only): no speed-motivated bounds -- gap fills over the whole -r band, end extensions over
+     * the whole remaining read in a band of -r diagonals (still z-drop terminated), chaining look-back 5000.  The drift of
+     * the tuned presets against this mode is gated by tests/test_faithful_gate.py. */
+    const int faithful = (mo->flags & (TELR_MF_FAITHFUL | 0x200)) != 0, faithful_ext = (mo->flags & (TELR_MF_FAITHFUL | 0x400)) != 0;
+    const int ext_max = faithful_ext ? (1 << 30) : mo->ext_max, ext_band = faithful_ext ? mo->bw : mo->ext_band;
+    cprob_t P; memset(&P, 0, sizeof(P));
+    const int32_t r0 = c->rs, q0 = c->qs;
+    /* left extension: reversed sequences starting at (q0-1, r0-1) going down */
+    if (q0 > 0 && r0 > 0) {
+        int mq = q0 < ext_max ? q0 : ext_max, mt = r0 < mq + ext_band ? r0 : mq + ext_band;
+        P.m = mq; P.n = mt; P.tstep = -1; P.t_off = r0 - 1; P.kind = 1; P.dlo = even_lo(-ext_band); P.dhi = ext_band; P.W = 0; P.is_long = 0;
+        if (c->rev) { P.qstep = 1; P.q_off = qlen - q0; } else { P.qstep = -1; P.q_off = q0 - 1; }
+        vpush(cprob_t, *out, P);
+    }
+    int32_t lr = r0, lq = q0;
+    for (int32_t i = 0; i < c->cnt; ++i) {
+        int32_t cr = A_G(ca[i]) - go + 1, cq = A_Q(ca[i]) + 1;
+        if (!(i == c->cnt - 1 || (cq - lq >= mo->min_ksw_len && cr - lr >= mo->min_ksw_len))) continue;
+        const int32_t sr = lr, sq = lq;
+        lr = cr; lq = cq;
+        P.m = cq - sq; P.n = cr - sr; P.tstep = 1; P.t_off = sr;
+        if (c->rev) { P.qstep = -1; P.q_off = qlen - 1 - sq; } else { P.qstep = 1; P.q_off = sq; }
+        /* long segments are few and a second pass over one of them is slow: they take the wide band at once */
+        P.is_long = P.m + P.n > ADAPT_MAX_STEPS;
+        int W = P.is_long ? fill_band_wide(P.m, P.n, mo) : fill_band(P.m, P.n, mo), dl = P.n - P.m;
+        if (faithful) W = mo->bw;               /* the whole -r band, whatever the segment */
+        int lo = even_lo((dl < 0 ? dl : 0) - W), hi = (dl > 0 ? dl : 0) + W;
+        if (faithful) { if (lo < -P.m) lo = even_lo(-P.m); if (hi > P.n) hi = P.n; }      /* no wider than the matrix */
+        P.W = W; P.dlo = lo; P.dhi = hi; P.kind = 0;
+        if (mo->bw_long > mo->bw && (dl > mo->bw || -dl > mo->bw)) { P.kind = 5; P.dlo = even_lo(-ext_band); P.dhi = ext_band; }      /* two bands of the extension width (longgap_fill) */
+        else if (!faithful && hi - lo + 1 > DP_DMAX) P.kind = 3;
+        vpush(cprob_t, *out, P);
+    }
+    if (c->qe < qlen && c->re < tlen) {
+        int rq = qlen - c->qe, rt = tlen - c->re;
+        int mq = rq < ext_max ? rq : ext_max, mt = rt < mq + ext_band ? rt : mq + ext_band;
+        P.m = mq; P.n = mt; P.tstep = 1; P.t_off = c->re; P.kind = 2; P.dlo = even_lo(-ext_band); P.dhi = ext_band; P.W = 0; P.is_long = 0;
+        if (c->rev) { P.qstep = -1; P.q_off = qlen - 1 - c->qe; } else { P.qstep = 1; P.q_off = c->qe; }
+        vpush(cprob_t, *out, P);
+    }
+}
+
 /* align one chain; fills the alignment fields of `al` and appends the CIGAR */
 static void align_chain(const tor_index *ix, const uint8_t *q, int qlen, const chain_t *c, const uint64_t *ca,
                         const telr_map_opt *mo, telr_aln *al, u32v_t *cigars, telr_counters *ctr)
 {
     const uint8_t *t = ix->seq[c->tid];
     const int tlen = ix->len[c->tid], go = (int32_t)ix->goff[c->tid];
-    /* TELR_MF_FAITHFUL (oracle only): no speed-motivated bounds -- gap fills over the whole -r band, end extensions over
-     * the whole remaining read in a band of -r diagonals (still z-drop terminated), chaining look-back 5000.  The drift of
-     * the tuned presets against this mode is gated by tests/test_faithful_gate.py. */
-    const int faithful = (mo->flags & (TELR_MF_FAITHFUL | 0x200)) != 0, faithful_ext = (mo->flags & (TELR_MF_FAITHFUL | 0x400)) != 0;
-    const int ext_max = faithful_ext ? (1 << 30) : mo->ext_max, ext_band = faithful_ext ? mo->bw : mo->ext_band;
+    const int faithful = (mo->flags & (TELR_MF_FAITHFUL | 0x200)) != 0;
     convex_t CX; const int cx = (mo->cx_scale > 0 || (mo->flags & MFX_CONVEX)) && convex_of(mo, &CX);       /* segment scores come back in 1/S units */
     /* query accessor on the chain's strand */
     dp_seq_t s; s.q = q; s.t = t; s.qcomp = c->rev;
-    /* breakpoints */
-    VEC(int32_t) bp = {0, 0, 0};
-    int32_t r0 = c->rs, q0 = c->qs;
-    vpush(int32_t, bp, r0); vpush(int32_t, bp, q0);
-    int32_t lr = r0, lq = q0;
-    for (int32_t i = 0; i < c->cnt; ++i) {
-        int32_t cr = A_G(ca[i]) - go + 1, cq = A_Q(ca[i]) + 1;
-        if (i == c->cnt - 1 || (cq - lq >= mo->min_ksw_len && cr - lr >= mo->min_ksw_len)) {
-            vpush(int32_t, bp, cr); vpush(int32_t, bp, cq); lr = cr; lq = cq;
-        }
-    }
-    int nseg = (int)(bp.n / 2) - 1;
+    cprobv_t pv = {0, 0, 0};
+    chain_problems(c, ca, go, qlen, tlen, mo, &pv);
     u32v_t cig = {0, 0, 0}, rc = {0, 0, 0};
     int32_t dp = 0, n_zdrop = 0;
-    /* left extension: reversed sequences starting at (q0-1, r0-1) going down */
-    int32_t qs = q0, rs = r0;
-    if (q0 > 0 && r0 > 0) {
-        int mq = q0 < ext_max ? q0 : ext_max, mt = r0 < mq + ext_band ? r0 : mq + ext_band;
-        s.m = mq; s.n = mt; s.tstep = -1; s.ti0 = r0 - 1;
-        if (c->rev) { s.qstep = 1; s.qi0 = qlen - q0; } else { s.qstep = -1; s.qi0 = q0 - 1; }
+    int32_t qs = c->qs, rs = c->rs, qe = c->qe, re = c->re;
+    for (int64_t g = 0; g < pv.n; ++g) {
+        const cprob_t *P = &pv.a[g];
+        s.m = P->m; s.n = P->n; s.tstep = P->tstep; s.ti0 = P->t_off; s.qstep = P->qstep; s.qi0 = P->q_off;
         rc.n = 0;
-        dp_res_t r = band_dp(&s, even_lo(-ext_band), ext_band, 1, mo, &rc);
-        ++ctr->dp_problems; ctr->dp_cells += r.cells; ctr->window_bases += mt;
-        dp += r.score; qs = q0 - r.bi; rs = r0 - r.bj;
-        /* rev_cig is end->start of the reversed problem == left-to-right on the forward sequences */
-        for (int64_t z = 0; z < rc.n; ++z) cig_push(&cig, rc.a[z] & 0xf, rc.a[z] >> 4);
-    }
-    for (int g = 0; g < nseg; ++g) {
-        int32_t sr = bp.a[2 * g], sq = bp.a[2 * g + 1], er = bp.a[2 * g + 2], eq = bp.a[2 * g + 3];
-        s.m = eq - sq; s.n = er - sr; s.tstep = 1; s.ti0 = sr;
-        if (c->rev) { s.qstep = -1; s.qi0 = qlen - 1 - sq; } else { s.qstep = 1; s.qi0 = sq; }
-        /* long segments are few and a second pass over one of them is slow: they take the wide band at once */
-        const int is_long = s.m + s.n > ADAPT_MAX_STEPS;
-        int W = is_long ? fill_band_wide(s.m, s.n, mo) : fill_band(s.m, s.n, mo), dl = s.n - s.m;
-        if (faithful) W = mo->bw;               /* the whole -r band, whatever the segment */
-        rc.n = 0;
-        int lo = even_lo((dl < 0 ? dl : 0) - W), hi = (dl > 0 ? dl : 0) + W, fb_mlen;
-        if (faithful) { if (lo < -s.m) lo = even_lo(-s.m); if (hi > s.n) hi = s.n; }      /* no wider than the matrix */
-        const int longgap = mo->bw_long > mo->bw && (dl > mo->bw || -dl > mo->bw);
-        dp_res_t r = longgap ? longgap_fill(&s, mo, &rc) : (!faithful && hi - lo + 1 > DP_DMAX) ? band_dp_fallback(&s, mo, &rc, &fb_mlen) : band_dp(&s, lo, hi, 0, mo, &rc);
-        if (cx && (longgap || (!faithful && hi - lo + 1 > DP_DMAX))) {
+        if (P->kind == 1) {
+            dp_res_t r = band_dp(&s, P->dlo, P->dhi, 1, mo, &rc);
+            ++ctr->dp_problems; ctr->dp_cells += r.cells; ctr->window_bases += P->n;
+            dp += r.score; qs = c->qs - r.bi; rs = c->rs - r.bj;
+            /* rev_cig is end->start of the reversed problem == left-to-right on the forward sequences */
+            for (int64_t z = 0; z < rc.n; ++z) cig_push(&cig, rc.a[z] & 0xf, rc.a[z] >> 4);
+            continue;
+        }
+        if (P->kind == 2) {
+            dp_res_t r = band_dp(&s, P->dlo, P->dhi, 1, mo, &rc);
+            ++ctr->dp_problems; ctr->dp_cells += r.cells; ctr->window_bases += P->n;
+            dp += r.score; qe += r.bi; re += r.bj;
+            for (int64_t z = rc.n - 1; z >= 0; --z) cig_push(&cig, rc.a[z] & 0xf, rc.a[z] >> 4);
+            continue;
+        }
+        const int is_long = P->is_long, W = P->W, dl = s.n - s.m, longgap = P->kind == 5, fallback = P->kind == 3;
+        int fb_mlen;
+        dp_res_t r = longgap ? longgap_fill(&s, mo, &rc) : fallback ? band_dp_fallback(&s, mo, &rc, &fb_mlen) : band_dp(&s, P->dlo, P->dhi, 0, mo, &rc);
+        if (cx && (longgap || fallback)) {
             /* the diagonal fall-back closes with ONE gap: its convex cost; (a long-gap fill keeps the envelope: telr_map refuses cx_scale with bw_long) */
-            if (!longgap) { int g = s.m > s.n ? s.m - s.n : s.n - s.m, c1 = mo->q + g * mo->e, c2 = mo->q2 + g * mo->e2; r.score = (r.score + (g ? (c1 < c2 ? c1 : c2) : 0)) * CX.S - (g ? (int)cx_cost(&CX, g) : 0); }
+            if (!longgap) { int g_ = s.m > s.n ? s.m - s.n : s.n - s.m, c1 = mo->q + g_ * mo->e, c2 = mo->q2 + g_ * mo->e2; r.score = (r.score + (g_ ? (c1 < c2 ? c1 : c2) : 0)) * CX.S - (g_ ? (int)cx_cost(&CX, g_) : 0); }
             else r.score *= CX.S;
         }
         ++ctr->dp_problems; ctr->dp_cells += r.cells; ctr->window_bases += s.n;
         if (r.touched && !is_long && !faithful && !longgap) {            /* second pass with the wide band */
             int W2 = fill_band_wide(s.m, s.n, mo);
-            lo = even_lo((dl < 0 ? dl : 0) - W2); hi = (dl > 0 ? dl : 0) + W2;
+            int lo = even_lo((dl < 0 ? dl : 0) - W2), hi = (dl > 0 ? dl : 0) + W2;
             if (W2 > W && hi - lo + 1 <= DP_DMAX) { rc.n = 0; r = band_dp(&s, lo, hi, 0, mo, &rc); ctr->dp_cells += r.cells; }
         }
         dp += r.score;
@@ -1181,18 +1216,6 @@ static void align_chain(const tor_index *ix, const uint8_t *q, int qlen, const c
         }
         for (int64_t z = rc.n - 1; z >= 0; --z) cig_push(&cig, rc.a[z] & 0xf, rc.a[z] >> 4);
     }
-    int32_t qe = c->qe, re = c->re;
-    if (qe < qlen && re < tlen) {
-        int rq = qlen - qe, rt = tlen - re;
-        int mq = rq < ext_max ? rq : ext_max, mt = rt < mq + ext_band ? rt : mq + ext_band;
-        s.m = mq; s.n = mt; s.tstep = 1; s.ti0 = re;
-        if (c->rev) { s.qstep = -1; s.qi0 = qlen - 1 - qe; } else { s.qstep = 1; s.qi0 = qe; }
-        rc.n = 0;
-        dp_res_t r = band_dp(&s, even_lo(-ext_band), ext_band, 1, mo, &rc);
-        ++ctr->dp_problems; ctr->dp_cells += r.cells; ctr->window_bases += mt;
-        dp += r.score; qe += r.bi; re += r.bj;
-        for (int64_t z = rc.n - 1; z >= 0; --z) cig_push(&cig, rc.a[z] & 0xf, rc.a[z] >> 4);
-    }
     /* statistics from the final CIGAR */
     int32_t mlen = 0, blen = 0, nambi = 0, qi = qs, ti = rs;
     for (int64_t z = 0; z < cig.n; ++z) {
@@ -1214,7 +1237,81 @@ static void align_chain(const tor_index *ix, const uint8_t *q, int qlen, const c
     al->mlen = mlen; al->blen = blen; al->n_ambi = n_zdrop; al->dp_score = dp; (void)nambi;      /* n_ambi: 0 unless the 0x10000 experiment counts z-dropped fills */
     al->n_cigar = (int32_t)cig.n; al->cigar_off = cigars->n;
     for (int64_t z = 0; z < cig.n; ++z) vpush(uint32_t, *cigars, cig.a[z]);
-    free(cig.a); free(rc.a); free(bp.a);
+    free(cig.a); free(rc.a); free(pv.a);
+}
+
+/* debug entry: what tor_map does between the chaining scores and the banded DP, on a caller's anchor lists -- the engine's test
+ * tap telr_debug_backtrack takes the same input and gives the same output.  In: nq queries, query q's sorted anchors (the 64-bit
+ * layout of A_REV / A_G / A_Q / A_SPAN) at keys[q_aoff[q] .. q_aoff[q + 1]) with their f and p (p relative to the query's first
+ * anchor, -1 for none), qlen[nq], and the targets as their global-offset table goff[n_targets + 1] and tlen[n_targets].
+ * Out: (a) every chain in discovery order as nine ints {qid, score, cnt, rev, tid, rs, re, qs, qe}, ch_off[nq + 1] the queries'
+ * places in that list; (b) the chains' anchors back to back, ch_aoff[n_chain + 1] their places; (c) the chains pass 1 keeps, query
+ * by query in rank order (chain_backtrack, then select_chains on the chain scores, ties by discovery order), as ten ints {qid,
+ * score, cnt, rev, tid, rs, re, qs, qe, row of the chain in (a)}; (d) with TELR_MF_CIGAR the DP problems of every kept chain
+ * (chain_problems: what align_chain runs) as telr_debug_dp rows {qid, q_off, tid, t_off, m, n, dlo, dhi, kind, qstep, tstep,
+ * qcomp}, prob_off[n_kept + 1] their places.  n_out = {chains, kept, problems}.  Returns 0, or -1 when prob_cap rows do not hold
+ * the problems.  The arrays (a) to (c) hold at most one row per anchor. */
+int32_t tor_debug_backtrack(int32_t nq, const int32_t *q_aoff, const uint64_t *keys, const int32_t *f, const int32_t *p, const int32_t *qlen,
+                            int32_t n_targets, const uint32_t *goff, const int32_t *tlen, const telr_map_opt *mo,
+                            int32_t *ch_off, int32_t *chains, int32_t *ch_aoff, uint64_t *canch, int32_t *kept, int32_t *prob_off, int32_t *probs,
+                            int64_t prob_cap, int64_t *n_out)
+{
+    tor_index ix; memset(&ix, 0, sizeof(ix));
+    ix.n_seq = n_targets; ix.goff = (uint32_t*)goff; ix.len = (int32_t*)tlen;
+    int64_t nch = 0, nca = 0, nk = 0, np = 0;
+    int rc = 0;
+    cprobv_t pv = {0, 0, 0};
+    for (int32_t qi = 0; qi < nq && !rc; ++qi) {
+        const int64_t a0 = q_aoff[qi], n_a = q_aoff[qi + 1] - a0;
+        chainv_t ch = {0, 0, 0}; u64v_t ca = {0, 0, 0};
+        chain_backtrack(&ix, keys + a0, n_a, f + a0, p + a0, mo, &ch, &ca);
+        ch_off[qi] = (int32_t)nch;
+        const int n = (int)ch.n;
+        const size_t n1 = n > 0 ? (size_t)n : 1;
+        for (int i = 0; i < n; ++i) {
+            const chain_t *c = &ch.a[i];
+            int32_t v[9] = { qi, c->score, c->cnt, c->rev, c->tid, c->rs, c->re, c->qs, c->qe };
+            memcpy(chains + (nch + i) * 9, v, sizeof(v));
+            ch_aoff[nch + i] = (int32_t)nca;
+            memcpy(canch + nca, ca.a + c->a_off, (size_t)c->cnt * 8);
+            nca += c->cnt;
+        }
+        /* pass 1: selection on chain scores (as tor_map) */
+        sel_t *s = (sel_t*)malloc(sizeof(sel_t) * n1);
+        int32_t *cscore = (int32_t*)malloc(4 * n1);
+        for (int i = 0; i < n; ++i) {
+            const chain_t *c = &ch.a[i];
+            s[i].ci = i; s[i].key = c->score; s[i].ord = c->disc; s[i].tid = c->tid;
+            if (c->rev) { s[i].fs = qlen[qi] - c->qe; s[i].fe = qlen[qi] - c->qs; } else { s[i].fs = c->qs; s[i].fe = c->qe; }
+            cscore[i] = c->score;
+        }
+        if (n) qsort(s, n, sizeof(sel_t), cmp_sel);
+        select_chains(s, n, mo, cscore);
+        for (int i = 0; i < n && !rc; ++i) {
+            if (!s[i].keep) continue;
+            const chain_t *c = &ch.a[s[i].ci];
+            int32_t v[10] = { qi, c->score, c->cnt, c->rev, c->tid, c->rs, c->re, c->qs, c->qe, (int32_t)(nch + s[i].ci) };
+            memcpy(kept + nk * 10, v, sizeof(v));
+            prob_off[nk] = (int32_t)np;
+            ++nk;
+            if (!(mo->flags & TELR_MF_CIGAR)) continue;
+            pv.n = 0;
+            chain_problems(c, ca.a + c->a_off, (int32_t)goff[c->tid], qlen[qi], tlen[c->tid], mo, &pv);
+            if (np + pv.n > prob_cap) { rc = -1; break; }
+            for (int64_t x = 0; x < pv.n; ++x) {
+                const cprob_t *P = &pv.a[x];
+                int32_t w[12] = { qi, P->q_off, c->tid, P->t_off, P->m, P->n, P->dlo, P->dhi, P->kind, P->qstep, P->tstep, c->rev };
+                memcpy(probs + (np + x) * 12, w, sizeof(w));
+            }
+            np += pv.n;
+        }
+        nch += n;
+        free(cscore); free(s); free(ch.a); free(ca.a);
+    }
+    ch_off[nq] = (int32_t)nch; ch_aoff[nch] = (int32_t)nca; prob_off[nk] = (int32_t)np;
+    n_out[0] = nch; n_out[1] = nk; n_out[2] = np;
+    free(pv.a);
+    return rc;
 }
 
 /* ------------------------------------------------------------------------- */

@@ -128,5 +128,7 @@ def lib():
     L.telr_debug_dp_limits.restype = C.c_int; L.telr_debug_dp_limits.argtypes = [C.POINTER(MapOpt), vp]
     L.telr_debug_dp.restype = C.c_int; L.telr_debug_dp.argtypes = [vp, vp, vp, C.POINTER(MapOpt), vp, i32, vp, vp, vp, i64]
     L.telr_debug_chain.restype = C.c_int; L.telr_debug_chain.argtypes = [vp, i32, vp, vp, C.POINTER(MapOpt), vp, vp]
+    L.telr_debug_backtrack.restype = C.c_int
+    L.telr_debug_backtrack.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(MapOpt), vp, vp, vp, vp, vp, vp, vp, i64, vp]
     _lib = L
     return L

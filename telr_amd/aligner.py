@@ -139,6 +139,35 @@ class Engine:
                   "telr_debug_chain")
         return f, p
 
+    def debug_backtrack(self, keys, q_aoff, f, p, qlen, goff, tlen, mo):
+        """peaks and back-tracking, pass-1 chain selection and DP segmenting of map() on anchor lists with their chaining scores -- test
+        tap.  keys / q_aoff as debug_chain takes them, f / p per anchor (p relative to the query's first anchor, -1 for none), qlen per
+        query, goff (n_targets + 1 ascending global offsets) and tlen per target.
+        -> dict: chains (n, 9) {qid, score, cnt, rev, tid, rs, re, qs, qe} in discovery order with ch_off per query; canch, the chains'
+        anchors back to back, with ch_aoff per chain; kept (k, 10), the same nine fields and the chain's row, query-major in rank order;
+        probs (np, 12) rows as debug_dp takes them with prob_off per kept chain (empty without TELR_MF_CIGAR)"""
+        K = np.ascontiguousarray(keys, dtype=np.uint64)
+        O = np.ascontiguousarray(q_aoff, dtype=np.int32)
+        F = np.ascontiguousarray(f, dtype=np.int32); P = np.ascontiguousarray(p, dtype=np.int32)
+        QL = np.ascontiguousarray(qlen, dtype=np.int32)
+        G = np.ascontiguousarray(goff, dtype=np.uint32); TL = np.ascontiguousarray(tlen, dtype=np.int32)
+        nq, nt, na = len(O) - 1, len(TL), len(K)
+        if nq < 0 or len(F) != na or len(P) != na or len(QL) != nq or len(G) != nt + 1:
+            raise ValueError("array lengths: q_aoff nq + 1, f / p one per key, qlen nq, goff n_targets + 1")
+        if nq < 1 or int(O[-1]) != na:
+            raise _lib.TelrError("telr_debug_backtrack: q_aoff must hold nq + 1 >= 2 offsets ending at len(keys)")
+        cap = 3 * na + 8
+        ch_off = np.zeros(nq + 1, np.int32); chains = np.zeros((na + 1, 9), np.int32); ch_aoff = np.zeros(na + 2, np.int32)
+        canch = np.zeros(na + 1, np.uint64); kept = np.zeros((na + 1, 10), np.int32); prob_off = np.zeros(na + 2, np.int32)
+        probs = np.zeros((cap, 12), np.int32); n_out = np.zeros(3, np.int64)
+        self._chk(self.L.telr_debug_backtrack(self.h, nq, O.ctypes.data, K.ctypes.data, F.ctypes.data, P.ctypes.data, QL.ctypes.data, nt,
+                                              G.ctypes.data, TL.ctypes.data, C.byref(mo), ch_off.ctypes.data, chains.ctypes.data,
+                                              ch_aoff.ctypes.data, canch.ctypes.data, kept.ctypes.data, prob_off.ctypes.data,
+                                              probs.ctypes.data, cap, n_out.ctypes.data), "telr_debug_backtrack")
+        nch, nk, npb = (int(v) for v in n_out)
+        return dict(chains=chains[:nch].copy(), ch_off=ch_off, ch_aoff=ch_aoff[:nch + 1].copy(), canch=canch[:int(ch_aoff[nch])].copy(),
+                    kept=kept[:nk].copy(), prob_off=prob_off[:nk + 1].copy(), probs=probs[:npb].copy())
+
     def release_scratch(self):
         """give the context's grow-only scratch back to the device (the next call allocates what it needs again)"""
         self._chk(self.L.telr_release_scratch(self.h), "telr_release_scratch")

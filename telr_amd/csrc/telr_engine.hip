@@ -1803,6 +1803,144 @@ static int chain_dispatch(telr_ctx *ctx, hipStream_t st, const telr_map_opt *mo,
     return TELR_OK;
 }
 
+// ---- peaks and back-tracking of chained anchor lists: the chain records of every query in discovery order, and their anchors
+// (map_batch; telr_debug_backtrack runs the same dispatch on a caller's f / p).  any_over: a query holds more than SEGSORT_CAP anchors.
+struct BtOut { uint64_t *d_canch; int32_t *d_choff, *d_nch; ChainRec *d_rec; int32_t npk_tot; };
+static int backtrack_dispatch(telr_ctx *ctx, hipStream_t st, const telr_map_opt *mo, const uint64_t *d_skeys, const int32_t *d_qaoff, int nq, int32_t na,
+                              bool any_over, const int32_t *d_qorder, const int32_t *d_f, const int32_t *d_p, BtOut *out)
+{
+    uint8_t *d_flags; uint64_t *d_pk, *d_pk2, *d_canch; int32_t *d_npk, *d_pkend, *d_choff, *d_nch;
+    TRY(ctx_buf_t(ctx, "flags", (size_t)na + 16, &d_flags));
+    uint8_t *d_nonpeak = d_flags;
+    TRY(ctx_buf_t(ctx, "pk", (size_t)na, &d_pk));
+    TRY(ctx_buf_t(ctx, "pk2", (size_t)na, &d_pk2));
+    TRY(ctx_buf_t(ctx, "canch", (size_t)na, &d_canch));
+    TRY(ctx_buf_t(ctx, "n_peaks", (size_t)nq + 1, &d_npk));
+    TRY(ctx_buf_t(ctx, "pk_end", (size_t)nq + 1, &d_pkend));
+    TRY(ctx_buf_t(ctx, "ch_off", (size_t)nq + 1, &d_choff));
+    TRY(ctx_buf_t(ctx, "n_chains", (size_t)nq + 1, &d_nch));
+    HIPCHK(hipMemsetAsync(d_flags, 0, (size_t)na + 16, st));
+    hipLaunchKernelGGL(k_nonpeak, dim3(nq), dim3(256), 0, st, d_qaoff, d_f, d_p, d_nonpeak);
+    hipLaunchKernelGGL(k_peaks, dim3(nq), dim3(256), 0, st, d_qaoff, d_f, d_nonpeak, mo->min_chain_score, d_pk, d_npk, d_pkend);
+    HIPCHK(hipGetLastError());
+    if (na > 0) TRY(seg_sort_u64(ctx, "so_p", d_pk, d_pk2, d_qaoff, d_pkend, nullptr, d_qorder, nq, (size_t)na, any_over, st));
+    HIPCHK(hipMemsetAsync(d_npk + nq, 0, 4, st));
+    TRY((dev_exclusive_scan<int32_t, int32_t>(ctx, d_npk, d_choff, (size_t)nq + 1)));
+    int32_t npk_tot = 0;
+    HIPCHK(hipMemcpyAsync(&npk_tot, d_choff + nq, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    ChainRec *d_rec;
+    TRY(ctx_buf_t(ctx, "chain_rec", (size_t)npk_tot, &d_rec));
+    {
+        // owner / depth sweeps (kernels.hip.h, "back-tracking without a walker"): five launches over all queries, longest first
+        uint32_t *d_owner; int32_t *d_depth, *d_chtop, *d_chaoff;
+        TRY(ctx_buf_t(ctx, "bt_owner", (size_t)na + 1, &d_owner));
+        TRY(ctx_buf_t(ctx, "bt_depth", (size_t)na + 1, &d_depth));
+        TRY(ctx_buf_t(ctx, "bt_chtop", (size_t)na + 1, &d_chtop));
+        TRY(ctx_buf_t(ctx, "bt_chaoff", (size_t)na + 1, &d_chaoff));
+        HIPCHK(hipMemsetAsync(d_owner, 0xff, ((size_t)na + 1) * 4, st));
+        hipLaunchKernelGGL(k_bt_rank, dim3(nq), dim3(256), 0, st, d_qaoff, d_pk2, d_npk, d_owner);
+        if (mo->flags & TELR_MF_CHAIN_SKIP) {      // links up to CHAIN_SCAN_H anchors back: the rings of BT_RING_SCAN entries
+            hipLaunchKernelGGL(k_bt_owner<BT_RING_SCAN>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, (int32_t)CHAIN_SCAN_H, d_owner, d_qorder);
+            hipLaunchKernelGGL(k_bt_depth<BT_RING_SCAN>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, d_owner, d_depth, d_chtop, d_qorder);
+        } else {
+            hipLaunchKernelGGL(k_bt_owner<BT_RING>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, mo->chain_lookback, d_owner, d_qorder);
+            hipLaunchKernelGGL(k_bt_depth<BT_RING>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, d_owner, d_depth, d_chtop, d_qorder);
+        }
+        hipLaunchKernelGGL(k_bt_emit, dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, d_f, d_p, d_pk2, d_npk, d_choff, mo->min_chain_score, mo->min_cnt,
+                           d_owner, d_depth, d_chtop, d_chaoff, d_rec, d_nch, d_qorder);
+        hipLaunchKernelGGL(k_bt_scatter, dim3(nq), dim3(256), 0, st, d_skeys, d_qaoff, d_owner, d_depth, d_chaoff, d_canch, d_qorder);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipGetLastError());
+    out->d_canch = d_canch; out->d_choff = d_choff; out->d_nch = d_nch; out->d_rec = d_rec; out->npk_tot = npk_tot;
+    return TELR_OK;
+}
+
+// ---- pass-1 chain selection of the chain records: the kept chains, query-major in rank order (map_batch; telr_debug_backtrack).
+// d_qlen / d_qboff: the queries' lengths and packed-base offsets; q_k0[nq + 1] (host, out): the queries' places in the kept list;
+// h_nch: the per-query chain counts, fetched here unless the caller has them (need_recs).
+struct SelOut { int nk; KeptLite *hl; KeptChain *d_kc; const uint64_t *d_sk2; const uint8_t *d_keep; };
+static int select1_dispatch(telr_ctx *ctx, hipStream_t st, const telr_map_opt *mo, const int32_t *d_choff, const int32_t *d_nch, const ChainRec *d_rec, int32_t npk_tot,
+                            const int32_t *d_qaoff, int nq, int32_t q0, const int32_t *d_qlen, const int64_t *d_qboff, const uint32_t *d_goff, const int32_t *d_tlen,
+                            const int64_t *d_tboff, int32_t n_targets, bool any_over, const int32_t *d_qorder, bool need_recs, int32_t *h_nch, int32_t *q_k0, SelOut *out)
+{
+    uint64_t *d_sk, *d_sk2; int32_t *d_segend, *d_pfs, *d_pfe, *d_ptid, *d_pkey, *d_tct, *d_tcn, *d_nkept, *d_koff; uint8_t *d_keep;
+    TRY(ctx_buf_t(ctx, "sel_key", (size_t)npk_tot + 1, &d_sk));
+    TRY(ctx_buf_t(ctx, "sel_key2", (size_t)npk_tot + 1, &d_sk2));
+    TRY(ctx_buf_t(ctx, "sel_segend", (size_t)nq + 1, &d_segend));
+    TRY(ctx_buf_t(ctx, "sel_pfs", (size_t)npk_tot + 1, &d_pfs));
+    TRY(ctx_buf_t(ctx, "sel_pfe", (size_t)npk_tot + 1, &d_pfe));
+    TRY(ctx_buf_t(ctx, "sel_ptid", (size_t)npk_tot + 1, &d_ptid));
+    TRY(ctx_buf_t(ctx, "sel_pkey", (size_t)npk_tot + 1, &d_pkey));
+    TRY(ctx_buf_t(ctx, "sel_tct", (size_t)npk_tot + 1, &d_tct));
+    TRY(ctx_buf_t(ctx, "sel_tcn", (size_t)npk_tot + 1, &d_tcn));
+    TRY(ctx_buf_t(ctx, "sel_keep", (size_t)npk_tot + 1, &d_keep));
+    TRY(ctx_buf_t(ctx, "sel_nkept", (size_t)nq + 2, &d_nkept));
+    TRY(ctx_buf_t(ctx, "sel_koff", (size_t)nq + 2, &d_koff));
+    hipLaunchKernelGGL(k_sel_keys, dim3(nq), dim3(64), 0, st, d_choff, d_nch, d_rec, d_sk, d_segend);
+    HIPCHK(hipGetLastError());
+    if (npk_tot > 0) TRY(seg_sort_u64(ctx, "so_c", d_sk, d_sk2, d_choff, d_segend, nullptr, d_qorder, nq, (size_t)npk_tot, any_over, st));
+    SelOpt so; so.mask_level = mo->mask_level; so.pri_ratio = mo->pri_ratio; so.best_n = mo->best_n; so.secondary = mo->secondary;
+    so.per_target = (mo->flags & TELR_MF_PER_TARGET) ? 1 : 0;
+    hipLaunchKernelGGL(k_select1, dim3(nq), dim3(64), 0, st, d_choff, d_nch, d_rec, d_sk2, d_qlen, d_goff, n_targets, so,
+                       d_pfs, d_pfe, d_ptid, d_pkey, d_tct, d_tcn, d_keep, d_nkept, d_qorder);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(d_nkept + nq, 0, 4, st));
+    TRY((dev_exclusive_scan<int32_t, int32_t>(ctx, d_nkept, d_koff, (size_t)nq + 1)));
+    HIPCHK(hipMemcpyAsync(q_k0, d_koff, (size_t)(nq + 1) * 4, hipMemcpyDeviceToHost, st));
+    if (!need_recs) HIPCHK(hipMemcpyAsync(h_nch, d_nch, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int nk = q_k0[nq];
+    KeptLite *d_kl;
+    KeptChain *d_kc; KeptLite *hl;
+    TRY(ctx_buf_t(ctx, "kept", (size_t)nk, &d_kc));
+    TRY(ctx_buf_t(ctx, "kept_lite", (size_t)nk, &d_kl));
+    TRY(ctx_hbuf_t(ctx, "h_kept_lite", (size_t)nk, &hl));
+    if (nk > 0) {
+        hipLaunchKernelGGL(k_select1_write, dim3(nq), dim3(64), 0, st, d_choff, d_nch, d_rec, d_sk2, d_keep, d_koff, d_qaoff, q0, d_qlen, d_qboff,
+                           d_goff, d_tlen, d_tboff, n_targets, d_kc, d_kl);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hl, d_kl, (size_t)nk * sizeof(KeptLite), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    out->nk = nk; out->hl = hl; out->d_kc = d_kc; out->d_sk2 = d_sk2; out->d_keep = d_keep;
+    return TELR_OK;
+}
+
+// ---- the DP problem list of the kept chains (map_batch; telr_debug_backtrack): h_poff[nk + 1] the chains' places in it
+static int segments_dispatch(telr_ctx *ctx, hipStream_t st, const telr_map_opt *mo, const KeptChain *d_kc, int nk, const uint64_t *d_canch,
+                             std::vector<int32_t> &h_poff, int *np_out, DpProb **d_probs_out)
+{
+    int32_t *d_nprob, *d_poff;             // (the kept-chain descriptors d_kc are on the device already)
+    TRY(ctx_buf_t(ctx, "nprob", (size_t)nk + 1, &d_nprob));
+    TRY(ctx_buf_t(ctx, "prob_off", (size_t)nk + 1, &d_poff));
+    hipLaunchKernelGGL(k_segments_w<0>, dim3(nk), dim3(64), 0, st, d_kc, nk, d_canch, mo->min_ksw_len, mo->bw, mo->fill_band_q4, mo->ext_max, mo->ext_band, mo->bw_long, d_nprob, (const int32_t*)nullptr, (DpProb*)nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(d_nprob + nk, 0, 4, st));
+    TRY((dev_exclusive_scan<int32_t, int32_t>(ctx, d_nprob, d_poff, (size_t)nk + 1)));
+    h_poff.resize(nk + 1);
+    HIPCHK(hipMemcpyAsync(h_poff.data(), d_poff, (size_t)(nk + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int np = h_poff[nk];
+    DpProb *d_probs;
+    TRY(ctx_buf_t(ctx, "probs", (size_t)np, &d_probs));
+    hipLaunchKernelGGL(k_segments_w<1>, dim3(nk), dim3(64), 0, st, d_kc, nk, d_canch, mo->min_ksw_len, mo->bw, mo->fill_band_q4, mo->ext_max, mo->ext_band, mo->bw_long, d_nprob, d_poff, d_probs);
+    HIPCHK(hipGetLastError());
+    *np_out = np; *d_probs_out = d_probs;
+    return TELR_OK;
+}
+
+// a chain record as the nine ints of the debug taps {qid, score, cnt, rev, tid, rs, re, qs, qe} (goff: the host's copy of the global offsets)
+static void chain_row(const ChainRec &r, int32_t qid, const uint32_t *goff, int n_targets, int32_t *v)
+{
+    const uint32_t g0 = (uint32_t)A_G(r.a0);
+    const int tid = (int)(std::upper_bound(goff, goff + n_targets, g0) - goff) - 1, go = (int)goff[tid];
+    v[0] = qid; v[1] = r.score; v[2] = r.cnt; v[3] = (int)(r.a0 >> 63); v[4] = tid;
+    v[5] = std::max(0, A_G(r.a0) - go - A_SPAN(r.a0) + 1);      // (start clamped at the target's first base, as the kept chains are: k_select1_write)
+    v[6] = A_G(r.a1) - go + 1; v[7] = A_Q(r.a0) - A_SPAN(r.a0) + 1; v[8] = A_Q(r.a1) + 1;
+}
+
 static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs, const int32_t *d_qtarget, int32_t q0, int32_t q1,
                      const telr_map_opt *mo, OccCut occ, telr_result *R, RangeTurn *gate = nullptr)
 {
@@ -1977,50 +2115,10 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
 
     // ---- peaks + back-tracking ----------------------------------------------------------------
     StageTimer t_bt(ctx, ST_BACKTRACK, true);
-    uint8_t *d_flags; uint64_t *d_pk, *d_pk2, *d_canch; int32_t *d_npk, *d_pkend, *d_choff, *d_nch;
-    TRY(ctx_buf_t(ctx, "flags", (size_t)na + 16, &d_flags));
-    uint8_t *d_nonpeak = d_flags;
-    TRY(ctx_buf_t(ctx, "pk", (size_t)na, &d_pk));
-    TRY(ctx_buf_t(ctx, "pk2", (size_t)na, &d_pk2));
-    TRY(ctx_buf_t(ctx, "canch", (size_t)na, &d_canch));
-    TRY(ctx_buf_t(ctx, "n_peaks", (size_t)nq + 1, &d_npk));
-    TRY(ctx_buf_t(ctx, "pk_end", (size_t)nq + 1, &d_pkend));
-    TRY(ctx_buf_t(ctx, "ch_off", (size_t)nq + 1, &d_choff));
-    TRY(ctx_buf_t(ctx, "n_chains", (size_t)nq + 1, &d_nch));
-    HIPCHK(hipMemsetAsync(d_flags, 0, (size_t)na + 16, st));
-    hipLaunchKernelGGL(k_nonpeak, dim3(nq), dim3(256), 0, st, d_qaoff, d_f, d_p, d_nonpeak);
-    hipLaunchKernelGGL(k_peaks, dim3(nq), dim3(256), 0, st, d_qaoff, d_f, d_nonpeak, mo->min_chain_score, d_pk, d_npk, d_pkend);
-    HIPCHK(hipGetLastError());
-    if (na > 0) TRY(seg_sort_u64(ctx, "so_p", d_pk, d_pk2, d_qaoff, d_pkend, nullptr, d_qorder, nq, (size_t)na, any_over, st));
-    HIPCHK(hipMemsetAsync(d_npk + nq, 0, 4, st));
-    TRY((dev_exclusive_scan<int32_t, int32_t>(ctx, d_npk, d_choff, (size_t)nq + 1)));
-    int32_t npk_tot = 0;
-    HIPCHK(hipMemcpyAsync(&npk_tot, d_choff + nq, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    ChainRec *d_rec;
-    TRY(ctx_buf_t(ctx, "chain_rec", (size_t)npk_tot, &d_rec));
-    {
-        // owner / depth sweeps (kernels.hip.h, "back-tracking without a walker"): five launches over all queries, longest first
-        uint32_t *d_owner; int32_t *d_depth, *d_chtop, *d_chaoff;
-        TRY(ctx_buf_t(ctx, "bt_owner", (size_t)na + 1, &d_owner));
-        TRY(ctx_buf_t(ctx, "bt_depth", (size_t)na + 1, &d_depth));
-        TRY(ctx_buf_t(ctx, "bt_chtop", (size_t)na + 1, &d_chtop));
-        TRY(ctx_buf_t(ctx, "bt_chaoff", (size_t)na + 1, &d_chaoff));
-        HIPCHK(hipMemsetAsync(d_owner, 0xff, ((size_t)na + 1) * 4, st));
-        hipLaunchKernelGGL(k_bt_rank, dim3(nq), dim3(256), 0, st, d_qaoff, d_pk2, d_npk, d_owner);
-        if (mo->flags & TELR_MF_CHAIN_SKIP) {      // links up to CHAIN_SCAN_H anchors back: the rings of BT_RING_SCAN entries
-            hipLaunchKernelGGL(k_bt_owner<BT_RING_SCAN>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, (int32_t)CHAIN_SCAN_H, d_owner, d_qorder);
-            hipLaunchKernelGGL(k_bt_depth<BT_RING_SCAN>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, d_owner, d_depth, d_chtop, d_qorder);
-        } else {
-            hipLaunchKernelGGL(k_bt_owner<BT_RING>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, mo->chain_lookback, d_owner, d_qorder);
-            hipLaunchKernelGGL(k_bt_depth<BT_RING>, dim3(nq), dim3(64), 0, st, d_qaoff, nq, d_p, d_owner, d_depth, d_chtop, d_qorder);
-        }
-        hipLaunchKernelGGL(k_bt_emit, dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, d_f, d_p, d_pk2, d_npk, d_choff, mo->min_chain_score, mo->min_cnt,
-                           d_owner, d_depth, d_chtop, d_chaoff, d_rec, d_nch, d_qorder);
-        hipLaunchKernelGGL(k_bt_scatter, dim3(nq), dim3(256), 0, st, d_skeys, d_qaoff, d_owner, d_depth, d_chaoff, d_canch, d_qorder);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipGetLastError());
+    BtOut bt;
+    TRY(backtrack_dispatch(ctx, st, mo, d_skeys, d_qaoff, nq, na, any_over, d_qorder, d_f, d_p, &bt));
+    uint64_t *const d_canch = bt.d_canch; int32_t *const d_choff = bt.d_choff, *const d_nch = bt.d_nch; ChainRec *const d_rec = bt.d_rec;
+    const int32_t npk_tot = bt.npk_tot;
     // Pass-1 chain selection runs on the device (k_select1).  The debug taps of the parity tests need every chain record on the host.
     const bool need_recs = ctx->debug != 0;
     int32_t *h_nch, *h_choff, *h_qaoff; ChainRec *h_rec;
@@ -2047,53 +2145,17 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
     int64_t n_chain_tot = 0;
     {
         StageTimer t_sel(ctx, ST_SELECT, true);
-        uint64_t *d_sk, *d_sk2; int32_t *d_segend, *d_pfs, *d_pfe, *d_ptid, *d_pkey, *d_tct, *d_tcn, *d_nkept, *d_koff; uint8_t *d_keep;
-        TRY(ctx_buf_t(ctx, "sel_key", (size_t)npk_tot + 1, &d_sk));
-        TRY(ctx_buf_t(ctx, "sel_key2", (size_t)npk_tot + 1, &d_sk2));
-        TRY(ctx_buf_t(ctx, "sel_segend", (size_t)nq + 1, &d_segend));
-        TRY(ctx_buf_t(ctx, "sel_pfs", (size_t)npk_tot + 1, &d_pfs));
-        TRY(ctx_buf_t(ctx, "sel_pfe", (size_t)npk_tot + 1, &d_pfe));
-        TRY(ctx_buf_t(ctx, "sel_ptid", (size_t)npk_tot + 1, &d_ptid));
-        TRY(ctx_buf_t(ctx, "sel_pkey", (size_t)npk_tot + 1, &d_pkey));
-        TRY(ctx_buf_t(ctx, "sel_tct", (size_t)npk_tot + 1, &d_tct));
-        TRY(ctx_buf_t(ctx, "sel_tcn", (size_t)npk_tot + 1, &d_tcn));
-        TRY(ctx_buf_t(ctx, "sel_keep", (size_t)npk_tot + 1, &d_keep));
-        TRY(ctx_buf_t(ctx, "sel_nkept", (size_t)nq + 2, &d_nkept));
-        TRY(ctx_buf_t(ctx, "sel_koff", (size_t)nq + 2, &d_koff));
-        hipLaunchKernelGGL(k_sel_keys, dim3(nq), dim3(64), 0, st, d_choff, d_nch, d_rec, d_sk, d_segend);
-        HIPCHK(hipGetLastError());
-        if (npk_tot > 0) TRY(seg_sort_u64(ctx, "so_c", d_sk, d_sk2, d_choff, d_segend, nullptr, d_qorder, nq, (size_t)npk_tot, any_over, st));
-        SelOpt so; so.mask_level = mo->mask_level; so.pri_ratio = mo->pri_ratio; so.best_n = mo->best_n; so.secondary = mo->secondary;
-        so.per_target = (mo->flags & TELR_MF_PER_TARGET) ? 1 : 0;
-        hipLaunchKernelGGL(k_select1, dim3(nq), dim3(64), 0, st, d_choff, d_nch, d_rec, d_sk2, qs->d_len + q0, ix->d_goff, tg->n, so,
-                           d_pfs, d_pfe, d_ptid, d_pkey, d_tct, d_tcn, d_keep, d_nkept, d_qorder);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemsetAsync(d_nkept + nq, 0, 4, st));
-        TRY((dev_exclusive_scan<int32_t, int32_t>(ctx, d_nkept, d_koff, (size_t)nq + 1)));
-        HIPCHK(hipMemcpyAsync(q_k0.data(), d_koff, (size_t)(nq + 1) * 4, hipMemcpyDeviceToHost, st));
-        if (!need_recs) HIPCHK(hipMemcpyAsync(h_nch, d_nch, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        nk = q_k0[nq];
+        SelOut so1;
+        TRY(select1_dispatch(ctx, st, mo, d_choff, d_nch, d_rec, npk_tot, d_qaoff, nq, q0, qs->d_len + q0, qs->d_boff + q0, ix->d_goff, tg->d_len, tg->d_boff, tg->n,
+                             any_over, d_qorder, need_recs, h_nch, q_k0.data(), &so1));
+        nk = so1.nk; hl = so1.hl; d_kc = so1.d_kc;
         for (int q = 0; q < nq; ++q) n_chain_tot += h_nch[q];
-        KeptLite *d_kl;
-        TRY(ctx_buf_t(ctx, "kept", (size_t)nk, &d_kc));
-        TRY(ctx_buf_t(ctx, "kept_lite", (size_t)nk, &d_kl));
-        TRY(ctx_hbuf_t(ctx, "h_kept_lite", (size_t)nk, &hl));
-        if (nk > 0) {
-            hipLaunchKernelGGL(k_select1_write, dim3(nq), dim3(64), 0, st, d_choff, d_nch, d_rec, d_sk2, d_keep, d_koff, d_qaoff, q0, qs->d_len + q0, qs->d_boff + q0,
-                               ix->d_goff, tg->d_len, tg->d_boff, tg->n, d_kc, d_kl);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(hl, d_kl, (size_t)nk * sizeof(KeptLite), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-        }
         t_sel.stop();
         if (ctx->debug) {                    // every chain with its box, in discovery order (stage-level parity tests)
             ctx->dbg_chain.clear();
             for (int q = 0; q < nq; ++q) for (int c = 0; c < h_nch[q]; ++c) {
-                const ChainRec &r = h_rec[h_choff[q] + c];
-                const uint32_t g0 = (uint32_t)A_G(r.a0);
-                const int tid = (int)(std::upper_bound(ix->goff.begin(), ix->goff.begin() + tg->n, g0) - ix->goff.begin()) - 1, go = (int)ix->goff[tid];
-                int32_t v[9] = { q0 + q, r.score, r.cnt, (int)(r.a0 >> 63), tid, std::max(0, A_G(r.a0) - go - A_SPAN(r.a0) + 1), A_G(r.a1) - go + 1, A_Q(r.a0) - A_SPAN(r.a0) + 1, A_Q(r.a1) + 1 };      // (start clamped at the target's first base, as the kept chains are: k_select1_write)
+                int32_t v[9];
+                chain_row(h_rec[h_choff[q] + c], q0 + q, ix->goff.data(), tg->n, v);
                 ctx->dbg_chain.insert(ctx->dbg_chain.end(), v, v + 9);
             }
         }
@@ -2122,21 +2184,8 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
     if (do_dp) {
         // ---- DP problem list ----------------------------------------------------------------
         StageTimer t_sg(ctx, ST_SEGMENTS, true);
-        int32_t *d_nprob, *d_poff;             // (the kept-chain descriptors d_kc are on the device already)
-        TRY(ctx_buf_t(ctx, "nprob", (size_t)nk + 1, &d_nprob));
-        TRY(ctx_buf_t(ctx, "prob_off", (size_t)nk + 1, &d_poff));
-        hipLaunchKernelGGL(k_segments_w<0>, dim3(nk), dim3(64), 0, st, d_kc, nk, d_canch, mo->min_ksw_len, mo->bw, mo->fill_band_q4, mo->ext_max, mo->ext_band, mo->bw_long, d_nprob, (const int32_t*)nullptr, (DpProb*)nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemsetAsync(d_nprob + nk, 0, 4, st));
-        TRY((dev_exclusive_scan<int32_t, int32_t>(ctx, d_nprob, d_poff, (size_t)nk + 1)));
-        h_poff.resize(nk + 1);
-        HIPCHK(hipMemcpyAsync(h_poff.data(), d_poff, (size_t)(nk + 1) * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        np = h_poff[nk];
         DpProb *d_probs;
-        TRY(ctx_buf_t(ctx, "probs", (size_t)np, &d_probs));
-        hipLaunchKernelGGL(k_segments_w<1>, dim3(nk), dim3(64), 0, st, d_kc, nk, d_canch, mo->min_ksw_len, mo->bw, mo->fill_band_q4, mo->ext_max, mo->ext_band, mo->bw_long, d_nprob, d_poff, d_probs);
-        HIPCHK(hipGetLastError());
+        TRY(segments_dispatch(ctx, st, mo, d_kc, nk, d_canch, h_poff, &np, &d_probs));
         t_sg.stop(); ht.mark("segments (sync: problems)");
         ctx->ctr.dp_problems += np;
 
@@ -2697,6 +2746,144 @@ extern "C" int telr_debug_chain(telr_ctx *ctx, int32_t nq, const uint64_t *keys,
     HIPCHK(hipMemcpyAsync(f, d_f, (size_t)na * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(p, d_p, (size_t)na * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return TELR_OK;
+}
+// The three stages of telr_map between the chaining scores and the banded DP -- peaks and back-tracking (backtrack_dispatch), pass-1
+// chain selection (select1_dispatch), DP segmenting (segments_dispatch) -- on a caller's anchor lists with their f and p (test tap:
+// the edges of those kernels without an index or sequences).  In: nq queries, query q's sorted anchors at keys[q_aoff[q] ..
+// q_aoff[q + 1]) in the engine's layout, f and p of every anchor (p relative to the query's first anchor, -1 for none), qlen[nq],
+// and the targets as their global-offset table goff[n_targets + 1] (ascending) and tlen[n_targets].  Out, sized by the caller for
+// na = q_aoff[nq] anchors: (a) every chain in discovery order, nine ints each {qid, score, cnt, rev, tid, rs, re, qs, qe}, ch_off
+// [nq + 1] the queries' places; (b) the chains' anchors back to back in canch[na], ch_aoff[chains + 1] their places; (c) the kept
+// chains of pass 1, query-major in rank order, ten ints each {qid, score, cnt, rev, tid, rs, re, qs, qe, row of the chain in (a)};
+// (d) with TELR_MF_CIGAR the DP problems of every kept chain as telr_debug_dp rows {qid, q_off, tid, t_off, m, n, dlo, dhi, kind,
+// qstep, tstep, qcomp} (offsets relative to the sequences), prob_off[kept + 1] their places; n_out = {chains, kept, problems}.
+// Everything a kernel indexes with is checked on the host first: a list that fails comes back as TELR_E_ARG with a message.
+extern "C" int telr_debug_backtrack(telr_ctx *ctx, int32_t nq, const int32_t *q_aoff, const uint64_t *keys, const int32_t *f, const int32_t *p, const int32_t *qlen,
+                                    int32_t n_targets, const uint32_t *goff, const int32_t *tlen, const telr_map_opt *mo,
+                                    int32_t *ch_off, int32_t *chains, int32_t *ch_aoff, uint64_t *canch, int32_t *kept, int32_t *prob_off, int32_t *probs,
+                                    int64_t prob_cap, int64_t *n_out)
+{
+    (void)hipGetLastError();
+    if (!ctx || !mo || !q_aoff || !qlen || !goff || !tlen || !ch_off || !ch_aoff || !prob_off || !n_out) return TELR_E_ARG;
+    auto bad = [&](const std::string &why) { ctx->err = "telr_debug_backtrack: " + why; return TELR_E_ARG; };
+    TRY(check_map_opt(ctx, mo));
+    if (nq < 1 || nq > (1 << 16)) return bad("nq must be 1..2^16");
+    if (n_targets < 1 || n_targets > (1 << 24)) return bad("n_targets must be 1..2^24");
+    if (q_aoff[0] != 0) return bad("q_aoff[0] must be 0");
+    for (int q = 0; q < nq; ++q) if (q_aoff[q + 1] < q_aoff[q] || q_aoff[q + 1] > (1 << 22)) return bad("q_aoff must ascend (at most 2^22 anchors)");
+    const int32_t na = q_aoff[nq];
+    if (na > 0 && (!keys || !f || !p || !chains || !canch || !kept)) return TELR_E_ARG;
+    if (prob_cap < 0 || (prob_cap > 0 && !probs)) return TELR_E_ARG;
+    for (int t = 0; t < n_targets; ++t) {
+        if (goff[t + 1] < goff[t] || goff[t + 1] >= (1u << 31)) return bad("goff must ascend below 2^31");
+        if (tlen[t] < 0 || (uint32_t)tlen[t] > goff[t + 1] - goff[t]) return bad("tlen[" + std::to_string(t) + "] outside its piece of goff");
+    }
+    const int32_t max_link = (mo->flags & TELR_MF_CHAIN_SKIP) ? (int32_t)CHAIN_SCAN_H : mo->chain_lookback;
+    bool any_over = false;
+    for (int q = 0; q < nq; ++q) {
+        const int32_t a0 = q_aoff[q], n = q_aoff[q + 1] - a0;
+        if (qlen[q] < 0 || qlen[q] > (1 << 24)) return bad("qlen[" + std::to_string(q) + "] must be 0..2^24");
+        if (n > SEGSORT_CAP) any_over = true;
+        for (int32_t i = 0; i < n; ++i) {
+            const uint64_t key = keys[a0 + i];
+            const std::string at = "anchor " + std::to_string(i) + " of query " + std::to_string(q);
+            if (p[a0 + i] < -1 || p[a0 + i] >= i) return bad(at + ": p must be -1 or an earlier anchor of the query");
+            if (p[a0 + i] >= 0 && i - p[a0 + i] > max_link) return bad(at + ": link longer than the look-back (" + std::to_string(max_link) + ")");
+            if ((uint32_t)A_G(key) < goff[0] || (uint32_t)A_G(key) >= goff[n_targets]) return bad(at + ": reference position outside goff");
+            if (A_Q(key) >= qlen[q]) return bad(at + ": query position outside the query");
+        }
+    }
+    n_out[0] = n_out[1] = n_out[2] = 0;
+    for (int q = 0; q <= nq; ++q) ch_off[q] = 0;
+    ch_aoff[0] = 0; prob_off[0] = 0;
+    if (na == 0) return TELR_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    uint64_t *d_keys; int32_t *d_qaoff, *d_f, *d_p, *d_qlen, *d_tlen; uint32_t *d_goff; int64_t *d_zero;
+    TRY(ctx_buf_t(ctx, "dbg_bt_keys", (size_t)na, &d_keys));
+    TRY(ctx_buf_t(ctx, "dbg_bt_qaoff", (size_t)nq + 1, &d_qaoff));
+    TRY(ctx_buf_t(ctx, "dbg_bt_f", (size_t)na, &d_f));
+    TRY(ctx_buf_t(ctx, "dbg_bt_p", (size_t)na, &d_p));
+    TRY(ctx_buf_t(ctx, "dbg_bt_qlen", (size_t)nq, &d_qlen));
+    TRY(ctx_buf_t(ctx, "dbg_bt_goff", (size_t)n_targets + 1, &d_goff));
+    TRY(ctx_buf_t(ctx, "dbg_bt_tlen", (size_t)n_targets, &d_tlen));
+    TRY(ctx_buf_t(ctx, "dbg_bt_zero", (size_t)std::max(nq, n_targets), &d_zero));          // packed-base offsets 0: the problems' offsets stay relative to their sequences
+    HIPCHK(hipMemcpyAsync(d_keys, keys, (size_t)na * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_qaoff, q_aoff, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_f, f, (size_t)na * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_p, p, (size_t)na * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_qlen, qlen, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_goff, goff, ((size_t)n_targets + 1) * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_tlen, tlen, (size_t)n_targets * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_zero, 0, (size_t)std::max(nq, n_targets) * 8, st));
+    BtOut bt;
+    TRY(backtrack_dispatch(ctx, st, mo, d_keys, d_qaoff, nq, na, any_over, nullptr, d_f, d_p, &bt));
+    std::vector<int32_t> h_nch((size_t)nq + 1), h_choff((size_t)nq + 1), q_k0((size_t)nq + 1, 0);
+    std::vector<ChainRec> h_rec((size_t)bt.npk_tot + 1);
+    std::vector<uint64_t> h_canch((size_t)na);
+    HIPCHK(hipMemcpyAsync(h_nch.data(), bt.d_nch, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_choff.data(), bt.d_choff, ((size_t)nq + 1) * 4, hipMemcpyDeviceToHost, st));
+    if (bt.npk_tot) HIPCHK(hipMemcpyAsync(h_rec.data(), bt.d_rec, (size_t)bt.npk_tot * sizeof(ChainRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_canch.data(), bt.d_canch, (size_t)na * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // (a), (b): the records of a query lie at ch_off[q] of the PEAK offsets; packed here, with the row of every record
+    std::vector<int32_t> row_of((size_t)bt.npk_tot + 1, -1);
+    int64_t nch = 0, nca = 0;
+    for (int q = 0; q < nq; ++q) {
+        ch_off[q] = (int32_t)nch;
+        for (int c = 0; c < h_nch[q]; ++c) {
+            const ChainRec &r = h_rec[(size_t)h_choff[q] + c];
+            if (nch >= na || r.cnt < 1 || r.a_off < 0 || nca + r.cnt > na || (int64_t)q_aoff[q] + r.a_off + r.cnt > q_aoff[q + 1]) { ctx->err = "telr_debug_backtrack: a chain record outside its query"; return TELR_E_RANGE; }
+            chain_row(r, q, goff, n_targets, chains + nch * 9);
+            row_of[(size_t)h_choff[q] + c] = (int32_t)nch;
+            ch_aoff[nch] = (int32_t)nca;
+            memcpy(canch + nca, h_canch.data() + q_aoff[q] + r.a_off, (size_t)r.cnt * 8);
+            nca += r.cnt; ++nch;
+        }
+    }
+    ch_off[nq] = (int32_t)nch; ch_aoff[nch] = (int32_t)nca;
+    // (c)
+    SelOut so;
+    TRY(select1_dispatch(ctx, st, mo, bt.d_choff, bt.d_nch, bt.d_rec, bt.npk_tot, d_qaoff, nq, 0, d_qlen, d_zero, d_goff, d_tlen, d_zero, n_targets, any_over, nullptr,
+                         true, h_nch.data(), q_k0.data(), &so));
+    const int nk = so.nk;
+    if (nk > nch) { ctx->err = "telr_debug_backtrack: more kept chains than chains"; return TELR_E_RANGE; }
+    std::vector<uint64_t> h_sk2((size_t)bt.npk_tot + 1); std::vector<uint8_t> h_keep((size_t)bt.npk_tot + 1);
+    if (bt.npk_tot) {
+        HIPCHK(hipMemcpyAsync(h_sk2.data(), so.d_sk2, (size_t)bt.npk_tot * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_keep.data(), so.d_keep, (size_t)bt.npk_tot, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    int x = 0;
+    for (int q = 0; q < nq; ++q) for (int i = 0; i < h_nch[q]; ++i) {
+        if (!h_keep[(size_t)h_choff[q] + i]) continue;
+        if (x >= nk) { ctx->err = "telr_debug_backtrack: the keep flags and the kept list disagree"; return TELR_E_RANGE; }
+        const uint32_t c = (uint32_t)(h_sk2[(size_t)h_choff[q] + i] & 0xffffffffu);
+        const KeptLite &L = so.hl[x];
+        int32_t v[10] = { L.qid, L.score, L.cnt, L.rev, L.tid, L.rs, L.re, L.qs, L.qe, c < (uint32_t)h_nch[q] ? row_of[(size_t)h_choff[q] + c] : -1 };
+        memcpy(kept + (size_t)x * 10, v, sizeof(v));
+        ++x;
+    }
+    if (x != nk) { ctx->err = "telr_debug_backtrack: the keep flags and the kept list disagree"; return TELR_E_RANGE; }
+    n_out[0] = nch; n_out[1] = nk;
+    for (int k = 0; k <= nk; ++k) prob_off[k] = 0;
+    // (d)
+    if ((mo->flags & TELR_MF_CIGAR) && nk > 0) {
+        std::vector<int32_t> h_poff; int np = 0; DpProb *d_probs;
+        TRY(segments_dispatch(ctx, st, mo, so.d_kc, nk, bt.d_canch, h_poff, &np, &d_probs));
+        if (np > prob_cap) { ctx->err = "telr_debug_backtrack: prob_cap too small"; return TELR_E_RANGE; }
+        std::vector<DpProb> hp((size_t)np + 1);
+        if (np) HIPCHK(hipMemcpyAsync(hp.data(), d_probs, (size_t)np * sizeof(DpProb), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int k = 0; k <= nk; ++k) prob_off[k] = h_poff[k];
+        for (int k = 0; k < nk; ++k) for (int z = h_poff[k]; z < h_poff[k + 1]; ++z) {
+            const DpProb &P = hp[(size_t)z]; const KeptLite &L = so.hl[k];
+            int32_t w[12] = { L.qid, (int32_t)P.qi0, L.tid, (int32_t)P.ti0, P.m, P.n, P.dlo, P.dhi, P.kind, P.qstep, P.tstep, P.qcomp };
+            memcpy(probs + (size_t)z * 12, w, sizeof(w));
+        }
+        n_out[2] = np;
+    }
     return TELR_OK;
 }
 // One DP pass over a caller's list of problems (test tap: every class of dp_pass against the oracle, problem by problem).
