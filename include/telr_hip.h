@@ -435,6 +435,49 @@ int  telr_depth_medians(telr_ctx *ctx, const telr_result *r, int32_t n_targets,
                         const int32_t *target_len, int32_t n_iv, const int32_t *iv_tid,
                         const int32_t *iv_start, const int32_t *iv_end, double *median_out);
 
+/* ---- insertion candidates from a mapped read set (opt-in; stands where the reference shells out to Sniffles, `detect_sv`,
+ *      src/telr/TELR_sv.py:49-51).  An OWN definition, not a restatement of Sniffles; parity with it is unpinned.
+ * Eligible records: not TELR_F_SECONDARY, mapq >= min_mapq.  Strand coordinates of a record: qs' = qs, qe' = qe forward;
+ * qs' = qlen - qe, qe' = qlen - qs on TELR_F_REV.
+ * Signatures:  kind 0 (intra) every I op of >= min_len of an eligible record: pos = ts + the M and D lengths before it, len = its
+ *              length (neighbouring I ops are not merged);
+ *              kind 1 (split) every ordered pair (a, b) of distinct eligible records of one query with the same tid and strand,
+ *              qgap = b.qs' - a.qe' >= 0, |tgap = b.ts - a.te| <= max_ref_gap, qgap - tgap >= min_len: pos = a.te,
+ *              len = qgap - tgap, rec = a, mate = b (all pairs: adjacency is not tested);
+ *              kind 2 (clip) qs' >= min_clip: pos = ts, len = qs'; qlen - qe' >= min_clip: pos = te, len = qlen - qe' (a lower bound).
+ *              [seg_start, seg_start + seg_len) are the inserted / unaligned bases on the FORWARD read.  Sorted ascending by
+ *              (tid, pos, rec, kind, len, mate).
+ * Clusters:    single linkage over (tid, pos): a new one where tid changes or pos - previous pos > cluster_dist.  A cluster is a
+ *              call when it has >= min_support distinct reads and >= min_sized distinct reads among its kind-0 / kind-1 signatures.
+ * Call:        pos = lower median of its signatures' positions; len = lower median of the sized signatures' len; rep = index (in
+ *              the signature array) of the sized signature holding it in the order (len, qid, rec, mate) (-1, len 0, without one);
+ *              support / n_sized = distinct reads; its reads ascending at reads[read_off[i] .. read_off[i + 1]).
+ * The CIGAR words are read on the device: the result's resident copy (TELR_MF_KEEP_CIGARS) or one upload.  The output is the
+ * same on every run.  TELR_E_ARG (text in telr_last_error): a negative option, min_sized > min_support, a record's tid outside
+ * [0, n_targets) or coordinates out of order.  No eligible record: zero calls, TELR_OK.  opt NULL = the defaults. */
+typedef struct telr_ins_opt {
+    int32_t min_len;       /* 50  */
+    int32_t min_mapq;      /* 20  */
+    int32_t min_clip;      /* 200 */
+    int32_t max_ref_gap;   /* 200 */
+    int32_t cluster_dist;  /* 50  */
+    int32_t min_support;   /* 10  */
+    int32_t min_sized;     /* 1   */
+    int32_t reserved;      /* 0   */
+} telr_ins_opt;
+typedef struct telr_ins_sig  { int32_t tid, pos, len, qid, kind, rec, mate, seg_start, seg_len; } telr_ins_sig;
+typedef struct telr_ins_call { int32_t tid, pos, len, support, n_sized, rep; } telr_ins_call;
+typedef struct telr_ins_calls telr_ins_calls;
+void telr_ins_opt_default(telr_ins_opt *o);
+int  telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t n_targets, const telr_ins_opt *opt, telr_ins_calls **out);
+int64_t telr_ins_calls_count(const telr_ins_calls *c);
+const telr_ins_call *telr_ins_calls_calls(const telr_ins_calls *c);
+int64_t telr_ins_calls_sig_count(const telr_ins_calls *c);
+const telr_ins_sig *telr_ins_calls_sigs(const telr_ins_calls *c);
+const int64_t *telr_ins_calls_read_off(const telr_ins_calls *c);      /* count + 1 offsets into telr_ins_calls_reads */
+const int32_t *telr_ins_calls_reads(const telr_ins_calls *c);
+void telr_ins_calls_free(telr_ins_calls *c);
+
 /* ---- window reads (a12) -------------------------------------------------------
  * Replaces the per-locus `pysam.AlignmentFile(bam).fetch(chr, bp-1000, bp+1000)` loop of prep_assembly_inputs
  * (src/telr/TELR_assembly.py:384-415, read_type="all"): for every window w = (win_tid, [win_lo, win_hi)) the ascending,

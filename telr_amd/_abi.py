@@ -35,6 +35,28 @@ class Aln(C.Structure):
     ]
 
 
+class InsOpt(C.Structure):
+    """telr_ins_opt: the options of telr_call_insertions (defaults: InsOpt.default())"""
+    _fields_ = [(n, C.c_int32) for n in ("min_len", "min_mapq", "min_clip", "max_ref_gap", "cluster_dist", "min_support", "min_sized", "reserved")]
+
+    @classmethod
+    def default(cls, **kw):
+        o = cls(50, 20, 200, 200, 50, 10, 1, 0)
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("InsOpt has no field %r" % k)
+            setattr(o, k, int(v))
+        return o
+
+
+class InsSig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tid", "pos", "len", "qid", "kind", "rec", "mate", "seg_start", "seg_len")]
+
+
+class InsCall(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tid", "pos", "len", "support", "n_sized", "rep")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "query_bases", "minimizers", "probes", "anchors", "chains", "dp_problems", "dp_cells",
@@ -55,3 +77,6 @@ import numpy as _np
 
 ALN_DTYPE = _np.dtype([(n, _np.int64 if t is C.c_int64 else _np.int32) for n, t in Aln._fields_], align=True)
 assert ALN_DTYPE.itemsize == C.sizeof(Aln) == 88, (ALN_DTYPE.itemsize, C.sizeof(Aln))
+INS_SIG_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsSig._fields_])
+INS_CALL_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsCall._fields_])
+assert INS_SIG_DTYPE.itemsize == C.sizeof(InsSig) == 36 and INS_CALL_DTYPE.itemsize == C.sizeof(InsCall) == 24

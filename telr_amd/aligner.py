@@ -6,7 +6,7 @@ boundary (TELR_alignment.py:69-82 and the five other sites listed in include/tel
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._abi import IdxOpt, MapOpt, Counters, ALN_DTYPE, N_STAGES, N_DPCLS
+from ._abi import IdxOpt, MapOpt, Counters, InsOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, N_STAGES, N_DPCLS
 from .fasta import concat
 
 
@@ -329,6 +329,16 @@ class MapResult:
         return "".join("%d%s" % (c >> 4, "MID"[c & 0xf]) for c in self.cigar(i))
 
 
+class InsCalls:
+    """what Index.call_insertions returns: calls (INS_CALL_DTYPE), sigs (INS_SIG_DTYPE, in key order; a call's `rep` indexes it),
+    and the ascending distinct read ids of call i at reads[read_off[i]:read_off[i + 1]]"""
+    def __init__(self, calls, sigs, read_off, reads):
+        self.calls, self.sigs, self.read_off, self.reads = calls, sigs, read_off, reads
+
+    def reads_of(self, i):
+        return self.reads[self.read_off[i]:self.read_off[i + 1]]
+
+
 class Index:
     def __init__(self, eng, targets, io):
         self.eng = eng
@@ -537,6 +547,23 @@ class Index:
         self.eng._chk(self.eng.L.telr_depth_medians(self.eng.h, r, len(tl), tl.ctypes.data, len(a), a.ctypes.data,
                                                     b.ctypes.data, c.ctypes.data, out.ctypes.data), "telr_depth_medians")
         return out
+
+    def call_insertions(self, r, opt=None):
+        """insertion candidates of raw result r (telr_call_insertions; include/telr_hip.h has the definition): opt an
+        _abi.InsOpt (None: the defaults) -> InsCalls: calls / sigs as numpy structured arrays, read_off / reads the calls' read ids"""
+        o = InsOpt.default() if opt is None else opt
+        h = C.c_void_p()
+        rc = self.eng.L.telr_call_insertions(self.eng.h, r, self.targets.n, C.byref(o), C.byref(h))
+        if rc != 0:
+            raise _lib.TelrError("telr_call_insertions: %s [%s]" % (self.eng.L.telr_strerror(rc).decode(), self.eng.L.telr_last_error(self.eng.h).decode()), rc)
+        try:
+            L = self.eng.L
+            nc, ns = int(L.telr_ins_calls_count(h)), int(L.telr_ins_calls_sig_count(h))
+            read_off = _np_from(L.telr_ins_calls_read_off(h), nc + 1, np.int64)
+            return InsCalls(_np_from(L.telr_ins_calls_calls(h), nc, INS_CALL_DTYPE), _np_from(L.telr_ins_calls_sigs(h), ns, INS_SIG_DTYPE),
+                            read_off, _np_from(L.telr_ins_calls_reads(h), int(read_off[-1]), np.int32))
+        finally:
+            self.eng.L.telr_ins_calls_free(h)
 
     # ---- debug taps for the stage-level parity tests ----------------------------------
     def debug_dump(self):

@@ -1,0 +1,403 @@
+// Insertion candidates from a mapped read set, on the device (include/telr_hip.h: telr_call_insertions).  Stands where
+// the reference shells out to Sniffles (`detect_sv`, src/telr/TELR_sv.py:49-51) -- with an own, fully specified definition, NOT a
+// restatement of Sniffles: signatures (an I run inside a record, a same-strand split between two records of a read, a clipped read
+// end) are sorted by (target, position), single-linkage clustered, and a cluster with enough distinct reads is a call.
+//
+//   k_ins_cigar    one wave per eligible record, 64 CIGAR words per step (coalesced dwords), wave prefix sums of the reference and
+//                  query lengths; run once to count the qualifying I runs of every record and, after a scan, once to write them: a
+//                  signature's place is (records before) + (qualifying runs before it in its record), never an atomic's arrival order;
+//   k_ins_query    one lane per eligible record: its clipped ends and the splits it starts (its read's other records are a short
+//                  contiguous run of the list), counted and written the same way;
+//   sorts          LSD over the complete key with radix.hip.h (stable; a permutation is carried, the keys of a round are gathered
+//                  through it): (kind, len, mate), then rec, then (tid, pos);
+//   clusters       head flags + scan; the distinct reads of a cluster from a sort by (cluster, read, unsized); its representative
+//                  from a sort by (cluster, unsized, len, read, rec, mate); counts are differences of scanned flags at the cluster's
+//                  bounds; calls and their read lists are compacted by two more scans.
+#pragma once
+
+struct InsRec {                 // an eligible record; qs / qe on the record's own strand
+    int32_t qid, tid, ts, te, qs, qe, qlen, rev;
+    int32_t n_cigar, rec, g0, g1;     // [g0, g1): the records of the same read in this list
+    int64_t cigar_off;
+};
+
+struct telr_ins_calls {
+    std::vector<telr_ins_call> calls;
+    std::vector<telr_ins_sig> sigs;
+    std::vector<int64_t> read_off;
+    std::vector<int32_t> reads;
+};
+
+static __device__ __forceinline__ int32_t ins_wave_incl(int32_t v, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int32_t x = __shfl_up(v, o); if (lane >= o) v += x; }
+    return v;
+}
+
+template <bool EMIT>
+__global__ void __launch_bounds__(256) k_ins_cigar(const InsRec *__restrict__ recs, int32_t ne, const uint32_t *__restrict__ cig, int32_t min_len,
+                                                   int32_t *__restrict__ cnt, const int64_t *__restrict__ off, telr_ins_sig *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t w = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+    if (w >= ne) return;
+    const InsRec R = recs[w];
+    const uint32_t *__restrict__ c = cig + R.cigar_off;
+    const int32_t n = R.n_cigar;
+    int32_t rbase = 0, qbase = 0, nout = 0;
+    const int64_t o0 = EMIT ? off[w] : 0;
+    for (int32_t i0 = 0; i0 < n; i0 += 64) {
+        const int32_t i = i0 + lane;
+        const uint32_t word = i < n ? c[i] : 0u;
+        const int32_t op = (int32_t)(word & 15u), len = (int32_t)(word >> 4);
+        const bool hit = i < n && op == 1 && len >= min_len;
+        const uint64_t m = __ballot(hit);
+        if (EMIT) {
+            const int32_t r = (op == 0 || op == 2) ? len : 0, q = (op == 0 || op == 1) ? len : 0;
+            const int32_t ri = ins_wave_incl(r, lane), qi = ins_wave_incl(q, lane);
+            if (hit) {
+                const int32_t rank = __builtin_popcountll(m & ((1ULL << lane) - 1ULL));
+                const int32_t qb = qbase + qi - q;          // query bases of the record before the run, on the record's strand
+                telr_ins_sig s;
+                s.tid = R.tid; s.pos = R.ts + rbase + ri - r; s.len = len; s.qid = R.qid; s.kind = 0; s.rec = R.rec; s.mate = -1;
+                s.seg_start = R.rev ? R.qlen - (R.qs + qb + len) : R.qs + qb; s.seg_len = len;
+                out[o0 + nout + rank] = s;
+            }
+            rbase += __shfl(ri, 63); qbase += __shfl(qi, 63);
+        }
+        nout += __builtin_popcountll(m);
+    }
+    if (!EMIT && lane == 0) cnt[w] = nout;
+}
+
+template <bool EMIT>
+__global__ void __launch_bounds__(256) k_ins_query(const InsRec *__restrict__ recs, int32_t ne, int32_t min_len, int32_t min_clip, int32_t max_ref_gap,
+                                                   int32_t *__restrict__ cnt, const int64_t *__restrict__ off, telr_ins_sig *__restrict__ out)
+{
+    const int64_t a = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (a >= ne) return;
+    const InsRec A = recs[a];
+    telr_ins_sig *o = EMIT ? out + off[a] : nullptr;
+    int32_t n = 0;
+    telr_ins_sig s;
+    s.tid = A.tid; s.qid = A.qid; s.rec = A.rec; s.mate = -1; s.kind = 2;
+    if (A.qs >= min_clip) {
+        if (EMIT) { s.pos = A.ts; s.len = s.seg_len = A.qs; s.seg_start = A.rev ? A.qlen - A.qs : 0; o[n] = s; }
+        ++n;
+    }
+    if (A.qlen - A.qe >= min_clip) {
+        if (EMIT) { s.pos = A.te; s.len = s.seg_len = A.qlen - A.qe; s.seg_start = A.rev ? 0 : A.qe; o[n] = s; }
+        ++n;
+    }
+    s.kind = 1;
+    for (int32_t b = A.g0; b < A.g1; ++b) {
+        if (b == a) continue;
+        const InsRec B = recs[b];
+        if (B.tid != A.tid || B.rev != A.rev) continue;
+        const int64_t qgap = (int64_t)B.qs - A.qe, tgap = (int64_t)B.ts - A.te;
+        if (qgap < 0 || tgap > max_ref_gap || -tgap > max_ref_gap || qgap - tgap < min_len) continue;
+        if (EMIT) {
+            s.pos = A.te; s.len = (int32_t)(qgap - tgap); s.mate = B.rec; s.seg_len = (int32_t)qgap;
+            s.seg_start = A.rev ? A.qlen - B.qs : A.qe;
+            o[n] = s;
+        }
+        ++n;
+    }
+    if (!EMIT) cnt[a] = n;
+}
+
+// the key of a sort round, gathered through the permutation the rounds before left
+enum { INS_K_KLM, INS_K_REC, INS_K_TP, INS_K_CQU, INS_K_RM, INS_K_LQ, INS_K_CU };
+__global__ void __launch_bounds__(256) k_ins_key(int mode, const telr_ins_sig *__restrict__ sig, const int32_t *__restrict__ cid, const uint32_t *__restrict__ perm,
+                                                 int64_t n, int b0, int b1, uint64_t *__restrict__ keys)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t p = perm[i];
+    const telr_ins_sig s = sig[p];
+    const uint64_t uns = s.kind == 2 ? 1u : 0u;
+    uint64_t k = 0;
+    switch (mode) {
+    case INS_K_KLM: k = ((((uint64_t)s.kind << 31) | (uint32_t)s.len) << b0) | (uint32_t)(s.mate + 1); break;      // b0: bits of a record number + 1
+    case INS_K_REC: k = (uint32_t)s.rec; break;
+    case INS_K_TP:  k = ((uint64_t)(uint32_t)s.tid << 32) | (uint32_t)s.pos; break;
+    case INS_K_CQU: k = ((((uint64_t)(uint32_t)cid[p] << b0) | (uint32_t)s.qid) << 1) | uns; break;                    // b0: bits of a read number
+    case INS_K_RM:  k = ((uint64_t)(uint32_t)s.rec << b0) | (uint32_t)(s.mate + 1); break;
+    case INS_K_LQ:  k = ((uint64_t)(uint32_t)s.len << b0) | (uint32_t)s.qid; break;
+    case INS_K_CU:  k = ((uint64_t)(uint32_t)cid[p] << 1) | uns; break;
+    }
+    keys[i] = k;
+}
+__global__ void __launch_bounds__(256) k_ins_iota(uint32_t *__restrict__ perm, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) perm[i] = (uint32_t)i;
+}
+__global__ void __launch_bounds__(256) k_ins_gather(const telr_ins_sig *__restrict__ in, const uint32_t *__restrict__ perm, int64_t n, telr_ins_sig *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = in[perm[i]];
+}
+// head[i] = signature i starts a cluster, sized[i] = it carries a length; both with a trailing 0 for the scans
+__global__ void __launch_bounds__(256) k_ins_heads(const telr_ins_sig *__restrict__ sig, int64_t n, int32_t dist, int32_t *__restrict__ head, int32_t *__restrict__ sized)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { head[i] = 0; sized[i] = 0; return; }
+    const telr_ins_sig s = sig[i];
+    int32_t h = 1;
+    if (i > 0) { const telr_ins_sig p = sig[i - 1]; h = (p.tid != s.tid || (int64_t)s.pos - p.pos > dist) ? 1 : 0; }
+    head[i] = h; sized[i] = s.kind != 2 ? 1 : 0;
+}
+// hx = exclusive scan of head (hx[n] = clusters): cid[i] and the clusters' first signatures (cstart[clusters] = n)
+__global__ void __launch_bounds__(256) k_ins_cid(const int32_t *__restrict__ head, const int32_t *__restrict__ hx, int64_t n, int32_t *__restrict__ cid, int32_t *__restrict__ cstart)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { cstart[hx[n]] = (int32_t)n; return; }
+    cid[i] = hx[i + 1] - 1;
+    if (head[i]) cstart[hx[i]] = (int32_t)i;
+}
+// over the order of the (cluster, read, unsized) sort: dflag = first signature of its read in its cluster, sdflag = ... and it is sized
+// (the sized ones of a read sort first, so the first is sized iff any is)
+__global__ void __launch_bounds__(256) k_ins_distinct(const telr_ins_sig *__restrict__ sig, const int32_t *__restrict__ cid, const uint32_t *__restrict__ perm, int64_t n,
+                                                      int32_t *__restrict__ dflag, int32_t *__restrict__ sdflag)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j > n) return;
+    if (j == n) { dflag[j] = 0; sdflag[j] = 0; return; }
+    const uint32_t p = perm[j];
+    int32_t d = 1;
+    if (j > 0) { const uint32_t q = perm[j - 1]; d = (cid[q] != cid[p] || sig[q].qid != sig[p].qid) ? 1 : 0; }
+    dflag[j] = d; sdflag[j] = d && sig[p].kind != 2 ? 1 : 0;
+}
+// per cluster: distinct reads, distinct sized reads, is it a call; qcnt = the reads it will list
+__global__ void __launch_bounds__(256) k_ins_cluster(const int32_t *__restrict__ cstart, int32_t nc, const int32_t *__restrict__ dx, const int32_t *__restrict__ sdx,
+                                                     int32_t min_support, int32_t min_sized, int32_t *__restrict__ cflag, int32_t *__restrict__ qcnt)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c > nc) return;
+    if (c == nc) { cflag[c] = 0; qcnt[c] = 0; return; }
+    const int32_t lo = cstart[c], hi = cstart[c + 1];
+    const int32_t sup = dx[hi] - dx[lo], nsz = sdx[hi] - sdx[lo];
+    const int32_t ok = sup >= min_support && nsz >= min_sized ? 1 : 0;
+    cflag[c] = ok; qcnt[c] = ok ? sup : 0;
+}
+__global__ void __launch_bounds__(256) k_ins_calls(const telr_ins_sig *__restrict__ sig, const int32_t *__restrict__ cstart, int32_t nc, const int32_t *__restrict__ dx,
+                                                   const int32_t *__restrict__ sdx, const int32_t *__restrict__ sx, const uint32_t *__restrict__ perm_rep,
+                                                   const int32_t *__restrict__ cflag, const int32_t *__restrict__ cx, const int64_t *__restrict__ qx,
+                                                   telr_ins_call *__restrict__ calls, int64_t *__restrict__ read_off)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c > nc) return;
+    if (c == nc) { read_off[cx[nc]] = qx[nc]; return; }
+    if (!cflag[c]) return;
+    const int32_t lo = cstart[c], hi = cstart[c + 1], ns = sx[hi] - sx[lo];
+    telr_ins_call k;
+    k.tid = sig[lo].tid; k.pos = sig[lo + (hi - lo - 1) / 2].pos;
+    k.support = dx[hi] - dx[lo]; k.n_sized = sdx[hi] - sdx[lo];
+    k.rep = ns > 0 ? (int32_t)perm_rep[lo + (ns - 1) / 2] : -1;          // the sized signatures of the cluster come first in the representative sort
+    k.len = ns > 0 ? sig[k.rep].len : 0;
+    calls[cx[c]] = k; read_off[cx[c]] = qx[c];
+}
+__global__ void __launch_bounds__(256) k_ins_reads(const telr_ins_sig *__restrict__ sig, const int32_t *__restrict__ cid, const uint32_t *__restrict__ perm, int64_t n,
+                                                   const int32_t *__restrict__ dflag, const int32_t *__restrict__ dx, const int32_t *__restrict__ cstart,
+                                                   const int32_t *__restrict__ cflag, const int64_t *__restrict__ qx, int32_t *__restrict__ reads)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n || !dflag[j]) return;
+    const uint32_t p = perm[j];
+    const int32_t c = cid[p];
+    if (cflag[c]) reads[qx[c] + (dx[j] - dx[cstart[c]])] = sig[p].qid;
+}
+
+struct InsSort { uint64_t *keys, *tkeys; uint32_t *perm, *tperm, *hist; };
+static int ins_bits(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
+static inline dim3 ins_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+// one stable round: sorts the permutation by `nbits` bits of the keys of `mode`
+static int ins_sort_round(telr_ctx *ctx, InsSort &S, int mode, const telr_ins_sig *sig, const int32_t *cid, int64_t n, int b0, int nbits)
+{
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(k_ins_key, ins_grid(n), dim3(256), 0, st, mode, sig, cid, S.perm, n, b0, 0, S.keys);
+    if (radix_sort_passes<uint64_t, true>(S.keys, S.perm, S.tkeys, S.tperm, n, nbits, S.hist, st)) { std::swap(S.keys, S.tkeys); std::swap(S.perm, S.tperm); }
+    HIPCHK(hipGetLastError());
+    return TELR_OK;
+}
+
+extern "C" void telr_ins_opt_default(telr_ins_opt *o)
+{
+    if (!o) return;
+    o->min_len = 50; o->min_mapq = 20; o->min_clip = 200; o->max_ref_gap = 200; o->cluster_dist = 50; o->min_support = 10; o->min_sized = 1; o->reserved = 0;
+}
+extern "C" int64_t telr_ins_calls_count(const telr_ins_calls *c) { return c ? (int64_t)c->calls.size() : 0; }
+extern "C" const telr_ins_call *telr_ins_calls_calls(const telr_ins_calls *c) { return c ? c->calls.data() : nullptr; }
+extern "C" int64_t telr_ins_calls_sig_count(const telr_ins_calls *c) { return c ? (int64_t)c->sigs.size() : 0; }
+extern "C" const telr_ins_sig *telr_ins_calls_sigs(const telr_ins_calls *c) { return c ? c->sigs.data() : nullptr; }
+extern "C" const int64_t *telr_ins_calls_read_off(const telr_ins_calls *c) { return c ? c->read_off.data() : nullptr; }
+extern "C" const int32_t *telr_ins_calls_reads(const telr_ins_calls *c) { return c ? c->reads.data() : nullptr; }
+extern "C" void telr_ins_calls_free(telr_ins_calls *c) { delete c; }
+
+extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t n_targets, const telr_ins_opt *opt, telr_ins_calls **out)
+{
+    (void)hipGetLastError();
+    if (!ctx) return TELR_E_ARG;
+    auto bad = [&](const std::string &why) { ctx->err = "telr_call_insertions: " + why; return TELR_E_ARG; };
+    if (!r || !out) return bad("null result or output");
+    if (n_targets <= 0) return bad("n_targets must be positive");
+    telr_ins_opt O;
+    if (opt) O = *opt; else telr_ins_opt_default(&O);
+    if (O.min_len < 0 || O.min_mapq < 0 || O.min_clip < 0 || O.max_ref_gap < 0 || O.cluster_dist < 0 || O.min_support < 0 || O.min_sized < 0)
+        return bad("negative option");
+    if (O.min_sized > O.min_support) return bad("min_sized > min_support");
+    const size_t n = r->alns.size();
+    if (n >= 0x7ffffff0u) { ctx->err = "telr_call_insertions: too many records"; return TELR_E_RANGE; }
+    // the eligible records, grouped by read (a mapped result is in read order already)
+    std::vector<InsRec> er;
+    int32_t max_qid = 0; bool in_order = true;
+    for (size_t i = 0; i < n; ++i) {
+        const telr_aln &a = r->alns[i];
+        if (a.tid < 0 || a.tid >= n_targets) return bad("record " + std::to_string(i) + ": tid outside n_targets");
+        if (a.qid < 0 || a.qlen < 0 || a.qs < 0 || a.qe < a.qs || a.qe > a.qlen || a.ts < 0 || a.te < a.ts)
+            return bad("record " + std::to_string(i) + ": coordinates");
+        if (a.n_cigar < 0 || a.cigar_off < 0 || (uint64_t)a.cigar_off + (uint64_t)a.n_cigar > (uint64_t)r->ncig)
+            return bad("record " + std::to_string(i) + ": CIGAR range outside the result's array");
+        if ((a.flags & TELR_F_SECONDARY) || a.mapq < O.min_mapq) continue;
+        InsRec e;
+        e.qid = a.qid; e.tid = a.tid; e.ts = a.ts; e.te = a.te; e.qlen = a.qlen; e.rev = (a.flags & TELR_F_REV) ? 1 : 0;
+        e.qs = e.rev ? a.qlen - a.qe : a.qs; e.qe = e.rev ? a.qlen - a.qs : a.qe;
+        e.n_cigar = a.n_cigar; e.rec = (int32_t)i; e.g0 = e.g1 = 0; e.cigar_off = a.cigar_off;
+        if (!er.empty() && er.back().qid > e.qid) in_order = false;
+        max_qid = std::max(max_qid, a.qid);
+        er.push_back(e);
+    }
+    if (!in_order) std::stable_sort(er.begin(), er.end(), [](const InsRec &x, const InsRec &y) { return x.qid < y.qid; });
+    const size_t ne = er.size();
+    for (size_t i = 0; i < ne; ) {
+        size_t j = i + 1;
+        while (j < ne && er[j].qid == er[i].qid) ++j;
+        for (size_t k = i; k < j; ++k) { er[k].g0 = (int32_t)i; er[k].g1 = (int32_t)j; }
+        i = j;
+    }
+    telr_ins_calls *C = new telr_ins_calls();
+    C->read_off.assign(1, 0);
+    std::unique_ptr<telr_ins_calls> guard(C);
+    if (ne == 0) { *out = guard.release(); return TELR_OK; }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    result_wait(r);
+    // the CIGAR array: the result's own device copy when it kept one (TELR_MF_KEEP_CIGARS), else uploaded
+    const bool twin = r->d_cig && !r->twin_off && r->twin_n == r->ncig;
+    uint32_t *d_cig;
+    if (twin) { d_cig = r->d_cig; HIPCHK(hipDeviceSynchronize()); }
+    else {
+        TRY(ctx_buf_t(ctx, "ins_cig", r->ncig, &d_cig));
+        if (r->ncig) HIPCHK(hipMemcpyAsync(d_cig, r->cig, r->ncig * 4, hipMemcpyHostToDevice, st));
+    }
+    InsRec *d_rec; int32_t *d_cnt0, *d_cnt1; int64_t *d_off0, *d_off1, *d_tot;
+    TRY(ctx_buf_t(ctx, "ins_rec", ne, &d_rec));
+    TRY(ctx_buf_t(ctx, "ins_cnt0", ne + 1, &d_cnt0));
+    TRY(ctx_buf_t(ctx, "ins_cnt1", ne + 1, &d_cnt1));
+    TRY(ctx_buf_t(ctx, "ins_off0", ne + 1, &d_off0));
+    TRY(ctx_buf_t(ctx, "ins_off1", ne + 1, &d_off1));
+    TRY(ctx_buf_t(ctx, "ins_tot", 4, &d_tot));
+    HIPCHK(hipMemcpyAsync(d_rec, er.data(), ne * sizeof(InsRec), hipMemcpyHostToDevice, st));
+    const dim3 gw((unsigned)((ne + 3) / 4)), gl = ins_grid((int64_t)ne);
+    hipLaunchKernelGGL((k_ins_cigar<false>), gw, dim3(256), 0, st, d_rec, (int32_t)ne, d_cig, O.min_len, d_cnt0, (const int64_t*)nullptr, (telr_ins_sig*)nullptr);
+    hipLaunchKernelGGL((k_ins_query<false>), gl, dim3(256), 0, st, d_rec, (int32_t)ne, O.min_len, O.min_clip, O.max_ref_gap, d_cnt1, (const int64_t*)nullptr, (telr_ins_sig*)nullptr);
+    HIPCHK(hipGetLastError());
+    TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt0, (int32_t)ne, d_off0, d_tot, 0, nullptr, nullptr)));
+    TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt1, (int32_t)ne, d_off1, d_tot + 1, 0, nullptr, nullptr)));
+    int64_t tot[2];
+    HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int64_t N = tot[0] + tot[1];
+    if (N == 0) { *out = guard.release(); return TELR_OK; }
+    if (N >= 0x7ffffff0LL) { ctx->err = "telr_call_insertions: too many signatures"; return TELR_E_RANGE; }
+    telr_ins_sig *d_raw, *d_sig;
+    TRY(ctx_buf_t(ctx, "ins_raw", (size_t)N, &d_raw));
+    TRY(ctx_buf_t(ctx, "ins_sig", (size_t)N, &d_sig));
+    hipLaunchKernelGGL((k_ins_cigar<true>), gw, dim3(256), 0, st, d_rec, (int32_t)ne, d_cig, O.min_len, d_cnt0, d_off0, d_raw);
+    hipLaunchKernelGGL((k_ins_query<true>), gl, dim3(256), 0, st, d_rec, (int32_t)ne, O.min_len, O.min_clip, O.max_ref_gap, d_cnt1, d_off1, d_raw + tot[0]);
+    HIPCHK(hipGetLastError());
+    // sort by (tid, pos, rec, kind, len, mate): least significant group first
+    InsSort S;
+    const size_t ntiles = ((size_t)N + RS_TILE - 1) / RS_TILE;
+    TRY(ctx_buf_t(ctx, "ins_keys", (size_t)N, &S.keys));
+    TRY(ctx_buf_t(ctx, "ins_tkeys", (size_t)N, &S.tkeys));
+    TRY(ctx_buf_t(ctx, "ins_perm", (size_t)N, &S.perm));
+    TRY(ctx_buf_t(ctx, "ins_tperm", (size_t)N, &S.tperm));
+    TRY(ctx_buf_t(ctx, "ins_hist", (size_t)RS_BINS * ntiles + RS_BINS, &S.hist));
+    const int rb = ins_bits((uint64_t)n), qb = ins_bits((uint64_t)max_qid), tb = ins_bits((uint64_t)n_targets - 1);
+    const dim3 gN = ins_grid(N), gN1 = ins_grid(N + 1);
+    hipLaunchKernelGGL(k_ins_iota, gN, dim3(256), 0, st, S.perm, N);
+    TRY(ins_sort_round(ctx, S, INS_K_KLM, d_raw, nullptr, N, rb, 33 + rb));
+    TRY(ins_sort_round(ctx, S, INS_K_REC, d_raw, nullptr, N, 0, rb));
+    TRY(ins_sort_round(ctx, S, INS_K_TP, d_raw, nullptr, N, 0, 32 + tb));
+    hipLaunchKernelGGL(k_ins_gather, gN, dim3(256), 0, st, d_raw, S.perm, N, d_sig);
+    // clusters
+    int32_t *d_head, *d_hx, *d_sized, *d_sx, *d_cid, *d_cstart, *d_dflag, *d_sdflag, *d_dx, *d_sdx;
+    TRY(ctx_buf_t(ctx, "ins_head", (size_t)N + 1, &d_head));
+    TRY(ctx_buf_t(ctx, "ins_hx", (size_t)N + 1, &d_hx));
+    TRY(ctx_buf_t(ctx, "ins_sized", (size_t)N + 1, &d_sized));
+    TRY(ctx_buf_t(ctx, "ins_sx", (size_t)N + 1, &d_sx));
+    TRY(ctx_buf_t(ctx, "ins_cid", (size_t)N + 1, &d_cid));
+    TRY(ctx_buf_t(ctx, "ins_cstart", (size_t)N + 1, &d_cstart));
+    TRY(ctx_buf_t(ctx, "ins_dflag", (size_t)N + 1, &d_dflag));
+    TRY(ctx_buf_t(ctx, "ins_sdflag", (size_t)N + 1, &d_sdflag));
+    TRY(ctx_buf_t(ctx, "ins_dx", (size_t)N + 1, &d_dx));
+    TRY(ctx_buf_t(ctx, "ins_sdx", (size_t)N + 1, &d_sdx));
+    hipLaunchKernelGGL(k_ins_heads, gN1, dim3(256), 0, st, d_sig, N, O.cluster_dist, d_head, d_sized);
+    HIPCHK(hipGetLastError());
+    TRY((dev_qscan<int32_t, int32_t>(ctx, d_head, (int32_t)N, d_hx, nullptr, 0, nullptr, nullptr)));
+    TRY((dev_qscan<int32_t, int32_t>(ctx, d_sized, (int32_t)N, d_sx, nullptr, 0, nullptr, nullptr)));
+    hipLaunchKernelGGL(k_ins_cid, gN1, dim3(256), 0, st, d_head, d_hx, N, d_cid, d_cstart);
+    int32_t nc = 0;
+    HIPCHK(hipMemcpyAsync(&nc, d_hx + N, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int cb = ins_bits((uint64_t)nc - 1);
+    // the distinct reads of every cluster
+    hipLaunchKernelGGL(k_ins_iota, gN, dim3(256), 0, st, S.perm, N);
+    TRY(ins_sort_round(ctx, S, INS_K_CQU, d_sig, d_cid, N, qb, cb + qb + 1));
+    uint32_t *d_permd;
+    TRY(ctx_buf_t(ctx, "ins_permd", (size_t)N, &d_permd));
+    HIPCHK(hipMemcpyAsync(d_permd, S.perm, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_ins_distinct, gN1, dim3(256), 0, st, d_sig, d_cid, d_permd, N, d_dflag, d_sdflag);
+    HIPCHK(hipGetLastError());
+    TRY((dev_qscan<int32_t, int32_t>(ctx, d_dflag, (int32_t)N, d_dx, nullptr, 0, nullptr, nullptr)));
+    TRY((dev_qscan<int32_t, int32_t>(ctx, d_sdflag, (int32_t)N, d_sdx, nullptr, 0, nullptr, nullptr)));
+    // the representative: (cluster, unsized, len, read, rec, mate)
+    hipLaunchKernelGGL(k_ins_iota, gN, dim3(256), 0, st, S.perm, N);
+    TRY(ins_sort_round(ctx, S, INS_K_RM, d_sig, d_cid, N, rb, 2 * rb));
+    TRY(ins_sort_round(ctx, S, INS_K_LQ, d_sig, d_cid, N, qb, 31 + qb));
+    TRY(ins_sort_round(ctx, S, INS_K_CU, d_sig, d_cid, N, 0, cb + 1));
+    // calls
+    int32_t *d_cflag, *d_qcnt, *d_cx; int64_t *d_qx;
+    TRY(ctx_buf_t(ctx, "ins_cflag", (size_t)nc + 1, &d_cflag));
+    TRY(ctx_buf_t(ctx, "ins_qcnt", (size_t)nc + 1, &d_qcnt));
+    TRY(ctx_buf_t(ctx, "ins_cx", (size_t)nc + 1, &d_cx));
+    TRY(ctx_buf_t(ctx, "ins_qx", (size_t)nc + 1, &d_qx));
+    const dim3 gC1 = ins_grid((int64_t)nc + 1);
+    hipLaunchKernelGGL(k_ins_cluster, gC1, dim3(256), 0, st, d_cstart, nc, d_dx, d_sdx, O.min_support, O.min_sized, d_cflag, d_qcnt);
+    HIPCHK(hipGetLastError());
+    TRY((dev_qscan<int32_t, int32_t>(ctx, d_cflag, nc, d_cx, d_tot, 0, nullptr, nullptr)));
+    TRY((dev_qscan<int32_t, int64_t>(ctx, d_qcnt, nc, d_qx, d_tot + 1, 0, nullptr, nullptr)));
+    HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int64_t ncall = tot[0], nread = tot[1];
+    telr_ins_call *d_calls; int64_t *d_roff; int32_t *d_reads;
+    TRY(ctx_buf_t(ctx, "ins_calls", (size_t)ncall, &d_calls));
+    TRY(ctx_buf_t(ctx, "ins_roff", (size_t)ncall + 1, &d_roff));
+    TRY(ctx_buf_t(ctx, "ins_reads", (size_t)nread, &d_reads));
+    hipLaunchKernelGGL(k_ins_calls, gC1, dim3(256), 0, st, d_sig, d_cstart, nc, d_dx, d_sdx, d_sx, S.perm, d_cflag, d_cx, d_qx, d_calls, d_roff);
+    hipLaunchKernelGGL(k_ins_reads, gN, dim3(256), 0, st, d_sig, d_cid, d_permd, N, d_dflag, d_dx, d_cstart, d_cflag, d_qx, d_reads);
+    HIPCHK(hipGetLastError());
+    C->sigs.resize((size_t)N); C->calls.resize((size_t)ncall); C->read_off.resize((size_t)ncall + 1); C->reads.resize((size_t)nread);
+    HIPCHK(hipMemcpyAsync(C->sigs.data(), d_sig, (size_t)N * sizeof(telr_ins_sig), hipMemcpyDeviceToHost, st));
+    if (ncall) HIPCHK(hipMemcpyAsync(C->calls.data(), d_calls, (size_t)ncall * sizeof(telr_ins_call), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(C->read_off.data(), d_roff, ((size_t)ncall + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (nread) HIPCHK(hipMemcpyAsync(C->reads.data(), d_reads, (size_t)nread * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *out = guard.release();
+    return TELR_OK;
+}

@@ -3589,3 +3589,4 @@ extern "C" int telr_write_bam(const telr_result *r, int32_t n_queries, const cha
 #include "fasta_io.hip.h"
 #include "pileup.hip.h"
 #include "poa.hip.h"
+#include "inscall.hip.h"

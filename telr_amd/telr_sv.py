@@ -4,7 +4,8 @@ Mirror of the table-side half of the reference's SV module: `merge_vcf` src/telr
 :143-150, `average` :153-156, `swap_coordinate` :183-190, `rm_vcf_redundancy` :193-228, `filter_vcf` :231-324,
 `write_ins_seqs` :328-334, `id_merge` :337-341, `get_unique_list` :343-348, `af_sum` :351-355, and `create_loci_set`
 src/telr/TELR_utility.py:44-50.  Calling Sniffles / bcftools (`detect_sv`, the query in `parse_vcf`) is outside the
-alignment path and not provided.  `filter_vcf` keeps the reference's table arithmetic and takes the TE intervals of the
+alignment path and not provided; its opt-in counterpart is `call_insertions`: the engine's own insertion caller
+(`telr_call_insertions`, a definition of its own, not Sniffles') run on the stage-1 result, returning rows of this table.  `filter_vcf` keeps the reference's table arithmetic and takes the TE intervals of the
 ALT sequences from a `screen`: `gff_screen` reads a RepeatMasker `.out.gff` (the reference's source, :256-295),
 `engine_screen` (opt-in: it changes which loci pass) maps the TE library onto the ALT sequences
 with the HIP engine instead.
@@ -21,6 +22,59 @@ the reference depends on PYTHONHASHSEED; the set of names, and therefore alt_cou
 """
 COLUMNS = ("chrom", "start", "end", "sv_length", "coverage", "sniffles_af", "sv_id", "ins_seq", "reads", "filter",
            "genotype", "ref_count", "alt_count", "ins_te_prop")
+
+
+_RC = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+# what a row made by call_insertions holds where Sniffles would supply a value this caller does not compute: an AF that parses as a
+# float (merge_rows and dedup_rows add the column up), the VCF missing genotype, a ref_count that is text (summed as text, printed as is)
+NO_AF, NO_GENOTYPE, NO_REF_COUNT, NO_TE_PROP = "nan", "./.", "NA", "NA"
+
+
+def call_insertions(index, result, tnames, qnames, reads, opt=None, sample="telr", te_prop_column=True):
+    """Candidate-locus rows (COLUMNS order; te_prop_column=False leaves the 14th out, for a table that goes through `filter_vcf`,
+    which appends it) from a stage-1 result, with the engine's
+    own insertion caller (`telr_call_insertions`) in the place of `detect_sv` + `parse_vcf` (TELR_sv.py:13-81,
+    159-181).  Opt-in and NOT Sniffles: another definition of a call, whose agreement with Sniffles is not pinned.
+    index: the aligner.Index the reads were mapped against; result: the raw handle of `index.map_raw`; tnames / qnames: target
+    and read names by id; reads: the read sequences (a list of str / bytes, or the (buffer, offsets, lengths) triple given to
+    `seqset`); opt: an `_abi.InsOpt` (None = defaults).
+    start = the call's position, end = start + 1, sv_length = the median length of the sized signatures, coverage = alt_count =
+    the distinct supporting reads, ins_seq = the representative signature's segment of its read, on the reference strand.
+    Rows are sorted by (target id, position), as `merge_rows` and `telr_assembly.window_reads` take them."""
+    import numpy as np
+    from .aligner import _np_from
+    from ._abi import ALN_DTYPE, F_REV
+    ic = index.call_insertions(result, opt)
+    L = index.eng.L
+    flags = _np_from(L.telr_result_alns(result), L.telr_result_count(result), ALN_DTYPE)["flags"] if len(ic.calls) else None
+
+    def segment(qid, s, n):
+        if isinstance(reads, tuple) and len(reads) == 3:
+            buf, off, _ = reads
+            return bytes(np.asarray(buf[int(off[qid]) + s:int(off[qid]) + s + n], dtype=np.uint8))
+        r = reads[qid]
+        return (r.encode() if isinstance(r, str) else bytes(r))[s:s + n]
+
+    rows = []
+    for k, c in enumerate(ic.calls):
+        seq = b"N"
+        if c["rep"] >= 0:
+            s = ic.sigs[c["rep"]]
+            seq = segment(int(s["qid"]), int(s["seg_start"]), int(s["seg_len"])) or b"N"
+            if int(flags[s["rec"]]) & F_REV:
+                seq = seq.translate(_RC)[::-1]
+        names = ",".join(qnames[q] for q in ic.reads_of(k).tolist())
+        rows.append([tnames[c["tid"]], str(int(c["pos"])), str(int(c["pos"]) + 1), str(int(c["len"])), str(int(c["support"])), NO_AF,
+                     "%s.INS.%d" % (sample, k), seq.decode(), names, "PASS", NO_GENOTYPE, NO_REF_COUNT, str(int(c["support"]))] +
+                    ([NO_TE_PROP] if te_prop_column else []))
+    return rows
+
+
+def write_locus_table(rows, path):
+    """rows -> the tab-separated table `read_locus_table` reads"""
+    with open(path, "w") as fh:
+        for r in rows:
+            fh.write("\t".join(str(v) for v in r) + "\n")
 
 
 def string2int(lst, integer=True):

@@ -1,0 +1,87 @@
+"""Times telr_call_insertions on a stage-1 result of BASELINE configs[2] shape (bench.py's data set: --coverage / --genome-scale
+make it smaller), once with the result's resident CIGAR copy (TELR_MF_KEEP_CIGARS) and once with the CIGAR array uploaded, and the
+plain-Python restatement (tests/inscall_ref.py) on a sample of the reads, scaled to the whole set.  Writes profiles/inscall_time.json.
+
+    python tools/inscall_time.py [--coverage 30] [--genome-scale 1.0] [--repeat 5] [--sample-reads 2000] [--out profiles/inscall_time.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--coverage", type=float, default=0.0)
+    ap.add_argument("--genome-scale", type=float, default=1.0)
+    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--sample-reads", type=int, default=2000)
+    ap.add_argument("--min-support", type=int, default=10)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "inscall_time.json"))
+    a = ap.parse_args()
+    import numpy as np
+    import bench
+    cfg = bench.CONFIGS["c2"]
+    ba = argparse.Namespace(config="c2", genome_scale=a.genome_scale, insertions=0, coverage=a.coverage, scaling="strong")
+    D = bench.build_dataset(ba, cfg, 0, 1, 1)                      # before the GPU is touched: the generator forks workers
+    import torch  # noqa: F401
+    import inscall_ref as ref
+    from telr_amd.aligner import Engine
+    from telr_amd.presets import preset
+    from telr_amd._abi import InsOpt, MF_KEEP_CIGARS
+    eng = Engine(0)
+    io, mo = preset(cfg["preset"])
+    ix = eng.index([bytes(r).decode() for r in D["ref"]], io)
+    qs = eng.seqset(D["reads"])
+    opt = InsOpt.default(min_support=a.min_support)
+
+    def timed(r):
+        ts = []
+        for _ in range(a.repeat + 1):
+            t0 = time.perf_counter()
+            ic = ix.call_insertions(r, opt)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return ic, ts[1:]                                          # the first call sizes the context's scratch
+
+    mk = mo.copy(); mk.flags |= MF_KEEP_CIGARS
+    r = ix.map_raw(qs, mk)
+    res = ix.result_arrays(r)
+    ic_res, ms_res = timed(r)
+    ix.free_raw(r)
+    r = ix.map_raw(qs, mo)
+    ic_up, ms_up = timed(r)
+    ix.free_raw(r)
+    assert ic_res.sigs.tobytes() == ic_up.sigs.tobytes() and ic_res.calls.tobytes() == ic_up.calls.tobytes()
+    # the plain restatement on the records of the first --sample-reads reads
+    alns = res.alns[res.alns["qid"] < a.sample_reads]
+    t0 = time.perf_counter()
+    sigs = ref.signatures(alns, res.cigars, dict(min_support=a.min_support))
+    ref.calls(sigs, dict(min_support=a.min_support))
+    py_s = time.perf_counter() - t0
+    ops_sample, ops_all = int(alns["n_cigar"].sum()), int(res.alns["n_cigar"].sum())
+    out = {
+        "workload": D["text"], "device": eng.device_name(), "preset": cfg["preset"], "options": {k: getattr(opt, k) for k, _ in InsOpt._fields_},
+        "reads": int(D["total_reads"]), "read_bases": int(D["total_bases"]), "records": int(len(res.alns)), "cigar_words": int(len(res.cigars)),
+        "cigar_words_of_records": ops_all, "signatures": int(len(ic_res.sigs)), "calls": int(len(ic_res.calls)),
+        "call_insertions_ms_resident_cigars": {"min": min(ms_res), "median": float(np.median(ms_res)), "all": ms_res},
+        "call_insertions_ms_uploaded_cigars": {"min": min(ms_up), "median": float(np.median(ms_up)), "all": ms_up},
+        "python_restatement": {"sample_reads": a.sample_reads, "sample_cigar_words": ops_sample, "seconds": py_s,
+                               "scaled_to_all_records_seconds": py_s * ops_all / max(1, ops_sample),
+                               "note": "tests/inscall_ref.py, one CPU thread; scaled by CIGAR words"},
+        "timing": "wall clock of Index.call_insertions (validation, record upload, kernels, the signatures and calls copied back), %d repeats after one untimed call" % a.repeat,
+    }
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps({k: out[k] for k in ("records", "cigar_words", "signatures", "calls", "call_insertions_ms_resident_cigars",
+                                          "call_insertions_ms_uploaded_cigars", "python_restatement")}))
+
+
+if __name__ == "__main__":
+    main()
