@@ -478,6 +478,47 @@ const int64_t *telr_ins_calls_read_off(const telr_ins_calls *c);      /* count +
 const int32_t *telr_ins_calls_reads(const telr_ins_calls *c);
 void telr_ins_calls_free(telr_ins_calls *c);
 
+/* ---- genotypes of those calls: reference reads, AF and GT (opt-in).  In the reference the three values come
+ *      from Sniffles (`%AF`, `%GT`, `%DR`, src/telr/TELR_sv.py:161).  An OWN definition like the caller's, NOT Sniffles' genotyper;
+ *      its agreement with Sniffles is unpinned.
+ * Input: a result and calls as telr_call_insertions returns them: calls[n_calls] strictly ascending by (tid, pos), and the supporter
+ *      set R_k of call k = reads[read_off[k] .. read_off[k + 1]), ascending and distinct.
+ * Eligible records: not TELR_F_SECONDARY, mapq >= min_mapq.  An eligible record SPANS call k = (tid, pos) iff rec.tid == tid,
+ *      rec.ts <= max(0, pos - flank) and rec.te >= pos + flank.
+ * Window indel of a spanning record for call k: walk its CIGAR with p = ts.  An M of length l: p += l.  An I of length l adds l iff
+ *      pos - flank <= p <= pos + flank (p unchanged).  A D of length l adds max(0, min(p + l, pos + flank) - max(p, pos - flank)),
+ *      then p += l.  A record with n_cigar == 0 has window indel 0.  The pair is CLEAN iff window indel <= max_window_indel.
+ * A read q outside R_k with at least one spanning record is a REFERENCE read of k if any of its spanning records is clean, and an
+ *      AMBIGUOUS read of k otherwise.  Reads in R_k are neither.
+ * Per call: alt = support; ref, ambig = the distinct reads of either kind, listed ascending at ref_reads[ref_off[k] ..
+ *      ref_off[k + 1]) and ambig_reads[ambig_off[k] .. ambig_off[k + 1]); gt = 2 (1/1) if 100 * alt >= hom_pct * (alt + ref), else
+ *      1 (0/1) if 100 * alt >= het_pct * (alt + ref), else 0 (0/0).  Ambiguous reads are in neither term.  Integer arithmetic only.
+ * The CIGAR words are read on the device (the result's resident copy, TELR_MF_KEEP_CIGARS, or one upload).  The output is the same
+ * on every run.  TELR_E_ARG (text in telr_last_error): a negative option, het_pct > hom_pct or either above 100, calls not strictly
+ * ascending, a call's tid outside [0, n_targets) or a negative pos, a read list not ascending, a record that telr_call_insertions
+ * would refuse.  TELR_E_RANGE from 2^31 - 16 (call, record) pairs on.  Zero calls: empty output.  Calls without a spanning record:
+ * zeros and empty lists.  opt NULL = the defaults. */
+typedef struct telr_geno_opt {
+    int32_t flank;             /* 50 */
+    int32_t min_mapq;          /* 20 */
+    int32_t max_window_indel;  /* 20 */
+    int32_t het_pct;           /* 30 */
+    int32_t hom_pct;           /* 80 */
+    int32_t reserved[3];       /* 0  */
+} telr_geno_opt;
+typedef struct telr_ins_gt { int32_t ref, ambig, alt, gt; } telr_ins_gt;
+typedef struct telr_ins_geno telr_ins_geno;
+void telr_geno_opt_default(telr_geno_opt *o);
+int  telr_genotype_insertions(telr_ctx *ctx, const telr_result *r, int32_t n_targets, int64_t n_calls, const telr_ins_call *calls,
+                              const int64_t *read_off, const int32_t *reads, const telr_geno_opt *opt, telr_ins_geno **out);
+int64_t telr_ins_geno_count(const telr_ins_geno *g);
+const telr_ins_gt *telr_ins_geno_gt(const telr_ins_geno *g);
+const int64_t *telr_ins_geno_ref_off(const telr_ins_geno *g);         /* count + 1 offsets into telr_ins_geno_ref_reads */
+const int32_t *telr_ins_geno_ref_reads(const telr_ins_geno *g);
+const int64_t *telr_ins_geno_ambig_off(const telr_ins_geno *g);       /* count + 1 offsets into telr_ins_geno_ambig_reads */
+const int32_t *telr_ins_geno_ambig_reads(const telr_ins_geno *g);
+void telr_ins_geno_free(telr_ins_geno *g);
+
 /* ---- window reads (a12) -------------------------------------------------------
  * Replaces the per-locus `pysam.AlignmentFile(bam).fetch(chr, bp-1000, bp+1000)` loop of prep_assembly_inputs
  * (src/telr/TELR_assembly.py:384-415, read_type="all"): for every window w = (win_tid, [win_lo, win_hi)) the ascending,

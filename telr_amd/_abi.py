@@ -57,6 +57,24 @@ class InsCall(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("tid", "pos", "len", "support", "n_sized", "rep")]
 
 
+class GenoOpt(C.Structure):
+    """telr_geno_opt: the options of telr_genotype_insertions (defaults: GenoOpt.default())"""
+    _fields_ = [(n, C.c_int32) for n in ("flank", "min_mapq", "max_window_indel", "het_pct", "hom_pct", "reserved0", "reserved1", "reserved2")]
+
+    @classmethod
+    def default(cls, **kw):
+        o = cls(50, 20, 20, 30, 80, 0, 0, 0)
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("GenoOpt has no field %r" % k)
+            setattr(o, k, int(v))
+        return o
+
+
+class InsGt(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("ref", "ambig", "alt", "gt")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "query_bases", "minimizers", "probes", "anchors", "chains", "dp_problems", "dp_cells",
@@ -80,3 +98,5 @@ assert ALN_DTYPE.itemsize == C.sizeof(Aln) == 88, (ALN_DTYPE.itemsize, C.sizeof(
 INS_SIG_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsSig._fields_])
 INS_CALL_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsCall._fields_])
 assert INS_SIG_DTYPE.itemsize == C.sizeof(InsSig) == 36 and INS_CALL_DTYPE.itemsize == C.sizeof(InsCall) == 24
+GENO_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsGt._fields_])
+assert GENO_DTYPE.itemsize == C.sizeof(InsGt) == 16 and C.sizeof(GenoOpt) == 32

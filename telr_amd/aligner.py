@@ -6,7 +6,7 @@ boundary (TELR_alignment.py:69-82 and the five other sites listed in include/tel
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._abi import IdxOpt, MapOpt, Counters, InsOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, N_STAGES, N_DPCLS
+from ._abi import IdxOpt, MapOpt, Counters, InsOpt, GenoOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, N_STAGES, N_DPCLS
 from .fasta import concat
 
 
@@ -339,6 +339,19 @@ class InsCalls:
         return self.reads[self.read_off[i]:self.read_off[i + 1]]
 
 
+class InsGenotypes:
+    """what Index.genotype_insertions returns: gt (GENO_DTYPE: ref, ambig, alt, gt with 0 = 0/0, 1 = 0/1, 2 = 1/1) per call, and the
+    ascending distinct ids of call i's reference reads at ref_reads[ref_off[i]:ref_off[i + 1]], of its ambiguous reads likewise"""
+    def __init__(self, gt, ref_off, ref_reads, ambig_off, ambig_reads):
+        self.gt, self.ref_off, self.ref_reads, self.ambig_off, self.ambig_reads = gt, ref_off, ref_reads, ambig_off, ambig_reads
+
+    def ref_reads_of(self, i):
+        return self.ref_reads[self.ref_off[i]:self.ref_off[i + 1]]
+
+    def ambig_reads_of(self, i):
+        return self.ambig_reads[self.ambig_off[i]:self.ambig_off[i + 1]]
+
+
 class Index:
     def __init__(self, eng, targets, io):
         self.eng = eng
@@ -564,6 +577,31 @@ class Index:
                             read_off, _np_from(L.telr_ins_calls_reads(h), int(read_off[-1]), np.int32))
         finally:
             self.eng.L.telr_ins_calls_free(h)
+
+    def genotype_insertions(self, r, ic, opt=None):
+        """reference reads, ambiguous reads and GT of the calls `ic` (an InsCalls of call_insertions, or anything with calls /
+        read_off / reads of that form) on raw result r (telr_genotype_insertions; include/telr_hip.h has the definition, which is
+        not Sniffles'): opt an _abi.GenoOpt (None: the defaults) -> InsGenotypes"""
+        o = GenoOpt.default() if opt is None else opt
+        calls = np.ascontiguousarray(ic.calls, dtype=INS_CALL_DTYPE)
+        read_off = np.ascontiguousarray(ic.read_off, dtype=np.int64)
+        reads = np.ascontiguousarray(ic.reads, dtype=np.int32)
+        if len(read_off) != len(calls) + 1 or (len(calls) and int(read_off[-1]) > len(reads)):
+            raise _lib.TelrError("telr_genotype_insertions: read_off must hold len(calls) + 1 offsets into reads")
+        h = C.c_void_p()
+        rc = self.eng.L.telr_genotype_insertions(self.eng.h, r, self.targets.n, len(calls), calls.ctypes.data, read_off.ctypes.data, reads.ctypes.data,
+                                                 C.byref(o), C.byref(h))
+        if rc != 0:
+            raise _lib.TelrError("telr_genotype_insertions: %s [%s]" % (self.eng.L.telr_strerror(rc).decode(), self.eng.L.telr_last_error(self.eng.h).decode()), rc)
+        try:
+            L = self.eng.L
+            nc = int(L.telr_ins_geno_count(h))
+            ref_off = _np_from(L.telr_ins_geno_ref_off(h), nc + 1, np.int64)
+            ambig_off = _np_from(L.telr_ins_geno_ambig_off(h), nc + 1, np.int64)
+            return InsGenotypes(_np_from(L.telr_ins_geno_gt(h), nc, GENO_DTYPE), ref_off, _np_from(L.telr_ins_geno_ref_reads(h), int(ref_off[-1]), np.int32),
+                                ambig_off, _np_from(L.telr_ins_geno_ambig_reads(h), int(ambig_off[-1]), np.int32))
+        finally:
+            self.eng.L.telr_ins_geno_free(h)
 
     # ---- debug taps for the stage-level parity tests ----------------------------------
     def debug_dump(self):

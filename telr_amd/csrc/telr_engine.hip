@@ -3590,3 +3590,4 @@ extern "C" int telr_write_bam(const telr_result *r, int32_t n_queries, const cha
 #include "pileup.hip.h"
 #include "poa.hip.h"
 #include "inscall.hip.h"
+#include "genotype.hip.h"

@@ -25,12 +25,13 @@ COLUMNS = ("chrom", "start", "end", "sv_length", "coverage", "sniffles_af", "sv_
 
 
 _RC = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
-# what a row made by call_insertions holds where Sniffles would supply a value this caller does not compute: an AF that parses as a
+# what a row made by call_insertions(genotype=None) holds where Sniffles would supply a value the caller does not compute: an AF that parses as a
 # float (merge_rows and dedup_rows add the column up), the VCF missing genotype, a ref_count that is text (summed as text, printed as is)
 NO_AF, NO_GENOTYPE, NO_REF_COUNT, NO_TE_PROP = "nan", "./.", "NA", "NA"
+GENOTYPES = ("0/0", "0/1", "1/1")          # telr_ins_gt.gt 0, 1, 2
 
 
-def call_insertions(index, result, tnames, qnames, reads, opt=None, sample="telr", te_prop_column=True):
+def call_insertions(index, result, tnames, qnames, reads, opt=None, sample="telr", te_prop_column=True, genotype=None):
     """Candidate-locus rows (COLUMNS order; te_prop_column=False leaves the 14th out, for a table that goes through `filter_vcf`,
     which appends it) from a stage-1 result, with the engine's
     own insertion caller (`telr_call_insertions`) in the place of `detect_sv` + `parse_vcf` (TELR_sv.py:13-81,
@@ -40,13 +41,18 @@ def call_insertions(index, result, tnames, qnames, reads, opt=None, sample="telr
     `seqset`); opt: an `_abi.InsOpt` (None = defaults).
     start = the call's position, end = start + 1, sv_length = the median length of the sized signatures, coverage = alt_count =
     the distinct supporting reads, ins_seq = the representative signature's segment of its read, on the reference strand.
-    Rows are sorted by (target id, position), as `merge_rows` and `telr_assembly.window_reads` take them."""
+    Rows are sorted by (target id, position), as `merge_rows` and `telr_assembly.window_reads` take them.
+    genotype: None leaves sniffles_af, genotype and ref_count at their placeholders ("nan", "./.", "NA"); True or an `_abi.GenoOpt`
+    runs the engine's genotyping step on the calls (`telr_genotype_insertions`, DESIGN.md 5.11 -- an own definition again, NOT
+    Sniffles' genotyper) and fills them: sniffles_af = "%.6f" % (alt / (alt + ref)), genotype = 0/0, 0/1 or 1/1, ref_count = the
+    distinct reads that cross the call with the reference allele."""
     import numpy as np
     from .aligner import _np_from
     from ._abi import ALN_DTYPE, F_REV
     ic = index.call_insertions(result, opt)
     L = index.eng.L
     flags = _np_from(L.telr_result_alns(result), L.telr_result_count(result), ALN_DTYPE)["flags"] if len(ic.calls) else None
+    gt = None if genotype is None or genotype is False else index.genotype_insertions(result, ic, None if genotype is True else genotype).gt
 
     def segment(qid, s, n):
         if isinstance(reads, tuple) and len(reads) == 3:
@@ -64,10 +70,21 @@ def call_insertions(index, result, tnames, qnames, reads, opt=None, sample="telr
             if int(flags[s["rec"]]) & F_REV:
                 seq = seq.translate(_RC)[::-1]
         names = ",".join(qnames[q] for q in ic.reads_of(k).tolist())
-        rows.append([tnames[c["tid"]], str(int(c["pos"])), str(int(c["pos"]) + 1), str(int(c["len"])), str(int(c["support"])), NO_AF,
-                     "%s.INS.%d" % (sample, k), seq.decode(), names, "PASS", NO_GENOTYPE, NO_REF_COUNT, str(int(c["support"]))] +
+        af, genotype_text, ref_count = NO_AF, NO_GENOTYPE, NO_REF_COUNT
+        if gt is not None:
+            alt, ref = int(gt[k]["alt"]), int(gt[k]["ref"])
+            af = "%.6f" % (alt / (alt + ref)) if alt + ref else NO_AF
+            genotype_text, ref_count = GENOTYPES[int(gt[k]["gt"])], str(ref)
+        rows.append([tnames[c["tid"]], str(int(c["pos"])), str(int(c["pos"]) + 1), str(int(c["len"])), str(int(c["support"])), af,
+                     "%s.INS.%d" % (sample, k), seq.decode(), names, "PASS", genotype_text, ref_count, str(int(c["support"]))] +
                     ([NO_TE_PROP] if te_prop_column else []))
     return rows
+
+
+def sv_info(rows):
+    """rows of the candidate-locus table -> {locus name: (genotype, ref_count, alt_count)}, what
+    `locus_pipeline.write_outputs(sv_info=...)` takes (columns 10-12)"""
+    return {locus_name(r): (r[10], r[11], r[12]) for r in rows}
 
 
 def write_locus_table(rows, path):

@@ -1,6 +1,7 @@
 """Times telr_call_insertions on a stage-1 result of BASELINE configs[2] shape (bench.py's data set: --coverage / --genome-scale
 make it smaller), once with the result's resident CIGAR copy (TELR_MF_KEEP_CIGARS) and once with the CIGAR array uploaded, and the
-plain-Python restatement (tests/inscall_ref.py) on a sample of the reads, scaled to the whole set.  Writes profiles/inscall_time.json.
+plain-Python restatement (tests/inscall_ref.py) on a sample of the reads, scaled to the whole set; then Index.genotype_insertions
+(telr_genotype_insertions) on the calls of that result, the same two ways.  Writes profiles/inscall_time.json.
 
     python tools/inscall_time.py [--coverage 30] [--genome-scale 1.0] [--repeat 5] [--sample-reads 2000] [--out profiles/inscall_time.json]
 """
@@ -33,12 +34,13 @@ def main():
     import inscall_ref as ref
     from telr_amd.aligner import Engine
     from telr_amd.presets import preset
-    from telr_amd._abi import InsOpt, MF_KEEP_CIGARS
+    from telr_amd._abi import InsOpt, GenoOpt, MF_KEEP_CIGARS
     eng = Engine(0)
     io, mo = preset(cfg["preset"])
     ix = eng.index([bytes(r).decode() for r in D["ref"]], io)
     qs = eng.seqset(D["reads"])
     opt = InsOpt.default(min_support=a.min_support)
+    gopt = GenoOpt.default()
 
     def timed(r):
         ts = []
@@ -48,15 +50,26 @@ def main():
             ts.append((time.perf_counter() - t0) * 1e3)
         return ic, ts[1:]                                          # the first call sizes the context's scratch
 
+    def timed_geno(r, ic):
+        ts = []
+        for _ in range(a.repeat + 1):
+            t0 = time.perf_counter()
+            ig = ix.genotype_insertions(r, ic, gopt)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return ig, ts[1:]
+
     mk = mo.copy(); mk.flags |= MF_KEEP_CIGARS
     r = ix.map_raw(qs, mk)
     res = ix.result_arrays(r)
     ic_res, ms_res = timed(r)
+    ig_res, gms_res = timed_geno(r, ic_res)
     ix.free_raw(r)
     r = ix.map_raw(qs, mo)
     ic_up, ms_up = timed(r)
+    ig_up, gms_up = timed_geno(r, ic_up)
     ix.free_raw(r)
     assert ic_res.sigs.tobytes() == ic_up.sigs.tobytes() and ic_res.calls.tobytes() == ic_up.calls.tobytes()
+    assert ig_res.gt.tobytes() == ig_up.gt.tobytes() and ig_res.ref_reads.tobytes() == ig_up.ref_reads.tobytes() and ig_res.ambig_reads.tobytes() == ig_up.ambig_reads.tobytes()
     # the plain restatement on the records of the first --sample-reads reads
     alns = res.alns[res.alns["qid"] < a.sample_reads]
     t0 = time.perf_counter()
@@ -70,17 +83,24 @@ def main():
         "cigar_words_of_records": ops_all, "signatures": int(len(ic_res.sigs)), "calls": int(len(ic_res.calls)),
         "call_insertions_ms_resident_cigars": {"min": min(ms_res), "median": float(np.median(ms_res)), "all": ms_res},
         "call_insertions_ms_uploaded_cigars": {"min": min(ms_up), "median": float(np.median(ms_up)), "all": ms_up},
+        "genotype_options": {k: getattr(gopt, k) for k, _ in GenoOpt._fields_},
+        "genotype_reference_reads": int(len(ig_res.ref_reads)), "genotype_ambiguous_reads": int(len(ig_res.ambig_reads)),
+        "genotype_gt_counts": [int((ig_res.gt["gt"] == v).sum()) for v in (0, 1, 2)],
+        "genotype_insertions_ms_resident_cigars": {"min": min(gms_res), "median": float(np.median(gms_res)), "all": gms_res},
+        "genotype_insertions_ms_uploaded_cigars": {"min": min(gms_up), "median": float(np.median(gms_up)), "all": gms_up},
         "python_restatement": {"sample_reads": a.sample_reads, "sample_cigar_words": ops_sample, "seconds": py_s,
                                "scaled_to_all_records_seconds": py_s * ops_all / max(1, ops_sample),
                                "note": "tests/inscall_ref.py, one CPU thread; scaled by CIGAR words"},
-        "timing": "wall clock of Index.call_insertions (validation, record upload, kernels, the signatures and calls copied back), %d repeats after one untimed call" % a.repeat,
+        "timing": "wall clock of Index.call_insertions (validation, record upload, kernels, the signatures and calls copied back) and of Index.genotype_insertions "
+                  "(validation, uploads, kernels, the genotypes and read lists copied back), %d repeats after one untimed call each" % a.repeat,
     }
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)
         fh.write("\n")
     print(json.dumps({k: out[k] for k in ("records", "cigar_words", "signatures", "calls", "call_insertions_ms_resident_cigars",
-                                          "call_insertions_ms_uploaded_cigars", "python_restatement")}))
+                                          "call_insertions_ms_uploaded_cigars", "genotype_insertions_ms_resident_cigars",
+                                          "genotype_insertions_ms_uploaded_cigars", "python_restatement")}))
 
 
 if __name__ == "__main__":
