@@ -7,91 +7,7 @@ from oracle import binding as ob
 from telr_amd.presets import preset
 from telr_amd.fasta import read_fasta, revcomp
 from telr_amd import synth
-
-
-def _hash64(key, mask):
-    key = (~key + (key << 21)) & mask
-    key = key ^ key >> 24
-    key = ((key + (key << 3)) + (key << 8)) & mask
-    key = key ^ key >> 14
-    key = ((key + (key << 2)) + (key << 4)) & mask
-    key = key ^ key >> 28
-    key = (key + (key << 31)) & mask
-    return key
-
-
-def brute_minimizers(seq, k, w):
-    """(w,k)-minimizers by the set definition (Li 2018, section 2.1.1), all windows enumerated."""
-    code = {"A": 0, "C": 1, "G": 2, "T": 3}
-    mask = (1 << 2 * k) - 1
-    ns = len(seq) - k + 1
-    xs = []
-    for u in range(ns):
-        kmer = seq[u:u + k]
-        if any(c not in code for c in kmer):
-            xs.append(None); continue
-        fw = 0
-        for c in kmer:
-            fw = fw << 2 | code[c]
-        rv = 0
-        for c in reversed(kmer):
-            rv = rv << 2 | (3 - code[c])
-        if fw == rv:
-            xs.append(None); continue
-        z = 0 if fw < rv else 1
-        xs.append((_hash64(rv if z else fw, mask) << 8 | k, (u + k - 1) << 1 | z))
-    sel = set()
-    win = min(w, ns)
-    for j in range(0, ns - win + 1):
-        vals = [xs[q][0] for q in range(j, j + win) if xs[q] is not None]
-        if not vals:
-            continue
-        m = min(vals)
-        for q in range(j, j + win):
-            if xs[q] is not None and xs[q][0] == m:
-                sel.add(q)
-    return [(xs[q][0], xs[q][1]) for q in sorted(sel)]
-
-
-def brute_minimizers_hpc(seq, k, w):
-    """homopolymer-compressed variant: k-mers over runs, span in original bases, position = last base of the last run"""
-    code = {"A": 0, "C": 1, "G": 2, "T": 3}
-    runs = []
-    i = 0
-    while i < len(seq):
-        j = i + 1
-        while j < len(seq) and (seq[j] == seq[i] or (seq[j] not in code and seq[i] not in code)):
-            j += 1
-        runs.append((seq[i], i, j - 1)); i = j
-    mask = (1 << 2 * k) - 1
-    ns = len(runs) - k + 1
-    xs = []
-    for u in range(ns):
-        rr = runs[u:u + k]
-        span = rr[-1][2] - rr[0][1] + 1
-        if any(c not in code for c, _, _ in rr) or span >= 256:
-            xs.append(None); continue
-        fw = 0
-        for c, _, _ in rr:
-            fw = fw << 2 | code[c]
-        rv = 0
-        for c, _, _ in reversed(rr):
-            rv = rv << 2 | (3 - code[c])
-        if fw == rv:
-            xs.append(None); continue
-        z = 0 if fw < rv else 1
-        xs.append((_hash64(rv if z else fw, mask) << 8 | span, rr[-1][2] << 1 | z))
-    sel = set()
-    win = min(w, ns)
-    for j in range(0, ns - win + 1):
-        vals = [xs[q][0] for q in range(j, j + win) if xs[q] is not None]
-        if not vals:
-            continue
-        m = min(vals)
-        for q in range(j, j + win):
-            if xs[q] is not None and xs[q][0] == m:
-                sel.add(q)
-    return [(xs[q][0], xs[q][1]) for q in sorted(sel)]
+from sketch_edges import _hash64, brute_minimizers, brute_minimizers_hpc      # noqa: F401  (the plain reference of the sketch)
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
