@@ -549,6 +549,9 @@ int  telr_last_counters(const telr_ctx *ctx, telr_counters *out);
  * [c*4+3] algorithmic bytes (2-bit bases read once + 4 B per CIGAR run + 32 B result) */
 #define TELR_N_DPCLS 25
 int  telr_last_dp_classes(const telr_ctx *ctx, int64_t *out /* [TELR_N_DPCLS*4] */);
+/* what defines each DP class (no device needed): widest band in diagonals, lanes per problem, registers per lane, dwords per
+ * trace-back row, trace-back interleaved across the problems of a wave (0/1), trace-back in tiles of four rows (0/1) */
+int  telr_debug_dp_class_table(int32_t *out /* [TELR_N_DPCLS][6] */);
 
 #ifdef __cplusplus
 }

@@ -97,7 +97,7 @@ class Engine:
         self.L.telr_last_dp_classes(self.h, a.ctypes.data)
         return a.reshape(N_DPCLS, 4)
 
-    # the eight host bounds of the packed int16 DP classes for `mo` (telr_engine.hip: pk_steps_limit ... tag8_steps)
+    # the eight host bounds of the packed int16 DP classes for `mo` (telr_engine.hip: dp_limits)
     DP_LIMITS = ("pk_steps_limit", "pk_wide_limit", "pk_wide_maxd", "pk_ext_limit", "pk_ext_maxd", "tb4_mask", "tb4_steps", "tag8_steps")
 
     @staticmethod
@@ -108,6 +108,17 @@ class Engine:
         if rc != 0:
             raise _lib.TelrError("telr_debug_dp_limits: %d" % rc, rc)
         return dict(zip(Engine.DP_LIMITS, (int(v) for v in a)))
+
+    DP_CLASS_COLUMNS = ("maxd", "lanes", "regs", "row_dwords", "interleaved", "tiled")
+
+    @staticmethod
+    def dp_class_table():
+        """-> (N_DPCLS, 6) int32, columns DP_CLASS_COLUMNS: what defines each DP class (no device needed)"""
+        a = np.zeros((N_DPCLS, 6), np.int32)
+        rc = _lib.lib().telr_debug_dp_class_table(a.ctypes.data)
+        if rc != 0:
+            raise _lib.TelrError("telr_debug_dp_class_table: %d" % rc, rc)
+        return a
 
     def debug_dp(self, queries, targets, mo, probs):
         """one DP pass (the map path's dp_pass) over a list of problems -- test tap.  probs: (np, 12) int32 rows

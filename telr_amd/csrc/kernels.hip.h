@@ -2344,68 +2344,120 @@ __global__ void __launch_bounds__(64) k_segments_w(const KeptChain *__restrict__
 
 // DP classes.  0-4: LDS-state kernel (z-drop extensions, very wide fills), by band width;
 // 5-9: register kernel for gap-fill problems: (lanes per problem, diagonal pairs per lane) =
-// (32,1) (64,1) (64,2) (64,4) (64,8)  ->  bands up to 64 / 128 / 256 / 512 / 1024 diagonals.
+// (32,1) (64,1) (64,2) (128,2) (256,2)  ->  bands up to 64 / 128 / 256 / 512 / 1024 diagonals.
 #define DP_NCLS 25
 // 10-17: packed-int16 register kernel d_dp_pkr<LPP, R> for short gap fills, by band width.  One lane per problem:
 // class 17 D <= 16 (R = 4), classes 10..13 D = 17-20 / 21-24 / 25-28 / 29-32 (R = 5 / 6 / 7 / 8: exact ranges, so that only
 // the last register of a lane can straddle the upper band edge); two lanes: classes 14..16 D <= 40 / 48 / 64 (R = 5 / 6 / 8).
 // 18: z-drop extensions with D <= 64 (four lanes, R = 4)
-// 19-21: wide fills in int16 while the scores fit (steps <= pk_wide_steps): D <= 256 / 512 / 1024, 1 / 2 / 4 waves per problem
+// 19-21: wide fills in int16 while the scores fit (steps <= pk_wide): D <= 256 / 512 / 1024, 1 / 2 / 4 waves per problem
 // 22: 65..128 diagonals, four lanes x R = 8 (16 problems per wave): the class of the retried fills (wide band of a ~200-base
 //     segment = 100-130 diagonals), which the margin rule of the band spec makes ~1 % of all fills
 // 23, 24: z-drop extensions with D <= 128 / 256 (eight / sixteen lanes, R = 4): presets with ext_band > 31 (ngmlr-ont, round 5)
-__device__ __forceinline__ int d_dp_class(int kind, int D, int steps, int pk_max_steps, int pk_ext_steps, int pk_wide_steps, int pk_wide_maxd = 1024, int pk_ext_maxd = 64)
+//
+// DP_CLASS below is where a class is defined: routing (d_dp_class), trace-back sizes and layouts, the packed launch's wave
+// table and the host's launch table (telr_engine.hip: SIDE_LAUNCH) all read it.
+enum DpClass : int {
+    CLS_LDS64 = 0, CLS_LDS128, CLS_LDS256, CLS_LDS1024, CLS_LDSMAX, CLS_REG64 = 5, CLS_REG128, CLS_REG256, CLS_REG512, CLS_REG1024,
+    CLS_PK20 = 10, CLS_PK24, CLS_PK28, CLS_PK32, CLS_PK40, CLS_PK48, CLS_PK64, CLS_PK16, CLS_PKX64 = 18,
+    CLS_PKW256 = 19, CLS_PKW512, CLS_PKW1024, CLS_PK128 = 22, CLS_PKX128 = 23, CLS_PKX256 = 24
+};
+enum DpFamily : int { DPF_LDS, DPF_REG, DPF_PK /* the one cost-ordered packed launch */, DPF_PKW /* wide packed fills */, DPF_PKX /* packed extensions */ };
+// trace-back layouts: a byte per cell, anti-diagonal major | rows of four anti-diagonals, a dword per diagonal pair | rows of
+// two anti-diagonals in whole 64-byte lines (d_traceback_rows) | tiles of four such rows (d_dp_pkx: a 64-byte line = four
+// consecutive rows of 16 bytes) | rows of two anti-diagonals, the 64 problems of a wave interleaved in 8-byte units (k_tb_gather)
+enum DpTbLayout : int { TBL_BYTES, TBL_REGROWS, TBL_LINES, TBL_TILES, TBL_INTERLEAVED };
+struct DpClassRow {
+    int family, maxd;        // widest band (diagonals)
+    int lpp, regs;           // lanes per problem, registers (LDS / register kernels: diagonal pairs) per lane
+    int slots;               // dwords per trace-back row
+    int layout;
+    int nibble;              // bit of DpLimits::tb4_mask if the four-bit cell can apply (one-piece gap cost: d_tb4), else 0
+};
+constexpr DpClassRow DP_CLASS[DP_NCLS] = {
+    /*  0 */ { DPF_LDS, 64, 64, 0, 0, TBL_BYTES, 0 },
+    /*  1 */ { DPF_LDS, 128, 64, 0, 0, TBL_BYTES, 0 },
+    /*  2 */ { DPF_LDS, 256, 64, 0, 0, TBL_BYTES, 0 },
+    /*  3 */ { DPF_LDS, 1024, 256, 0, 0, TBL_BYTES, 0 },
+    /*  4 */ { DPF_LDS, DP_DMAX, 256, 0, 0, TBL_BYTES, 0 },
+    /*  5 */ { DPF_REG, 64, 32, 1, 32, TBL_REGROWS, 0 },
+    /*  6 */ { DPF_REG, 128, 64, 1, 64, TBL_REGROWS, 0 },
+    /*  7 */ { DPF_REG, 256, 64, 2, 128, TBL_REGROWS, 0 },
+    /*  8 */ { DPF_REG, 512, 128, 2, 256, TBL_REGROWS, 0 },
+    /*  9 */ { DPF_REG, 1024, 256, 2, 512, TBL_REGROWS, 0 },
+    /* 10 */ { DPF_PK, 20, 1, 5, 5, TBL_INTERLEAVED, 2 },
+    /* 11 */ { DPF_PK, 24, 1, 6, 6, TBL_INTERLEAVED, 0 },
+    /* 12 */ { DPF_PK, 28, 1, 7, 7, TBL_INTERLEAVED, 0 },
+    /* 13 */ { DPF_PK, 32, 1, 8, 8, TBL_INTERLEAVED, 0 },
+    /* 14 */ { DPF_PK, 40, 2, 5, 10, TBL_LINES, 0 },
+    /* 15 */ { DPF_PK, 48, 2, 6, 12, TBL_LINES, 0 },
+    /* 16 */ { DPF_PK, 64, 2, 8, 16, TBL_LINES, 0 },
+    /* 17 */ { DPF_PK, 16, 1, 4, 4, TBL_INTERLEAVED, 1 },
+    /* 18 */ { DPF_PKX, 64, 4, 4, 16, TBL_TILES, 0 },
+    /* 19 */ { DPF_PKW, 256, 64, 1, 64, TBL_LINES, 0 },
+    /* 20 */ { DPF_PKW, 512, 128, 1, 128, TBL_LINES, 0 },
+    /* 21 */ { DPF_PKW, 1024, 256, 1, 256, TBL_LINES, 0 },
+    /* 22 */ { DPF_PK, 128, 4, 8, 32, TBL_LINES, 0 },
+    /* 23 */ { DPF_PKX, 128, 8, 4, 32, TBL_TILES, 0 },
+    /* 24 */ { DPF_PKX, 256, 16, 4, 64, TBL_TILES, 0 },
+};
+// The int16 bounds of a pass, computed once on the host (telr_engine.hip: dp_limits) in the order of telr_debug_dp_limits:
+// longest fill (m + n) of the one-launch packed classes; of the wide ones and their widest band; of the packed extensions
+// and their widest band; which nibble classes spill four bits per cell (bit 0: class 17, bit 1: class 10) and up to how
+// many steps; and the steps up to which a wave of the two-piece classes takes the tagged cell d_cell_pk8 (0 = never)
+struct DpLimits { int32_t pk_steps, pk_wide, pk_wide_maxd, pk_ext, pk_ext_maxd, tb4_mask, tb4_steps, tag8_steps; };
+
+// the narrowest class of a family that holds D diagonals and is no wider than cap (-1: none); the table is a constant, so
+// this unrolls into one comparison per row of the family
+template <int FAMILY> __host__ __device__ __forceinline__ constexpr int d_cls_fit(int D, int cap)
 {
-    if ((kind == 1 || kind == 2) && steps <= pk_ext_steps) {
-        if (D <= 64) return 18;
-        if (D <= 128 && pk_ext_maxd >= 128) return 23;
-        if (D <= 256 && pk_ext_maxd >= 256) return 24;
-    }
-    if (kind == 0 && steps <= pk_max_steps) {
-        if (D <= 16) return 17;
-        if (D <= 20) return 10;
-        if (D <= 24) return 11;
-        if (D <= 28) return 12;
-        if (D <= 32) return 13;
-        if (D <= 40) return 14;
-        if (D <= 48) return 15;
-        if (D <= 64) return 16;
-        if (D <= 128) return 22;
-    }
-    if (kind == 0 && steps <= pk_wide_steps && D > 64 && D <= pk_wide_maxd) {
-        if (D <= 256) return 19;
-        if (D <= 512) return 20;
-        if (D <= 1024) return 21;
-    }
-    if (kind == 0) {
-        if (D <= 64) return 5;
-        if (D <= 128) return 6;
-        if (D <= 256) return 7;
-        if (D <= 512) return 8;
-        if (D <= 1024) return 9;
-    }
-    return D <= 64 ? 0 : D <= 128 ? 1 : D <= 256 ? 2 : D <= 1024 ? 3 : 4;
+    int best = -1;
+    for (int c = 0; c < DP_NCLS; ++c)
+        if (DP_CLASS[c].family == FAMILY && D <= DP_CLASS[c].maxd && DP_CLASS[c].maxd <= cap && (best < 0 || DP_CLASS[c].maxd < DP_CLASS[best].maxd)) best = c;
+    return best;
 }
+// extensions, then packed fills, then wide packed fills, then register fills, then the LDS kernel
+__host__ __device__ __forceinline__ int d_dp_class(int kind, int D, int steps, const DpLimits &L)
+{
+    int c = -1;
+    if ((kind == 1 || kind == 2) && steps <= L.pk_ext) c = d_cls_fit<DPF_PKX>(D, L.pk_ext_maxd);
+    if (c < 0 && kind == 0 && steps <= L.pk_steps) c = d_cls_fit<DPF_PK>(D, DP_DMAX);
+    if (c < 0 && kind == 0 && steps <= L.pk_wide && D > DP_CLASS[CLS_PK64].maxd) c = d_cls_fit<DPF_PKW>(D, L.pk_wide_maxd);
+    if (c < 0 && kind == 0) c = d_cls_fit<DPF_REG>(D, DP_DMAX);
+    if (c < 0) c = d_cls_fit<DPF_LDS>(D, DP_DMAX);
+    return c < 0 ? (int)CLS_LDSMAX : c;
+}
+// classes with a property, as a bit mask folded from the table: a test on a run-time class is a shift, never a memory read
+template <typename F> constexpr uint32_t dp_cls_mask(F f) { uint32_t m = 0; for (int c = 0; c < DP_NCLS; ++c) if (f(DP_CLASS[c])) m |= 1u << c; return m; }
+constexpr bool dp_row_is_reg(const DpClassRow &r) { return r.layout != TBL_BYTES; }
+constexpr bool dp_row_is_rows2(const DpClassRow &r) { return r.layout == TBL_LINES || r.layout == TBL_TILES || r.layout == TBL_INTERLEAVED; }
+constexpr bool dp_row_is_tiled(const DpClassRow &r) { return r.layout == TBL_TILES; }
+constexpr bool dp_row_is_interleaved(const DpClassRow &r) { return r.layout == TBL_INTERLEAVED; }
+constexpr bool dp_row_counts_cells(const DpClassRow &r) { return r.family == DPF_PK || r.family == DPF_PKW; }
+constexpr bool dp_row_is_pk(const DpClassRow &r) { return r.family == DPF_PK; }
+constexpr uint32_t CLSM_REGS = dp_cls_mask(dp_row_is_reg), CLSM_ROWS2 = dp_cls_mask(dp_row_is_rows2), CLSM_TILED = dp_cls_mask(dp_row_is_tiled),
+                   CLSM_INTERLEAVED = dp_cls_mask(dp_row_is_interleaved), CLSM_CELLS = dp_cls_mask(dp_row_counts_cells), CLSM_PK = dp_cls_mask(dp_row_is_pk);
+__host__ __device__ __forceinline__ constexpr bool d_cls_in(int cls, uint32_t mask) { return (mask >> cls) & 1u; }
+// the register kernels (rows of dwords) are the classes from 5 up, the packed int16 ones (rows of two anti-diagonals) those from 10 up
+constexpr int CLS_REGS_FIRST = __builtin_ctz(CLSM_REGS), CLS_ROWS2_FIRST = __builtin_ctz(CLSM_ROWS2);
+static_assert(CLSM_REGS == ((1u << DP_NCLS) - (1u << CLS_REGS_FIRST)) && CLSM_ROWS2 == ((1u << DP_NCLS) - (1u << CLS_ROWS2_FIRST)), "these layouts take the upper class numbers");
+__host__ __device__ __forceinline__ bool d_tb_regs(int cls) { return cls >= CLS_REGS_FIRST; }
+__host__ __device__ __forceinline__ bool d_tb_rows2(int cls) { return cls >= CLS_ROWS2_FIRST; }
+__host__ __device__ __forceinline__ bool d_tb_tiled(int cls) { return d_cls_in(cls, CLSM_TILED); }
+__host__ __device__ __forceinline__ bool d_tb_interleaved(int cls) { return d_cls_in(cls, CLSM_INTERLEAVED); }
+// dwords per trace-back row
+__host__ __device__ __forceinline__ int d_cls_slots(int cls) { return DP_CLASS[cls].slots; }
 // Four bits per cell.  The one-piece cell (classes 17 and 10 when the preset's gap costs allow it: d_cell_pk) has three
 // sources and two extension flags -- a nibble -- once the "bases equal" bit is gone, and that bit is not needed: with one
 // affine piece and no ambiguous base the number of matching columns follows from the score of the path,
 // a * match - b * (M columns - match) - sum over gap runs (q + e * length) = score.  Row k (anti-diagonals 2k, 2k+1) of
 // register r is one 16-bit word {even step: low nibbles, odd step: high nibbles} x {low-half diagonal, high-half
 // diagonal}; a row is ceil(R/2) dwords, a row PAIR a whole number of 8-byte units of the wave-interleaved layout.
+// d_onep_d: the widest band in which the second affine piece can never pay, (D - 1)(e - e2) < q2 - q; a nibble class is
+// one-piece when that covers its widest band
 __host__ __device__ __forceinline__ int d_onep_d(int q, int e, int q2, int e2) { return e > e2 ? (q2 - q + (e - e2) - 1) / (e - e2) : 1 << 20; }
-__host__ __device__ __forceinline__ bool d_tb4(int cls, int tb4) { return (cls == 17 && (tb4 & 1)) || (cls == 10 && (tb4 & 2)); }
-__host__ __device__ __forceinline__ int d_tb4_rowb(int cls) { return cls == 17 ? 8 : 12; }       // bytes per row: 4 * ceil(R / 2)
-// the z-drop extension classes spill in tiles of four rows (d_dp_pkx): a 64-byte line = four consecutive rows of 16 bytes
-__host__ __device__ __forceinline__ bool d_tb_tiled(int cls) { return cls == 18 || cls == 23 || cls == 24; }
-// dwords per packed trace-back row
-__device__ __forceinline__ int d_cls_slots(int cls)
-{
-    if (cls == 22 || cls == 23) return 32;
-    if (cls == 24) return 64;
-    if (cls >= 19) return 64 << (cls - 19);
-    if (cls >= 10) return cls <= 13 ? cls - 5 : cls == 14 ? 10 : cls == 15 ? 12 : cls == 17 ? 4 : 16;
-    return cls == 5 ? 32 : 64 << (cls - 6);
-}
+__host__ __device__ __forceinline__ bool d_tb4(int cls, int tb4) { return (DP_CLASS[cls].nibble & tb4) != 0; }
+__host__ __device__ __forceinline__ int d_tb4_rowb(int cls) { return 4 * ((DP_CLASS[cls].regs + 1) / 2); }       // bytes per row: 4 * ceil(R / 2)
 // any ambiguous base among the n bases from absolute index lo on?
 __device__ __forceinline__ bool d_any_n(const uint32_t *__restrict__ nmask, int64_t lo, int n)
 {
@@ -2419,21 +2471,22 @@ __device__ __forceinline__ bool d_any_n(const uint32_t *__restrict__ nmask, int6
     }
     return false;
 }
-__global__ void k_prob_sizes(DpProb *__restrict__ probs, int32_t np, int fill_margin, int32_t pk_max_steps, int32_t pk_ext_steps, int32_t pk_wide_steps,
+__global__ void k_prob_sizes(DpProb *__restrict__ probs, int32_t np, int fill_margin, DpLimits L,
                              const uint32_t *__restrict__ qnmask, const uint32_t *__restrict__ tnmask,
-                             int64_t *__restrict__ tb_bytes, int64_t *__restrict__ cig_ops, int32_t tb4, int32_t tb4_steps, int32_t pk_wide_maxd, int32_t pk_ext_maxd)
+                             int64_t *__restrict__ tb_bytes, int64_t *__restrict__ cig_ops)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= np) return;
     const DpProb P = probs[i];
     int D = P.dhi - P.dlo + 1, stride = (D + 2) / 2;
-    int cls = d_dp_class(P.kind, D, P.m + P.n, pk_max_steps, pk_ext_steps, pk_wide_steps, pk_wide_maxd, pk_ext_maxd);
-    if (cls >= 10 && P.kind < 3) {
+    int cls = d_dp_class(P.kind, D, P.m + P.n, L);
+    if (d_tb_rows2(cls) && P.kind < 3) {
         // the packed kernels have no ambiguity case: a problem with an N inside either window takes an int32 class
         const bool hasn = d_any_n(qnmask, P.qstep > 0 ? P.qi0 : P.qi0 - P.m + 1, P.m) || d_any_n(tnmask, P.tstep > 0 ? P.ti0 : P.ti0 - P.n + 1, P.n);
-        if (hasn) cls = d_dp_class(P.kind, D, P.m + P.n, 0, 0, 0);
+        if (hasn) { DpLimits L0 = L; L0.pk_steps = L0.pk_ext = L0.pk_wide = 0; cls = d_dp_class(P.kind, D, P.m + P.n, L0); }
     }
-    if (d_tb4(cls, tb4) && P.m + P.n > tb4_steps) cls = 14;        // the nibble cell keeps scores times four: longer fills take the two-lane class
+    const int tb4 = L.tb4_mask;
+    if (d_tb4(cls, tb4) && P.m + P.n > L.tb4_steps) cls = CLS_PK40;        // the nibble cell keeps scores times four: longer fills take the two-lane class
     // every size below is a multiple of 64 bytes, so every problem's piece (and every interleaved wave's) starts on a 64-byte
     // line: the tiled walk reads the rows above a cell inside the cell's own line (d_traceback_lane: w - 16 / 32 / 48)
     int64_t tb;
@@ -2444,11 +2497,11 @@ __global__ void k_prob_sizes(DpProb *__restrict__ probs, int32_t np, int fill_ma
     else if (P.kind >= 3) tb = 0;
     else if (d_tb4(cls, tb4)) tb = ((int64_t)(((P.m + P.n) / 2 + 2) / 2) * (2 * d_tb4_rowb(cls)) + 63) & ~63LL;     // row pairs of nibbles
     else if (d_tb_tiled(cls)) tb = (int64_t)(((P.m + P.n) / 2 + 4) / 4) * d_cls_slots(cls) * 16;     // tiles of four rows (d_dp_pkx)
-    else if (cls >= 10) tb = ((int64_t)((P.m + P.n) / 2 + 1) * d_cls_slots(cls) * 4 + 63) & ~63LL;     // whole 64-byte lines (d_traceback_rows)
-    else if (cls >= 5) tb = (int64_t)((P.m + P.n) / 4 + 1) * d_cls_slots(cls) * 4;
+    else if (d_tb_rows2(cls)) tb = ((int64_t)((P.m + P.n) / 2 + 1) * d_cls_slots(cls) * 4 + 63) & ~63LL;     // whole 64-byte lines (d_traceback_rows)
+    else if (d_tb_regs(cls)) tb = (int64_t)((P.m + P.n) / 4 + 1) * d_cls_slots(cls) * 4;
     else tb = ((int64_t)(P.m + P.n + 1) * stride + 127) & ~127LL;
     int cells = 0;
-    if (cls >= 10 && cls != 18 && cls < 23) for (int d = P.dlo; d <= P.dhi; ++d) {
+    if (d_cls_in(cls, CLSM_CELLS)) for (int d = P.dlo; d <= P.dhi; ++d) {
         int ilo = d < 0 ? 1 - d : 1, ihi = P.n - d < P.m ? P.n - d : P.m;
         if (ihi >= ilo) cells += ihi - ilo + 1;
     }
@@ -2469,7 +2522,6 @@ struct ClsOff { int32_t off[DP_NCLS + 1]; };
 // instruction of the walk covers 512 contiguous bytes and a whole row pair / line of the wave is one contiguous 2.5-4 KB
 // block: both kernels stream instead of touching 64 different lines per instruction.  The wave's piece is sized by its
 // first (longest) problem; tb_off of a problem points at its unit 0.
-__device__ __forceinline__ bool d_tb_interleaved(int cls) { return (cls >= 10 && cls <= 13) || cls == 17; }
 __device__ __forceinline__ int d_cls_of_pos(const ClsOff &off, int i) { int c = 0; while (c < DP_NCLS - 1 && i >= off.off[c + 1]) ++c; return c; }
 __global__ void __launch_bounds__(256) k_tb_gather(const int64_t *__restrict__ tb_bytes, const int32_t *__restrict__ list, int32_t np, ClsOff off, int64_t *__restrict__ out)
 {
@@ -3628,11 +3680,10 @@ __device__ __forceinline__ void d_dp_pkr(const DpArgs &A, const int32_t *__restr
 // All packed classes run as ONE launch: a wave is described by (class, first problem of its class list) and the
 // wave table is ordered by decreasing estimated cost (steps x registers per lane), so the long waves start first and
 // no class leaves the machine idle behind its own tail.
-#define PK_NC 9                            /* packed fill classes of the one cost-ordered launch: 10 .. 17 and 22 */
-__host__ __device__ __forceinline__ int PK_CLS(int c) { return c < 8 ? 10 + c : 22; }
-__host__ __device__ __forceinline__ int PK_IDX(int cls) { return cls == 22 ? 8 : cls - 10; }
-__device__ __constant__ const int PK_LPP[PK_NC] = { 1, 1, 1, 1, 2, 2, 2, 1, 4 };
-__device__ __constant__ const int PK_R[PK_NC]   = { 5, 6, 7, 8, 5, 6, 8, 4, 8 };
+#define PK_NC 9                            /* packed fill classes of the one cost-ordered launch (family DPF_PK): 10 .. 17 and 22 */
+static_assert(__builtin_popcount(CLSM_PK) == PK_NC, "PK_NC counts the DPF_PK rows of DP_CLASS");
+__host__ __device__ __forceinline__ constexpr int PK_IDX(int cls) { return __builtin_popcount(CLSM_PK & ((1u << cls) - 1u)); }      // position among the DPF_PK classes
+__host__ __device__ __forceinline__ constexpr int PK_CLS(int c) { int cls = 0; for (int k = 0; k < DP_NCLS; ++k) if (d_cls_in(k, CLSM_PK) && PK_IDX(k) == c) cls = k; return cls; }
 struct PkPlan { int32_t woff[PK_NC + 1]; };   // first wave of class 10+c in the unsorted wave table
 __global__ void k_pk_waves(const DpProb *__restrict__ probs, const int32_t *__restrict__ cls_list, ClsOff off, PkPlan plan,
                            uint32_t *__restrict__ keys, uint32_t *__restrict__ vals)
@@ -3641,11 +3692,49 @@ __global__ void k_pk_waves(const DpProb *__restrict__ probs, const int32_t *__re
     if (i >= plan.woff[PK_NC]) return;
     int c = 0;
     while (i >= plan.woff[c + 1]) ++c;
-    const int first = (i - plan.woff[c]) * (64 / PK_LPP[c]);
-    const DpProb P = probs[cls_list[off.off[PK_CLS(c)] + first]];     // lists are sorted by decreasing steps
-    const uint32_t cost = (uint32_t)((P.m + P.n) * PK_R[c]);          // < 2^16 (packed fills: m + n <= 7,900, at most 8 registers): two radix passes
+    const int cls = PK_CLS(c), first = (i - plan.woff[c]) * (64 / DP_CLASS[cls].lpp);
+    const DpProb P = probs[cls_list[off.off[cls] + first]];     // lists are sorted by decreasing steps
+    const uint32_t cost = (uint32_t)((P.m + P.n) * DP_CLASS[cls].regs);          // < 2^16 (packed fills: m + n <= 7,900, at most 8 registers): two radix passes
     keys[i] = cost > 0xFFFFu ? 0xFFFFu : cost;
-    vals[i] = (uint32_t)PK_CLS(c) << 26 | (uint32_t)first;
+    vals[i] = (uint32_t)cls << 26 | (uint32_t)first;
+}
+// The cell a packed wave of the one launch uses; k_dp_pk fills with it and k_traceback_pk reads it back.  Convex cost: its
+// own cell (plain flags, byte spill) in every class.  The two nibble classes are one-piece when d_onep_d covers their band,
+// with the four-bit spill if the pass allows it (tb4: DpLimits::tb4_mask).  Two-piece classes: provenance tags (scores times
+// eight) when the wave's longest problem -- probs[*first]: the lists are sorted by decreasing steps -- fits an eighth of
+// the int16 range.
+enum PkCell : int { CELL_PLAIN, CELL_TAG8, CELL_CX, CELL_ONEP, CELL_NIBBLE };
+__device__ __forceinline__ int d_pk_cell(int cls, const DpOpt &o, int tb4, int tag8_steps, const DpProb *__restrict__ probs, const int32_t *__restrict__ first)
+{
+    if (o.cx_scale) return CELL_CX;
+    const int onep_d = d_onep_d(o.q, o.e, o.q2, o.e2);
+    static_assert(DP_CLASS[CLS_PK16].nibble == 1 && DP_CLASS[CLS_PK20].nibble == 2, "the nibble classes and their tb4_mask bits");
+    if ((cls == CLS_PK16 && onep_d >= DP_CLASS[CLS_PK16].maxd) || (cls == CLS_PK20 && onep_d >= DP_CLASS[CLS_PK20].maxd)) return d_tb4(cls, tb4) ? CELL_NIBBLE : CELL_ONEP;
+    const DpProb P0 = probs[*first];
+    return P0.m + P0.n <= tag8_steps ? CELL_TAG8 : CELL_PLAIN;
+}
+// d_dp_pkr of a class of the one launch, lanes and registers from the table.  EXACT: the class takes an exact range of bands
+// (classes 10-13), so all registers but the last are inside the band
+template <int CLS, bool EXACT, bool ONEP, bool TB4, bool TAG8, bool CX>
+__device__ __forceinline__ void d_dp_pk_cls(const DpArgs &A, const int32_t *__restrict__ list, int n, int first)
+{
+    static_assert(DP_CLASS[CLS].family == DPF_PK && EXACT == (DP_CLASS[CLS].layout == TBL_INTERLEAVED && CLS != CLS_PK16), "class table");
+    d_dp_pkr<DP_CLASS[CLS].lpp, DP_CLASS[CLS].regs, false, 1, EXACT ? DP_CLASS[CLS].regs - 1 : 0, ONEP, TB4, TAG8, CX>(A, list, n, first);
+}
+template <bool TAG8, bool CX>
+__device__ __forceinline__ void d_dp_pk_any(int cls, const DpArgs &A, const int32_t *__restrict__ list, int n, int first)
+{
+    switch (cls) {
+    case CLS_PK20: d_dp_pk_cls<CLS_PK20, true, false, false, TAG8, CX>(A, list, n, first); break;      // 17..20 diagonals: registers 0-3 are inside the band
+    case CLS_PK24: d_dp_pk_cls<CLS_PK24, true, false, false, TAG8, CX>(A, list, n, first); break;
+    case CLS_PK28: d_dp_pk_cls<CLS_PK28, true, false, false, TAG8, CX>(A, list, n, first); break;
+    case CLS_PK32: d_dp_pk_cls<CLS_PK32, true, false, false, TAG8, CX>(A, list, n, first); break;
+    case CLS_PK16: d_dp_pk_cls<CLS_PK16, false, false, false, TAG8, CX>(A, list, n, first); break;     // up to 16 diagonals
+    case CLS_PK40: d_dp_pk_cls<CLS_PK40, false, false, false, TAG8, CX>(A, list, n, first); break;
+    case CLS_PK48: d_dp_pk_cls<CLS_PK48, false, false, false, TAG8, CX>(A, list, n, first); break;
+    case CLS_PK128: d_dp_pk_cls<CLS_PK128, false, false, false, TAG8, CX>(A, list, n, first); break;   // 65..128 diagonals
+    default: d_dp_pk_cls<CLS_PK64, false, false, false, TAG8, CX>(A, list, n, first); break;
+    }
 }
 #ifndef PK_WPE
 #define PK_WPE 2
@@ -3657,52 +3746,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PK_WPE)
     const int cls = (int)(w >> 26), first = (int)(w & 0x3ffffffu);
     const int32_t *list = cls_list + off.off[cls];
     const int n = off.off[cls + 1] - off.off[cls];
-    // widest band in which the second affine piece can never pay (see d_cell_pk): (D - 1)(e - e2) < q2 - q
-    if (A.o.cx_scale) {          // convex gap cost: its own cell (plain flags, byte spill) in every class
-        switch (cls) {
-        case 10: d_dp_pkr<1, 5, false, 1, 4, false, false, false, true>(A, list, n, first); break;
-        case 11: d_dp_pkr<1, 6, false, 1, 5, false, false, false, true>(A, list, n, first); break;
-        case 12: d_dp_pkr<1, 7, false, 1, 6, false, false, false, true>(A, list, n, first); break;
-        case 13: d_dp_pkr<1, 8, false, 1, 7, false, false, false, true>(A, list, n, first); break;
-        case 17: d_dp_pkr<1, 4, false, 1, 0, false, false, false, true>(A, list, n, first); break;
-        case 14: d_dp_pkr<2, 5, false, 1, 0, false, false, false, true>(A, list, n, first); break;
-        case 15: d_dp_pkr<2, 6, false, 1, 0, false, false, false, true>(A, list, n, first); break;
-        case 22: d_dp_pkr<4, 8, false, 1, 0, false, false, false, true>(A, list, n, first); break;
-        default: d_dp_pkr<2, 8, false, 1, 0, false, false, false, true>(A, list, n, first); break;
-        }
-        return;
-    }
-    const int onep_d = d_onep_d(A.o.q, A.o.e, A.o.q2, A.o.e2);
-    if (cls == 17 && onep_d >= 16) { if (A.tb4 & 1) d_dp_pkr<1, 4, false, 1, 0, true, true>(A, list, n, first); else d_dp_pkr<1, 4, false, 1, 0, true>(A, list, n, first); return; }
-    if (cls == 10 && onep_d >= 20) { if (A.tb4 & 2) d_dp_pkr<1, 5, false, 1, 4, true, true>(A, list, n, first); else d_dp_pkr<1, 5, false, 1, 4, true>(A, list, n, first); return; }
-    // two-piece classes: provenance tags (scores times eight) when the wave's longest problem -- its first: the lists are sorted
-    // by decreasing steps -- fits an eighth of the int16 range; k_traceback_pk decides the same way
-    const DpProb P0 = A.probs[list[first]];
-    if (P0.m + P0.n <= A.tag8_steps) {
-        switch (cls) {
-        case 10: d_dp_pkr<1, 5, false, 1, 4, false, false, true>(A, list, n, first); break;
-        case 11: d_dp_pkr<1, 6, false, 1, 5, false, false, true>(A, list, n, first); break;
-        case 12: d_dp_pkr<1, 7, false, 1, 6, false, false, true>(A, list, n, first); break;
-        case 13: d_dp_pkr<1, 8, false, 1, 7, false, false, true>(A, list, n, first); break;
-        case 17: d_dp_pkr<1, 4, false, 1, 0, false, false, true>(A, list, n, first); break;
-        case 14: d_dp_pkr<2, 5, false, 1, 0, false, false, true>(A, list, n, first); break;
-        case 15: d_dp_pkr<2, 6, false, 1, 0, false, false, true>(A, list, n, first); break;
-        case 22: d_dp_pkr<4, 8, false, 1, 0, false, false, true>(A, list, n, first); break;
-        default: d_dp_pkr<2, 8, false, 1, 0, false, false, true>(A, list, n, first); break;
-        }
-        return;
-    }
-    switch (cls) {
-    case 10: d_dp_pkr<1, 5, false, 1, 4>(A, list, n, first); break;      // 17..20 diagonals: registers 0-3 are inside the band
-    case 11: d_dp_pkr<1, 6, false, 1, 5>(A, list, n, first); break;
-    case 12: d_dp_pkr<1, 7, false, 1, 6>(A, list, n, first); break;
-    case 13: d_dp_pkr<1, 8, false, 1, 7>(A, list, n, first); break;
-    case 17: d_dp_pkr<1, 4, false>(A, list, n, first); break;            // up to 16 diagonals
-    case 14: d_dp_pkr<2, 5, false>(A, list, n, first); break;
-    case 15: d_dp_pkr<2, 6, false>(A, list, n, first); break;
-    case 22: d_dp_pkr<4, 8, false>(A, list, n, first); break;            // 65..128 diagonals
-    default: d_dp_pkr<2, 8, false>(A, list, n, first); break;
-    }
+    const int cell = d_pk_cell(cls, A.o, A.tb4, A.tag8_steps, A.probs, list + first);
+    if (cell == CELL_CX) { d_dp_pk_any<false, true>(cls, A, list, n, first); return; }
+    // the two one-piece classes, with and without the nibble spill
+    if (cell >= CELL_ONEP && cls == CLS_PK16) { if (cell == CELL_NIBBLE) d_dp_pk_cls<CLS_PK16, false, true, true, false, false>(A, list, n, first); else d_dp_pk_cls<CLS_PK16, false, true, false, false, false>(A, list, n, first); return; }
+    if (cell >= CELL_ONEP) { if (cell == CELL_NIBBLE) d_dp_pk_cls<CLS_PK20, true, true, true, false, false>(A, list, n, first); else d_dp_pk_cls<CLS_PK20, true, true, false, false, false>(A, list, n, first); return; }
+    if (cell == CELL_TAG8) { d_dp_pk_any<true, false>(cls, A, list, n, first); return; }
+    d_dp_pk_any<false, false>(cls, A, list, n, first);
 }
 // wide gap fills in int16 (classes 19-21: bands up to 256 / 512 / 1024 diagonals): one problem per workgroup of
 // NW waves, four diagonals per lane; these are few and long, so what counts is the time of one step
@@ -3716,8 +3766,7 @@ __global__ void __launch_bounds__(64 * NW) k_dp_pkw(DpArgs A)
 }
 // z-drop extensions (class 18): their own launch on a side stream; four lanes per problem keep the single-wave
 // latency of the long windows down
-#define PKX_LPP 4
-#define PKX_R 4
+constexpr int PKX_LPP = DP_CLASS[CLS_PKX64].lpp, PKX_R = DP_CLASS[CLS_PKX64].regs;
 __global__ void __launch_bounds__(64) k_dp_pkx(DpArgs A)
 {
     __builtin_amdgcn_s_setprio(3);
@@ -3734,7 +3783,8 @@ __global__ void __launch_bounds__(64) k_dp_pkx16(DpArgs A)
 }
 
 // the wider extension bands (classes 23 / 24: D <= 128 / 256), same cell, same spill layout rule (32 / 64 dwords per row)
-#define PKX8_LPP 8           /* lanes per problem of class 23: 8 lanes x 4 registers; 4 x 8 (16 problems per wave, 132 VGPRs) measured slower in round 5: 15.1 vs 11.7 ms per range */
+constexpr int PKX8_LPP = DP_CLASS[CLS_PKX128].lpp;           // lanes per problem of class 23: 8 lanes x 4 registers; 4 x 8 (16 problems per wave, 132 VGPRs) measured slower in round 5: 15.1 vs 11.7 ms per range
+static_assert(DP_CLASS[CLS_PKX128].regs == 32 / PKX8_LPP && DP_CLASS[CLS_PKX256].lpp == 16 && DP_CLASS[CLS_PKX256].regs == 4, "class table");
 __global__ void __launch_bounds__(64) k_dp_pkx_w8(DpArgs A)
 {
     __builtin_amdgcn_s_setprio(3);
@@ -3769,8 +3819,8 @@ __device__ __forceinline__ void d_traceback_lane(const DpProb *__restrict__ prob
     const int dhi_ = P.dhi; int touched = 0;
     const int cls = P.pad[0] & 0xff, dlo = P.dlo, mg = P.pad[0] >> 8;
     const int D = P.dhi - dlo + 1, stride = (D + 2) / 2;
-    const int lpp = cls >= 5 ? d_cls_slots(cls) : 0;
-    const bool packed = cls >= 5, tiled = d_tb_tiled(cls);
+    const int lpp = d_cls_slots(cls);
+    const bool packed = d_tb_regs(cls), tiled = d_tb_tiled(cls), rows2 = d_tb_rows2(cls);
     int i = res[pi].bi, j = res[pi].bj;
     uint32_t *cg = cig + P.cig_off;
     int no = 0, ml = 0, mc = 0, state = 0, cur_op = -1, cur_len = 0;
@@ -3781,7 +3831,7 @@ __device__ __forceinline__ void d_traceback_lane(const DpProb *__restrict__ prob
         const int a = i + j, sl = (j - i - dlo) >> 1;
         // tiled (the extension classes, d_dp_pkx): row k = a >> 1 of dword x = sl >> 1 at dword (k >> 2) 4 lpp + (x >> 2) 16 + (k & 3) 4 + (x & 3)
         const int64_t off = tiled ? ((((int64_t)(a >> 3) * (4 * lpp) + ((sl >> 3) << 4) + (((a >> 1) & 3) << 2) + ((sl >> 1) & 3)) << 2) + ((a & 1) << 1) + (sl & 1))
-                          : (LAYOUT == 2 || cls >= 10) ? ((((int64_t)(a >> 1) * lpp + (sl >> 1)) << 2) + ((a & 1) << 1) + (sl & 1))
+                          : (LAYOUT == 2 || rows2) ? ((((int64_t)(a >> 1) * lpp + (sl >> 1)) << 2) + ((a & 1) << 1) + (sl & 1))
                           : packed ? ((((int64_t)(a >> 2) * lpp + sl) << 2) + (a & 3)) : ((int64_t)a * stride + sl);
         // lines are taken relative to the 64-byte grid of the whole scratch buffer; the wave-interleaved classes keep their
         // bytes in 8-byte units 512 bytes apart (k_tb_gather) -- this generic walk reaches them only in the TELR_AB=tb_one_launch mode
@@ -3999,15 +4049,14 @@ __global__ void __launch_bounds__(64) k_traceback_pk(const DpProb *__restrict__ 
     __shared__ uint32_t stage[TB_SLOTS * 16 * 64];
     const uint32_t w = waves[blockIdx.x];
     const int cls = (int)(w >> 26), first = (int)(w & 0x3ffffffu);
-    const int ppw = 64 / PK_LPP[PK_IDX(cls)], t = threadIdx.x;
+    const int ppw = 64 / DP_CLASS[cls].lpp, t = threadIdx.x;
     const bool have = t < ppw && first + t < off.off[cls + 1] - off.off[cls];
-    const int rb4 = d_tb4(cls, tb4) ? d_tb4_rowb(cls) : 0;
-    const DpProb P0 = probs[cls_list[off.off[cls] + first]];                   // the wave's longest problem: k_dp_pk chose the cell by it
-    const bool tag8 = !rb4 && !(cls == 17 && d_onep_d(o.q, o.e, o.q2, o.e2) >= 16) && !(cls == 10 && d_onep_d(o.q, o.e, o.q2, o.e2) >= 20) && P0.m + P0.n <= tag8_steps;
+    const int cell = d_pk_cell(cls, o, tb4, tag8_steps, probs, cls_list + off.off[cls] + first), rb4 = cell == CELL_NIBBLE ? d_tb4_rowb(cls) : 0;
+    const bool tag8 = cell == CELL_TAG8;
 #ifdef TB_PROF
     const unsigned long long t0_ = wall_clock64();
 #endif
-    const int pi_ = cls_list[off.off[cls] + (have ? first + t : first)], lpp_ = PK_LPP[PK_IDX(cls)] * PK_R[PK_IDX(cls)];
+    const int pi_ = cls_list[off.off[cls] + (have ? first + t : first)], lpp_ = d_cls_slots(cls);
     if (d_tb_interleaved(cls)) {
         if (rb4) d_traceback_rows<2, true>(probs, res, pi_, have, lpp_, rb4, o, tb_all, cig, retry, stage);
         else if (tag8) d_traceback_rows<1, true>(probs, res, pi_, have, lpp_, 0, o, tb_all, cig, retry, stage);
@@ -4017,7 +4066,8 @@ __global__ void __launch_bounds__(64) k_traceback_pk(const DpProb *__restrict__ 
 #ifdef TB_PROF
     if (threadIdx.x == 0) {
         const unsigned long long t1_ = wall_clock64(), dt = t1_ - t0_;
-        const int rowb_ = rb4 ? rb4 : PK_LPP[PK_IDX(cls)] * PK_R[PK_IDX(cls)] * 4;
+        const int rowb_ = rb4 ? rb4 : d_cls_slots(cls) * 4;
+        const DpProb P0 = probs[cls_list[off.off[cls] + first]];                   // the wave's longest problem
         unsigned long long lines = (unsigned long long)(((P0.m + P0.n) / 2 + 1) * rowb_ + 63) >> 6; if (lines > 65535) lines = 65535;
         atomicAdd(&g_tb_prof[0], dt); atomicMax(&g_tb_prof[1], dt << 16 | lines); atomicAdd(&g_tb_prof[2], 1ULL); atomicAdd(&g_tb_prof[3], lines);
         atomicMin(&g_tb_prof[4], t0_); atomicMax(&g_tb_prof[5], t1_);
@@ -4042,8 +4092,8 @@ __global__ void __launch_bounds__(64) k_traceback_w(const DpProb *__restrict__ p
     const int dhi_ = P.dhi; int touched = 0;
     const int cls = P.pad[0] & 0xff, dlo = P.dlo, mg = P.pad[0] >> 8;
     const int D = P.dhi - dlo + 1, stride = (D + 2) / 2;
-    const int lpp = cls >= 5 ? d_cls_slots(cls) : 0;
-    const bool packed = cls >= 5;
+    const int lpp = d_cls_slots(cls);
+    const bool packed = d_tb_regs(cls), rows2 = d_tb_rows2(cls);
     const int64_t rowb = packed ? (int64_t)lpp * 4 : stride;        // bytes per row of the trace-back matrix
     const uint8_t *tb = tb_all + P.tb_off;
     int i = res[pi].bi, j = res[pi].bj;
@@ -4053,7 +4103,7 @@ __global__ void __launch_bounds__(64) k_traceback_w(const DpProb *__restrict__ p
     while (i > 0 && j > 0) {
         const int a = i + j, sl = (j - i - dlo) >> 1;
         int row; int64_t col;                  // row and byte column of this cell's trace-back byte
-        if (cls >= 10) { row = a >> 1; col = ((int64_t)(sl >> 1) << 2) + ((a & 1) << 1) + (sl & 1); }
+        if (rows2) { row = a >> 1; col = ((int64_t)(sl >> 1) << 2) + ((a & 1) << 1) + (sl & 1); }
         else if (packed) { row = a >> 2; col = ((int64_t)sl << 2) + (a & 3); }
         else { row = a; col = sl; }
         const int k = r0 - row;
@@ -4092,7 +4142,7 @@ __global__ void __launch_bounds__(64) k_traceback_w(const DpProb *__restrict__ p
             // the run of "H came from the diagonal" cells from the current cell on: the whole run is one step of the loop.
             const int ik = i - lane, jk = j - lane, ak = a - 2 * lane;
             int rowk; int64_t colk;
-            if (cls >= 10) { rowk = ak >> 1; colk = ((int64_t)(sl >> 1) << 2) + ((ak & 1) << 1) + (sl & 1); }
+            if (rows2) { rowk = ak >> 1; colk = ((int64_t)(sl >> 1) << 2) + ((ak & 1) << 1) + (sl & 1); }
             else if (packed) { rowk = ak >> 2; colk = ((int64_t)sl << 2) + (ak & 3); }
             else { rowk = ak; colk = sl; }
             const int kk = r0 - rowk, wk = (int)(colk - c0);

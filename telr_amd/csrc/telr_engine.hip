@@ -47,7 +47,7 @@ struct telr_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t side[8] = {nullptr};
-    hipEvent_t ev_fork = nullptr, ev_side[8] = {nullptr}, ev_chunk[8] = {nullptr};
+    hipEvent_t ev_fork = nullptr, ev_side[8] = {nullptr}, ev_pk = nullptr;      // ev_pk: the packed launch is done (its trace-back waits for it)
     hipStream_t tb_stream = nullptr;      // packed trace-back chunks run here, underneath the next forward chunk
     hipStream_t copy_stream = nullptr;    // the result CIGAR DMA: may still run when telr_map has returned and the next call starts
     hipEvent_t ev_stitched = nullptr, ev_dma = nullptr; bool dma_inflight = false;
@@ -96,7 +96,10 @@ struct telr_ctx {
 //                            no_pk / no_pkw / no_pkext (int32 classes instead of the packed fills / wide fills / extensions), tb8 (byte
 //                            spill in the one-piece classes), no_tag8 (untagged two-piece cell), tb_one_launch (ONE trace-back launch
 //                            after all forward kernels), no_avx2 (scalar host packer), fasta_copy (no in-place use of the mapped file),
-//                            bam_no_populate, bam_no_twin (BAM writer: no pre-faulted mapping / CIGARs uploaded again)
+//                            bam_no_populate, bam_no_twin (BAM writer: no pre-faulted mapping / CIGARs uploaded again), scan_lib /
+//                            index_sort_lib (rocPRIM's scan / its sort of the index build), chain_lazy, chain_no_mw (the lazy far
+//                            look-back everywhere / no second kernel for the long dense runs), over_routed (only the over-size queries of a
+//                            range take the two-step form)
 //   TELR_TRACE=tok[,tok...]  stderr traces: host (wall-clock marks of every batch's host side), mem (device memory at the points
 //                            where the engine runs out of it or gives it back), fasta (phases of telr_fasta_load)
 // The others are operational: TELR_DEBUG, TELR_HOST_THREADS, TELR_PACK_THREADS, TELR_BATCH_MBP / TELR_BATCH_KBP (range size),
@@ -293,7 +296,7 @@ static int ctx_init(int device, bool background, telr_ctx **out)
     for (int i = 0; i < 6; ++i) if (hipEventCreate(&ctx->evk[i]) != hipSuccess) { delete ctx; return TELR_E_NODEVICE; }
     for (int i = 0; i < TELR_N_STAGES; ++i) for (int j = 0; j < 2; ++j) if (hipEventCreate(&ctx->ev_st[i][j]) != hipSuccess) { delete ctx; return TELR_E_NODEVICE; }
     for (int i = 0; i < TELR_NSIDE; ++i) if (hipStreamCreate(&ctx->side[i]) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_side[i], hipEventDisableTiming) != hipSuccess) { delete ctx; return TELR_E_NODEVICE; }
-    for (int i = 0; i < 8; ++i) if (hipEventCreateWithFlags(&ctx->ev_chunk[i], hipEventDisableTiming) != hipSuccess) { delete ctx; return TELR_E_NODEVICE; }
+    if (hipEventCreateWithFlags(&ctx->ev_pk, hipEventDisableTiming) != hipSuccess) { delete ctx; return TELR_E_NODEVICE; }
     if (hipStreamCreate(&ctx->tb_stream) != hipSuccess) { delete ctx; return TELR_E_NODEVICE; }
     if (hipStreamCreate(&ctx->copy_stream) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_stitched, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_dma, hipEventDisableTiming) != hipSuccess) { delete ctx; return TELR_E_NODEVICE; }
@@ -319,7 +322,7 @@ extern "C" void telr_destroy(telr_ctx *ctx)
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (int i = 0; i < TELR_NSIDE; ++i) { if (ctx->side[i]) (void)hipStreamDestroy(ctx->side[i]); if (ctx->ev_side[i]) (void)hipEventDestroy(ctx->ev_side[i]); }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    for (int i = 0; i < 8; ++i) if (ctx->ev_chunk[i]) (void)hipEventDestroy(ctx->ev_chunk[i]);
+    if (ctx->ev_pk) (void)hipEventDestroy(ctx->ev_pk);
     if (ctx->tb_stream) (void)hipStreamDestroy(ctx->tb_stream);
     if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
     if (ctx->ev_stitched) (void)hipEventDestroy(ctx->ev_stitched);
@@ -1429,75 +1432,81 @@ static inline bool pk_cx_ok(const telr_map_opt *mo, int D)
     if (ab_on("no_pk") || bS > 400 || aS > 400 || mo->sc_ambi * S > 400 || mo->cx_open + mo->cx_ext_max > 320 || mo->cx_ext_max < mo->cx_ext_min || mo->cx_ext_min < 0 || mo->cx_decay < 0) return false;
     return cx_gap(mo, D) + aS * D / 2 <= 11900;
 }
-static inline int pk_steps_limit(const telr_map_opt *mo)
+// the affine int16 bound on m + n: b (m + n) / 2 + open + D ext stays below hb and a (m + n) / 2 below ha / 2
+static inline int affine_steps(const telr_map_opt *mo, int hb, int D, int ha, int gap_open, int gap_ext)
 {
-    // (convex cost: the single-wave packed classes re-bias their scores as they go -- kernels.hip.h, REB -- so only the constants have to fit)
-    if (mo->cx_scale > 0) return pk_cx_ok(mo, 128) ? 7900 : 0;
-    if (!(mo->b <= 9 && mo->a <= 4 && mo->q2 + mo->e2 <= 64 && mo->sc_ambi <= 9) || ab_on("no_pk")) return 0;
-    const int by_b = 2 * (15800 - mo->q2 - 128 * mo->e2) / (mo->b > 0 ? mo->b : 1) - 2, by_a = 32000 / (mo->a > 0 ? mo->a : 1) - 2;
-    const int lim = by_b < by_a ? by_b : by_a;
-    return lim > 0 ? lim : 0;
-}
-// same bound for the wide int16 classes (bands up to 1024 diagonals)
-static inline int pk_wide_limit(const telr_map_opt *mo)
-{
-    if (!pk_steps_limit(mo) || ab_on("no_pkw")) return 0;
-    if (mo->cx_scale > 0) return pk_cx_ok(mo, 256) ? 7900 : 0;          // (which of the three wide classes: pk_wide_maxd)
-    const int by_b = 2 * (15800 - mo->q2 - 1024 * mo->e2) / (mo->b > 0 ? mo->b : 1) - 2, by_a = 32000 / (mo->a > 0 ? mo->a : 1) - 2;
-    const int lim = by_b < by_a ? by_b : by_a;
-    return lim > 0 ? lim : 0;
-}
-// the widest band the wide int16 classes take (19: 256, 20: 512, 21: 1,024 diagonals)
-static inline int pk_wide_maxd(const telr_map_opt *mo)
-{
-    if (mo->cx_scale <= 0) return 1024;
-    return pk_cx_ok(mo, 1024) ? 1024 : pk_cx_ok(mo, 512) ? 512 : pk_cx_ok(mo, 256) ? 256 : 0;
-}
-// longest z-drop extension window (m+n) the packed int16 kernel takes: scores stay inside +-16000
-// classes that spill four bits per cell (kernels.hip.h: d_tb4): the one-piece classes of the preset, when every class has its
-// own trace-back launch (the one-launch walk of TELR_AB=tb_one_launch reads bytes); TELR_AB=tb8 keeps the byte spill for A/B
-static inline int tb4_mask(const telr_map_opt *mo)
-{
-    static const bool off = ab_on("tb_one_launch") || ab_on("tb8");
-    if (off || !pk_steps_limit(mo) || mo->cx_scale > 0) return 0;          // (the convex cell spills plain bytes)
-    const int d = d_onep_d(mo->q, mo->e, mo->q2, mo->e2);
-    return (d >= 16 ? 1 : 0) | (d >= 20 ? 2 : 0);
-}
-// steps (m + n) up to which the nibble cell's quarter of the int16 range holds: 4 (b steps / 2 + q + e D) stays below 15,400
-static inline int tb4_steps(const telr_map_opt *mo)
-{
-    const int by_b = 2 * (3850 - mo->q - 32 * mo->e) / (mo->b > 0 ? mo->b : 1) - 2, by_a = 7700 / (mo->a > 0 ? mo->a : 1) - 2;
-    const int lim = by_b < by_a ? by_b : by_a;
-    return lim > 0 ? lim : 0;
-}
-// the same for the two-piece tagged cell (scores times eight); off with the one-launch trace-back (it reads plain flags) or TELR_AB=no_tag8
-static inline int tag8_steps(const telr_map_opt *mo)
-{
-    static const bool off = ab_on("tb_one_launch") || ab_on("no_tag8");
-    if (off || !pk_steps_limit(mo) || mo->cx_scale > 0) return 0;
-    const int by_b = 2 * (1975 - mo->q2 - 128 * mo->e2) / (mo->b > 0 ? mo->b : 1) - 2, by_a = 4000 / (mo->a > 0 ? mo->a : 1) - 2;
+    const int by_b = 2 * (hb - gap_open - D * gap_ext) / (mo->b > 0 ? mo->b : 1) - 2, by_a = ha / (mo->a > 0 ? mo->a : 1) - 2;
     const int lim = by_b < by_a ? by_b : by_a;
     return lim > 0 ? lim : 0;
 }
 // diagonals of the preset's extension band (-ext_band rounded to even .. ext_band), as the packed extension classes cut them: 64 / 128 / 256
-static inline int pk_ext_d(const telr_map_opt *mo) { const int D = 2 * mo->ext_band + 2; return D <= 64 ? 64 : D <= 128 ? 128 : 256; }
-static inline int pk_ext_limit(const telr_map_opt *mo)
+static inline int pk_ext_d(const telr_map_opt *mo) { const int c = d_cls_fit<DPF_PKX>(2 * mo->ext_band + 2, DP_DMAX); return DP_CLASS[c < 0 ? (int)CLS_PKX256 : c].maxd; }
+// The int16 bounds of a pass (kernels.hip.h: DpLimits), computed once per dp_pass.
+static DpLimits dp_limits(const telr_map_opt *mo)
 {
-    if (!pk_steps_limit(mo) || ab_on("no_pkext")) return 0;
-    const int D = pk_ext_d(mo);
+    static const bool one_launch = ab_on("tb_one_launch"), tb8 = ab_on("tb8"), no_tag8 = ab_on("no_tag8");
+    const bool cx = mo->cx_scale > 0;
+    DpLimits L = { 0, 0, 0, 0, 64, 0, 0, 0 };
+    // longest gap fill (m + n) the packed int16 kernels take: |H| <= b (m + n) / 2 + q2 + 128 e2 and a (m + n) / 2 must stay inside
+    // +-16000 (bands of these classes have at most 128 diagonals); 0 disables the packed classes
+    // (convex cost: the single-wave packed classes re-bias their scores as they go -- kernels.hip.h, REB -- so only the constants have to fit)
+    if (cx) L.pk_steps = pk_cx_ok(mo, 128) ? 7900 : 0;
+    else if (mo->b <= 9 && mo->a <= 4 && mo->q2 + mo->e2 <= 64 && mo->sc_ambi <= 9 && !ab_on("no_pk")) L.pk_steps = affine_steps(mo, 15800, 128, 32000, mo->q2, mo->e2);
+    // the widest band the wide int16 classes take (19: 256, 20: 512, 21: 1,024 diagonals), and the same bound for them
+    L.pk_wide_maxd = !cx || pk_cx_ok(mo, 1024) ? 1024 : pk_cx_ok(mo, 512) ? 512 : pk_cx_ok(mo, 256) ? 256 : 0;
+    if (L.pk_steps && !ab_on("no_pkw")) L.pk_wide = cx ? (pk_cx_ok(mo, 256) ? 7900 : 0) : affine_steps(mo, 15800, 1024, 32000, mo->q2, mo->e2);
+    // longest z-drop extension window (m + n) the packed int16 kernels take, and the widest band of theirs (18: 64, 23: 128, 24: 256 diagonals)
     // (convex cost: the z-drop test runs on the re-biased row maximum + the sum of the moves, in int32 -- kernels.hip.h, REB)
-    if (mo->cx_scale > 0) return mo->zdrop * mo->cx_scale <= 30000 && pk_cx_ok(mo, D) ? 7900 : 0;
-    if (mo->zdrop > 4000) return 0;
-    const int by_b = 2 * (15800 - mo->q2 - D * mo->e2) / (mo->b > 0 ? mo->b : 1) - 2, by_a = 32000 / (mo->a > 0 ? mo->a : 1) - 2;
-    const int lim = by_b < by_a ? by_b : by_a;
-    return lim > 0 ? lim : 0;
+    if (L.pk_steps && !ab_on("no_pkext")) {
+        const int D = pk_ext_d(mo);
+        if (cx) L.pk_ext = mo->zdrop * mo->cx_scale <= 30000 && pk_cx_ok(mo, D) ? 7900 : 0;
+        else if (mo->zdrop <= 4000) L.pk_ext = affine_steps(mo, 15800, D, 32000, mo->q2, mo->e2);
+        if (L.pk_ext) L.pk_ext_maxd = D;
+    }
+    // classes that spill four bits per cell (kernels.hip.h: d_tb4): the one-piece classes of the preset, when every class has its
+    // own trace-back launch (the one-launch walk of TELR_AB=tb_one_launch reads bytes); TELR_AB=tb8 keeps the byte spill for A/B
+    // (the convex cell spills plain bytes)
+    if (L.pk_steps && !cx && !one_launch && !tb8) {
+        const int d = d_onep_d(mo->q, mo->e, mo->q2, mo->e2);
+        for (const DpClassRow &r : DP_CLASS) if (r.nibble && d >= r.maxd) L.tb4_mask |= r.nibble;
+    }
+    // steps (m + n) up to which the nibble cell's quarter of the int16 range holds: 4 (b steps / 2 + q + e D) stays below 15,400
+    L.tb4_steps = affine_steps(mo, 3850, 32, 7700, mo->q, mo->e);
+    // the same for the two-piece tagged cell (scores times eight); off with the one-launch trace-back (it reads plain flags) or TELR_AB=no_tag8
+    if (L.pk_steps && !cx && !one_launch && !no_tag8) L.tag8_steps = affine_steps(mo, 1975, 128, 4000, mo->q2, mo->e2);
+    return L;
 }
-// the widest band the packed extension classes take (18: 64, 23: 128, 24: 256 diagonals)
-static inline int pk_ext_maxd(const telr_map_opt *mo) { return pk_ext_limit(mo) ? pk_ext_d(mo) : 64; }
+// The forward kernel of a class outside the one packed launch.  Lanes and registers come from the class table; a block is
+// max(64, lanes per problem) threads and holds 64 / lanes problems (at least one).
+typedef void (*DpKernel)(DpArgs);
+template <int CLS> static constexpr DpKernel reg_kernel() { return k_dp_reg<DP_CLASS[CLS].lpp, DP_CLASS[CLS].regs, (DP_CLASS[CLS].lpp + 63) / 64>; }
+template <int CLS> static constexpr DpKernel pkw_kernel() { return k_dp_pkw<DP_CLASS[CLS].lpp / 64>; }
+// The side-stream classes in launch order = expected single-problem latency, longest first (the device offers only a few
+// hardware queues, so streams beyond that share one and run in submission order), and the walk that follows: few long
+// problems: one wave walks one problem (k_traceback_w: latency); the extensions and class 0, which come by the thousand:
+// one lane per problem (k_traceback: throughput)
+struct SideLaunch { int cls; DpKernel kernel; bool lane_walk; };
+static const SideLaunch SIDE_LAUNCH[] = {
+    { CLS_REG1024, reg_kernel<CLS_REG1024>(), false },
+    { CLS_LDSMAX, k_dp_w4, false },              // classes 3 and 4 (bands of 257 .. DP_DMAX diagonals: fills only) with four waves per problem
+    { CLS_LDS1024, k_dp_w4, false },
+    { CLS_PKW1024, pkw_kernel<CLS_PKW1024>(), false },
+    { CLS_REG512, reg_kernel<CLS_REG512>(), false },
+    { CLS_PKW512, pkw_kernel<CLS_PKW512>(), false },
+    { CLS_PKX256, k_dp_pkx_w16, true },
+    { CLS_PKX128, k_dp_pkx_w8, true },
+    { CLS_PKX64, k_dp_pkx, true },               // (k_dp_pkx16 when the problems are few: dp_pass)
+    { CLS_LDS256, k_dp, false },
+    { CLS_REG256, reg_kernel<CLS_REG256>(), false },
+    { CLS_PKW256, pkw_kernel<CLS_PKW256>(), false },
+    { CLS_LDS128, k_dp, false },
+    { CLS_LDS64, k_dp, true },
+};
 static int dp_pass(telr_ctx *ctx, const telr_seqset *qs, const telr_seqset *tg, const telr_map_opt *mo, DpProb *d_probs, int np, DpRes *d_res,
                    uint32_t **d_rawcig_io, int32_t *d_retry, const std::string &sfx, bool primary)
 {
     hipStream_t st = ctx->stream;
+    const DpLimits L = dp_limits(mo);
     int64_t *d_tbb, *d_cgo, *d_tboff, *d_cgoff; int32_t *d_clscnt, *d_clslist; uint32_t *d_clskey, *d_keytmp; int32_t *d_listtmp;
     ClsOff coff;
     TRY(ctx_buf_t(ctx, ("tb_bytes" + sfx).c_str(), (size_t)np + 1, &d_tbb));
@@ -1509,7 +1518,7 @@ static int dp_pass(telr_ctx *ctx, const telr_seqset *qs, const telr_seqset *tg, 
     TRY(ctx_buf_t(ctx, ("cls_key" + sfx).c_str(), (size_t)np, &d_clskey));
     TRY(ctx_buf_t(ctx, ("cls_keytmp" + sfx).c_str(), (size_t)np, &d_keytmp));
     TRY(ctx_buf_t(ctx, ("cls_listtmp" + sfx).c_str(), (size_t)np, &d_listtmp));
-    hipLaunchKernelGGL(k_prob_sizes, dim3((np + 255) / 256), dim3(256), 0, st, d_probs, np, primary ? mo->fill_margin : 0, pk_steps_limit(mo), pk_ext_limit(mo), pk_wide_limit(mo), qs->d_nmask, tg->d_nmask, d_tbb, d_cgo, tb4_mask(mo), tb4_steps(mo), pk_wide_maxd(mo), pk_ext_maxd(mo));
+    hipLaunchKernelGGL(k_prob_sizes, dim3((np + 255) / 256), dim3(256), 0, st, d_probs, np, primary ? mo->fill_margin : 0, L, qs->d_nmask, tg->d_nmask, d_tbb, d_cgo);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(d_tbb + np, 0, 8, st));
     HIPCHK(hipMemsetAsync(d_cgo + np, 0, 8, st));
@@ -1557,8 +1566,7 @@ static int dp_pass(telr_ctx *ctx, const telr_seqset *qs, const telr_seqset *tg, 
         D.o.cx_flat = mo->cx_decay > 0 && mo->cx_ext_max > mo->cx_ext_min ? (mo->cx_ext_max - mo->cx_ext_min + mo->cx_decay - 1) / mo->cx_decay : 0;
     }
     D.tb = d_tb; D.cig = *d_rawcig_io; D.res = d_res; D.dcap = 0;
-    D.retry = d_retry; D.tb4 = tb4_mask(mo); D.tag8_steps = tag8_steps(mo);
-    static const int CAP[5] = { 64, 128, 256, 1024, DP_DMAX };
+    D.retry = d_retry; D.tb4 = L.tb4_mask; D.tag8_steps = L.tag8_steps;
     // trace-back per class list, right behind the class's forward kernel on the same stream (TELR_AB=tb_one_launch: one
     // trace-back launch over all problems after every forward kernel has finished)
     static const bool tb_split = !ab_on("tb_one_launch");
@@ -1566,9 +1574,8 @@ static int dp_pass(telr_ctx *ctx, const telr_seqset *qs, const telr_seqset *tg, 
     // before the tail classes are started so that these two small launches do not queue behind them
     int nw = 0; uint32_t *d_wv2 = nullptr;
     {
-        static const int LPP_[PK_NC] = { 1, 1, 1, 1, 2, 2, 2, 1, 4 };
         PkPlan plan; plan.woff[0] = 0;
-        for (int c = 0; c < PK_NC; ++c) { const int ppw = 64 / LPP_[c]; plan.woff[c + 1] = plan.woff[c] + (h_cls[PK_CLS(c)] + ppw - 1) / ppw; }
+        for (int c = 0; c < PK_NC; ++c) { const int ppw = 64 / DP_CLASS[PK_CLS(c)].lpp; plan.woff[c + 1] = plan.woff[c] + (h_cls[PK_CLS(c)] + ppw - 1) / ppw; }
         nw = plan.woff[PK_NC];
         if (nw > 0) {
             uint32_t *d_wk, *d_wv, *d_wk2;
@@ -1591,82 +1598,66 @@ static int dp_pass(telr_ctx *ctx, const telr_seqset *qs, const telr_seqset *tg, 
     std::vector<hipStream_t> used;
     static const bool serial = getenv("TELR_SERIAL") != nullptr;      // profiling aid: every class on the main stream
     auto side_stream = [&]() { if (serial) return st; hipStream_t s2 = ctx->side[side % TELR_NSIDE]; ++side; used.push_back(s2); return s2; };
-    // launch order = expected single-problem latency, longest first (the device offers only a few hardware queues,
-    // so streams beyond that share one and run in submission order)
-    static const int SIDE_ORDER[] = { 9, 4, 3, 21, 8, 20, 24, 23, 18, 2, 7, 19, 1, 0 };
-    for (int c : SIDE_ORDER) {
-        if (h_cls[c] == 0) continue;
+    // forward kernel of one class list on stream s2
+    auto launch = [&](int c, DpKernel kernel, hipStream_t s2) -> int {
+        const int nl = h_cls[c];
+        int threads = DP_CLASS[c].lpp > 64 ? DP_CLASS[c].lpp : 64, ppb = DP_CLASS[c].lpp < 64 ? 64 / DP_CLASS[c].lpp : 1;
+        size_t lds = 0;
+        D.list = d_clslist + coff.off[c]; D.nlist = nl; D.dcap = 0;
+        if (DP_CLASS[c].family == DPF_LDS) {
+            D.dcap = DP_CLASS[c].maxd;
+            lds = (size_t)(D.dcap + 2) * 5 * 4;
+            static const bool one_wave = ab_on("dp_one_wave");      // TELR_AB=dp_one_wave: one wave per problem in classes 3 and 4 too, as classes 0-2
+            if (one_wave) { kernel = k_dp; threads = 64; }
+            if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
+        if (c == CLS_PKX64 && nl < 8192) { kernel = k_dp_pkx16; ppb = 4; }       // few problems: latency counts (sixteen lanes per problem)
+        hipLaunchKernelGGL(kernel, dim3((nl + ppb - 1) / ppb), dim3(threads), lds, s2, D);
+        HIPCHK(hipGetLastError());
+        return TELR_OK;
+    };
+    for (const SideLaunch &row : SIDE_LAUNCH) {
+        const int c = row.cls, nl = h_cls[c];
+        if (nl == 0) continue;
         hipStream_t s2 = side_stream();
         HIPCHK(hipStreamWaitEvent(s2, ctx->ev_fork, 0));
-        const int nl = h_cls[c];
-        D.list = d_clslist + coff.off[c]; D.nlist = nl; D.dcap = 0;
-        if (c <= 4) {
-            D.dcap = CAP[c];
-            size_t lds = (size_t)(CAP[c] + 2) * 5 * 4;
-            // classes 3 and 4 (bands of 257 .. DP_DMAX diagonals: fills only) with four waves per problem (TELR_AB=dp_one_wave: one, as classes 0-2)
-            static const bool one_wave = ab_on("dp_one_wave");
-            if (c >= 3 && !one_wave) {
-                if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_dp_w4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(k_dp_w4, dim3(nl), dim3(256), lds, s2, D);
-            } else {
-                if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_dp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(k_dp, dim3(nl), dim3(64), lds, s2, D);
-            }
-        }
-        else if (c == 9) hipLaunchKernelGGL((k_dp_reg<256, 2, 4>), dim3(nl), dim3(256), 0, s2, D);
-        else if (c == 8) hipLaunchKernelGGL((k_dp_reg<128, 2, 2>), dim3(nl), dim3(128), 0, s2, D);
-        else if (c == 7) hipLaunchKernelGGL((k_dp_reg<64, 2>), dim3(nl), dim3(64), 0, s2, D);
-        else if (c == 21) hipLaunchKernelGGL((k_dp_pkw<4>), dim3(nl), dim3(256), 0, s2, D);
-        else if (c == 20) hipLaunchKernelGGL((k_dp_pkw<2>), dim3(nl), dim3(128), 0, s2, D);
-        else if (c == 19) hipLaunchKernelGGL((k_dp_pkw<1>), dim3(nl), dim3(64), 0, s2, D);
-        else if (c == 23) { const int ppw = 64 / PKX8_LPP; hipLaunchKernelGGL(k_dp_pkx_w8, dim3((nl + ppw - 1) / ppw), dim3(64), 0, s2, D); }
-        else if (c == 24) hipLaunchKernelGGL(k_dp_pkx_w16, dim3((nl + 3) / 4), dim3(64), 0, s2, D);
-        else if (nl < 8192) hipLaunchKernelGGL(k_dp_pkx16, dim3((nl + 3) / 4), dim3(64), 0, s2, D);       // few problems: latency counts
-        else { const int ppw = 64 / PKX_LPP; hipLaunchKernelGGL(k_dp_pkx, dim3((nl + ppw - 1) / ppw), dim3(64), 0, s2, D); }
-        HIPCHK(hipGetLastError());
+        TRY(launch(c, row.kernel, s2));
         if (tb_split) {
-            // few long problems: one wave walks one problem (latency); many (extensions, or a tail class with thousands of problems
-            // on a repeat-rich genome): one lane per problem (throughput)
+            // (a tail class with thousands of problems on a repeat-rich genome: one lane per problem as well)
             const int tbw_max = 2048;
-            if (c == 18 || c == 23 || c == 24 || c == 0 || nl > tbw_max) hipLaunchKernelGGL(k_traceback, dim3((nl + 63) / 64), dim3(64), 0, s2, d_probs, d_res, nl, d_tb, *d_rawcig_io, d_retry, D.list);
+            if (row.lane_walk || nl > tbw_max) hipLaunchKernelGGL(k_traceback, dim3((nl + 63) / 64), dim3(64), 0, s2, d_probs, d_res, nl, d_tb, *d_rawcig_io, d_retry, D.list);
             else hipLaunchKernelGGL(k_traceback_w, dim3(nl), dim3(64), 0, s2, d_probs, d_res, nl, d_tb, *d_rawcig_io, d_retry, D.list);
             HIPCHK(hipGetLastError());
         }
     }
     D.dcap = 0;
-    // packed classes: the wave table is cut into chunks; the trace-back of a chunk (memory bound) runs on its own
-    // stream underneath the forward pass (issue bound) of the next chunk
-    const int pk_chunks = 1;
+    // packed classes: their trace-back (memory bound) runs on its own stream
     const bool tb_over = tb_split && !serial && nw > 0;
     if (primary) HIPCHK(hipEventRecord(ctx->evk[5], st));
     if (primary && nw > 0) ++ctx->pk_launches;
     if (nw > 0) {
         D.list = nullptr; D.nlist = 0;
-        const int G = nw < 4096 ? 1 : pk_chunks;
         if (tb_over) { HIPCHK(hipStreamWaitEvent(ctx->tb_stream, ctx->ev_fork, 0)); if (primary) HIPCHK(hipEventRecord(ctx->evk[3], ctx->tb_stream)); }
-        for (int g = 0; g < G; ++g) {
-            const int w0 = (int)((int64_t)nw * g / G), w1 = (int)((int64_t)nw * (g + 1) / G);
-            if (w1 <= w0) continue;
-            hipLaunchKernelGGL(k_dp_pk, dim3(w1 - w0), dim3(64), 0, st, D, d_wv2 + w0, d_clslist, coff);
+        hipLaunchKernelGGL(k_dp_pk, dim3(nw), dim3(64), 0, st, D, d_wv2, d_clslist, coff);
+        HIPCHK(hipGetLastError());
+        if (tb_over) {
+            HIPCHK(hipEventRecord(ctx->ev_pk, st));
+            HIPCHK(hipStreamWaitEvent(ctx->tb_stream, ctx->ev_pk, 0));
+            hipLaunchKernelGGL(k_traceback_pk, dim3(nw), dim3(64), 0, ctx->tb_stream, d_probs, d_res, d_tb, *d_rawcig_io, d_retry, d_wv2, d_clslist, coff, L.tb4_mask, D.o, L.tag8_steps);
             HIPCHK(hipGetLastError());
-            static const bool dbg_tb_skip = ab_on("dbg_tb_skip");        // EXPERIMENT ONLY (wrong records): what would the step be without the packed classes' trace-back?
-            if (tb_over && !dbg_tb_skip) {
-                HIPCHK(hipEventRecord(ctx->ev_chunk[g], st));
-                HIPCHK(hipStreamWaitEvent(ctx->tb_stream, ctx->ev_chunk[g], 0));
-                hipLaunchKernelGGL(k_traceback_pk, dim3(w1 - w0), dim3(64), 0, ctx->tb_stream, d_probs, d_res, d_tb, *d_rawcig_io, d_retry, d_wv2 + w0, d_clslist, coff, D.tb4, D.o, D.tag8_steps);
-                HIPCHK(hipGetLastError());
-            }
+            if (primary) HIPCHK(hipEventRecord(ctx->evk[4], ctx->tb_stream));
+            used.push_back(ctx->tb_stream);
         }
-        if (tb_over) { if (primary) HIPCHK(hipEventRecord(ctx->evk[4], ctx->tb_stream)); used.push_back(ctx->tb_stream); }
     }
     if (primary) HIPCHK(hipEventRecord(ctx->evk[0], st));
-    if (h_cls[5]) { D.list = d_clslist + coff.off[5]; D.nlist = h_cls[5]; hipLaunchKernelGGL((k_dp_reg<32, 1>), dim3((h_cls[5] + 1) / 2), dim3(64), 0, st, D); }
-    if (h_cls[6]) { D.list = d_clslist + coff.off[6]; D.nlist = h_cls[6]; hipLaunchKernelGGL((k_dp_reg<64, 1>), dim3(h_cls[6]), dim3(64), 0, st, D); }
+    // the two narrow register classes are many: on the main stream behind the packed launch
+    if (h_cls[CLS_REG64]) TRY(launch(CLS_REG64, reg_kernel<CLS_REG64>(), st));
+    if (h_cls[CLS_REG128]) TRY(launch(CLS_REG128, reg_kernel<CLS_REG128>(), st));
     if (primary) HIPCHK(hipEventRecord(ctx->evk[1], st));
     if (tb_split) {
         if (!tb_over && primary) HIPCHK(hipEventRecord(ctx->evk[3], st));
-        if (!tb_over && nw > 0) hipLaunchKernelGGL(k_traceback_pk, dim3(nw), dim3(64), 0, st, d_probs, d_res, d_tb, *d_rawcig_io, d_retry, d_wv2, d_clslist, coff, D.tb4, D.o, D.tag8_steps);
-        for (int c = 6; c >= 5; --c) {
+        if (!tb_over && nw > 0) hipLaunchKernelGGL(k_traceback_pk, dim3(nw), dim3(64), 0, st, d_probs, d_res, d_tb, *d_rawcig_io, d_retry, d_wv2, d_clslist, coff, L.tb4_mask, D.o, L.tag8_steps);
+        for (int c : { (int)CLS_REG128, (int)CLS_REG64 }) {
             if (h_cls[c] == 0) continue;
             hipLaunchKernelGGL(k_traceback, dim3((h_cls[c] + 63) / 64), dim3(64), 0, st, d_probs, d_res, h_cls[c], d_tb, *d_rawcig_io, d_retry, (const int32_t*)(d_clslist + coff.off[c]));
         }
@@ -2699,13 +2690,26 @@ extern "C" int telr_debug_index(telr_ctx *ctx, const telr_index *ix, uint64_t *e
     return TELR_OK;
 }
 extern "C" int32_t telr_debug_mid_occ(const telr_index *ix, const telr_map_opt *mo) { return ix && mo ? index_mid_occ(ix, mo) : -1; }
-// The host's int16 bounds of the DP classes for `mo` (tests aim their problems at them): pk_steps_limit, pk_wide_limit,
-// pk_wide_maxd, pk_ext_limit, pk_ext_maxd, tb4_mask, tb4_steps, tag8_steps.  No device needed.
+// The host's int16 bounds of the DP classes for `mo` (tests aim their problems at them): dp_limits' pk_steps, pk_wide,
+// pk_wide_maxd, pk_ext, pk_ext_maxd, tb4_mask, tb4_steps, tag8_steps.  No device needed.
 extern "C" int telr_debug_dp_limits(const telr_map_opt *mo, int32_t *out)
 {
     if (!mo || !out) return TELR_E_ARG;
-    out[0] = pk_steps_limit(mo); out[1] = pk_wide_limit(mo); out[2] = pk_wide_maxd(mo); out[3] = pk_ext_limit(mo);
-    out[4] = pk_ext_maxd(mo); out[5] = tb4_mask(mo); out[6] = tb4_steps(mo); out[7] = tag8_steps(mo);
+    const DpLimits L = dp_limits(mo);
+    out[0] = L.pk_steps; out[1] = L.pk_wide; out[2] = L.pk_wide_maxd; out[3] = L.pk_ext;
+    out[4] = L.pk_ext_maxd; out[5] = L.tb4_mask; out[6] = L.tb4_steps; out[7] = L.tag8_steps;
+    return TELR_OK;
+}
+// The class table (kernels.hip.h: DP_CLASS), per class: widest band, lanes per problem, registers per lane, dwords per
+// trace-back row, interleaved flag, tiled flag.  No device needed.
+extern "C" int telr_debug_dp_class_table(int32_t *out)
+{
+    if (!out) return TELR_E_ARG;
+    for (int c = 0; c < DP_NCLS; ++c) {
+        const DpClassRow &r = DP_CLASS[c];
+        int32_t *o = out + c * 6;
+        o[0] = r.maxd; o[1] = r.lpp; o[2] = r.regs; o[3] = r.slots; o[4] = d_tb_interleaved(c); o[5] = d_tb_tiled(c);
+    }
     return TELR_OK;
 }
 // The chaining stage of telr_map (chain_dispatch) on a caller's anchor lists (test tap: the scan's edges without seeding).

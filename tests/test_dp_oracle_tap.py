@@ -165,7 +165,7 @@ def test_oracle_extension_without_zdrop_is_the_band_maximum(name, mo):
             assert H[r["bi"][x], r["bj"][x]] == best
 
 
-# the engine's int16 bounds for the presets (telr_engine.hip: pk_steps_limit ... tag8_steps; TELR_AB unset)
+# the engine's int16 bounds for the presets (telr_engine.hip: dp_limits; TELR_AB unset)
 PRESET_LIMITS = {
     "map-ont": (7822, 7374, 1024, 7854, 64, 3, 1889, 909),
     "map-pb": (7822, 7374, 1024, 7854, 64, 3, 1889, 909),
@@ -207,3 +207,19 @@ def test_dp_limits_edges_of_the_affine_acceptance():
         m2 = preset("map-ont")[1]
         m2.zdrop = z
         assert (Engine.dp_limits(m2)["pk_ext_limit"] > 0) == on
+
+
+def test_dp_class_table():
+    """the engine's class table (kernels.hip.h: DP_CLASS) against this suite's own statement of the classes (dp_edges) and
+    against the dwords per trace-back row as the kernels had them before the table (literals)"""
+    T = Engine.dp_class_table()
+    col = {k: T[:, x] for x, k in enumerate(Engine.DP_CLASS_COLUMNS)}
+    assert T.shape == (25, 6)
+    assert {c: int(col["maxd"][c]) for c in range(25)} == {**de.UPPER_D, 4: 4096}
+    assert {c for c in range(25) if col["interleaved"][c]} == set(de.INTERLEAVED)
+    assert {c for c in range(25) if col["tiled"][c]} == {18, 23, 24}
+    for c in (10, 11, 12, 13, 14, 15, 16, 17, 22):
+        assert col["row_dwords"][c] == col["lanes"][c] * col["regs"][c], c
+    row_dwords = {0: 0, 1: 0, 2: 0, 3: 0, 4: 0, 5: 32, 6: 64, 7: 128, 8: 256, 9: 512, 10: 5, 11: 6, 12: 7, 13: 8, 14: 10, 15: 12,
+                  16: 16, 17: 4, 18: 16, 19: 64, 20: 128, 21: 256, 22: 32, 23: 32, 24: 64}
+    assert {c: int(col["row_dwords"][c]) for c in range(25)} == row_dwords

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of environment switches (TELR_AB tokens) and prebuilt library variants against the tree's library on one box, alternating runs:
 # usage (through gpurun): bash tools/ab_env.sh <config> <steps> [bench args] -- name1[=ENV=VALUE] name2 ...
-#   a name with '=': the run gets that environment assignment (e.g. skip=TELR_AB=dbg_tb_skip); a plain name: gpurun_variants/libtelrhip_<name>.so
+#   a name with '=': the run gets that environment assignment (e.g. tb8=TELR_AB=tb8); a plain name: the prebuilt variant libtelrhip_<name>.so (TELR_LIB below)
 set -u
 cfg=$1; steps=$2; shift; shift
 X=""; while [ $# -gt 0 ] && [ "$1" != "--" ]; do X="$X $1"; shift; done; shift
