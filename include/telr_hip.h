@@ -519,6 +519,48 @@ const int64_t *telr_ins_geno_ambig_off(const telr_ins_geno *g);       /* count +
 const int32_t *telr_ins_geno_ambig_reads(const telr_ins_geno *g);
 void telr_ins_geno_free(telr_ins_geno *g);
 
+/* ---- a draft contig per call, cut out of one of its supporting reads (opt-in).  Stands where the reference shells
+ *      out to wtdbg2 or flye (src/telr/TELR_assembly.py:264-382).  An OWN definition: NOT an assembler, and NOT wtdbg2 or flye -- one
+ *      supporting read is the backbone, the piece of it that carries the insertion between reference-aligned flanks is the draft.
+ * Input: a result, the calls of telr_call_insertions on it (calls, read_off, reads as telr_genotype_insertions takes them), the
+ *      signature array sigs[n_sig] as that call returned it (ascending by (tid, pos)), and read_set = the set the result was mapped from.
+ * Walk of a record: states (p, u) start at (ts, qs').  M l: l unit steps (p + 1, u + 1).  I l: one step to (p, u + l).  D l: l unit
+ *      steps (p + 1, u).  For a reference coordinate x: lo(x) = the smallest, hi(x) = the largest u over the states with p == x (an I
+ *      at x lies between the two; an x inside a D has lo = hi).
+ * Candidate of call k = (tid, pos, len): a signature s with kind 0 or 1, s.tid == tid, |s.pos - pos| <= reach and s.qid in R_k.  Then
+ *      a = s.rec; b = s.rec (kind 0) or s.mate (kind 1); lpos = s.pos; rpos = s.pos (kind 0) or b.ts (kind 1);
+ *      xL = max(a.ts, lpos - flank); xR = min(b.te, rpos + flank).  It is VALID iff both records have CIGAR ops,
+ *      lpos - xL >= min_flank, xR - rpos >= min_flank, lo_a(xL) and hi_b(xR) exist, 1 <= n = hi_b(xR) - lo_a(xL) <= max_len, and
+ *      0 <= lo_a(xL), hi_b(xR) <= qlen (true of every record whose CIGAR agrees with its coordinates).
+ * Backbone: the valid candidate with the smallest key (|s.len - len|, -min(lpos - xL, xR - rpos), s.qid, s.rec, s.mate, index of s).
+ * Draft:   bases [lo, hi) of the read on the record's strand; on the forward read start = lo, rc = 0 for a forward record and
+ *      start = qlen - hi, rc = 1 on TELR_F_REV.  Sequence set_index of *set is that piece, reverse-complemented when rc == 1, so every
+ *      draft is on the reference strand; an N keeps its mask bit.  ins_len = s.seg_len, ins_off = the strand coordinate of the
+ *      signature's segment - lo.  A call without a valid candidate: sig = set_index = -1, zeros, no sequence; the set holds the
+ *      other calls' drafts in call order.  It is made on the device from the packed words of read_set and is the caller's
+ *      (telr_seqset_free).  Zero calls: an empty set, TELR_OK.
+ * The CIGAR words are read on the device (the result's resident copy, TELR_MF_KEEP_CIGARS, or one upload).  The output is the same on
+ * every run.  TELR_E_ARG (text in telr_last_error): a negative option, min_flank > flank, calls not strictly ascending, a tid, rec, mate
+ * or qid out of range, a signature whose qid is not its records', signatures not ascending by (tid, pos), a read list not ascending, a
+ * record that telr_call_insertions refuses, a read set whose count or lengths disagree with the records' qid / qlen.  TELR_E_RANGE from
+ * 2^31 - 16 (signature, call) pairs on.  opt NULL = the defaults. */
+typedef struct telr_draft_opt {
+    int32_t flank;        /* 2000   */
+    int32_t min_flank;    /* 500    */
+    int32_t reach;        /* 50     */
+    int32_t max_len;      /* 100000 */
+    int32_t reserved[4];  /* 0      */
+} telr_draft_opt;
+typedef struct telr_draft { int32_t sig, qid, start, len, rc, ins_off, ins_len, set_index; } telr_draft;
+typedef struct telr_drafts telr_drafts;
+void telr_draft_opt_default(telr_draft_opt *o);
+int  telr_draft_contigs(telr_ctx *ctx, const telr_result *r, int32_t n_targets, int64_t n_calls, const telr_ins_call *calls,
+                        const int64_t *read_off, const int32_t *reads, int64_t n_sig, const telr_ins_sig *sigs,
+                        const telr_seqset *read_set, const telr_draft_opt *opt, telr_drafts **out, telr_seqset **set);
+int64_t telr_drafts_count(const telr_drafts *d);                      /* = n_calls */
+const telr_draft *telr_drafts_data(const telr_drafts *d);
+void telr_draft_contigs_free(telr_drafts *d);
+
 /* ---- window reads (a12) -------------------------------------------------------
  * Replaces the per-locus `pysam.AlignmentFile(bam).fetch(chr, bp-1000, bp+1000)` loop of prep_assembly_inputs
  * (src/telr/TELR_assembly.py:384-415, read_type="all"): for every window w = (win_tid, [win_lo, win_hi)) the ascending,

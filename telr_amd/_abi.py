@@ -75,6 +75,24 @@ class InsGt(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("ref", "ambig", "alt", "gt")]
 
 
+class DraftOpt(C.Structure):
+    """telr_draft_opt: the options of telr_draft_contigs (defaults: DraftOpt.default())"""
+    _fields_ = [(n, C.c_int32) for n in ("flank", "min_flank", "reach", "max_len", "reserved0", "reserved1", "reserved2", "reserved3")]
+
+    @classmethod
+    def default(cls, **kw):
+        o = cls(2000, 500, 50, 100000, 0, 0, 0, 0)
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("DraftOpt has no field %r" % k)
+            setattr(o, k, int(v))
+        return o
+
+
+class Draft(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sig", "qid", "start", "len", "rc", "ins_off", "ins_len", "set_index")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "query_bases", "minimizers", "probes", "anchors", "chains", "dp_problems", "dp_cells",
@@ -100,3 +118,5 @@ INS_CALL_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsCall._fields_])
 assert INS_SIG_DTYPE.itemsize == C.sizeof(InsSig) == 36 and INS_CALL_DTYPE.itemsize == C.sizeof(InsCall) == 24
 GENO_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsGt._fields_])
 assert GENO_DTYPE.itemsize == C.sizeof(InsGt) == 16 and C.sizeof(GenoOpt) == 32
+DRAFT_DTYPE = _np.dtype([(n, _np.int32) for n, _ in Draft._fields_])
+assert DRAFT_DTYPE.itemsize == C.sizeof(Draft) == 32 and C.sizeof(DraftOpt) == 32

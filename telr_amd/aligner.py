@@ -6,7 +6,7 @@ boundary (TELR_alignment.py:69-82 and the five other sites listed in include/tel
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._abi import IdxOpt, MapOpt, Counters, InsOpt, GenoOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, N_STAGES, N_DPCLS
+from ._abi import IdxOpt, MapOpt, Counters, InsOpt, GenoOpt, DraftOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, DRAFT_DTYPE, N_STAGES, N_DPCLS
 from .fasta import concat
 
 
@@ -613,6 +613,33 @@ class Index:
                                 ambig_off, _np_from(L.telr_ins_geno_ambig_reads(h), int(ambig_off[-1]), np.int32))
         finally:
             self.eng.L.telr_ins_geno_free(h)
+
+    def draft_contigs(self, r, ic, read_set, opt=None):
+        """a draft contig per call of `ic` (an InsCalls of call_insertions on raw result r: calls, sigs, read_off, reads), cut out of
+        one of the call's supporting reads on the device (telr_draft_contigs; include/telr_hip.h has the definition -- not an assembler):
+        read_set the SeqSet r was mapped from, opt an _abi.DraftOpt (None: the defaults) -> (drafts, set): one DRAFT_DTYPE record per
+        call (sig = set_index = -1: no draft) and the SeqSet of the drafts, in call order, on the reference strand"""
+        o = DraftOpt.default() if opt is None else opt
+        calls = np.ascontiguousarray(ic.calls, dtype=INS_CALL_DTYPE)
+        sigs = np.ascontiguousarray(ic.sigs, dtype=INS_SIG_DTYPE)
+        read_off = np.ascontiguousarray(ic.read_off, dtype=np.int64)
+        reads = np.ascontiguousarray(ic.reads, dtype=np.int32)
+        if len(read_off) != len(calls) + 1 or (len(calls) and int(read_off[-1]) > len(reads)):
+            raise _lib.TelrError("telr_draft_contigs: read_off must hold len(calls) + 1 offsets into reads")
+        h, hs = C.c_void_p(), C.c_void_p()
+        L = self.eng.L
+        rc = L.telr_draft_contigs(self.eng.h, r, self.targets.n, len(calls), calls.ctypes.data, read_off.ctypes.data, reads.ctypes.data,
+                                  len(sigs), sigs.ctypes.data, read_set.h, C.byref(o), C.byref(h), C.byref(hs))
+        if rc != 0:
+            raise _lib.TelrError("telr_draft_contigs: %s [%s]" % (L.telr_strerror(rc).decode(), L.telr_last_error(self.eng.h).decode()), rc)
+        try:
+            drafts = _np_from(L.telr_drafts_data(h), int(L.telr_drafts_count(h)), DRAFT_DTYPE)
+        finally:
+            L.telr_draft_contigs_free(h)
+        out = SeqSet.__new__(SeqSet)
+        out.eng = self.eng; out.h = hs
+        out.len = np.ascontiguousarray(drafts["len"][drafts["sig"] >= 0], dtype=np.int32); out.n = len(out.len)
+        return drafts, out
 
     # ---- debug taps for the stage-level parity tests ----------------------------------
     def debug_dump(self):

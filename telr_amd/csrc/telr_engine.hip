@@ -395,6 +395,34 @@ struct telr_seqset {
     uint8_t *d_qual = nullptr;    // telr_seqset_attach_qual: one Phred value per base in the set's base layout (sequence i at boff[i]), else null
 };
 
+// The layout and the device arrays of a set whose n and len[] are filled in -- the one place that states them: sequence i at base offset
+// boff[i] = the 64-base padded lengths before it; 16 bases per 2-bit word, 32 per mask word; 8 slack words behind either array (the
+// window loads of the kernels read past the last sequence), zeroed here when zero_slack (telr_seqset_create sends them with its words);
+// d_boff / d_len go up on `st` (not waited for).  On failure the set is freed and the code returned; `what` opens the error text.
+static int seqset_alloc(telr_ctx *ctx, telr_seqset *s, const char *what, bool zero_slack, hipStream_t st)
+{
+    const int32_t n = s->n;
+    s->boff.resize((size_t)n + 1);
+    int64_t tot = 0;
+    s->total_bases = 0; s->max_len = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        s->boff[i] = tot; tot += ((int64_t)s->len[i] + 63) & ~63LL; s->total_bases += s->len[i];
+        if (s->len[i] > s->max_len) s->max_len = s->len[i];
+    }
+    s->boff[n] = tot; s->padded_bases = tot;
+    const size_t w2 = (size_t)(tot / 16) + 8, wn = (size_t)(tot / 32) + 8;
+    auto fail = [&](hipError_t e) { ctx->err = std::string(what) + ": " + hipGetErrorString(e); telr_seqset_free(s); return e == hipErrorOutOfMemory ? TELR_E_NOMEM : TELR_E_HIP; };
+    hipError_t e;
+    if ((e = hipMalloc(&s->d_seq2, w2 * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&s->d_nmask, wn * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&s->d_boff, ((size_t)n + 1) * 8)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&s->d_len, (size_t)(n ? n : 1) * 4)) != hipSuccess) return fail(e);
+    if (zero_slack && ((e = hipMemsetAsync(s->d_seq2 + (w2 - 8), 0, 32, st)) != hipSuccess || (e = hipMemsetAsync(s->d_nmask + (wn - 8), 0, 32, st)) != hipSuccess)) return fail(e);
+    if ((e = hipMemcpyAsync(s->d_boff, s->boff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
+    if (n && (e = hipMemcpyAsync(s->d_len, s->len.data(), (size_t)n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
+    return TELR_OK;
+}
+
 static inline uint8_t nt4_of(unsigned char c)
 {
     switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2;
@@ -564,30 +592,17 @@ static int seqset_subset_impl(telr_ctx *ctx, const telr_seqset *parent, int32_t 
     HIPCHK(hipSetDevice(ctx->device));
     for (int i = 0; i < n; ++i) if (idx[i] < 0 || idx[i] >= parent->n) return TELR_E_ARG;
     telr_seqset *s = new telr_seqset();
-    s->ctx = ctx; s->n = n; s->boff.resize(n + 1); s->len.resize(n);
-    int64_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        const int32_t L = parent->len[idx[i]];
-        s->len[i] = L; s->boff[i] = tot; tot += ((int64_t)L + 63) & ~63LL; s->total_bases += L;
-        if (L > s->max_len) s->max_len = L;
-    }
-    s->boff[n] = tot; s->padded_bases = tot;
-    const size_t w2 = (size_t)(tot / 16) + 8, wn = (size_t)(tot / 32) + 8;
+    s->ctx = ctx; s->n = n; s->len.resize(n);
+    for (int i = 0; i < n; ++i) s->len[i] = parent->len[idx[i]];
+    hipStream_t st = ctx->stream;
+    TRY(seqset_alloc(ctx, s, "seqset subset", true, st));         // (the 8 slack words behind the last sequence are read by window loads: kept defined)
     auto fail = [&](hipError_t e) { ctx->err = std::string("seqset subset: ") + hipGetErrorString(e); telr_seqset_free(s); return e == hipErrorOutOfMemory ? TELR_E_NOMEM : TELR_E_HIP; };
     hipError_t e; int32_t *d_idx = nullptr; uint8_t *d_rc = nullptr;
-    if ((e = hipMalloc(&s->d_seq2, w2 * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&s->d_nmask, wn * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&s->d_boff, (n + 1) * 8)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&s->d_len, (n ? n : 1) * 4)) != hipSuccess) return fail(e);
     // the index list lives in the context's scratch: a hipMalloc / hipFree pair per call would make the call wait for the whole device
     { void *p = nullptr; const int rc_ = ctx_buf(ctx, "subset_idx", (size_t)(n ? n : 1) * 4, &p); if (rc_ != TELR_OK) { telr_seqset_free(s); return rc_; } d_idx = (int32_t*)p; }
     if (rc) { void *p = nullptr; const int rc_ = ctx_buf(ctx, "subset_rc", (size_t)(n ? n : 1), &p); if (rc_ != TELR_OK) { telr_seqset_free(s); return rc_; } d_rc = (uint8_t*)p; }
-    hipStream_t st = ctx->stream;
-    // the 8 slack words behind the last sequence are read by window loads: keep them defined
-    if ((e = hipMemsetAsync(s->d_seq2 + (w2 - 8), 0, 32, st)) != hipSuccess || (e = hipMemsetAsync(s->d_nmask + (wn - 8), 0, 32, st)) != hipSuccess) return fail(e);
-    if ((e = hipMemcpyAsync(s->d_boff, s->boff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
     if (n) {
-        if ((e = hipMemcpyAsync(s->d_len, s->len.data(), n * 4, hipMemcpyHostToDevice, st)) != hipSuccess || (e = hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
+        if ((e = hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
         if (d_rc && (e = hipMemcpyAsync(d_rc, rc, n, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
         hipLaunchKernelGGL(k_seq_gather, dim3(n), dim3(256), 0, st, parent->d_seq2, parent->d_nmask, parent->d_boff, d_idx, s->d_boff, n, s->d_seq2, s->d_nmask, (const uint8_t*)d_rc, (const int32_t*)s->d_len);
         if ((e = hipGetLastError()) != hipSuccess) return fail(e);
@@ -616,27 +631,15 @@ extern "C" int telr_seqset_from_packed(telr_ctx *ctx, int32_t n, const int32_t *
     (void)hipGetLastError();
     if (!ctx || n < 0 || !out || (n > 0 && !len)) return TELR_E_ARG;
     HIPCHK(hipSetDevice(ctx->device));
-    telr_seqset *s = new telr_seqset();
-    s->ctx = ctx; s->n = n; s->boff.resize(n + 1); s->len.resize(n);
     int64_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        const int32_t L = len[i];
-        if (L < 0) { delete s; return TELR_E_ARG; }
-        s->len[i] = L; s->boff[i] = tot; tot += ((int64_t)L + 63) & ~63LL; s->total_bases += L;
-        if (L > s->max_len) s->max_len = L;
-    }
-    s->boff[n] = tot; s->padded_bases = tot;
-    if (nwords2 != tot / 16 || nwordsn != tot / 32 || (tot > 0 && (!d_seq2 || !d_nmask))) { delete s; return TELR_E_ARG; }
-    const size_t w2 = (size_t)(tot / 16) + 8, wn = (size_t)(tot / 32) + 8;
+    for (int i = 0; i < n; ++i) { if (len[i] < 0) return TELR_E_ARG; tot += ((int64_t)len[i] + 63) & ~63LL; }
+    if (nwords2 != tot / 16 || nwordsn != tot / 32 || (tot > 0 && (!d_seq2 || !d_nmask))) return TELR_E_ARG;
+    telr_seqset *s = new telr_seqset();
+    s->ctx = ctx; s->n = n; s->len.assign(len, len + n);
+    hipStream_t st = ctx->stream;
+    TRY(seqset_alloc(ctx, s, "seqset from packed words", true, st));
     auto fail = [&](hipError_t e) { ctx->err = std::string("seqset from packed words: ") + hipGetErrorString(e); telr_seqset_free(s); return e == hipErrorOutOfMemory ? TELR_E_NOMEM : TELR_E_HIP; };
-    hipError_t e; hipStream_t st = ctx->stream;
-    if ((e = hipMalloc(&s->d_seq2, w2 * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&s->d_nmask, wn * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&s->d_boff, (n + 1) * 8)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&s->d_len, (n ? n : 1) * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMemsetAsync(s->d_seq2 + (w2 - 8), 0, 32, st)) != hipSuccess || (e = hipMemsetAsync(s->d_nmask + (wn - 8), 0, 32, st)) != hipSuccess) return fail(e);
-    if ((e = hipMemcpyAsync(s->d_boff, s->boff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
-    if (n && (e = hipMemcpyAsync(s->d_len, s->len.data(), n * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
+    hipError_t e;
     if (tot) {
         if ((e = hipMemcpyAsync(s->d_seq2, d_seq2, (size_t)(tot / 16) * 4, hipMemcpyDeviceToDevice, st)) != hipSuccess) return fail(e);
         if ((e = hipMemcpyAsync(s->d_nmask, d_nmask, (size_t)(tot / 32) * 4, hipMemcpyDeviceToDevice, st)) != hipSuccess) return fail(e);
@@ -3595,3 +3598,4 @@ extern "C" int telr_write_bam(const telr_result *r, int32_t n_queries, const cha
 #include "poa.hip.h"
 #include "inscall.hip.h"
 #include "genotype.hip.h"
+#include "draft.hip.h"

@@ -57,6 +57,27 @@ def concat(seqs):
 _COMP = bytes.maketrans(b"ACGTUNacgtun", b"TGCAANtgcaan")
 
 
+# the bases as the packed form on the device holds them (telr_seqset_create): A C G T (U reads as T), either case; anything else N
+_PACKED = bytearray(b"N" * 256)
+for _c, _b in zip(b"ACGTUacgtu", b"ACGTTACGTT"):
+    _PACKED[_c] = _b
+_PACKED = bytes(_PACKED)
+
+
+def as_packed(seq):
+    """bytes -> the same bases as a sequence set on the device holds them: upper-case A C G T, anything else N"""
+    return bytes(seq).translate(_PACKED)
+
+
+def segment(reads, qid, start, n):
+    """bases [start, start + n) of read qid as bytes; reads: a list of str / bytes, or the (buffer, offsets, lengths) triple of `concat`"""
+    if isinstance(reads, tuple) and len(reads) == 3:
+        buf, off, _ = reads
+        return bytes(np.asarray(buf[int(off[qid]) + start:int(off[qid]) + start + n], dtype=np.uint8))
+    r = reads[qid]
+    return (r.encode() if isinstance(r, str) else bytes(r))[start:start + n]
+
+
 def revcomp(s):
     if isinstance(s, str):
         return s.encode().translate(_COMP)[::-1].decode()

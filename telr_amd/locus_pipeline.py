@@ -15,18 +15,25 @@ def run_loci(backend, *args, **kw):
 
 
 def run_loci_impl(backend, ref_index, ref_names, ref_seq, loci, lib_names, lib_seqs, presets="ont", ref_te_rows=None,
-             flank_len=500, gap=20, overlap=20, af_params=(100, 200, 50, 50), read_set=None, polish=None, polish_iterations=1, overlap_af=True):
+             flank_len=500, gap=20, overlap=20, af_params=(100, 200, 50, 50), read_set=None, polish=None, polish_iterations=1, overlap_af=True,
+             contig_set=None):
     """loci: list of dicts(name, contig, alt, reads).  With `read_set` (the stage-1 read SeqSet resident on the
     device) a locus gives `read_idx` (indices into it) instead of `reads`.  polish="pileup": the draft contigs are first
     polished on the device with the locus' reads (telr_assembly.polish_consensus: the polishing loop of
     TELR_assembly.py:185-262 with a pile-up consensus in the place of wtpoa-cns -- a different algorithm, hence opt-in);
     polish="poa": the same with the window partial-order consensus (spec 3.13).
+    contig_set: a SeqSet that holds the loci's contigs in this order on the device already (telr_assembly.draft_loci): the polishing
+    indexes it as it is, and without polishing S4 - S6 use it instead of packing and uploading the contigs again (None: today's behaviour).
     -> dict(annotation, liftover, summary, af[, contigs])"""
+    if contig_set is not None and (not hasattr(backend, "worker") or getattr(contig_set, "n", -1) != len(loci)):
+        raise ValueError("contig_set: an engine SeqSet with one sequence per locus")
     if polish in ("pileup", "poa") and loci:
         from . import telr_assembly
         rs = [l["read_idx"] if read_set is not None else l["reads"] for l in loci]
         pol = telr_assembly.polish_consensus(backend, [l["name"] for l in loci], [l["contig"] for l in loci], rs, presets=presets,
-                                             iterations=polish_iterations, read_set=read_set, method=polish)
+                                             iterations=polish_iterations, read_set=read_set, method=polish,
+                                             **({} if contig_set is None else {"contig_set": contig_set}))
+        contig_set = None                       # (the polished contigs are new sequences)
         loci = [dict(l, contig=c) for l, c in zip(loci, pol)]
     elif polish not in (None, "", "none"):
         raise ValueError("polish must be None, 'pileup' or 'poa'")
@@ -38,7 +45,7 @@ def run_loci_impl(backend, ref_index, ref_names, ref_seq, loci, lib_names, lib_s
     job = None
     # on the engine the contigs are packed and uploaded ONCE: S4 / S5 index that set as it is, S6 takes its forward + reverse-complement
     # target set from it on the device
-    cset = backend.seqset([l["contig"] for l in loci]) if loci and hasattr(backend, "worker") else None
+    cset = (contig_set if contig_set is not None else backend.seqset([l["contig"] for l in loci])) if loci and hasattr(backend, "worker") else None
     cwhere = {l["name"]: k for k, l in enumerate(loci)} if cset is not None else None
     if cwhere is not None and len(cwhere) != len(loci):
         cset = cwhere = None                    # (duplicate locus names: contigs[name] is the last one, the set's order would not say so)

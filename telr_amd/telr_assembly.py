@@ -14,6 +14,10 @@ read ORDER depends on PYTHONHASHSEED; here reads come out in input order (the co
 * `polish_alignments`: the aligner half of `run_wtdbg2_polishing` (:185-260): `minimap2 -t N -ax P -r2k CNS READS | samtools
 sort` followed by `samtools view -F0x900 BAM | wtpoa-cns -d CNS -i -` (:199-236).  wtpoa-cns itself is a hand-off point and
 is not built here; what it reads on stdin is.
+
+* `draft_loci`: a draft contig per call of the engine's insertion caller, cut out of one of the call's supporting reads on the device
+(`telr_draft_contigs`).  It stands where the reference runs wtdbg2 or flye on the window reads (:264-382) and is not
+an assembler, and not wtdbg2 or flye: the piece of one read is the draft that `polish_consensus` then polishes.
 """
 import os
 
@@ -62,6 +66,35 @@ def window_reads(alns, chrom_ids, loci, window=1000):
 def annotate_vcf_with_counts(loci, reads_per_locus):
     """the `.new` copy of the table: every row + the number of window reads (column 14)"""
     return [list(r) + [str(len(x))] for r, x in zip(loci, reads_per_locus)]
+
+
+def draft_loci(index, result, ic, rows, read_set, reads, chrom_ids, window=1000, opt=None):
+    """The loci `locus_pipeline.run_loci(..., read_set=read_set)` takes, one per call that has a draft: index / result as in
+    `telr_sv.call_insertions`, ic = `index.call_insertions(result)`, rows = the candidate-locus rows of those calls (one per call, in
+    call order), read_set = the SeqSet the result was mapped from, reads = the same reads on the host (a list of str / bytes, or the
+    (buffer, offsets, lengths) triple), opt an `_abi.DraftOpt`.  The backbone pieces come from `index.draft_contigs` (not an assembler:
+    one supporting read per call); `contig` is that piece sliced from `reads` (reverse-complemented on the reverse strand; A C G T, anything
+    else N, as the device set holds it), `alt` the row's ins_seq, `read_idx` the window reads (`window_reads`).
+    -> (list of dict(name, contig, alt, read_idx), the contigs' SeqSet in the same order -- `run_loci(..., contig_set=...)` --, the names
+    of the calls without a draft)"""
+    from . import telr_sv
+    from .fasta import revcomp, segment, as_packed
+    if len(rows) != len(ic.calls):
+        raise ValueError("draft_loci: one row per call")
+    drafts, cset = index.draft_contigs(result, ic, read_set, opt)
+    wr = window_reads(index.result_arrays(result).alns, chrom_ids, rows, window) if len(rows) else []
+
+    loci, skipped = [], []
+    for k, row in enumerate(rows):
+        d = drafts[k]
+        if d["sig"] < 0:
+            skipped.append(telr_sv.locus_name(row))
+            continue
+        seq = as_packed(segment(reads, int(d["qid"]), int(d["start"]), int(d["len"])))
+        if d["rc"]:
+            seq = revcomp(seq)
+        loci.append(dict(name=telr_sv.locus_name(row), contig=seq.decode(), alt=row[7], read_idx=np.asarray(wr[k], np.int32)))
+    return loci, cset, skipped
 
 
 def polish_alignments(engine, contig_names, contig_seqs, reads_by_locus, read_names=None, presets="ont", tmp_path=None):
@@ -120,7 +153,8 @@ def polish_alignments(engine, contig_names, contig_seqs, reads_by_locus, read_na
     return ["".join(mapped[k]) + "".join(unmapped[k]) for k in range(len(contig_names))], res.alns, res.cigars
 
 
-def polish_consensus(engine, contig_names, contig_seqs, reads_by_locus, presets="ont", iterations=1, min_depth=3, read_set=None, method="pileup", timings=None):
+def polish_consensus(engine, contig_names, contig_seqs, reads_by_locus, presets="ont", iterations=1, min_depth=3, read_set=None, method="pileup", timings=None,
+                     contig_set=None):
     """The polishing loop of `run_wtdbg2_polishing` (TELR_assembly.py:185-262) with the consensus made on the device: per
     iteration ONE engine call maps the reads of every locus to its draft contig (`-ax P -r2k`, as S3) and ONE pile-up pass over
     the primary records (`-F0x900`) rewrites all contigs (`telr_consensus_build`: majority vote per position, spec 3.12).
@@ -130,6 +164,8 @@ def polish_consensus(engine, contig_names, contig_seqs, reads_by_locus, presets=
     method="poa": the window partial-order consensus instead (`telr_poa_build`, spec 3.13: the reads are re-aligned to a graph of
     each 200-base window; closer to what wtpoa-cns does, still not its code).
     timings: a dict that receives the wall-clock seconds of the pass's phases (read set, index, map, consensus).
+    contig_set: a SeqSet that holds contig_seqs in this order on the device already (`draft_loci`): the first iteration indexes it as it
+    is instead of packing and uploading the strings (None: today's behaviour).
     -> list of polished contig sequences (a contig no read maps to stays as it is)."""
     if method not in ("pileup", "poa"):
         raise ValueError("method must be 'pileup' or 'poa'")
@@ -151,26 +187,35 @@ def polish_consensus(engine, contig_names, contig_seqs, reads_by_locus, presets=
         t_b = {} if timings is not None else None
         def second():
             try:
-                out[1] = _polish_part(engine.worker(), contig_seqs[cut:], reads_by_locus[cut:], presets, iterations, min_depth, read_set, method, t_b)
+                out[1] = _polish_part(engine.worker(), contig_seqs[cut:], reads_by_locus[cut:], presets, iterations, min_depth, read_set, method, t_b, second_set)
             except Exception as e:            # no room beside the first half (or any other failure of the second context): that half in turn, below
                 err[0] = e
+        first_set = second_set = None
+        if contig_set is not None:                      # (both gathers on this context, before the second one starts: contexts are not re-entrant)
+            first_set = contig_set.subset(np.arange(cut, dtype=np.int32), eng=engine)
+            second_set = contig_set.subset(np.arange(cut, len(reads_by_locus), dtype=np.int32), eng=engine)
         th = threading.Thread(target=second); th.start()
         try:
-            out[0] = _polish_part(engine, contig_seqs[:cut], reads_by_locus[:cut], presets, iterations, min_depth, read_set, method, timings)
+            try:
+                out[0] = _polish_part(engine, contig_seqs[:cut], reads_by_locus[:cut], presets, iterations, min_depth, read_set, method, timings, first_set)
+            finally:
+                th.join()
+            if err[0] is not None:
+                if "out of device memory" not in str(err[0]) and "out of memory" not in str(err[0]):
+                    raise err[0]
+                engine.worker().release_scratch()
+                out[1] = _polish_part(engine, contig_seqs[cut:], reads_by_locus[cut:], presets, iterations, min_depth, read_set, method, timings, second_set)
+            elif timings is not None:
+                timings["second_half_s"] = sum(t_b.values())
         finally:
-            th.join()
-        if err[0] is not None:
-            if "out of device memory" not in str(err[0]) and "out of memory" not in str(err[0]):
-                raise err[0]
-            engine.worker().release_scratch()
-            out[1] = _polish_part(engine, contig_seqs[cut:], reads_by_locus[cut:], presets, iterations, min_depth, read_set, method, timings)
-        elif timings is not None:
-            timings["second_half_s"] = sum(t_b.values())
+            for x in (first_set, second_set):
+                if x is not None:
+                    x.free()
         return out[0] + out[1]
-    return _polish_part(engine, contig_seqs, reads_by_locus, presets, iterations, min_depth, read_set, method, timings)
+    return _polish_part(engine, contig_seqs, reads_by_locus, presets, iterations, min_depth, read_set, method, timings, contig_set)
 
 
-def _polish_part(engine, contig_seqs, reads_by_locus, presets, iterations, min_depth, read_set, method, timings):
+def _polish_part(engine, contig_seqs, reads_by_locus, presets, iterations, min_depth, read_set, method, timings, contig_set=None):
     """polish_consensus for the loci given, one engine call per iteration on `engine`"""
     import time
     def _t(key, t0):
@@ -197,8 +242,8 @@ def _polish_part(engine, contig_seqs, reads_by_locus, presets, iterations, min_d
     else:
         qset = engine.seqset([r for rs in reads_by_locus for r in rs])
     t0 = _t("read_set_s", t0)
-    for _ in range(max(1, int(iterations))):
-        ix = engine.index(contigs, io)
+    for it in range(max(1, int(iterations))):
+        ix = engine.index(contig_set if it == 0 and contig_set is not None else contigs, io)
         t0 = _t("index_s", t0)
         r = ix.map_raw(qset, mo, qtarget=qt)
         t0 = _t("map_s", t0)

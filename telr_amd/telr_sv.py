@@ -49,24 +49,18 @@ def call_insertions(index, result, tnames, qnames, reads, opt=None, sample="telr
     import numpy as np
     from .aligner import _np_from
     from ._abi import ALN_DTYPE, F_REV
+    from .fasta import segment
     ic = index.call_insertions(result, opt)
     L = index.eng.L
     flags = _np_from(L.telr_result_alns(result), L.telr_result_count(result), ALN_DTYPE)["flags"] if len(ic.calls) else None
     gt = None if genotype is None or genotype is False else index.genotype_insertions(result, ic, None if genotype is True else genotype).gt
-
-    def segment(qid, s, n):
-        if isinstance(reads, tuple) and len(reads) == 3:
-            buf, off, _ = reads
-            return bytes(np.asarray(buf[int(off[qid]) + s:int(off[qid]) + s + n], dtype=np.uint8))
-        r = reads[qid]
-        return (r.encode() if isinstance(r, str) else bytes(r))[s:s + n]
 
     rows = []
     for k, c in enumerate(ic.calls):
         seq = b"N"
         if c["rep"] >= 0:
             s = ic.sigs[c["rep"]]
-            seq = segment(int(s["qid"]), int(s["seg_start"]), int(s["seg_len"])) or b"N"
+            seq = segment(reads, int(s["qid"]), int(s["seg_start"]), int(s["seg_len"])) or b"N"
             if int(flags[s["rec"]]) & F_REV:
                 seq = seq.translate(_RC)[::-1]
         names = ",".join(qnames[q] for q in ic.reads_of(k).tolist())

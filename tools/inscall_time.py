@@ -1,7 +1,7 @@
 """Times telr_call_insertions on a stage-1 result of BASELINE configs[2] shape (bench.py's data set: --coverage / --genome-scale
 make it smaller), once with the result's resident CIGAR copy (TELR_MF_KEEP_CIGARS) and once with the CIGAR array uploaded, and the
 plain-Python restatement (tests/inscall_ref.py) on a sample of the reads, scaled to the whole set; then Index.genotype_insertions
-(telr_genotype_insertions) on the calls of that result, the same two ways.  Writes profiles/inscall_time.json.
+(telr_genotype_insertions) on the calls of that result, the same two ways, and Index.draft_contigs (telr_draft_contigs) on the same calls.  Writes profiles/inscall_time.json.
 
     python tools/inscall_time.py [--coverage 30] [--genome-scale 1.0] [--repeat 5] [--sample-reads 2000] [--out profiles/inscall_time.json]
 """
@@ -34,13 +34,14 @@ def main():
     import inscall_ref as ref
     from telr_amd.aligner import Engine
     from telr_amd.presets import preset
-    from telr_amd._abi import InsOpt, GenoOpt, MF_KEEP_CIGARS
+    from telr_amd._abi import InsOpt, GenoOpt, DraftOpt, MF_KEEP_CIGARS
     eng = Engine(0)
     io, mo = preset(cfg["preset"])
     ix = eng.index([bytes(r).decode() for r in D["ref"]], io)
     qs = eng.seqset(D["reads"])
     opt = InsOpt.default(min_support=a.min_support)
     gopt = GenoOpt.default()
+    dopt = DraftOpt.default()
 
     def timed(r):
         ts = []
@@ -58,18 +59,31 @@ def main():
             ts.append((time.perf_counter() - t0) * 1e3)
         return ig, ts[1:]
 
+    def timed_draft(r, ic):
+        ts = []
+        for _ in range(a.repeat + 1):
+            t0 = time.perf_counter()
+            d, s = ix.draft_contigs(r, ic, qs, dopt)
+            ts.append((time.perf_counter() - t0) * 1e3)
+            out = d, int(s.len.sum())
+            s.free()
+        return out, ts[1:]
+
     mk = mo.copy(); mk.flags |= MF_KEEP_CIGARS
     r = ix.map_raw(qs, mk)
     res = ix.result_arrays(r)
     ic_res, ms_res = timed(r)
     ig_res, gms_res = timed_geno(r, ic_res)
+    (dr_res, dr_bases), dms_res = timed_draft(r, ic_res)
     ix.free_raw(r)
     r = ix.map_raw(qs, mo)
     ic_up, ms_up = timed(r)
     ig_up, gms_up = timed_geno(r, ic_up)
+    (dr_up, _), dms_up = timed_draft(r, ic_up)
     ix.free_raw(r)
     assert ic_res.sigs.tobytes() == ic_up.sigs.tobytes() and ic_res.calls.tobytes() == ic_up.calls.tobytes()
     assert ig_res.gt.tobytes() == ig_up.gt.tobytes() and ig_res.ref_reads.tobytes() == ig_up.ref_reads.tobytes() and ig_res.ambig_reads.tobytes() == ig_up.ambig_reads.tobytes()
+    assert dr_res.tobytes() == dr_up.tobytes()
     # the plain restatement on the records of the first --sample-reads reads
     alns = res.alns[res.alns["qid"] < a.sample_reads]
     t0 = time.perf_counter()
@@ -88,11 +102,16 @@ def main():
         "genotype_gt_counts": [int((ig_res.gt["gt"] == v).sum()) for v in (0, 1, 2)],
         "genotype_insertions_ms_resident_cigars": {"min": min(gms_res), "median": float(np.median(gms_res)), "all": gms_res},
         "genotype_insertions_ms_uploaded_cigars": {"min": min(gms_up), "median": float(np.median(gms_up)), "all": gms_up},
+        "draft_options": {k: getattr(dopt, k) for k, _ in DraftOpt._fields_},
+        "draft_calls_with_a_draft": int((dr_res["sig"] >= 0).sum()), "draft_bases": dr_bases,
+        "draft_contigs_ms_resident_cigars": {"min": min(dms_res), "median": float(np.median(dms_res)), "all": dms_res},
+        "draft_contigs_ms_uploaded_cigars": {"min": min(dms_up), "median": float(np.median(dms_up)), "all": dms_up},
         "python_restatement": {"sample_reads": a.sample_reads, "sample_cigar_words": ops_sample, "seconds": py_s,
                                "scaled_to_all_records_seconds": py_s * ops_all / max(1, ops_sample),
                                "note": "tests/inscall_ref.py, one CPU thread; scaled by CIGAR words"},
         "timing": "wall clock of Index.call_insertions (validation, record upload, kernels, the signatures and calls copied back) and of Index.genotype_insertions "
-                  "(validation, uploads, kernels, the genotypes and read lists copied back), %d repeats after one untimed call each" % a.repeat,
+                  "(validation, uploads, kernels, the genotypes and read lists copied back) and of Index.draft_contigs (validation, uploads, kernels, the draft "
+                  "records copied back, the set left on the device), %d repeats after one untimed call each" % a.repeat,
     }
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
@@ -100,7 +119,8 @@ def main():
         fh.write("\n")
     print(json.dumps({k: out[k] for k in ("records", "cigar_words", "signatures", "calls", "call_insertions_ms_resident_cigars",
                                           "call_insertions_ms_uploaded_cigars", "genotype_insertions_ms_resident_cigars",
-                                          "genotype_insertions_ms_uploaded_cigars", "python_restatement")}))
+                                          "genotype_insertions_ms_uploaded_cigars", "draft_contigs_ms_resident_cigars",
+                                          "draft_contigs_ms_uploaded_cigars", "python_restatement")}))
 
 
 if __name__ == "__main__":
