@@ -594,6 +594,13 @@ int  telr_last_dp_classes(const telr_ctx *ctx, int64_t *out /* [TELR_N_DPCLS*4] 
 /* what defines each DP class (no device needed): widest band in diagonals, lanes per problem, registers per lane, dwords per
  * trace-back row, trace-back interleaved across the problems of a wave (0/1), trace-back in tiles of four rows (0/1) */
 int  telr_debug_dp_class_table(int32_t *out /* [TELR_N_DPCLS][6] */);
+/* how telr_map would cut reads of these lengths into ranges and run them (no device needed; TELR_BATCH_MBP / TELR_BATCH_KBP /
+ * TELR_PIPELINE are read as telr_map reads them).  max_len: the longest read; per_base: anchors per read base (0: unknown);
+ * has_qtarget / vote: the call has per-query targets / sub-read voting applies to it; debug, pipe_nomem: the context's.
+ * out[0] mode (0 one range at a time, 1 per-query targets: one range, else the ranges in turn, 2 two ranges in flight),
+ * out[1] bases per range at most, out[2] number of ranges; range_end (nullable, n entries suffice): the end of every range */
+int  telr_debug_map_plan(const int32_t *len, int32_t n, int32_t max_len, double per_base, int has_qtarget, int vote, int debug,
+                         int pipe_nomem, int64_t *out /* [3] */, int32_t *range_end);
 
 #ifdef __cplusplus
 }

@@ -151,6 +151,7 @@ def lib():
     L.telr_debug_mid_occ.restype = i32; L.telr_debug_mid_occ.argtypes = [vp, C.POINTER(MapOpt)]
     L.telr_debug_dp_limits.restype = C.c_int; L.telr_debug_dp_limits.argtypes = [C.POINTER(MapOpt), vp]
     L.telr_debug_dp_class_table.restype = C.c_int; L.telr_debug_dp_class_table.argtypes = [vp]
+    L.telr_debug_map_plan.restype = C.c_int; L.telr_debug_map_plan.argtypes = [vp, i32, i32, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.telr_debug_dp.restype = C.c_int; L.telr_debug_dp.argtypes = [vp, vp, vp, C.POINTER(MapOpt), vp, i32, vp, vp, vp, i64]
     L.telr_debug_chain.restype = C.c_int; L.telr_debug_chain.argtypes = [vp, i32, vp, vp, C.POINTER(MapOpt), vp, vp]
     L.telr_debug_backtrack.restype = C.c_int

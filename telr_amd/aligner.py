@@ -120,6 +120,20 @@ class Engine:
             raise _lib.TelrError("telr_debug_dp_class_table: %d" % rc, rc)
         return a
 
+    MAP_PLAN_MODES = ("serial", "in_turn", "two_in_flight")
+
+    @staticmethod
+    def map_plan(lengths, per_base=0.0, qtarget=False, vote=False, debug=0, pipe_nomem=False):
+        """-> (mode, batch_bases, range ends): how telr_map would cut reads of these lengths into ranges and run them, under the
+        TELR_BATCH_MBP / TELR_BATCH_KBP / TELR_PIPELINE of the moment (no device needed).  mode: one of MAP_PLAN_MODES"""
+        a = np.ascontiguousarray(lengths, dtype=np.int32)
+        out = np.zeros(3, np.int64); ends = np.zeros(max(len(a), 1), np.int32)
+        rc = _lib.lib().telr_debug_map_plan(a.ctypes.data, len(a), int(a.max()) if len(a) else 0, float(per_base), int(bool(qtarget)),
+                                            int(bool(vote)), int(debug), int(bool(pipe_nomem)), out.ctypes.data, ends.ctypes.data)
+        if rc != 0:
+            raise _lib.TelrError("telr_debug_map_plan: %d" % rc, rc)
+        return Engine.MAP_PLAN_MODES[int(out[0])], int(out[1]), [int(e) for e in ends[:int(out[2])]]
+
     def debug_dp(self, queries, targets, mo, probs):
         """one DP pass (the map path's dp_pass) over a list of problems -- test tap.  probs: (np, 12) int32 rows
         {qid, q_off, tid, t_off, m, n, dlo, dhi, kind, qstep, tstep, qcomp}; queries / targets: SeqSet.

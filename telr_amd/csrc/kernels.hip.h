@@ -1249,10 +1249,10 @@ __global__ void __launch_bounds__(64 * VOTE_WAVES) k_seed_vote(SeedArgs A, VoteO
 #undef VOTE_PIN
 // staging -> dense keys (only ahead of the library sort: the LDS sort of segsort.hip.h reads the staging pieces in place)
 __global__ void __launch_bounds__(256) k_vote_compact(const uint64_t *__restrict__ stage, const int64_t *__restrict__ q_soff, const int32_t *__restrict__ q_aoff, int32_t nq,
-                                                      uint64_t *__restrict__ keys, const int32_t *__restrict__ list)
+                                                      uint64_t *__restrict__ keys)
 {
     if ((int)blockIdx.x >= nq) return;
-    const int q = list ? list[blockIdx.x] : (int)blockIdx.x;        // list: only these queries (the over-size ones ahead of the library sort)
+    const int q = (int)blockIdx.x;
     const int64_t s0 = q_soff[q]; const int a0 = q_aoff[q], n = q_aoff[q + 1] - a0;
     for (int i = threadIdx.x; i < n; i += 256) {
         const uint64_t k = stage[s0 + i];

@@ -27,6 +27,7 @@
 #include <vector>
 #include "../../include/telr_hip.h"
 #include "kernels.hip.h"
+#include "range_plan.h"
 #define TELR_HAVE_SEED_ARGS 1
 #include "segsort.hip.h"
 #include "radix.hip.h"
@@ -98,8 +99,7 @@ struct telr_ctx {
 //                            after all forward kernels), no_avx2 (scalar host packer), fasta_copy (no in-place use of the mapped file),
 //                            bam_no_populate, bam_no_twin (BAM writer: no pre-faulted mapping / CIGARs uploaded again), scan_lib /
 //                            index_sort_lib (rocPRIM's scan / its sort of the index build), chain_lazy, chain_no_mw (the lazy far
-//                            look-back everywhere / no second kernel for the long dense runs), over_routed (only the over-size queries of a
-//                            range take the two-step form)
+//                            look-back everywhere / no second kernel for the long dense runs)
 //   TELR_TRACE=tok[,tok...]  stderr traces: host (wall-clock marks of every batch's host side), mem (device memory at the points
 //                            where the engine runs out of it or gives it back), fasta (phases of telr_fasta_load)
 // The others are operational: TELR_DEBUG, TELR_HOST_THREADS, TELR_PACK_THREADS, TELR_BATCH_MBP / TELR_BATCH_KBP (range size),
@@ -171,12 +171,11 @@ template <typename T> static int ctx_buf_t(telr_ctx *ctx, const char *name, size
 // Segmented sort of 64-bit keys (segsort.hip.h): every segment of at most SEGSORT_CAP keys is sorted by ONE workgroup in
 // LDS; `any_over` (known to the caller from the anchor counts) sends the larger ones through rocPRIM afterwards.
 // TELR_AB=sort64 keeps the library sort for every segment (A/B).  out[beg[s] .. end[s]) <- sorted in[...]; src_beg (nullable)
-// gives the segments' places in `in` when they differ from their places in `out`.  fb_in (round 6): where the OVER-SIZE segments' keys lie
-// (at their places in `out`) when the producer makes the others on the spot or reads them through src_beg -- only those queries take the
-// two-step form then, not the whole range.
+// gives the segments' places in `in` when they differ from their places in `out` (the library's sort reads them at their places in `out`:
+// not with over-size segments).
 template <class P = LoadKeys>
 static int seg_sort_u64(telr_ctx *ctx, const char *tag, const uint64_t *in, uint64_t *out, const int32_t *beg, const int32_t *end, const int64_t *src_beg,
-                        const int32_t *order, int nseg, size_t nkeys, bool any_over, hipStream_t st, P prod = P(), const uint64_t *fb_in = nullptr, hipEvent_t fb_ready = nullptr)
+                        const int32_t *order, int nseg, size_t nkeys, bool any_over, hipStream_t st, P prod = P())
 {
     static const bool lib_sort = ab_on("sort64");
     if (nseg <= 0 || nkeys == 0) return TELR_OK;
@@ -189,7 +188,7 @@ static int seg_sort_u64(telr_ctx *ctx, const char *tag, const uint64_t *in, uint
         HIPCHK(rocprim::segmented_radix_sort_keys(tmp, tb, in, out, (unsigned)nkeys, (unsigned)nseg, beg, end, 0, 64, st));
         return TELR_OK;
     }
-    if (src_beg && any_over && !fb_in) return TELR_E_ARG;
+    if (src_beg && any_over) return TELR_E_ARG;
     // the opt-in to more than 64 KiB of dynamic LDS belongs to the DEVICE's function object: one bit per device (and per producer
     // type: a function-local static of the template instance); setting it twice from two host threads is harmless
     static std::atomic<uint64_t> attr_dev{0};
@@ -212,12 +211,10 @@ static int seg_sort_u64(telr_ctx *ctx, const char *tag, const uint64_t *in, uint
     hipStream_t fbs = any_over ? ctx->side[1] : nullptr;
     if (any_over) {
         HIPCHK(hipEventRecord(ctx->ev_side[1], st)); HIPCHK(hipStreamWaitEvent(fbs, ctx->ev_side[1], 0));
-        if (fb_ready) HIPCHK(hipStreamWaitEvent(fbs, fb_ready, 0));        // the over-size queries' keys are written on another side stream
-        const uint64_t *fin = fb_in ? fb_in : in;
         size_t tb = 0;
-        HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, tb, fin, out, (unsigned)nkeys, (unsigned)nseg, A.fb_beg, A.fb_end, 0, 64, fbs));
+        HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, tb, in, out, (unsigned)nkeys, (unsigned)nseg, A.fb_beg, A.fb_end, 0, 64, fbs));
         void *tmp; TRY(ctx_buf(ctx, "rp_tmp_fb", tb, &tmp));
-        HIPCHK(rocprim::segmented_radix_sort_keys(tmp, tb, fin, out, (unsigned)nkeys, (unsigned)nseg, A.fb_beg, A.fb_end, 0, 64, fbs));
+        HIPCHK(rocprim::segmented_radix_sort_keys(tmp, tb, in, out, (unsigned)nkeys, (unsigned)nseg, A.fb_beg, A.fb_end, 0, 64, fbs));
         HIPCHK(hipEventRecord(ctx->ev_side[1], fbs));
     }
     const int ncu = ctx->n_cu > 0 ? ctx->n_cu : 256;
@@ -1935,94 +1932,113 @@ static void chain_row(const ChainRec &r, int32_t qid, const uint32_t *goff, int 
     v[6] = A_G(r.a1) - go + 1; v[7] = A_Q(r.a0) - A_SPAN(r.a0) + 1; v[8] = A_Q(r.a1) + 1;
 }
 
-static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs, const int32_t *d_qtarget, int32_t q0, int32_t q1,
-                     const telr_map_opt *mo, OccCut occ, telr_result *R, RangeTurn *gate = nullptr)
-{
-    const int32_t mid_occ = occ.mid_occ;
-    const int nq = q1 - q0, k = ix->io.k, w = ix->io.w;
-    const telr_seqset *tg = ix->targets;
-    hipStream_t st = ctx->stream;
-    HostTrace ht("batch");
+// ---- the stages of map_batch that are not a dispatch of their own above: each takes its inputs as parameters and leaves its outputs
+//      in a small struct; the stage timers, the trace marks and the counters stay with map_batch ------------------------------------
 
-    // ---- sketch -------------------------------------------------------------------------
-    // queries in descending length order for the one-block-per-query kernels (their tail is the longest read): sorted by
-    // a helper thread while the sketch kernels run, uploaded from pinned memory before the seeding stage
-    int32_t *d_qorder, *h_ord;
-    TRY(ctx_hbuf_t(ctx, "h_qorder", (size_t)nq + 1, &h_ord));
-    TRY(ctx_buf_t(ctx, "q_order", (size_t)nq + 1, &d_qorder));
-    std::thread ord_thread([&]() {
+// queries in descending length order for the one-block-per-query kernels (their tail is the longest read): sorted by
+// a helper thread while the sketch kernels run, uploaded from pinned memory before the seeding stage
+struct QueryOrder {
+    int32_t *d = nullptr, *h = nullptr; std::thread t;
+    ~QueryOrder() { if (t.joinable()) t.join(); }       // error paths return early
+};
+static int query_order_start(telr_ctx *ctx, const telr_seqset *qs, int32_t q0, int nq, QueryOrder *o)
+{
+    TRY(ctx_hbuf_t(ctx, "h_qorder", (size_t)nq + 1, &o->h));
+    TRY(ctx_buf_t(ctx, "q_order", (size_t)nq + 1, &o->d));
+    int32_t *h_ord = o->h;
+    o->t = std::thread([=]() {
         for (int i = 0; i < nq; ++i) h_ord[i] = i;
         std::stable_sort(h_ord, h_ord + nq, [&](int32_t x, int32_t y) { return qs->len[q0 + x] > qs->len[q0 + y]; });
     });
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } ord_join{ord_thread};     // error paths return early
-    StageTimer t_sk(ctx, ST_SKETCH, true);
+    return TELR_OK;
+}
+static int query_order_upload(telr_ctx *ctx, hipStream_t st, int nq, QueryOrder *o)
+{
+    o->t.join();
+    HIPCHK(hipMemcpyAsync(o->d, o->h, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    return TELR_OK;
+}
+
+// the minimizers of the queries and every query's offset among them (= tile_off[first tile of the query])
+struct SketchOut { uint64_t *d_mx; uint32_t *d_my; int32_t *d_toff, *d_first, *d_qmz; int32_t nmz; bool mz_staged; };
+static int sketch_stage(telr_ctx *ctx, hipStream_t st, const telr_index *ix, const telr_seqset *qs, int32_t q0, int32_t q1, bool vote, SketchOut *o)
+{
+    const int nq = q1 - q0, k = ix->io.k, w = ix->io.w;
     TileList &T = ctx_tiles(ctx);
-    uint64_t *d_mx; uint32_t *d_my; int32_t *d_toff; int32_t nmz = 0;
+    o->nmz = 0;
     // the seeding kernels read the sketch kernel's staging arrays in place (no compaction copy); TELR_AB=mz_compact for A/B
+    // (the vote kernel reads the compacted minimizer arrays)
     static const bool mz_compact_env = ab_on("mz_compact");
-    // sub-read voting (spec 3.10) applies to all-vs-all calls only; its kernel reads the compacted minimizer arrays
-    const bool vote = mo->vote_len > 0 && !d_qtarget && !(mo->flags & TELR_MF_PER_TARGET);
-    const bool mz_staged = !ix->io.is_hpc && !mz_compact_env && !vote;
+    o->mz_staged = !ix->io.is_hpc && !mz_compact_env && !vote;
     if (ix->io.is_hpc) {
         SketchHpcArgs H; std::vector<int32_t> nrun;
         TRY(build_hpc(ctx, qs, q0, q1, "qh_", &H, &nrun));
         make_tiles_f(q0, q1, q0, [&](int32_t q) { return nrun[q - q0] - k + 1; }, T);
-        TRY(run_sketch(ctx, qs, T, k, w, nullptr, "q_", &d_mx, &d_my, &d_toff, &nmz, &H));
+        TRY(run_sketch(ctx, qs, T, k, w, nullptr, "q_", &o->d_mx, &o->d_my, &o->d_toff, &o->nmz, &H));
     } else {
         make_tiles(qs, q0, q1, k, T);
-        TRY(run_sketch(ctx, qs, T, k, w, nullptr, "q_", &d_mx, &d_my, &d_toff, &nmz, nullptr, mz_staged));
+        TRY(run_sketch(ctx, qs, T, k, w, nullptr, "q_", &o->d_mx, &o->d_my, &o->d_toff, &o->nmz, nullptr, o->mz_staged));
     }
-    // per-query minimizer offsets = tile_off[first tile of the query]
-    int32_t *d_first, *d_qmz;
-    TRY(ctx_buf_t(ctx, "q_first", (size_t)nq + 1, &d_first));
-    TRY(ctx_buf_t(ctx, "q_mzoff", (size_t)nq + 1, &d_qmz));
-    HIPCHK(hipMemcpyAsync(d_first, T.first.data(), (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_first + nq, &T.n, 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_gather_i32, dim3((nq + 256) / 256), dim3(256), 0, st, d_toff, d_first, nq, nmz, d_qmz);
+    TRY(ctx_buf_t(ctx, "q_first", (size_t)nq + 1, &o->d_first));
+    TRY(ctx_buf_t(ctx, "q_mzoff", (size_t)nq + 1, &o->d_qmz));
+    HIPCHK(hipMemcpyAsync(o->d_first, T.first.data(), (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(o->d_first + nq, &T.n, 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_gather_i32, dim3((nq + 256) / 256), dim3(256), 0, st, o->d_toff, o->d_first, nq, o->nmz, o->d_qmz);
     HIPCHK(hipGetLastError());
-    t_sk.stop(); ht.mark("sketch issued");
+    return TELR_OK;
+}
 
-    ord_thread.join();
-    HIPCHK(hipMemcpyAsync(d_qorder, h_ord, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-
-    // ---- seeding --------------------------------------------------------------------------
-    StageTimer t_sd(ctx, ST_SEED, true);
+// Seeding: the per-query anchor counts and offsets, and the anchor keys where the form of the range keeps them in memory.
+//   fused (the default)   the keys are MADE inside the sort (SeedProducer: the seeding routine writes a query's keys straight into the
+//                         sorting workgroup's LDS), so unsorted keys never exist in HBM
+//   vote_in_place         sub-read voting: the LDS sort reads the survivors from the staging pieces in place
+//   two-step              keys to memory, then the sort: TELR_AB=seed_unfused / sort64 (A/B), and every range that holds a query above
+//                         the LDS limit (its library sort reads the keys from memory; the round-5 rule: the range as a whole)
+struct SeedOut {
+    SeedArgs S; bool fused, vote_in_place;
+    uint64_t *d_keys, *d_skeys, *d_stage; int64_t *d_qsoff; int32_t *d_qaoff, *d_overlist;
+    int32_t na, n_over;                  // anchors of the range; its queries with more anchors than one workgroup sorts in LDS (d_overlist)
+};
+static int seed_stage(telr_ctx *ctx, hipStream_t st, const telr_index *ix, const telr_seqset *qs, const int32_t *d_qtarget, int32_t q0, int nq,
+                      const telr_map_opt *mo, OccCut occ, bool vote, const SketchOut &sk, const int32_t *d_qorder, SeedOut *o)
+{
+    const telr_seqset *tg = ix->targets;
+    const int k = ix->io.k, nmz = sk.nmz;
     IndexView I; I.ent_hash = ix->d_ent_hash; I.ent_off = ix->d_ent_off; I.pos = ix->d_pos; I.bstart = nullptr; I.goff = ix->d_goff;
-    I.tlen = tg->d_len; I.n_ent = ix->n_ent; I.shift = ix->shift; I.k = k; I.w = w;
+    I.tlen = tg->d_len; I.n_ent = ix->n_ent; I.shift = ix->shift; I.k = k; I.w = ix->io.w;
     I.ht = ix->d_ht; I.ht_shift = ix->ht_shift; I.ht_mask = ix->ht_mask; I.ht_home = ix->d_ht_home;
-    int32_t *d_mcnt, *d_maoff, *d_qaoff;
-    int32_t *d_ment, *d_mn;
+    int32_t *d_mcnt, *d_maoff, *d_qaoff, *d_ment, *d_mn, *d_qcnt;
     TRY(ctx_buf_t(ctx, "mz_ent", (size_t)nmz + 1, &d_ment));
     TRY(ctx_buf_t(ctx, "mz_n", (size_t)nmz + 1, &d_mn));
     TRY(ctx_buf_t(ctx, "mz_cnt", (size_t)nmz + 1, &d_mcnt));
     TRY(ctx_buf_t(ctx, "mz_aoff", (size_t)nmz + 1, &d_maoff));
     TRY(ctx_buf_t(ctx, "q_aoff", (size_t)nq + 1, &d_qaoff));
-    SeedArgs S; S.I = I; S.mz_x = d_mx; S.mz_y = d_my; S.q_mzoff = d_qmz; S.qlen = qs->d_len + q0; S.qtarget = d_qtarget ? d_qtarget + q0 : nullptr;
-    S.mid_occ = mid_occ; S.tmid = occ.d_tmid; S.per_target = (mo->flags & TELR_MF_PER_TARGET) ? 1 : 0; S.n_targets = tg->n; S.mz_cnt = d_mcnt; S.mz_ent = d_ment; S.mz_n = d_mn; S.mz_aoff = nullptr; S.q_cnt = nullptr; S.q_aoff = nullptr; S.lds_keys = nullptr; S.keys = nullptr; S.q_order = d_qorder;
-    S.tile_off = mz_staged ? d_toff : nullptr; S.q_tile0 = mz_staged ? d_first : nullptr;
-    // TELR_MF_SEED_RESCUE applies to the calls the pooled cut-off applies to: not to TELR_MF_PER_TARGET, and not to a query with a target of its own
-    S.rescue = (mo->flags & TELR_MF_SEED_RESCUE) && !(mo->flags & TELR_MF_PER_TARGET) ? 1 : 0;
-    VoteOpt VO; VO.len = mo->vote_len; VO.shift = mo->vote_bin_shift; VO.vmin = mo->vote_min; VO.frac_q8 = mo->vote_frac_q8;
-    VoteArgs VA; memset(&VA, 0, sizeof(VA));
     // the per-query anchor counts: from the seeding kernel (which also leaves every minimizer's offset inside its query), or from the
     // vote kernel when the sub-reads vote (it appends a query's survivors to its piece of a staging array; k_vote_compact moves them to
     // the scanned offsets)
-    int32_t *d_qcnt;
     TRY(ctx_buf_t(ctx, "q_cnt", (size_t)nq + 2, &d_qcnt));
-    S.q_cnt = d_qcnt; S.mz_aoff = d_maoff; S.q_aoff = d_qaoff;
+    SeedArgs &S = o->S;
+    S.I = I; S.mz_x = sk.d_mx; S.mz_y = sk.d_my; S.q_mzoff = sk.d_qmz; S.qlen = qs->d_len + q0; S.qtarget = d_qtarget ? d_qtarget + q0 : nullptr;
+    S.mid_occ = occ.mid_occ; S.tmid = occ.d_tmid; S.per_target = (mo->flags & TELR_MF_PER_TARGET) ? 1 : 0; S.n_targets = tg->n;
+    S.mz_cnt = d_mcnt; S.mz_ent = d_ment; S.mz_n = d_mn; S.mz_aoff = d_maoff; S.q_cnt = d_qcnt; S.q_aoff = d_qaoff; S.lds_keys = nullptr; S.keys = nullptr; S.q_order = d_qorder;
+    S.tile_off = sk.mz_staged ? sk.d_toff : nullptr; S.q_tile0 = sk.mz_staged ? sk.d_first : nullptr;
+    // TELR_MF_SEED_RESCUE applies to the calls the pooled cut-off applies to: not to TELR_MF_PER_TARGET, and not to a query with a target of its own
+    S.rescue = (mo->flags & TELR_MF_SEED_RESCUE) && !(mo->flags & TELR_MF_PER_TARGET) ? 1 : 0;
     int64_t *d_qsoff = nullptr; uint64_t *d_stage = nullptr;
     int64_t *d_na64; TRY(ctx_buf_t(ctx, "seed_na64", 2, &d_na64));
     int32_t *d_nover = (int32_t*)(d_na64 + 1);
     if (vote) {
+        VoteOpt VO; VO.len = mo->vote_len; VO.shift = mo->vote_bin_shift; VO.vmin = mo->vote_min; VO.frac_q8 = mo->vote_frac_q8;
+        VoteArgs VA; memset(&VA, 0, sizeof(VA));
         int64_t *d_qhits;
         TRY(ctx_buf_t(ctx, "vote_qhits", (size_t)nq + 2, &d_qhits)); TRY(ctx_buf_t(ctx, "vote_qsoff", (size_t)nq + 2, &d_qsoff));
         if (nmz) {
             static const bool always_filter = ab_on("vote_filter");
-            if (k <= 13 && !always_filter) hipLaunchKernelGGL(k_vote_lookup<false>, dim3((unsigned)((nmz + 255) / 256)), dim3(256), 0, st, I, d_mx, nmz, mid_occ, d_ment, d_mn, S.rescue);
-            else hipLaunchKernelGGL(k_vote_lookup<true>, dim3((unsigned)((nmz + 255) / 256)), dim3(256), 0, st, I, d_mx, nmz, mid_occ, d_ment, d_mn, S.rescue);
+            if (k <= 13 && !always_filter) hipLaunchKernelGGL(k_vote_lookup<false>, dim3((unsigned)((nmz + 255) / 256)), dim3(256), 0, st, I, sk.d_mx, nmz, occ.mid_occ, d_ment, d_mn, S.rescue);
+            else hipLaunchKernelGGL(k_vote_lookup<true>, dim3((unsigned)((nmz + 255) / 256)), dim3(256), 0, st, I, sk.d_mx, nmz, occ.mid_occ, d_ment, d_mn, S.rescue);
             if (S.rescue) hipLaunchKernelGGL(k_vote_rescue, dim3(nq), dim3(256), 0, st, S);
         }
-        hipLaunchKernelGGL(k_vote_qhits, dim3(nq + 1), dim3(64), 0, st, d_qmz, d_mn, nq, d_qhits);
+        hipLaunchKernelGGL(k_vote_qhits, dim3(nq + 1), dim3(64), 0, st, sk.d_qmz, d_mn, nq, d_qhits);
         TRY((dev_qscan<int64_t, int64_t>(ctx, d_qhits, nq, d_qsoff, nullptr, 0, nullptr, nullptr)));
         HIPCHK(hipGetLastError());
         int64_t nhits = 0;
@@ -2031,16 +2047,15 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
         TRY(ctx_buf_t(ctx, "vote_stage", (size_t)nhits + 1, &d_stage));
         VA.q_soff = d_qsoff; VA.stage = d_stage; VA.q_cnt = d_qcnt;
         // queries whose hits fit 16-bit vote counters (nearly all) with the half-size table, the others with 32-bit counters
-        const int64_t lim16 = 65535;
-        hipLaunchKernelGGL(k_seed_vote<true>, dim3(nq), dim3(64 * VOTE_WAVES), 0, st, S, VO, VA, std::min<int64_t>(lim16, 65535));
-        hipLaunchKernelGGL(k_seed_vote<false>, dim3(nq), dim3(64 * VOTE_WAVES), 0, st, S, VO, VA, std::min<int64_t>(lim16, 65535));
+        hipLaunchKernelGGL(k_seed_vote<true>, dim3(nq), dim3(64 * VOTE_WAVES), 0, st, S, VO, VA, (int64_t)65535);
+        hipLaunchKernelGGL(k_seed_vote<false>, dim3(nq), dim3(64 * VOTE_WAVES), 0, st, S, VO, VA, (int64_t)65535);
     } else hipLaunchKernelGGL(k_seed<0>, dim3(nq), dim3(256), 0, st, S);
     HIPCHK(hipGetLastError());
     // per-query anchor offsets (ONE workgroup: k_qscan), the anchor total in 64 bits -- the anchors of a batch are addressed with int32
     // offsets, a batch with 2^31 anchors or more is handed back to the caller, which halves it -- and how many queries hold more anchors
     // than one workgroup sorts in LDS (segsort.hip.h)
-    int32_t *d_overlist; TRY(ctx_buf_t(ctx, "q_overlist", (size_t)nq + 1, &d_overlist));
-    TRY((dev_qscan<int32_t, int32_t>(ctx, d_qcnt, nq, d_qaoff, d_na64, (int64_t)SEGSORT_CAP, d_nover, d_overlist)));
+    TRY(ctx_buf_t(ctx, "q_overlist", (size_t)nq + 1, &o->d_overlist));
+    TRY((dev_qscan<int32_t, int32_t>(ctx, d_qcnt, nq, d_qaoff, d_na64, (int64_t)SEGSORT_CAP, d_nover, o->d_overlist)));
     HIPCHK(hipGetLastError());
     int32_t na = 0; int64_t na64 = 0; int32_t n_over = 0;
     HIPCHK(hipMemcpyAsync(&na, d_qaoff + nq, 4, hipMemcpyDeviceToHost, st));
@@ -2048,115 +2063,52 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
     HIPCHK(hipMemcpyAsync(&n_over, d_nover, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (na64 >= (1LL << 31) - 256) { stage_collect(ctx); return TELR_SPLIT_RANGE; }
-    ctx->ctr.minimizers += nmz; ctx->ctr.probes += nmz;
-    ctx->ctr.over_queries += n_over; ctx->ctr.over_ranges += n_over > 0;
     static const bool lib_sort = ab_on("sort64");      // A/B: rocPRIM's segmented radix sort for every query
-    const bool any_over = n_over > 0;
-    uint64_t *d_keys, *d_skeys;
-    static const bool seed_unfused_env = ab_on("seed_unfused");
-    TRY(ctx_buf_t(ctx, "keys", (!lib_sort && !any_over && (vote || !seed_unfused_env)) ? (size_t)1 : (size_t)na, &d_keys));       // only the two-step forms need the unsorted keys in memory
-    TRY(ctx_buf_t(ctx, "skeys", (size_t)na, &d_skeys));
-    S.keys = d_keys;
-    // sub-read voting: the LDS sort reads the survivors from the staging pieces in place; only the library sort needs them dense
-    // A range that holds an over-size query takes the two-step form as a whole (the round-5 rule).  TELR_AB=over_routed: only the over-size
-    // queries do (their keys written on a side stream under the LDS sort of the others) -- built in round 6 for the hard genome, where EVERY
-    // range holds such a read, and measured SLOWER on configs[2] (196.7 against 185.0 ms per step, same box, three alternating runs each:
-    // profiles/r06_oversize_routing_ab.txt) and no faster on the hard genome; kept behind the switch, tests/test_gpu_switches.py.
-    static const bool over_routed = ab_on("over_routed");
-    const bool over_whole = any_over && !over_routed;
-    const bool vote_in_place = vote && !lib_sort && !over_whole;
-    // The anchor keys are MADE inside the sort (SeedProducer: the seeding routine writes a query's keys straight into the sorting
-    // workgroup's LDS), so unsorted keys never exist in HBM; TELR_AB=seed_unfused keeps the two-step form for A/B, and a range with a
-    // query above the LDS limit takes it too (its library sort reads the keys from memory)
     static const bool seed_unfused = ab_on("seed_unfused");
-    const bool seed_fused = !vote && !lib_sort && !seed_unfused && !over_whole;
-    S.lds_keys = nullptr;
-    // (TELR_AB=over_routed: the over-size queries' keys go to memory on a SIDE stream, under the LDS sort of everybody else; the library's sort waits for it)
-    hipEvent_t over_ready = nullptr;
-    if (vote) {
-        if (!vote_in_place) hipLaunchKernelGGL(k_vote_compact, dim3(nq), dim3(256), 0, st, d_stage, d_qsoff, d_qaoff, nq, d_keys, (const int32_t*)nullptr);
-        else if (any_over) {
-            HIPCHK(hipEventRecord(ctx->ev_fork, st)); HIPCHK(hipStreamWaitEvent(ctx->side[0], ctx->ev_fork, 0));
-            hipLaunchKernelGGL(k_vote_compact, dim3(n_over), dim3(256), 0, ctx->side[0], d_stage, d_qsoff, d_qaoff, n_over, d_keys, (const int32_t*)d_overlist);
-            HIPCHK(hipEventRecord(ctx->ev_side[0], ctx->side[0])); over_ready = ctx->ev_side[0];
-        }
-    }
-    else if (!seed_fused) hipLaunchKernelGGL(k_seed<1>, dim3(nq), dim3(256), 0, st, S);
-    else if (any_over) {
-        SeedArgs So = S; So.q_order = d_overlist;
-        HIPCHK(hipEventRecord(ctx->ev_fork, st)); HIPCHK(hipStreamWaitEvent(ctx->side[0], ctx->ev_fork, 0));
-        hipLaunchKernelGGL(k_seed<1>, dim3(n_over), dim3(256), 0, ctx->side[0], So);
-        HIPCHK(hipEventRecord(ctx->ev_side[0], ctx->side[0])); over_ready = ctx->ev_side[0];
-    }
+    const bool any_over = n_over > 0;
+    o->vote_in_place = vote && !lib_sort && !any_over;
+    o->fused = !vote && !lib_sort && !seed_unfused && !any_over;
+    TRY(ctx_buf_t(ctx, "keys", (!lib_sort && !any_over && (vote || !seed_unfused)) ? (size_t)1 : (size_t)na, &o->d_keys));       // only the two-step forms need the unsorted keys in memory
+    TRY(ctx_buf_t(ctx, "skeys", (size_t)na, &o->d_skeys));
+    S.keys = o->d_keys;
+    if (vote) { if (!o->vote_in_place) hipLaunchKernelGGL(k_vote_compact, dim3(nq), dim3(256), 0, st, d_stage, d_qsoff, d_qaoff, nq, o->d_keys); }
+    else if (!o->fused) hipLaunchKernelGGL(k_seed<1>, dim3(nq), dim3(256), 0, st, S);
     HIPCHK(hipGetLastError());
-    t_sd.stop(); ht.mark("seed (sync: anchor total)");
-    ctx->ctr.anchors += na;
+    o->d_stage = d_stage; o->d_qsoff = d_qsoff; o->d_qaoff = d_qaoff; o->na = na; o->n_over = n_over;
+    return TELR_OK;
+}
 
-    // ---- per-query sort of the anchor keys --------------------------------------------------
-    StageTimer t_so(ctx, ST_SORT, true);
-    if (na > 0 && seed_fused) { SeedProducer sp; sp.S = S; TRY((seg_sort_u64<SeedProducer>(ctx, "so_a", nullptr, d_skeys, d_qaoff, d_qaoff + 1, nullptr, d_qorder, nq, (size_t)na, any_over, st, sp, d_keys, over_ready))); }
-    else if (na > 0) TRY(seg_sort_u64(ctx, "so_a", vote_in_place ? d_stage : d_keys, d_skeys, d_qaoff, d_qaoff + 1, vote_in_place ? d_qsoff : nullptr, d_qorder, nq, (size_t)na, any_over, st, LoadKeys(), d_keys, over_ready));
-    t_so.stop();
+// the per-query sort of the anchor keys -> d_skeys
+static int sort_stage(telr_ctx *ctx, hipStream_t st, const SeedOut &sd, int nq, const int32_t *d_qorder)
+{
+    const bool any_over = sd.n_over > 0;
+    if (sd.na > 0 && sd.fused) { SeedProducer sp; sp.S = sd.S; TRY((seg_sort_u64<SeedProducer>(ctx, "so_a", nullptr, sd.d_skeys, sd.d_qaoff, sd.d_qaoff + 1, nullptr, d_qorder, nq, (size_t)sd.na, any_over, st, sp))); }
+    else if (sd.na > 0) TRY(seg_sort_u64(ctx, "so_a", sd.vote_in_place ? sd.d_stage : sd.d_keys, sd.d_skeys, sd.d_qaoff, sd.d_qaoff + 1, sd.vote_in_place ? sd.d_qsoff : nullptr, d_qorder, nq, (size_t)sd.na, any_over, st));
+    return TELR_OK;
+}
 
-    // ---- chaining ---------------------------------------------------------------------------
-    StageTimer t_ch(ctx, ST_CHAIN, true);
-    int32_t *d_f, *d_p;
-    TRY(ctx_buf_t(ctx, "chain_f", (size_t)na, &d_f));
-    TRY(ctx_buf_t(ctx, "chain_p", (size_t)na, &d_p));
-    TRY(chain_dispatch(ctx, st, mo, d_skeys, d_qaoff, nq, na, n_over, d_overlist, d_qorder, d_f, d_p));
-    HIPCHK(hipGetLastError());
-    t_ch.stop();
-
-    // ---- peaks + back-tracking ----------------------------------------------------------------
-    StageTimer t_bt(ctx, ST_BACKTRACK, true);
-    BtOut bt;
-    TRY(backtrack_dispatch(ctx, st, mo, d_skeys, d_qaoff, nq, na, any_over, d_qorder, d_f, d_p, &bt));
-    uint64_t *const d_canch = bt.d_canch; int32_t *const d_choff = bt.d_choff, *const d_nch = bt.d_nch; ChainRec *const d_rec = bt.d_rec;
-    const int32_t npk_tot = bt.npk_tot;
-    // Pass-1 chain selection runs on the device (k_select1).  The debug taps of the parity tests need every chain record on the host.
-    const bool need_recs = ctx->debug != 0;
-    int32_t *h_nch, *h_choff, *h_qaoff; ChainRec *h_rec;
-    TRY(ctx_hbuf_t(ctx, "h_nch", (size_t)nq + 1, &h_nch));
-    TRY(ctx_hbuf_t(ctx, "h_choff", (size_t)nq + 1, &h_choff));
-    TRY(ctx_hbuf_t(ctx, "h_qaoff", (size_t)nq + 1, &h_qaoff));
-    TRY(ctx_hbuf_t(ctx, "h_rec", need_recs ? (size_t)npk_tot + 1 : 1, &h_rec));
+// Pass-1 chain selection runs on the device (k_select1): the host arrays it fills are allocated here.  The debug taps of the parity
+// tests need every chain record on the host as well (need_recs).
+struct HostChains { int32_t *h_nch, *h_choff, *h_qaoff; ChainRec *h_rec; };
+static int chains_to_host(telr_ctx *ctx, hipStream_t st, const BtOut &bt, const int32_t *d_qaoff, int nq, bool need_recs, HostChains *o)
+{
+    TRY(ctx_hbuf_t(ctx, "h_nch", (size_t)nq + 1, &o->h_nch));
+    TRY(ctx_hbuf_t(ctx, "h_choff", (size_t)nq + 1, &o->h_choff));
+    TRY(ctx_hbuf_t(ctx, "h_qaoff", (size_t)nq + 1, &o->h_qaoff));
+    TRY(ctx_hbuf_t(ctx, "h_rec", need_recs ? (size_t)bt.npk_tot + 1 : 1, &o->h_rec));
     if (need_recs) {
-        HIPCHK(hipMemcpyAsync(h_nch, d_nch, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(h_choff, d_choff, (size_t)(nq + 1) * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(h_qaoff, d_qaoff, (size_t)(nq + 1) * 4, hipMemcpyDeviceToHost, st));
-        if (npk_tot) HIPCHK(hipMemcpyAsync(h_rec, d_rec, (size_t)npk_tot * sizeof(ChainRec), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(o->h_nch, bt.d_nch, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(o->h_choff, bt.d_choff, (size_t)(nq + 1) * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(o->h_qaoff, d_qaoff, (size_t)(nq + 1) * 4, hipMemcpyDeviceToHost, st));
+        if (bt.npk_tot) HIPCHK(hipMemcpyAsync(o->h_rec, bt.d_rec, (size_t)bt.npk_tot * sizeof(ChainRec), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
-    t_bt.stop(); ht.mark("sort+chain+backtrack issued");
-    ctx->dbg_na = na; ctx->dbg_nq = nq;
+    return TELR_OK;
+}
 
-    // ---- chain boxes + selection pass 1 -> the kept chains (query-major, pass-1 rank order) ------------------------
-    const int NT = host_threads();
-    std::vector<int32_t> q_k0(nq + 1, 0);
-    KeptLite *hl = nullptr;                  // what the host needs of the kept chains
-    KeptChain *d_kc = nullptr;               // their descriptors for the problem builder (device)
-    int nk = 0;
-    int64_t n_chain_tot = 0;
-    {
-        StageTimer t_sel(ctx, ST_SELECT, true);
-        SelOut so1;
-        TRY(select1_dispatch(ctx, st, mo, d_choff, d_nch, d_rec, npk_tot, d_qaoff, nq, q0, qs->d_len + q0, qs->d_boff + q0, ix->d_goff, tg->d_len, tg->d_boff, tg->n,
-                             any_over, d_qorder, need_recs, h_nch, q_k0.data(), &so1));
-        nk = so1.nk; hl = so1.hl; d_kc = so1.d_kc;
-        for (int q = 0; q < nq; ++q) n_chain_tot += h_nch[q];
-        t_sel.stop();
-        if (ctx->debug) {                    // every chain with its box, in discovery order (stage-level parity tests)
-            ctx->dbg_chain.clear();
-            for (int q = 0; q < nq; ++q) for (int c = 0; c < h_nch[q]; ++c) {
-                int32_t v[9];
-                chain_row(h_rec[h_choff[q] + c], q0 + q, ix->goff.data(), tg->n, v);
-                ctx->dbg_chain.insert(ctx->dbg_chain.end(), v, v + 9);
-            }
-        }
-    }
-    ctx->ctr.chains += n_chain_tot; ht.mark("selection (sync: kept chains)");
-
-    // results per kept chain (chain-level numbers; overwritten by the DP numbers below)
+// results per kept chain from the chain-level numbers (the DP numbers overwrite them: chain_numbers) -> ctx->h_kal
+static telr_aln *kept_records(telr_ctx *ctx, int NT, const telr_seqset *qs, const telr_seqset *tg, const KeptLite *hl, int nk)
+{
     if (ctx->h_kal.size() < (size_t)nk) ctx->h_kal.resize((size_t)nk + (size_t)nk / 8);
     telr_aln *kal = ctx->h_kal.data();
     parallel_ranges(NT, nk, [&](int, int xa, int xb) {
@@ -2170,139 +2122,144 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
             r.mlen = std::min(c.score, c.qe - c.qs); r.blen = std::max(c.qe - c.qs, c.re - c.rs); r.dp_score = c.score;
         }
     });
+    return kal;
+}
 
-    const bool do_dp = (mo->flags & TELR_MF_CIGAR) && nk > 0;
-    std::vector<int32_t> &h_poff = ctx->h_poffv;
-    int64_t *h_foff = nullptr; size_t cig_base = 0; ChainStat *h_cs = nullptr; unsigned long long *h_acc = nullptr;
-    int np = 0;
-    if (do_dp) {
-        // ---- DP problem list ----------------------------------------------------------------
-        StageTimer t_sg(ctx, ST_SEGMENTS, true);
-        DpProb *d_probs;
-        TRY(segments_dispatch(ctx, st, mo, d_kc, nk, d_canch, h_poff, &np, &d_probs));
-        t_sg.stop(); ht.mark("segments (sync: problems)");
-        ctx->ctr.dp_problems += np;
-
-        // ---- banded DP: narrow-band pass, then a wide-band pass for the problems whose path touched a band edge
-        StageTimer t_dp(ctx, ST_DP, true);
-        uint32_t *d_rawcig = nullptr; DpRes *d_res; int32_t *d_retry, *d_rcnt, *d_rlist;
-        TRY(ctx_buf_t(ctx, "dp_res", (size_t)np, &d_res));
-        TRY(ctx_buf_t(ctx, "retry_flag", (size_t)np + 1, &d_retry));
-        TRY(ctx_buf_t(ctx, "retry_list", (size_t)np + 1, &d_rlist));
-        TRY(ctx_buf_t(ctx, "retry_cnt", 4, &d_rcnt));
-        HIPCHK(hipMemsetAsync(d_retry, 0, ((size_t)np + 1) * 4, st));
-        HIPCHK(hipMemsetAsync(d_rcnt, 0, 16, st));
-        TRY(dp_pass(ctx, qs, tg, mo, d_probs, np, d_res, &d_rawcig, d_retry, "", true));
-        hipLaunchKernelGGL(k_retry_collect, dim3((np + 255) / 256), dim3(256), 0, st, d_retry, np, d_rcnt, d_rlist);
+// banded DP: narrow-band pass, then a wide-band pass for the problems whose path touched a band edge -> d_res, d_rawcig, *n_retry
+static int dp_passes(telr_ctx *ctx, hipStream_t st, const telr_seqset *qs, const telr_seqset *tg, const telr_map_opt *mo, DpProb *d_probs, int np,
+                     DpRes **d_res_out, uint32_t **d_rawcig, int32_t *n_retry_out)
+{
+    DpRes *d_res; int32_t *d_retry, *d_rcnt, *d_rlist;
+    *d_rawcig = nullptr;
+    TRY(ctx_buf_t(ctx, "dp_res", (size_t)np, &d_res));
+    TRY(ctx_buf_t(ctx, "retry_flag", (size_t)np + 1, &d_retry));
+    TRY(ctx_buf_t(ctx, "retry_list", (size_t)np + 1, &d_rlist));
+    TRY(ctx_buf_t(ctx, "retry_cnt", 4, &d_rcnt));
+    HIPCHK(hipMemsetAsync(d_retry, 0, ((size_t)np + 1) * 4, st));
+    HIPCHK(hipMemsetAsync(d_rcnt, 0, 16, st));
+    TRY(dp_pass(ctx, qs, tg, mo, d_probs, np, d_res, d_rawcig, d_retry, "", true));
+    hipLaunchKernelGGL(k_retry_collect, dim3((np + 255) / 256), dim3(256), 0, st, d_retry, np, d_rcnt, d_rlist);
+    HIPCHK(hipGetLastError());
+    int32_t n_retry = 0;
+    HIPCHK(hipMemcpyAsync(&n_retry, d_rcnt, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    { float ms = 0;
+      if (hipEventElapsedTime(&ms, ctx->evk[5], ctx->evk[0]) == hipSuccess) ctx->stage_ms[ST_K_PK] += ms;
+      if (hipEventElapsedTime(&ms, ctx->evk[0], ctx->evk[1]) == hipSuccess) ctx->stage_ms[ST_K_REG] += ms;
+      if (hipEventElapsedTime(&ms, ctx->evk[3], ctx->evk[4]) == hipSuccess) ctx->stage_ms[ST_K_TRACEBACK] += ms; }
+    if (n_retry > 0) {
+        DpProb *d_probs2; DpRes *d_res2;
+        TRY(ctx_buf_t(ctx, "probs_r", (size_t)n_retry, &d_probs2));
+        TRY(ctx_buf_t(ctx, "dp_res_r", (size_t)n_retry, &d_res2));
+        hipLaunchKernelGGL(k_retry_build, dim3((n_retry + 255) / 256), dim3(256), 0, st, d_probs, d_rlist, n_retry, mo->bw, mo->fill_band_q4, d_probs2);
         HIPCHK(hipGetLastError());
-        int32_t n_retry = 0;
-        HIPCHK(hipMemcpyAsync(&n_retry, d_rcnt, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        { float ms = 0;
-          if (hipEventElapsedTime(&ms, ctx->evk[5], ctx->evk[0]) == hipSuccess) ctx->stage_ms[ST_K_PK] += ms;
-          if (hipEventElapsedTime(&ms, ctx->evk[0], ctx->evk[1]) == hipSuccess) ctx->stage_ms[ST_K_REG] += ms;
-          if (hipEventElapsedTime(&ms, ctx->evk[3], ctx->evk[4]) == hipSuccess) ctx->stage_ms[ST_K_TRACEBACK] += ms; }
-        if (n_retry > 0) {
-            DpProb *d_probs2; DpRes *d_res2;
-            TRY(ctx_buf_t(ctx, "probs_r", (size_t)n_retry, &d_probs2));
-            TRY(ctx_buf_t(ctx, "dp_res_r", (size_t)n_retry, &d_res2));
-            hipLaunchKernelGGL(k_retry_build, dim3((n_retry + 255) / 256), dim3(256), 0, st, d_probs, d_rlist, n_retry, mo->bw, mo->fill_band_q4, d_probs2);
-            HIPCHK(hipGetLastError());
-            TRY(dp_pass(ctx, qs, tg, mo, d_probs2, n_retry, d_res2, &d_rawcig, nullptr, "_r", false));
-            hipLaunchKernelGGL(k_retry_merge, dim3((n_retry + 255) / 256), dim3(256), 0, st, d_probs2, d_res2, n_retry, d_res);
-            HIPCHK(hipGetLastError());
-        }
-        ctx->dp_retries += n_retry;
-        t_dp.stop(); ht.mark("dp passes");
-
-        // ---- CIGARs of ALL kept chains are stitched now and travel to the (pinned) result buffer while the host does
-        //      its second selection pass on the per-problem results; chains that pass drops leave unused gaps behind
-        StageTimer t_g(ctx, ST_GATHER, true);
-        {
-            StitchRec *h_sv, *d_sv; int64_t *d_nfin, *d_foff; StitchProb *d_sp;
-            TRY(ctx_hbuf_t(ctx, "h_stitch", (size_t)nk, &h_sv));
-            TRY(ctx_buf_t(ctx, "stitch", (size_t)nk, &d_sv));
-            TRY(ctx_buf_t(ctx, "stitch_n", (size_t)nk + 1, &d_nfin));
-            TRY(ctx_buf_t(ctx, "stitch_off", (size_t)nk + 1, &d_foff));
-            TRY(ctx_buf_t(ctx, "stitch_prob", (size_t)np, &d_sp));
-            parallel_ranges(NT, nk, [&](int, int xa, int xb) {
-                for (int x = xa; x < xb; ++x) {
-                    const KeptLite &c = hl[x];
-                    h_sv[x].p0 = h_poff[x]; h_sv[x].p1 = h_poff[x + 1]; h_sv[x].has_left = (c.qs > 0 && c.rs > 0) ? 1 : 0; h_sv[x].pad = 0;
-                }
-            });
-            HIPCHK(hipMemcpyAsync(d_sv, h_sv, (size_t)nk * sizeof(StitchRec), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemsetAsync(d_sp, 0xff, (size_t)np * sizeof(StitchProb), st));
-            hipLaunchKernelGGL(k_stitch_count, dim3(nk), dim3(64), 0, st, d_sv, nk, d_probs, d_res, d_rawcig, d_nfin, d_sp);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemsetAsync(d_nfin + nk, 0, 8, st));
-            TRY((dev_exclusive_scan<int64_t, int64_t>(ctx, d_nfin, d_foff, (size_t)nk + 1)));
-            TRY(ctx_hbuf_t(ctx, "h_stitch_off", (size_t)nk + 1, &h_foff));
-            HIPCHK(hipMemcpyAsync(h_foff, d_foff, (size_t)(nk + 1) * 8, hipMemcpyDeviceToHost, st));
-            ChainStat *d_cs; unsigned long long *d_acc;
-            TRY(ctx_buf_t(ctx, "chain_stat", (size_t)nk, &d_cs));
-            TRY(ctx_buf_t(ctx, "dp_acc", (size_t)TELR_N_DPCLS * 4 + 1, &d_acc));
-            TRY(ctx_hbuf_t(ctx, "h_chain_stat", (size_t)nk, &h_cs));
-            TRY(ctx_hbuf_t(ctx, "h_dp_acc", (size_t)TELR_N_DPCLS * 4 + 1, &h_acc));
-            HIPCHK(hipMemsetAsync(d_acc, 0, ((size_t)TELR_N_DPCLS * 4 + 1) * 8, st));
-            hipLaunchKernelGGL(k_chain_stats, dim3(nk), dim3(64), 0, st, d_sv, nk, d_res, d_cs, mo->cx_scale > 0 ? mo->cx_scale : 0);
-            hipLaunchKernelGGL(k_dp_account, dim3((np + 255) / 256), dim3(256), 0, st, d_probs, d_res, np, d_acc);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(h_cs, d_cs, (size_t)nk * sizeof(ChainStat), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(h_acc, d_acc, ((size_t)TELR_N_DPCLS * 4 + 1) * 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            t_g.stop(); ht.mark("stitch count (sync)");                           // what follows is not waited for here
-            const int64_t tot = h_foff[nk];
-            uint32_t *d_fin;
-            TRY(ctx_buf_t(ctx, "stitched", (size_t)tot + 1, &d_fin));
-            // the stitched scratch is overwritten here: the previous call's DMA out of it must be over (it is, tens of ms ago)
-            if (ctx->dma_inflight) HIPCHK(hipStreamWaitEvent(st, ctx->ev_dma, 0));
-            hipLaunchKernelGGL(k_stitch_write, dim3((np + 31) / 32), dim3(256), 0, st, np, d_sp, d_probs, d_res, d_sv, d_rawcig, d_foff, d_fin);
-            HIPCHK(hipGetLastError());
-            if (!gate_enter(R, gate)) { ctx->err = "an earlier range of the call failed"; return TELR_E_HIP; }
-            result_wait(R);                        // an earlier batch of this call may still be writing into the buffer that grows below
-            cig_base = R->ncig;
-            if (cig_base + (size_t)tot + 1 > R->cap) {
-                if (!R->cig) pool_get(ctx, &R->cig, &R->cap);
-                if (!cig_grow(&R->cig, &R->cap, cig_base, cig_base + (size_t)tot + 1 + (size_t)tot / 8)) return TELR_E_NOMEM;
-            }
-            R->ncig = cig_base + (size_t)tot;
-            if (R->twin_n > cig_base) R->twin_n = cig_base;          // a range that was rolled back and runs again
-            twin_put(ctx->twin_owner ? ctx->twin_owner : ctx, R, mo, cig_base, (size_t)tot, d_fin, ctx->twin_bases, st);
-            if (tot) {
-                // DMA on its own stream: the caller gets the records back while the CIGAR array is still travelling
-                HIPCHK(hipEventRecord(ctx->ev_stitched, st));
-                HIPCHK(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_stitched, 0));
-                HIPCHK(hipMemcpyAsync(R->cig + cig_base, d_fin, (size_t)tot * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
-                HIPCHK(hipEventRecord(ctx->ev_dma, ctx->copy_stream)); ctx->dma_inflight = true;
-                HIPCHK(hipEventCreateWithFlags(&R->dma_done, hipEventDisableTiming));
-                HIPCHK(hipEventRecord(R->dma_done, ctx->copy_stream));
-            }
-        }
-
-        // ---- host: per-chain numbers from the per-problem results (no op walking) ---------------------
-        StageTimer t_as(ctx, ST_ASSEMBLE, false);
-        for (int z = 0; z < TELR_N_DPCLS * 4; ++z) ctx->dpcls[z] += (int64_t)h_acc[z];
-        for (int c = 0; c < TELR_N_DPCLS; ++c) ctx->ctr.dp_cells += (int64_t)h_acc[c * 4 + 1];
-        ctx->ctr.window_bases += (int64_t)h_acc[TELR_N_DPCLS * 4];
-        parallel_ranges(NT, nk, [&](int, int xa, int xb) {
-            for (int x = xa; x < xb; ++x) {
-                const KeptLite &c = hl[x]; telr_aln &r = kal[x]; const ChainStat &S = h_cs[x];
-                const int qlen = r.qlen, tlen = r.tlen;
-                int32_t qs_ = c.qs, rs_ = c.rs, qe_ = c.qe, re_ = c.re;
-                const bool has_left = c.qs > 0 && c.rs > 0, has_right = c.qe < qlen && c.re < tlen;
-                if (has_left) { qs_ = c.qs - S.l_bi; rs_ = c.rs - S.l_bj; }
-                if (has_right) { qe_ = c.qe + S.r_bi; re_ = c.re + S.r_bj; }
-                r.ts = rs_; r.te = re_;
-                if (c.rev) { r.qs = qlen - qe_; r.qe = qlen - qs_; } else { r.qs = qs_; r.qe = qe_; }
-                r.mlen = S.mlen; r.blen = S.blen; r.dp_score = S.dp;
-            }
-        });
-        t_as.stop();
+        TRY(dp_pass(ctx, qs, tg, mo, d_probs2, n_retry, d_res2, d_rawcig, nullptr, "_r", false));
+        hipLaunchKernelGGL(k_retry_merge, dim3((n_retry + 255) / 256), dim3(256), 0, st, d_probs2, d_res2, n_retry, d_res);
+        HIPCHK(hipGetLastError());
     }
+    *d_res_out = d_res; *n_retry_out = n_retry;
+    return TELR_OK;
+}
 
-    // ---- host: pass-2 selection, flags, mapq (threads over queries) --------------------------------------
-    StageTimer t_as2(ctx, ST_ASSEMBLE, false);
+// The CIGARs of ALL kept chains are stitched and travel to the (pinned) result buffer while the host does its second selection pass
+// on the per-problem results; chains that pass drops leave unused gaps behind.  stitch_count sizes them (and fetches the per-chain
+// numbers and the per-class accounts; it ends with a synchronisation), stitch_emit writes them and starts their DMA.
+struct StitchOut { StitchRec *d_sv; StitchProb *d_sp; int64_t *d_foff, *h_foff; ChainStat *h_cs; unsigned long long *h_acc; };
+static int stitch_count(telr_ctx *ctx, hipStream_t st, int NT, const telr_map_opt *mo, const KeptLite *hl, int nk, const std::vector<int32_t> &h_poff,
+                        const DpProb *d_probs, int np, const DpRes *d_res, const uint32_t *d_rawcig, StitchOut *o)
+{
+    StitchRec *h_sv, *d_sv; int64_t *d_nfin, *d_foff; StitchProb *d_sp;
+    TRY(ctx_hbuf_t(ctx, "h_stitch", (size_t)nk, &h_sv));
+    TRY(ctx_buf_t(ctx, "stitch", (size_t)nk, &d_sv));
+    TRY(ctx_buf_t(ctx, "stitch_n", (size_t)nk + 1, &d_nfin));
+    TRY(ctx_buf_t(ctx, "stitch_off", (size_t)nk + 1, &d_foff));
+    TRY(ctx_buf_t(ctx, "stitch_prob", (size_t)np, &d_sp));
+    parallel_ranges(NT, nk, [&](int, int xa, int xb) {
+        for (int x = xa; x < xb; ++x) {
+            const KeptLite &c = hl[x];
+            h_sv[x].p0 = h_poff[x]; h_sv[x].p1 = h_poff[x + 1]; h_sv[x].has_left = (c.qs > 0 && c.rs > 0) ? 1 : 0; h_sv[x].pad = 0;
+        }
+    });
+    HIPCHK(hipMemcpyAsync(d_sv, h_sv, (size_t)nk * sizeof(StitchRec), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_sp, 0xff, (size_t)np * sizeof(StitchProb), st));
+    hipLaunchKernelGGL(k_stitch_count, dim3(nk), dim3(64), 0, st, d_sv, nk, d_probs, d_res, d_rawcig, d_nfin, d_sp);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(d_nfin + nk, 0, 8, st));
+    TRY((dev_exclusive_scan<int64_t, int64_t>(ctx, d_nfin, d_foff, (size_t)nk + 1)));
+    TRY(ctx_hbuf_t(ctx, "h_stitch_off", (size_t)nk + 1, &o->h_foff));
+    HIPCHK(hipMemcpyAsync(o->h_foff, d_foff, (size_t)(nk + 1) * 8, hipMemcpyDeviceToHost, st));
+    ChainStat *d_cs; unsigned long long *d_acc;
+    TRY(ctx_buf_t(ctx, "chain_stat", (size_t)nk, &d_cs));
+    TRY(ctx_buf_t(ctx, "dp_acc", (size_t)TELR_N_DPCLS * 4 + 1, &d_acc));
+    TRY(ctx_hbuf_t(ctx, "h_chain_stat", (size_t)nk, &o->h_cs));
+    TRY(ctx_hbuf_t(ctx, "h_dp_acc", (size_t)TELR_N_DPCLS * 4 + 1, &o->h_acc));
+    HIPCHK(hipMemsetAsync(d_acc, 0, ((size_t)TELR_N_DPCLS * 4 + 1) * 8, st));
+    hipLaunchKernelGGL(k_chain_stats, dim3(nk), dim3(64), 0, st, d_sv, nk, d_res, d_cs, mo->cx_scale > 0 ? mo->cx_scale : 0);
+    hipLaunchKernelGGL(k_dp_account, dim3((np + 255) / 256), dim3(256), 0, st, d_probs, d_res, np, d_acc);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(o->h_cs, d_cs, (size_t)nk * sizeof(ChainStat), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(o->h_acc, d_acc, ((size_t)TELR_N_DPCLS * 4 + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    o->d_sv = d_sv; o->d_sp = d_sp; o->d_foff = d_foff;
+    return TELR_OK;
+}
+// -> *cig_base: where the range's CIGARs start in the result's array (the result is touched in the range's turn only; not waited for here)
+static int stitch_emit(telr_ctx *ctx, hipStream_t st, const telr_map_opt *mo, telr_result *R, RangeTurn *gate, int nk, const StitchOut &so,
+                       const DpProb *d_probs, int np, const DpRes *d_res, const uint32_t *d_rawcig, size_t *cig_base_out)
+{
+    const int64_t tot = so.h_foff[nk];
+    uint32_t *d_fin;
+    TRY(ctx_buf_t(ctx, "stitched", (size_t)tot + 1, &d_fin));
+    // the stitched scratch is overwritten here: the previous call's DMA out of it must be over (it is, tens of ms ago)
+    if (ctx->dma_inflight) HIPCHK(hipStreamWaitEvent(st, ctx->ev_dma, 0));
+    hipLaunchKernelGGL(k_stitch_write, dim3((np + 31) / 32), dim3(256), 0, st, np, so.d_sp, d_probs, d_res, so.d_sv, d_rawcig, so.d_foff, d_fin);
+    HIPCHK(hipGetLastError());
+    if (!gate_enter(R, gate)) { ctx->err = "an earlier range of the call failed"; return TELR_E_HIP; }
+    result_wait(R);                        // an earlier batch of this call may still be writing into the buffer that grows below
+    const size_t cig_base = R->ncig;
+    if (cig_base + (size_t)tot + 1 > R->cap) {
+        if (!R->cig) pool_get(ctx, &R->cig, &R->cap);
+        if (!cig_grow(&R->cig, &R->cap, cig_base, cig_base + (size_t)tot + 1 + (size_t)tot / 8)) return TELR_E_NOMEM;
+    }
+    R->ncig = cig_base + (size_t)tot;
+    if (R->twin_n > cig_base) R->twin_n = cig_base;          // a range that was rolled back and runs again
+    twin_put(ctx->twin_owner ? ctx->twin_owner : ctx, R, mo, cig_base, (size_t)tot, d_fin, ctx->twin_bases, st);
+    if (tot) {
+        // DMA on its own stream: the caller gets the records back while the CIGAR array is still travelling
+        HIPCHK(hipEventRecord(ctx->ev_stitched, st));
+        HIPCHK(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_stitched, 0));
+        HIPCHK(hipMemcpyAsync(R->cig + cig_base, d_fin, (size_t)tot * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
+        HIPCHK(hipEventRecord(ctx->ev_dma, ctx->copy_stream)); ctx->dma_inflight = true;
+        HIPCHK(hipEventCreateWithFlags(&R->dma_done, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(R->dma_done, ctx->copy_stream));
+    }
+    *cig_base_out = cig_base;
+    return TELR_OK;
+}
+
+// host: per-chain numbers from the per-problem results (no op walking)
+static void chain_numbers(int NT, const KeptLite *hl, int nk, const ChainStat *h_cs, telr_aln *kal)
+{
+    parallel_ranges(NT, nk, [&](int, int xa, int xb) {
+        for (int x = xa; x < xb; ++x) {
+            const KeptLite &c = hl[x]; telr_aln &r = kal[x]; const ChainStat &S = h_cs[x];
+            const int qlen = r.qlen, tlen = r.tlen;
+            int32_t qs_ = c.qs, rs_ = c.rs, qe_ = c.qe, re_ = c.re;
+            const bool has_left = c.qs > 0 && c.rs > 0, has_right = c.qe < qlen && c.re < tlen;
+            if (has_left) { qs_ = c.qs - S.l_bi; rs_ = c.rs - S.l_bj; }
+            if (has_right) { qe_ = c.qe + S.r_bi; re_ = c.re + S.r_bj; }
+            r.ts = rs_; r.te = re_;
+            if (c.rev) { r.qs = qlen - qe_; r.qe = qlen - qs_; } else { r.qs = qs_; r.qe = qe_; }
+            r.mlen = S.mlen; r.blen = S.blen; r.dp_score = S.dp;
+        }
+    });
+}
+
+// host: pass-2 selection, flags, mapq (threads over queries), and the survivors appended to the result in the range's turn.
+// h_foff (null without DP): the CIGAR offsets of the kept chains behind cig_base.  -> *n_rec records, *n_ops CIGAR operations of theirs
+static int assemble_stage(telr_ctx *ctx, int NT, const telr_map_opt *mo, int nq, const std::vector<int32_t> &q_k0, int nk, const telr_aln *kal,
+                          const int64_t *h_foff, size_t cig_base, telr_result *R, RangeTurn *gate, int *n_rec, int64_t *n_ops)
+{
     const bool per_t = (mo->flags & TELR_MF_PER_TARGET) != 0;
     // survivors of query q go to stage[k0 .. k0 + n_surv[q]) in rank order (a query keeps at most as many records as it had
     // kept chains), then one prefix sum over the queries places them in the result: no per-thread vectors, no re-copying
@@ -2345,7 +2302,7 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
                     r.flags |= first ? TELR_F_PRIMARY : TELR_F_SUPPL;
                 } else r.flags |= TELR_F_SECONDARY;
                 r.mapq = mapq_of(r, mo);
-                if (do_dp) { r.cigar_off = (int64_t)cig_base + h_foff[x]; r.n_cigar = (int32_t)(h_foff[x + 1] - h_foff[x]); }
+                if (h_foff) { r.cigar_off = (int64_t)cig_base + h_foff[x]; r.n_cigar = (int32_t)(h_foff[x + 1] - h_foff[x]); }
             }
             nsurv[q] = w;
         }
@@ -2367,11 +2324,122 @@ static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs,
         }
         tops[t] = ops;
     });
-    t_as2.stop();
-    if (do_dp) {
-        for (int t = 0; t < NT; ++t) ctx->ctr.cigar_ops += tops[t];
-        // (the CIGAR DMA is waited for by whoever reads the CIGARs: result_wait)
+    *n_rec = ns; *n_ops = 0;
+    for (int t = 0; t < NT; ++t) *n_ops += tops[t];
+    return TELR_OK;
+}
+
+// One range [q0, q1) of the queries through the stages, in the order of their launches; every stage above and every *_dispatch issues
+// to ctx->stream (the DP classes and the library sorts fork from it and join it) and says where it waits for the device.
+static int map_batch(telr_ctx *ctx, const telr_index *ix, const telr_seqset *qs, const int32_t *d_qtarget, int32_t q0, int32_t q1,
+                     const telr_map_opt *mo, OccCut occ, telr_result *R, RangeTurn *gate = nullptr)
+{
+    const int nq = q1 - q0;
+    const telr_seqset *tg = ix->targets;
+    hipStream_t st = ctx->stream;
+    HostTrace ht("batch");
+    const int NT = host_threads();
+    // sub-read voting (spec 3.10) applies to all-vs-all calls only
+    const bool vote = mo->vote_len > 0 && !d_qtarget && !(mo->flags & TELR_MF_PER_TARGET);
+
+    // ---- 1. sketch and query order ----------------------------------------------------------------------
+    QueryOrder qo;
+    TRY(query_order_start(ctx, qs, q0, nq, &qo));
+    StageTimer t_sk(ctx, ST_SKETCH, true);
+    SketchOut sk;
+    TRY(sketch_stage(ctx, st, ix, qs, q0, q1, vote, &sk));
+    t_sk.stop(); ht.mark("sketch issued");
+    TRY(query_order_upload(ctx, st, nq, &qo));
+    const int32_t *d_qorder = qo.d;
+
+    // ---- 2. seeding and the per-query sort of the anchor keys ----------------------------------------------
+    StageTimer t_sd(ctx, ST_SEED, true);
+    SeedOut sd;
+    TRY(seed_stage(ctx, st, ix, qs, d_qtarget, q0, nq, mo, occ, vote, sk, d_qorder, &sd));      // (TELR_SPLIT_RANGE: the caller halves the range)
+    t_sd.stop(); ht.mark("seed (sync: anchor total)");
+    const int32_t na = sd.na, n_over = sd.n_over; const bool any_over = n_over > 0;
+    ctx->ctr.minimizers += sk.nmz; ctx->ctr.probes += sk.nmz;
+    ctx->ctr.over_queries += n_over; ctx->ctr.over_ranges += any_over;
+    ctx->ctr.anchors += na;
+    StageTimer t_so(ctx, ST_SORT, true);
+    TRY(sort_stage(ctx, st, sd, nq, d_qorder));
+    t_so.stop();
+
+    // ---- 3. chaining ------------------------------------------------------------------------------------
+    StageTimer t_ch(ctx, ST_CHAIN, true);
+    int32_t *d_f, *d_p;
+    TRY(ctx_buf_t(ctx, "chain_f", (size_t)na, &d_f));
+    TRY(ctx_buf_t(ctx, "chain_p", (size_t)na, &d_p));
+    TRY(chain_dispatch(ctx, st, mo, sd.d_skeys, sd.d_qaoff, nq, na, n_over, sd.d_overlist, d_qorder, d_f, d_p));
+    HIPCHK(hipGetLastError());
+    t_ch.stop();
+
+    // ---- 4. peaks + back-tracking -------------------------------------------------------------------------
+    StageTimer t_bt(ctx, ST_BACKTRACK, true);
+    BtOut bt;
+    TRY(backtrack_dispatch(ctx, st, mo, sd.d_skeys, sd.d_qaoff, nq, na, any_over, d_qorder, d_f, d_p, &bt));
+    const bool need_recs = ctx->debug != 0;
+    HostChains hc;
+    TRY(chains_to_host(ctx, st, bt, sd.d_qaoff, nq, need_recs, &hc));
+    t_bt.stop(); ht.mark("sort+chain+backtrack issued");
+    ctx->dbg_na = na; ctx->dbg_nq = nq;
+
+    // ---- 5. chain boxes + selection pass 1 -> the kept chains (query-major, pass-1 rank order) ------------------------
+    std::vector<int32_t> q_k0(nq + 1, 0);
+    StageTimer t_sel(ctx, ST_SELECT, true);
+    SelOut so1;
+    TRY(select1_dispatch(ctx, st, mo, bt.d_choff, bt.d_nch, bt.d_rec, bt.npk_tot, sd.d_qaoff, nq, q0, qs->d_len + q0, qs->d_boff + q0, ix->d_goff, tg->d_len, tg->d_boff, tg->n,
+                         any_over, d_qorder, need_recs, hc.h_nch, q_k0.data(), &so1));
+    const int nk = so1.nk; const KeptLite *hl = so1.hl;      // what the host needs of the kept chains (so1.d_kc: their descriptors for the problem builder)
+    int64_t n_chain_tot = 0;
+    for (int q = 0; q < nq; ++q) n_chain_tot += hc.h_nch[q];
+    t_sel.stop();
+    if (ctx->debug) {                    // every chain with its box, in discovery order (stage-level parity tests)
+        ctx->dbg_chain.clear();
+        for (int q = 0; q < nq; ++q) for (int c = 0; c < hc.h_nch[q]; ++c) {
+            int32_t v[9];
+            chain_row(hc.h_rec[hc.h_choff[q] + c], q0 + q, ix->goff.data(), tg->n, v);
+            ctx->dbg_chain.insert(ctx->dbg_chain.end(), v, v + 9);
+        }
     }
+    ctx->ctr.chains += n_chain_tot; ht.mark("selection (sync: kept chains)");
+    telr_aln *kal = kept_records(ctx, NT, qs, tg, hl, nk);
+
+    // ---- 6. DP passes and stitching ------------------------------------------------------------------------
+    const bool do_dp = (mo->flags & TELR_MF_CIGAR) && nk > 0;
+    StitchOut sto; sto.h_foff = nullptr; size_t cig_base = 0;
+    if (do_dp) {
+        StageTimer t_sg(ctx, ST_SEGMENTS, true);
+        DpProb *d_probs; int np = 0;
+        TRY(segments_dispatch(ctx, st, mo, so1.d_kc, nk, bt.d_canch, ctx->h_poffv, &np, &d_probs));
+        t_sg.stop(); ht.mark("segments (sync: problems)");
+        ctx->ctr.dp_problems += np;
+
+        StageTimer t_dp(ctx, ST_DP, true);
+        uint32_t *d_rawcig; DpRes *d_res; int32_t n_retry;
+        TRY(dp_passes(ctx, st, qs, tg, mo, d_probs, np, &d_res, &d_rawcig, &n_retry));
+        ctx->dp_retries += n_retry;
+        t_dp.stop(); ht.mark("dp passes");
+
+        StageTimer t_g(ctx, ST_GATHER, true);
+        TRY(stitch_count(ctx, st, NT, mo, hl, nk, ctx->h_poffv, d_probs, np, d_res, d_rawcig, &sto));
+        t_g.stop(); ht.mark("stitch count (sync)");                           // what follows is not waited for here
+        TRY(stitch_emit(ctx, st, mo, R, gate, nk, sto, d_probs, np, d_res, d_rawcig, &cig_base));
+
+        StageTimer t_as(ctx, ST_ASSEMBLE, false);
+        for (int z = 0; z < TELR_N_DPCLS * 4; ++z) ctx->dpcls[z] += (int64_t)sto.h_acc[z];
+        for (int c = 0; c < TELR_N_DPCLS; ++c) ctx->ctr.dp_cells += (int64_t)sto.h_acc[c * 4 + 1];
+        ctx->ctr.window_bases += (int64_t)sto.h_acc[TELR_N_DPCLS * 4];
+        chain_numbers(NT, hl, nk, sto.h_cs, kal);
+        t_as.stop();
+    }
+
+    // ---- 7. pass-2 selection and append to the result --------------------------------------------------------
+    StageTimer t_as2(ctx, ST_ASSEMBLE, false);
+    int ns = 0; int64_t n_ops = 0;
+    TRY(assemble_stage(ctx, NT, mo, nq, q_k0, nk, kal, do_dp ? sto.h_foff : nullptr, cig_base, R, gate, &ns, &n_ops));
+    t_as2.stop();
+    if (do_dp) ctx->ctr.cigar_ops += n_ops;          // (the CIGAR DMA is waited for by whoever reads the CIGARs: result_wait)
     ctx->ctr.records += ns;
     ht.mark("host assembly");
     stage_collect(ctx);
@@ -2422,6 +2490,127 @@ static int check_map_opt(telr_ctx *ctx, const telr_map_opt *mo)
     return TELR_OK;
 }
 
+// ---- telr_map: the plan of its ranges (range_plan.h) and the three ways a plan runs ---------------------------------------------
+struct MapCall { const telr_index *ix; const telr_seqset *queries; const int32_t *qtarget, *d_qt; const telr_map_opt *mo; OccCut mid_occ; telr_result *R; };
+static int run_range(telr_ctx *ctx, const MapCall &C, int32_t q0, int32_t q1, int turn = -1)
+{
+    return map_range(ctx, C.ix, C.queries, C.qtarget, C.d_qt, q0, q1, C.mo, C.mid_occ, C.R, turn);
+}
+// what a call counts and times (ctx->err is the caller's: some places keep the message of what went before)
+static void call_reset(telr_ctx *c)
+{
+    memset(c->stage_ms, 0, sizeof(c->stage_ms)); memset(&c->ctr, 0, sizeof(c->ctr)); memset(c->dpcls, 0, sizeof(c->dpcls));
+    c->dp_retries = 0; c->pk_launches = 0; c->st_pending = 0;
+}
+// the second slot's share of a call, added to the context's
+static void call_merge(telr_ctx *ctx, const telr_ctx *c)
+{
+    for (int z = 0; z < TELR_N_STAGES; ++z) ctx->stage_ms[z] += c->stage_ms[z];
+    const int64_t *src = (const int64_t*)&c->ctr; int64_t *dst = (int64_t*)&ctx->ctr;
+    for (size_t z = 0; z < sizeof(telr_counters) / 8; ++z) dst[z] += src[z];
+    for (int z = 0; z < TELR_N_DPCLS * 4; ++z) ctx->dpcls[z] += c->dpcls[z];
+    ctx->dp_retries += c->dp_retries; ctx->pk_launches += c->pk_launches;
+}
+// a call that starts over: the result as it was handed out
+static void result_rollback(telr_result *R)
+{
+    result_wait(R); R->alns.clear(); R->ncig = 0; R->twin_n = 0;
+    std::lock_guard<std::mutex> lk(R->gate_m); R->turn = 0;
+}
+// the anchor density the call has seen so far becomes the index's (the next plan's `per_base`) -> whether it had enough bases to say
+static bool density_update(const telr_ctx *ctx, const telr_index *ix)
+{
+    if (!(ctx->ctr.anchors > 0 && ctx->ctr.query_bases > (64LL << 20))) return false;
+    ix->anchors_per_base = (double)ctx->ctr.anchors / (double)ctx->ctr.query_bases;
+    return true;
+}
+
+// one range at a time, cut under a limit that follows the density after every range
+static int run_serial(telr_ctx *ctx, const MapCall &C, const RangePlan &P, double per_base)
+{
+    const int32_t *len = C.queries->len.data(); const int32_t nq = C.queries->n;
+    int64_t limit = P.batch_bases;
+    if (!P.fixed && per_base > 0) limit = range_density_limit(P.batch_bases, per_base);
+    for (int32_t q0 = 0; q0 < nq; ) {
+        const int32_t q1 = range_cut(len, nq, q0, limit);
+        TRY(run_range(ctx, C, q0, q1));
+        if (density_update(ctx, C.ix) && !P.fixed) limit = range_density_limit(P.batch_bases, C.ix->anchors_per_base);
+        q0 = q1;
+    }
+    return TELR_OK;
+}
+
+// per-query targets: ONE range when the device has room for it (what such a call waits for is its longest chaining run, once per range: two
+// ranges in turn took 1.57 s per 1,000 c2r loci, one range 0.88), the ranges of the plan in turn when it has not
+static int run_in_turn(telr_ctx *ctx, const MapCall &C, const RangePlan &P)
+{
+    int r = P.total_bases <= (1600LL << 20) ? run_range(ctx, C, 0, C.queries->n) : TELR_E_NOMEM;
+    if (r == TELR_OK && getenv("TELR_TEST_PIPE_NOMEM")) r = TELR_E_NOMEM;      // tests: exercise the fall-back
+    if (r == TELR_E_NOMEM) {
+        (void)hipGetLastError();          // (the failed allocation's error is sticky for this thread)
+        mem_note(ctx, "telr_map: one range with per-query targets ran out");
+        (void)hipDeviceSynchronize();
+        result_rollback(C.R);
+        call_reset(ctx); ctx->err.clear();
+        r = TELR_OK;
+        for (size_t i = 0; i < P.ranges.size() && r == TELR_OK; ++i) r = run_range(ctx, C, P.ranges[i].first, P.ranges[i].second);
+    }
+    if (r == TELR_OK) density_update(ctx, C.ix);
+    return r;
+}
+
+// two ranges in flight on two slots, the context and a second one of the same kind; one at a time when the two do not fit
+static int run_two_slots(telr_ctx *ctx, const MapCall &C, const RangePlan &P)
+{
+    if (!ctx->slot1) TRY(ctx_init(ctx->device, ctx->background, &ctx->slot1));
+    telr_ctx *S[2] = { ctx, ctx->slot1 };
+    S[1]->twin_owner = ctx; S[1]->twin_bases = P.total_bases;
+    call_reset(S[1]); S[1]->err.clear();
+    int rc[2] = { TELR_OK, TELR_OK };
+    std::atomic<size_t> next_range{0};
+    auto slot = [&](int s) {
+        (void)hipSetDevice(ctx->device);
+        for (size_t i; (i = next_range.fetch_add(1)) < P.ranges.size(); ) {        // whichever slot is free takes the next range; results are appended in range order (turn gate)
+            int r = run_range(S[s], C, P.ranges[i].first, P.ranges[i].second, (int)i);
+            gate_leave(C.R, (int)i, r == TELR_OK);
+            if (r != TELR_OK) { rc[s] = r; return; }
+        }
+    };
+    std::thread t1(slot, 1);
+    slot(0);
+    t1.join();
+    // the failing range's error, not that of the range it made leave
+    int prc = TELR_OK;
+    for (int s = 0; s < 2 && prc == TELR_OK; ++s) if (rc[s] != TELR_OK && S[s]->err != "an earlier range of the call failed") { if (s) ctx->err = S[1]->err; prc = rc[s]; }
+    for (int s = 0; s < 2 && prc == TELR_OK; ++s) if (rc[s] != TELR_OK) { if (s) ctx->err = S[1]->err; prc = rc[s]; }
+    const bool test_nomem = prc == TELR_OK && getenv("TELR_TEST_PIPE_NOMEM");      // tests: exercise the fall-back below
+    if (test_nomem) prc = TELR_E_NOMEM;
+    if (prc == TELR_E_NOMEM) {
+        if (!test_nomem) ctx->pipe_nomem = true;
+        // two ranges in flight did not fit (a device shared with something else, a denser index than the hint said, or
+        // the BAM writer's buffers of an earlier call still held): give the second slot's scratch and the writer's
+        // buffers back and run the call again one range at a time, in ranges of 1 Gbp at most
+        (void)hipGetLastError();          // the failed allocation's error is sticky for this thread: the next launch check would report it again
+        mem_note(ctx, "telr_map: two ranges in flight ran out");
+        telr_destroy(ctx->slot1); ctx->slot1 = nullptr;
+        (void)hipDeviceSynchronize();
+        for (auto &kv : ctx->bufs) if (kv.first.compare(0, 4, "bam_") == 0 && kv.second.p) { (void)hipFree(kv.second.p); kv.second.p = nullptr; kv.second.bytes = 0; }
+        result_rollback(C.R);
+        mem_note(ctx, "telr_map: after giving back slot 2 + writer");
+        call_reset(ctx);
+        const int32_t *len = C.queries->len.data(); const int32_t nq = C.queries->n;
+        const int64_t lim = std::min<int64_t>(P.batch_bases, 1024LL << 20);
+        for (int32_t q0 = 0; q0 < nq; ) {
+            const int32_t q1 = range_cut(len, nq, q0, lim);
+            TRY(run_range(ctx, C, q0, q1));
+            q0 = q1;
+        }
+    } else if (prc != TELR_OK) return prc;
+    else call_merge(ctx, S[1]);
+    density_update(ctx, C.ix);
+    return TELR_OK;
+}
+
 extern "C" int telr_map(telr_ctx *ctx, const telr_index *ix, const telr_seqset *queries, const int32_t *qtarget, const telr_map_opt *mo, telr_result **out)
 {
     (void)hipGetLastError();          // a failed allocation of an EARLIER call leaves its error with the thread: not this call's
@@ -2429,10 +2618,7 @@ extern "C" int telr_map(telr_ctx *ctx, const telr_index *ix, const telr_seqset *
     TRY(check_map_opt(ctx, mo));
     if (queries->max_len >= (1 << 24)) return TELR_E_RANGE;
     HIPCHK(hipSetDevice(ctx->device));
-    memset(ctx->stage_ms, 0, sizeof(ctx->stage_ms));
-    memset(&ctx->ctr, 0, sizeof(ctx->ctr));
-    memset(ctx->dpcls, 0, sizeof(ctx->dpcls));
-    ctx->dp_retries = 0; ctx->pk_launches = 0; ctx->st_pending = 0;
+    call_reset(ctx);
     const int nq = queries->n;
     if (qtarget) for (int i = 0; i < nq; ++i) if (qtarget[i] >= ix->targets->n) return TELR_E_ARG;
     int32_t *d_qt = nullptr;
@@ -2451,160 +2637,33 @@ extern "C" int telr_map(telr_ctx *ctx, const telr_index *ix, const telr_seqset *
         ctx->aln_pool.erase(ctx->aln_pool.begin() + best);
     }
     const auto t_wall0 = std::chrono::steady_clock::now();
-    int64_t total_bases = 0;
-    for (int i = 0; i < nq; ++i) total_bases += queries->len[i];
-    ctx->twin_owner = ctx; ctx->twin_bases = total_bases;
-    {
-        // Ranges bounded by bases: a read set of any size streams through as consecutive ranges.  HBM is 288 GB and a range
-        // needs ~75 B of scratch per read base at 0.25 anchors per base: a read set of up to 1.6 Gbp is ONE range (configs[2]
-        // reads alone in ranges of 0.5 / 1 / 1.4 / 2.1 Gbp: 13.7 / 14.9 / 15.3 / 15.5 Gbp/s -- fewer synchronisation points and
-        // tails; 151 GB in use at 2.1), a larger one is cut into ranges of at most 1.4 Gbp that run two at a time (below; the
-        // scratch of context and second slot is grow-only: ~115 + ~100 GB at this density).  What really bounds a range is its
-        // anchors (int32 offsets, ~50 B each): ranges hold at most 1.6 G anchors (0.8 G each when two are in flight) at the
-        // density the last call on the index has seen -- before any call, at an upper bound computed from the index's
-        // occurrence counts; a range that overflows all the same is halved by map_range.
-        int64_t batch_bases = 1600LL << 20;
-        bool fixed = false;
-        if (const char *e = getenv("TELR_BATCH_MBP")) { long v = atol(e); if (v > 0) { batch_bases = (int64_t)v << 20; fixed = true; } }
-        if (const char *e = getenv("TELR_BATCH_KBP")) { long v = atol(e); if (v > 0) { batch_bases = (int64_t)v << 10; fixed = true; } }     // tests
-        // Range pipelining: a read set that needs more than one range runs TWO ranges at a time on two slots (the context and
-        // a second one of the same kind), so the host work between the stages of a range -- synchronisations, the second
-        // selection pass, the record assembly -- and its latency-bound stretches are covered by the other range's kernels;
-        // results are appended in range order through the turn gate of the result (round 2: configs[2] from 15.7 to 16.5-17.4 Gbp/s,
-        // ranges of 0.7-1.6 Gbp: flat).  A read set that fits ONE range is halved when it holds 0.67 Gbp or more (below that the halves lose: 5-17 % at
-        // 0.4-0.5 Gbp).  TELR_PIPELINE=1 switches it off; =force pipelines any multi-range call (tests).
-        int pipe = 2; bool force = false;
-        if (const char *e = getenv("TELR_PIPELINE")) { force = !strcmp(e, "force"); pipe = force || atoi(e) >= 2 ? 2 : 1; }
-        // Round 6: a call with per-query targets (S6: every window read against the forward and the reverse-complement contig of its locus,
-        // 0.75-0.9 Gbp; the polishing map) runs its ranges one at a time: it shares the device with the other calls of the loci pass already,
-        // and on the hard genome its ranges are a few long chaining / sorting kernels on reads that bring 10^6 anchors each -- two in flight took
-        // 0.96 or 1.45 s per 1,000 c2r loci from pass to pass, one at a time 0.89; configs[2]: 96 -> 90 ms (profiles/r06_chain_loop_choice_ab.txt, part 8).
-        if (ctx->pipe_nomem || (!force && (ctx->debug || nq < 4000))) pipe = 1;
-        const bool in_turn = pipe == 2 && qtarget && !force;          // one range, or the ranges of the plan below in turn (no more scratch per range than two in flight took)
-        if (pipe == 2 && !fixed) {
-            // ranges of at most 1.4 Gbp (two in flight: ~200 GB of scratch at configs[2]'s anchor density) and at most 1.6 G
-            // anchors at the density seen by the last call on this index; a read set within one such range is not split
-            int64_t cap = 1400LL << 20;
-            // sub-read voting carries ~25 B per query base more (hits staged at 8 B each, compacted minimizers): two 1.4-Gbp
-            // ranges in flight fill the device (2 x 152 GB measured at configs[3]) and leave the BAM writer nothing
-            if (mo->vote_len > 0 && !qtarget && !(mo->flags & TELR_MF_PER_TARGET)) cap = 1100LL << 20;
-            const double per_base = ix->anchors_per_base > 0 ? ix->anchors_per_base : call_density_bound(ix, mid_occ.mid_occ, mo);
-            if (per_base > 0) cap = std::min<int64_t>(cap, std::max<int64_t>(256LL << 20, (int64_t)(0.8e9 / per_base)));      // two in flight: half the anchor budget each
-            // ... or that is large enough for two halves in flight to win: measured on configs[2] reads, two ranges against one:
-            // 0.40 Gbp 30.7 / 27.4 ms, 0.51 Gbp 32.9 / 33.9, 0.81 Gbp 47.2 / 51.3, 1.01 Gbp 57.3 / 63.2 (the shard of a 4-rank run)
-            if (total_bases > std::min<int64_t>(batch_bases, (int64_t)(per_base > 0 ? 1.6e9 / per_base : 1e18)) || total_bases >= (640LL << 20) || force) {
-                int64_t nr = std::max<int64_t>(2, (total_bases + cap - 1) / cap);
-                nr += nr & 1;          // an even number of equal ranges keeps both slots busy to the end (configs[2]: 3 ranges 215 ms, 4 ranges 205 ms per step)
-                batch_bases = (total_bases + nr - 1) / nr + queries->max_len + 1;      // the slack keeps the greedy cut below from leaving a stub range behind
-            } else pipe = 1;
-        }
-        std::vector<std::pair<int32_t, int32_t>> ranges;
-        for (int32_t q0 = 0; q0 < nq; ) {
-            int32_t q1 = q0; int64_t b = 0;
-            while (q1 < nq && (q1 == q0 || b + queries->len[q1] <= batch_bases)) { b += queries->len[q1]; ++q1; }
-            ranges.push_back(std::make_pair(q0, q1));
-            q0 = q1;
-        }
-        { static const bool tr = trace_on("host");
-          if (tr) fprintf(stderr, "[host plan] %d queries, %.1f Mbp, %zu range(s) of <= %.1f Mbp, %s, anchors per base seen %.3f%s\n", nq, total_bases / 1048576.0, ranges.size(), batch_bases / 1048576.0,
-                          pipe == 2 && ranges.size() >= 2 && !in_turn ? "two in flight" : "one at a time", ix->anchors_per_base, qtarget ? ", per-query targets" : ""); }
-        if (in_turn && ranges.size() >= 2) {
-            // ONE range when the device has room for it (what such a call waits for is its longest chaining run, once per range: two ranges
-            // in turn took 1.57 s per 1,000 c2r loci, one range 0.88), the ranges of the plan above in turn when it has not
-            int r = total_bases <= (1600LL << 20) ? map_range(ctx, ix, queries, qtarget, d_qt, 0, nq, mo, mid_occ, R) : TELR_E_NOMEM;
-            if (r == TELR_OK && getenv("TELR_TEST_PIPE_NOMEM")) r = TELR_E_NOMEM;      // tests: exercise the fall-back
-            if (r == TELR_E_NOMEM) {
-                (void)hipGetLastError();          // (the failed allocation's error is sticky for this thread)
-                mem_note(ctx, "telr_map: one range with per-query targets ran out");
-                (void)hipDeviceSynchronize();
-                result_wait(R); R->alns.clear(); R->ncig = 0; R->twin_n = 0;
-                { std::lock_guard<std::mutex> lk(R->gate_m); R->turn = 0; }
-                memset(ctx->stage_ms, 0, sizeof(ctx->stage_ms)); memset(&ctx->ctr, 0, sizeof(ctx->ctr)); memset(ctx->dpcls, 0, sizeof(ctx->dpcls));
-                ctx->dp_retries = 0; ctx->pk_launches = 0; ctx->st_pending = 0; ctx->err.clear();
-                r = TELR_OK;
-                for (size_t i = 0; i < ranges.size() && r == TELR_OK; ++i) r = map_range(ctx, ix, queries, qtarget, d_qt, ranges[i].first, ranges[i].second, mo, mid_occ, R);
-            }
-            if (r != TELR_OK) { delete R; return r; }
-            if (ctx->ctr.anchors > 0 && ctx->ctr.query_bases > (64LL << 20)) ix->anchors_per_base = (double)ctx->ctr.anchors / (double)ctx->ctr.query_bases;
-        } else if (pipe == 2 && ranges.size() >= 2) {
-            if (!ctx->slot1) {
-                int r = ctx_init(ctx->device, ctx->background, &ctx->slot1);
-                if (r != TELR_OK) { delete R; return r; }
-            }
-            telr_ctx *P[2] = { ctx, ctx->slot1 };
-            P[1]->twin_owner = ctx; P[1]->twin_bases = total_bases;
-            { telr_ctx *c = P[1]; memset(c->stage_ms, 0, sizeof(c->stage_ms)); memset(&c->ctr, 0, sizeof(c->ctr)); memset(c->dpcls, 0, sizeof(c->dpcls)); c->dp_retries = 0; c->pk_launches = 0; c->st_pending = 0; c->err.clear(); }
-            int rc[2] = { TELR_OK, TELR_OK };
-            std::atomic<size_t> next_range{0};
-            auto slot = [&](int s) {
-                (void)hipSetDevice(ctx->device);
-                for (size_t i; (i = next_range.fetch_add(1)) < ranges.size(); ) {        // whichever slot is free takes the next range; results are appended in range order (turn gate)
-                    int r = map_range(P[s], ix, queries, qtarget, d_qt, ranges[i].first, ranges[i].second, mo, mid_occ, R, (int)i);
-                    gate_leave(R, (int)i, r == TELR_OK);
-                    if (r != TELR_OK) { rc[s] = r; return; }
-                }
-            };
-            std::thread t1(slot, 1);
-            slot(0);
-            t1.join();
-            // the failing range's error, not that of the range it made leave
-            int prc = TELR_OK;
-            for (int s = 0; s < 2 && prc == TELR_OK; ++s) if (rc[s] != TELR_OK && P[s]->err != "an earlier range of the call failed") { if (s) ctx->err = P[1]->err; prc = rc[s]; }
-            for (int s = 0; s < 2 && prc == TELR_OK; ++s) if (rc[s] != TELR_OK) { if (s) ctx->err = P[1]->err; prc = rc[s]; }
-            const bool test_nomem = prc == TELR_OK && getenv("TELR_TEST_PIPE_NOMEM");      // tests: exercise the fall-back below
-            if (test_nomem) prc = TELR_E_NOMEM;
-            if (prc == TELR_E_NOMEM) {
-                if (!test_nomem) ctx->pipe_nomem = true;
-                // two ranges in flight did not fit (a device shared with something else, a denser index than the hint said, or
-                // the BAM writer's buffers of an earlier call still held): give the second slot's scratch and the writer's
-                // buffers back and run the call again one range at a time, in ranges of 1 Gbp at most
-                (void)hipGetLastError();          // the failed allocation's error is sticky for this thread: the next launch check would report it again
-                mem_note(ctx, "telr_map: two ranges in flight ran out");
-                telr_destroy(ctx->slot1); ctx->slot1 = nullptr;
-                (void)hipDeviceSynchronize();
-                for (auto &kv : ctx->bufs) if (kv.first.compare(0, 4, "bam_") == 0 && kv.second.p) { (void)hipFree(kv.second.p); kv.second.p = nullptr; kv.second.bytes = 0; }
-                result_wait(R); R->alns.clear(); R->ncig = 0; R->twin_n = 0;
-                { std::lock_guard<std::mutex> lk(R->gate_m); R->turn = 0; }
-                mem_note(ctx, "telr_map: after giving back slot 2 + writer");
-                memset(ctx->stage_ms, 0, sizeof(ctx->stage_ms)); memset(&ctx->ctr, 0, sizeof(ctx->ctr)); memset(ctx->dpcls, 0, sizeof(ctx->dpcls));
-                ctx->dp_retries = 0; ctx->pk_launches = 0; ctx->st_pending = 0;
-                int64_t lim = std::min<int64_t>(batch_bases, 1024LL << 20);
-                prc = TELR_OK;
-                for (int32_t q0 = 0; q0 < nq && prc == TELR_OK; ) {
-                    int32_t q1 = q0; int64_t b = 0;
-                    while (q1 < nq && (q1 == q0 || b + queries->len[q1] <= lim)) { b += queries->len[q1]; ++q1; }
-                    prc = map_range(ctx, ix, queries, qtarget, d_qt, q0, q1, mo, mid_occ, R);
-                    q0 = q1;
-                }
-                if (prc != TELR_OK) { delete R; return prc; }
-            } else if (prc != TELR_OK) { delete R; return prc; }
-            else
-            { telr_ctx *c = P[1];
-              for (int z = 0; z < TELR_N_STAGES; ++z) ctx->stage_ms[z] += c->stage_ms[z];
-              const int64_t *src = (const int64_t*)&c->ctr; int64_t *dst = (int64_t*)&ctx->ctr;
-              for (size_t z = 0; z < sizeof(telr_counters) / 8; ++z) dst[z] += src[z];
-              for (int z = 0; z < TELR_N_DPCLS * 4; ++z) ctx->dpcls[z] += c->dpcls[z];
-              ctx->dp_retries += c->dp_retries; ctx->pk_launches += c->pk_launches; }
-            if (ctx->ctr.anchors > 0 && ctx->ctr.query_bases > (64LL << 20)) ix->anchors_per_base = (double)ctx->ctr.anchors / (double)ctx->ctr.query_bases;
-        } else {
-            auto limit_for = [&](double per_base) { return std::min<int64_t>(batch_bases, std::max<int64_t>(256LL << 20, (int64_t)(1.6e9 / per_base))); };
-            int64_t limit = batch_bases;
-            if (!fixed) { const double pb = ix->anchors_per_base > 0 ? ix->anchors_per_base : call_density_bound(ix, mid_occ.mid_occ, mo); if (pb > 0) limit = limit_for(pb); }
-            for (int32_t q0 = 0; q0 < nq; ) {
-                int32_t q1 = q0; int64_t b = 0;
-                while (q1 < nq && (q1 == q0 || b + queries->len[q1] <= limit)) { b += queries->len[q1]; ++q1; }
-                int r = map_range(ctx, ix, queries, qtarget, d_qt, q0, q1, mo, mid_occ, R);
-                if (r != TELR_OK) { delete R; return r; }
-                if (ctx->ctr.anchors > 0 && ctx->ctr.query_bases > (64LL << 20)) {
-                    ix->anchors_per_base = (double)ctx->ctr.anchors / (double)ctx->ctr.query_bases;
-                    if (!fixed) limit = limit_for(ix->anchors_per_base);
-                }
-                q0 = q1;
-            }
-        }
-    }
+    // the anchor density the plan and the serial limit go by: what the last call on the index has seen, before any call a bound from
+    // the index's occurrence counts (a range size fixed by the environment asks for neither)
+    int64_t env_bases = 0; double per_base = 0;
+    if (!range_size_from_env(&env_bases)) per_base = ix->anchors_per_base > 0 ? ix->anchors_per_base : call_density_bound(ix, mid_occ.mid_occ, mo);
+    const bool vote = mo->vote_len > 0 && !qtarget && !(mo->flags & TELR_MF_PER_TARGET);
+    const RangePlan P = plan_ranges(queries->len.data(), nq, queries->max_len, per_base, qtarget != nullptr, vote, ctx->debug, ctx->pipe_nomem);
+    ctx->twin_owner = ctx; ctx->twin_bases = P.total_bases;
+    { static const bool tr = trace_on("host");
+      if (tr) fprintf(stderr, "[host plan] %d queries, %.1f Mbp, %zu range(s) of <= %.1f Mbp, %s, anchors per base seen %.3f%s\n", nq, P.total_bases / 1048576.0, P.ranges.size(), P.batch_bases / 1048576.0,
+                      P.mode == RANGE_TWO ? "two in flight" : "one at a time", ix->anchors_per_base, qtarget ? ", per-query targets" : ""); }
+    const MapCall C = { ix, queries, qtarget, d_qt, mo, mid_occ, R };
+    const int r = P.mode == RANGE_IN_TURN ? run_in_turn(ctx, C, P) : P.mode == RANGE_TWO ? run_two_slots(ctx, C, P) : run_serial(ctx, C, P, per_base);
+    if (r != TELR_OK) { delete R; return r; }
     ctx->stage_ms[ST_MAP_WALL] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_wall0).count();
     *out = R;
+    return TELR_OK;
+}
+
+// the plan of a call on reads of these lengths, without a device (tests/test_map_plan.py): out[0] mode (0 one range at a time, 1 in turn,
+// 2 two in flight), out[1] batch_bases, out[2] the number of ranges; range_end[i] the end of range i when range_end is given (n entries suffice)
+extern "C" int telr_debug_map_plan(const int32_t *len, int32_t n, int32_t max_len, double per_base, int has_qtarget, int vote, int debug, int pipe_nomem,
+                                   int64_t *out, int32_t *range_end)
+{
+    if (n < 0 || (n > 0 && !len) || !out) return TELR_E_ARG;
+    const RangePlan P = plan_ranges(len, n, max_len, per_base, has_qtarget != 0, vote != 0, debug, pipe_nomem != 0);
+    out[0] = P.mode; out[1] = P.batch_bases; out[2] = (int64_t)P.ranges.size();
+    if (range_end) for (size_t i = 0; i < P.ranges.size(); ++i) range_end[i] = P.ranges[i].second;
     return TELR_OK;
 }
 

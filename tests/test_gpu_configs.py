@@ -43,7 +43,7 @@ def _truth_ok(g, plan, ids, alns, slack=100):
 
 def test_c2_shape_many_chromosomes_ranges_and_lane(engine):
     """all eight dm6 arm lengths in one index; 0.6x of reads mapped as ONE call that the engine cuts into several ranges
-    (TELR_BATCH_MBP) each with its own long-read lane: same records as the un-split call; origins recovered"""
+    (TELR_BATCH_MBP), one at a time and two in flight: same records as the un-split call; origins recovered"""
     import os
     g = synth.make_genome(20261002, synth.DM6_ARMS, n_ins=200, threads=8)
     plan = synth.plan_reads(g, 0.6)
@@ -65,7 +65,7 @@ def test_c2_shape_many_chromosomes_ranges_and_lane(engine):
         del os.environ["TELR_BATCH_MBP"], os.environ["TELR_PIPELINE"]
     assert _digest_of_digests(_per_read_digest(res2.alns, res2.cigars)) == whole
     assert (np.diff(res2.alns["qid"]) >= 0).all()
-    # the same with two ranges in flight (range pipelining; default on calls of 200 Mbp and more)
+    # the same with two ranges in flight (range pipelining; default on calls of 4,000 reads and 640 Mbp and more)
     os.environ["TELR_BATCH_MBP"] = "12"; os.environ["TELR_PIPELINE"] = "force"
     try:
         res3 = ix.map(qs, mo)

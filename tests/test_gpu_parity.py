@@ -413,10 +413,16 @@ def test_pipelined_ranges(engine):
     reads[7:7] = long_reads[:3]; reads.extend(long_reads[3:]); reads.insert(20, np.zeros(0, np.uint8))
     io, mo = preset("map-ont")
     qt = np.array([i % 3 - 1 for i in range(len(reads))], np.int32)
+
+    def ranges_run_are_the_plan():
+        # one packed launch per range that had packed problems (every range of this input has): the ranges the call ran are the plan's
+        mode, _, ends = engine.map_plan([len(r) for r in reads], debug=int(os.environ.get("TELR_DEBUG", "0")))
+        assert int(engine.L.telr_debug_pk_launches(engine.h)) == len(ends), (mode, ends)
     for kbp in ("60", "45", "1000"):
         os.environ["TELR_PIPELINE"] = "force"; os.environ["TELR_BATCH_KBP"] = kbp
         try:
             res, _ = compare_all(engine, genome, reads, io, mo, stages=False)
+            ranges_run_are_the_plan()
             compare_all(engine, genome, reads, io, mo, qtarget=qt, stages=False)
         finally:
             del os.environ["TELR_PIPELINE"], os.environ["TELR_BATCH_KBP"]
@@ -426,6 +432,7 @@ def test_pipelined_ranges(engine):
     os.environ["TELR_PIPELINE"] = "force"; os.environ["TELR_BATCH_KBP"] = "60"; os.environ["TELR_TEST_PIPE_NOMEM"] = "1"
     try:
         res, _ = compare_all(engine, genome, reads, io, mo, stages=False)
+        ranges_run_are_the_plan()          # (the fall-back cuts under the same 60 kb: the count is that of the second run alone)
         res2, _ = compare_all(engine, genome, reads, io, mo, qtarget=qt, stages=False)
     finally:
         del os.environ["TELR_PIPELINE"], os.environ["TELR_BATCH_KBP"], os.environ["TELR_TEST_PIPE_NOMEM"]

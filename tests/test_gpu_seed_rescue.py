@@ -181,11 +181,10 @@ def test_two_family_both_bits(engine, pname):
 
 
 # the other launch paths of the seeding stage, each in a process of its own (the switches are read once per process): the two-step
-# seeding, the library sort, only the over-size queries two-step, compacted minimizer arrays, and several ranges
+# seeding, the library sort, compacted minimizer arrays, and several ranges
 PATHS = [
     {"TELR_AB": "seed_unfused"},
     {"TELR_AB": "sort64"},
-    {"TELR_AB": "over_routed"},
     {"TELR_AB": "mz_compact"},
     {"TELR_BATCH_KBP": "40"},
     {"TELR_BATCH_KBP": "40", "TELR_PIPELINE": "force"},
