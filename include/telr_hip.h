@@ -561,6 +561,60 @@ int64_t telr_drafts_count(const telr_drafts *d);                      /* = n_cal
 const telr_draft *telr_drafts_data(const telr_drafts *d);
 void telr_draft_contigs_free(telr_drafts *d);
 
+/* ---- a BAM file as input (opt-in).  The reference accepts a BAM as `--reads`: parse_input skips the alignment
+ *      (src/telr/TELR_input.py:300-305) and bam2fasta makes the read file with `samtools fasta`, first name wins (:329-361).  Here
+ *      the file is inflated and parsed on the device and becomes the two things the stage-1 consumers take: a resident read set and
+ *      a result whose CIGARs are resident (telr_call_insertions, telr_genotype_insertions, telr_draft_contigs, telr_window_reads,
+ *      telr_write_bam_dev, ...).  tests/bam_in_ref.py states the definition in plain Python.
+ * Framing:  BGZF members (magic 1f 8b 08 04, the BC subfield anywhere among the extra subfields, CRC32 and ISIZE <= 65,536 at the end);
+ *      members of ISIZE 0 anywhere; no_eof = 1 when the file does not end with the 28-byte EOF marker (accepted).  TELR_E_ARG with
+ *      "block K" in telr_last_error: a truncated member, bytes that are no member, a deflate stream that is invalid (an over-subscribed
+ *      code-length set, more than 286 / 30 symbols, no end-of-block code, bits that are no code, a length / distance symbol that does
+ *      not exist; an incomplete set is accepted), that gives more or fewer bytes than ISIZE, reaches before the member's start or reads
+ *      past its member, or a CRC mismatch.  Bytes between the stream's end and the trailer are ignored.  TELR_E_IO: the file cannot be read.
+ * Stream:   the BAM header (magic, text, references; SAM specification 4.2) and records to the stream's end, either across any number
+ *      of members.  A record that runs past the end, a block_size below 32, fields or tags that run past their record: TELR_E_ARG
+ *      with "record K" (file order, from 0).
+ * CIGAR of a mapped record (flag & 4 == 0, refID >= 0; refID >= n_ref or pos < 0 is TELR_E_ARG): the CG:B,I array when the record
+ *      holds exactly <l_seq>S <n>N and that tag.  An H first / last and an S first / last or next to that H are clips (clip5, clip3 =
+ *      their sums).  M = X -> M, D N -> D, I -> I, P and zero-length ops vanish, neighbours of one kind merge.  A clip elsewhere or
+ *      an op code above 8: TELR_E_ARG.  A merged length >= 2^28, or coordinates >= 2^31: TELR_E_RANGE.  No M / I / D: the record is
+ *      dropped (no_cigar).  qlen = clip5 + M + I + clip3, ts = pos, te = ts + M + D; qs = clip5, qe = qlen - clip3 forward,
+ *      qs = clip3, qe = qlen - clip5 with flag 0x10.
+ * Reads:    a record is sequence-bearing iff flag & 0x900 == 0, l_seq > 0 and it is unmapped or l_seq == qlen.  Read q = the q-th
+ *      distinct QNAME in file order of its first sequence-bearing record; its bases are that record's SEQ (1 2 4 8 -> A C G T, any
+ *      other code N), reverse-complemented with flag 0x10.  Qualities (Phred bytes, reversed with 0x10) are attached iff keep_qual
+ *      and no sequence-bearing record's QUAL starts with 0xff; a kept value above 93 is TELR_E_ARG.
+ * Records:  a mapped record with M / I / D is kept when its QNAME is a read's (else: orphans) and its qlen that read's length (else:
+ *      len_mismatch).  blen = M + I + D; mlen = max(0, blen - NM) with an NM tag, else M; dp_score, cnt, score, subsc = AS, cm, s1,
+ *      s2 (integer types c C s S i I, truncated to 32 bits; the last occurrence wins), else 0; n_sub = n_ambi = 0; mapq, tid = refID,
+ *      tlen from the header.  flags: 0x100 -> TELR_F_SECONDARY, 0x800 -> TELR_F_SUPPL, neither -> TELR_F_PRIMARY, 0x10 -> TELR_F_REV.
+ *      Order: qid, then class (neither; 0x800; 0x100), then file order; parent = the record's index within its read, 0 for a
+ *      secondary; CIGAR words packed in that order.  2^31 - 16 or more members, records or reads: TELR_E_RANGE.  A file that does
+ *      not fit into device memory next to its inflated stream: TELR_E_NOMEM (both live in the context's scratch until
+ *      telr_release_scratch).
+ * counters: members, records, mapped, kept, reads, orphans, len_mismatch, no_cigar, no_eof.  The set and the result belong to the
+ *      handle (telr_bam_in_free frees them) until detached; after that they are the caller's (telr_seqset_free / telr_result_free)
+ *      and the handle's accessors stay valid while they live.  Not read: .bai, CRAM, SAM, the header text beyond its length. */
+typedef struct telr_bam_in telr_bam_in;
+int  telr_bam_load(telr_ctx *ctx, const char *path, int32_t keep_qual, telr_bam_in **out);
+void telr_bam_in_free(telr_bam_in *in);
+int32_t telr_bam_in_target_count(const telr_bam_in *in);
+const char *const *telr_bam_in_target_names(const telr_bam_in *in);
+const int32_t *telr_bam_in_target_lens(const telr_bam_in *in);
+int32_t telr_bam_in_read_count(const telr_bam_in *in);
+const char *const *telr_bam_in_read_names(const telr_bam_in *in);
+const int32_t *telr_bam_in_read_lens(const telr_bam_in *in);
+telr_seqset *telr_bam_in_seqset(const telr_bam_in *in);
+telr_result *telr_bam_in_result(const telr_bam_in *in);
+telr_seqset *telr_bam_in_detach_seqset(telr_bam_in *in);      /* NULL when detached before */
+telr_result *telr_bam_in_detach_result(telr_bam_in *in);
+int  telr_bam_in_counters(const telr_bam_in *in, int64_t *out /* [9] */);
+/* the `bam2fasta` text, decoded on demand on the device: buf[off[q] .. off[q] + len[q]) = read q, off[q] = the bases before it */
+int  telr_bam_in_ascii(const telr_bam_in *in, char *buf, int64_t *off);
+/* wall-clock milliseconds of the load's phases: host hop, upload, inflate, chain, parse, names on the host, sequences, total */
+int  telr_bam_in_phase_ms(const telr_bam_in *in, float *out /* [8] */);
+
 /* ---- window reads (a12) -------------------------------------------------------
  * Replaces the per-locus `pysam.AlignmentFile(bam).fetch(chr, bp-1000, bp+1000)` loop of prep_assembly_inputs
  * (src/telr/TELR_assembly.py:384-415, read_type="all"): for every window w = (win_tid, [win_lo, win_hi)) the ascending,

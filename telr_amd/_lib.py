@@ -22,6 +22,9 @@ EXPORTS = [
     "telr_geno_opt_default", "telr_genotype_insertions", "telr_ins_geno_count", "telr_ins_geno_gt", "telr_ins_geno_ref_off", "telr_ins_geno_ref_reads",
     "telr_ins_geno_ambig_off", "telr_ins_geno_ambig_reads", "telr_ins_geno_free",
     "telr_draft_opt_default", "telr_draft_contigs", "telr_drafts_count", "telr_drafts_data", "telr_draft_contigs_free",
+    "telr_bam_load", "telr_bam_in_free", "telr_bam_in_target_count", "telr_bam_in_target_names", "telr_bam_in_target_lens", "telr_bam_in_read_count",
+    "telr_bam_in_read_names", "telr_bam_in_read_lens", "telr_bam_in_seqset", "telr_bam_in_result", "telr_bam_in_detach_seqset", "telr_bam_in_detach_result",
+    "telr_bam_in_counters", "telr_bam_in_ascii", "telr_bam_in_phase_ms",
 ]
 
 _lib = None
@@ -93,6 +96,18 @@ def lib():
     L.telr_drafts_count.restype = i64; L.telr_drafts_count.argtypes = [vp]
     L.telr_drafts_data.restype = vp; L.telr_drafts_data.argtypes = [vp]
     L.telr_draft_contigs_free.restype = None; L.telr_draft_contigs_free.argtypes = [vp]
+    L.telr_bam_load.restype = C.c_int; L.telr_bam_load.argtypes = [vp, cp, i32, C.POINTER(vp)]
+    L.telr_bam_in_free.restype = None; L.telr_bam_in_free.argtypes = [vp]
+    for fn in ("telr_bam_in_target_count", "telr_bam_in_read_count"):
+        getattr(L, fn).restype = i32; getattr(L, fn).argtypes = [vp]
+    for fn in ("telr_bam_in_target_names", "telr_bam_in_target_lens", "telr_bam_in_read_names", "telr_bam_in_read_lens", "telr_bam_in_seqset", "telr_bam_in_result",
+               "telr_bam_in_detach_seqset", "telr_bam_in_detach_result"):
+        getattr(L, fn).restype = vp; getattr(L, fn).argtypes = [vp]
+    L.telr_bam_in_counters.restype = C.c_int; L.telr_bam_in_counters.argtypes = [vp, vp]
+    L.telr_bam_in_ascii.restype = C.c_int; L.telr_bam_in_ascii.argtypes = [vp, vp, vp]
+    L.telr_bam_in_phase_ms.restype = C.c_int; L.telr_bam_in_phase_ms.argtypes = [vp, vp]
+    L.telr_debug_bgzf_inflate.restype = C.c_int; L.telr_debug_bgzf_inflate.argtypes = [vp, cp, vp, i64, C.POINTER(i64)]
+    L.telr_debug_seqset_qual.restype = i64; L.telr_debug_seqset_qual.argtypes = [vp, vp, i64]
     L.telr_window_reads.restype = C.c_int; L.telr_window_reads.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, i64, vp]
     L.telr_write_paf.restype = C.c_int; L.telr_write_paf.argtypes = [vp, vp, vp, C.c_int, cp, C.c_int]
     L.telr_write_sam.restype = C.c_int

@@ -81,6 +81,11 @@ class Engine:
     def index(self, targets, io):
         return Index(self, targets, io)
 
+    def load_bam(self, path, keep_qual=False):
+        """a BAM file as stage-1 input, inflated and parsed on the device (telr_bam_load; include/telr_hip.h has the definition)
+        -> BamInput.  keep_qual: attach the reads' base qualities to the read set when every sequence-bearing record has them"""
+        return BamInput(self, path, keep_qual)
+
     def stage_ms(self):
         a = np.zeros(N_STAGES, np.float32)
         self.L.telr_stage_ms(self.h, a.ctypes.data)
@@ -352,6 +357,85 @@ class MapResult:
 
     def cigar_string(self, i):
         return "".join("%d%s" % (c >> 4, "MID"[c & 0xf]) for c in self.cigar(i))
+
+
+class BamInput:
+    """what Engine.load_bam returns: tnames / tlens (the header's references), qnames (the reads, in file order of their first
+    sequence-bearing record), read_set (a SeqSet resident on the device, qualities attached when kept), result (a raw result handle with
+    its CIGARs resident: Index.call_insertions, genotype_insertions, draft_contigs, write_bam_device, result_arrays, ...), counters
+    (dict: members, records, mapped, kept, reads, orphans, len_mismatch, no_cigar, no_eof) and phase_ms (dict)"""
+    COUNTERS = ("members", "records", "mapped", "kept", "reads", "orphans", "len_mismatch", "no_cigar", "no_eof")
+    PHASES = ("host_hop", "upload", "inflate", "chain", "parse", "names_host", "sequences", "total")
+
+    def __init__(self, eng, path, keep_qual=False):
+        L = eng.L
+        self.eng = eng
+        h = C.c_void_p()
+        rc = L.telr_bam_load(eng.h, str(path).encode(), 1 if keep_qual else 0, C.byref(h))
+        if rc != 0:
+            raise _lib.TelrError("telr_bam_load: %s [%s]" % (L.telr_strerror(rc).decode(), L.telr_last_error(eng.h).decode()), rc)
+        self.h = h
+        nt, nq = int(L.telr_bam_in_target_count(h)), int(L.telr_bam_in_read_count(h))
+        self.tnames = [x.decode("latin-1") for x in _cstrs(L.telr_bam_in_target_names(h), nt)]
+        self.tlens = _np_from(L.telr_bam_in_target_lens(h), nt, np.int32)
+        self.qnames = [x.decode("latin-1") for x in _cstrs(L.telr_bam_in_read_names(h), nq)]
+        c = np.zeros(len(self.COUNTERS), np.int64); ph = np.zeros(len(self.PHASES), np.float32)
+        L.telr_bam_in_counters(h, c.ctypes.data); L.telr_bam_in_phase_ms(h, ph.ctypes.data)
+        self.counters = dict(zip(self.COUNTERS, (int(x) for x in c)))
+        self.phase_ms = dict(zip(self.PHASES, (float(x) for x in ph)))
+        # the set and the result become this object's: a SeqSet like any other, and a raw handle freed with the object
+        rs = SeqSet.__new__(SeqSet)
+        rs.eng = eng; rs.len = _np_from(L.telr_bam_in_read_lens(h), nq, np.int32); rs.n = nq
+        rs.h = C.c_void_p(L.telr_bam_in_detach_seqset(h))
+        self.read_set = rs
+        self.result = C.c_void_p(L.telr_bam_in_detach_result(h))
+        self._reads = None
+
+    def reads(self):
+        """the `bam2fasta` product as the (buffer, offsets, lengths) triple that seqset() and telr_sv.call_insertions take,
+        decoded on the device from the packed set (telr_bam_in_ascii), once"""
+        if self._reads is None:
+            ln = self.read_set.len
+            buf = np.zeros(max(1, int(ln.sum(dtype=np.int64))), np.uint8); off = np.zeros(max(1, len(ln)), np.int64)
+            self.eng._chk(self.eng.L.telr_bam_in_ascii(self.h, buf.ctypes.data, off.ctypes.data), "telr_bam_in_ascii")
+            self._reads = (buf[:int(ln.sum(dtype=np.int64))], off[:len(ln)], ln)
+        return self._reads
+
+    def map_result(self):
+        """-> MapResult: the records and CIGAR words on the host"""
+        L = self.eng.L
+        return MapResult(_np_from(L.telr_result_alns(self.result), L.telr_result_count(self.result), ALN_DTYPE),
+                         _np_from(L.telr_result_cigars(self.result), L.telr_result_cigar_count(self.result), np.uint32))
+
+    def write_fasta(self, path):
+        """the reads as FASTA, one line per sequence (what bam2fasta leaves behind, TELR_input.py:329-361)"""
+        buf, off, ln = self.reads()
+        with open(path, "wb") as f:
+            for n, o, l in zip(self.qnames, off, ln):
+                f.write(b">" + n.encode("latin-1") + b"\n" + buf[int(o):int(o) + int(l)].tobytes() + b"\n")
+
+    def check_targets(self, tnames, tlens):
+        """raises ValueError unless the file's references equal these by name, length and order (there is no remapping)"""
+        if list(self.tnames) != [n.decode() if isinstance(n, bytes) else str(n) for n in tnames] or [int(x) for x in self.tlens] != [int(x) for x in tlens]:
+            raise ValueError("the BAM's references are not the index's targets (names, lengths and order must agree)")
+
+    def free(self):
+        if getattr(self, "result", None):
+            self.eng.L.telr_result_free(self.result); self.result = None
+        if getattr(self, "h", None):
+            self.eng.L.telr_bam_in_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _cstrs(ptr, n):
+    if n == 0 or not ptr:
+        return []
+    return list((C.c_char_p * n).from_address(ptr))
 
 
 class InsCalls:

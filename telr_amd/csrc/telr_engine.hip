@@ -3658,3 +3658,4 @@ extern "C" int telr_write_bam(const telr_result *r, int32_t n_queries, const cha
 #include "inscall.hip.h"
 #include "genotype.hip.h"
 #include "draft.hip.h"
+#include "bam_in.hip.h"

@@ -40,6 +40,25 @@ def wait_release():
 atexit.register(wait_release)
 
 
+def bam_input(bam, out, sample_name, engine=None, index=None, keep_qual=False):
+    """The `.bam` branch of parse_input (TELR_input.py:300-305, 329-361): the alignment is skipped and the reads come out of the BAM.
+    The file is loaded on the device (Engine.load_bam); <out>/<sample_name>.telr.fasta is written as bam2fasta writes it (first
+    record of a name wins) and the BamInput is returned: its read_set and result are what alignment() + a re-read of the BAM would
+    have left on the device.  index: an Index whose targets the file's references must equal (names, lengths, order; ValueError).
+    A coordinate-sorted file needs no sort_index_bam; another order is accepted as it is."""
+    eng = engine or (index.eng if index is not None else Engine(0))
+    bi = eng.load_bam(bam, keep_qual=keep_qual)
+    if index is not None:
+        names = getattr(index, "tnames", None)
+        if names is not None:
+            bi.check_targets(names, index.targets.len)
+        elif [int(x) for x in bi.tlens] != [int(x) for x in index.targets.len]:
+            raise ValueError("the BAM's references are not the index's targets (lengths and order must agree)")
+    bi.write_fasta(os.path.join(out, sample_name + ".telr.fasta"))
+    logging.info("BAM input: %d reads, %d of %d mapped records kept" % (bi.counters["reads"], bi.counters["kept"], bi.counters["mapped"]))
+    return bi
+
+
 def alignment(bam, read, reference, out, sample_name, thread, method, presets, engine=None, chain_skip=False, seed_rescue=False, mm2_mapq=False,
               keep_qual=False):
     """keep_qual: carry the base qualities of a FASTQ `read` file into QUAL of the BAM, as ngmlr and `minimap2 -a` do (1 byte of
