@@ -238,6 +238,19 @@ int  telr_seqset_from_packed(telr_ctx *ctx, int32_t n, const int32_t *len, const
  * telr_amd/shard.py, which moves packed reads between ranks, writes 0xff). */
 int  telr_seqset_attach_qual(telr_ctx *ctx, telr_seqset *s, const char *qual_ascii, const int64_t *qual_off, int32_t phred_offset);
 int  telr_seqset_has_qual(const telr_seqset *s);
+/* Pieces of a resident set as text (tests/seq_extract_ref.py states the definition in plain Python).  Piece k is
+ * bases [start[k], start[k] + len[k]) of sequence idx[k]: the letters A C G T, N for a base whose mask bit is set; with rc[k] != 0
+ * (rc NULL = all forward) the piece is reverse-complemented, the complement of N being N.  Pieces may repeat, overlap and come in
+ * any order; len[k] == 0 writes nothing; no terminator is written.  The caller's `out` is dense: piece k at out[out_off[k] ..
+ * out_off[k + 1]), out_off[n + 1] with out_off[0] >= 0 and out_off[k + 1] - out_off[k] == len[k].  n == 0 returns TELR_OK and
+ * touches nothing.  The letters are made on the device from the packed words (one lane per 16 letters, each piece in a 16-byte
+ * aligned slot of the device text); only the pieces travel to the host, the set is not copied; the bytes are the same on every run.
+ * Everything is checked on the host before a kernel is launched, and a refused call leaves `out` untouched.  TELR_E_ARG (text in
+ * telr_last_error): a negative n, an idx outside the set, a negative start or len, start + len beyond the sequence, out_off not
+ * matching len, a null pointer where n > 0.  TELR_E_RANGE: 2^31 - 16 pieces or more, or slots (len rounded up to 16 bytes,
+ * summed) of 2^35 bytes or more in one call. */
+int  telr_seqset_extract(telr_ctx *ctx, const telr_seqset *s, int64_t n, const int32_t *idx, const int32_t *start, const int32_t *len,
+                         const uint8_t *rc /* NULL = all forward */, char *out, const int64_t *out_off /* [n + 1] */);
 
 /* ---- FASTA / FASTQ text -> the arrays above (host code; plain files, not gzip).  Replaces handing the file names to
  *      ngmlr / minimap2 (src/telr/TELR_alignment.py:31-51, 69-82).  Names end at the first white space. */

@@ -25,6 +25,7 @@ EXPORTS = [
     "telr_bam_load", "telr_bam_in_free", "telr_bam_in_target_count", "telr_bam_in_target_names", "telr_bam_in_target_lens", "telr_bam_in_read_count",
     "telr_bam_in_read_names", "telr_bam_in_read_lens", "telr_bam_in_seqset", "telr_bam_in_result", "telr_bam_in_detach_seqset", "telr_bam_in_detach_result",
     "telr_bam_in_counters", "telr_bam_in_ascii", "telr_bam_in_phase_ms",
+    "telr_seqset_extract",
 ]
 
 _lib = None
@@ -64,6 +65,7 @@ def lib():
     L.telr_seqset_count.restype = i32; L.telr_seqset_count.argtypes = [vp]
     L.telr_seqset_attach_qual.restype = C.c_int; L.telr_seqset_attach_qual.argtypes = [vp, vp, vp, vp, i32]
     L.telr_seqset_has_qual.restype = C.c_int; L.telr_seqset_has_qual.argtypes = [vp]
+    L.telr_seqset_extract.restype = C.c_int; L.telr_seqset_extract.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp]
     L.telr_index_build.restype = C.c_int; L.telr_index_build.argtypes = [vp, vp, C.POINTER(IdxOpt), C.POINTER(vp)]
     L.telr_index_free.restype = None; L.telr_index_free.argtypes = [vp]
     L.telr_index_stats.restype = C.c_int; L.telr_index_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]

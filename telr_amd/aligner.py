@@ -298,6 +298,31 @@ class SeqSet:
         sub.h = h; sub.len = self.len[idx].copy(); sub.n = len(idx)
         return sub
 
+    def extract(self, idx, start, length, rc=None):
+        """pieces of the resident set as text, cut on the device in ONE engine call (telr_seqset_extract; include/telr_hip.h has the
+        definition): piece k = bases [start[k], start[k] + length[k]) of sequence idx[k], reverse-complemented where rc[k] != 0 (rc None:
+        all forward) -> list of bytes, the letters A C G T and N as the set holds them.  Only the pieces come to the host."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        n = len(idx)
+        if len(start) != n or len(length) != n:
+            raise ValueError("extract: one start and one length per index")
+        if rc is not None:
+            rc = np.ascontiguousarray(rc, dtype=np.uint8)
+            if len(rc) != n:
+                raise ValueError("extract: one rc flag per index")
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(length, dtype=np.int64, out=off[1:])
+        out = np.zeros(max(1, int(off[-1])), np.uint8)          # (a negative length is refused before anything is written)
+        L = self.eng.L
+        code = L.telr_seqset_extract(self.eng.h, self.h, n, idx.ctypes.data, start.ctypes.data, length.ctypes.data,
+                                     None if rc is None else rc.ctypes.data, out.ctypes.data, off.ctypes.data)
+        if code != 0:
+            raise _lib.TelrError("telr_seqset_extract: %s [%s]" % (L.telr_strerror(code).decode(), L.telr_last_error(self.eng.h).decode()), code)
+        buf = out.tobytes()
+        return [buf[int(off[k]):int(off[k + 1])] for k in range(n)]
+
     def packed(self):
         """the set's two word arrays as torch int32 tensors ON THE DEVICE, zero-copy views of the library's memory (valid while
         the set lives): what the N > 1 hand-offs put on the wire (telr_seqset_packed)"""

@@ -3659,3 +3659,4 @@ extern "C" int telr_write_bam(const telr_result *r, int32_t n_queries, const cha
 #include "genotype.hip.h"
 #include "draft.hip.h"
 #include "bam_in.hip.h"
+#include "seq_extract.hip.h"

@@ -75,6 +75,9 @@ def draft_loci(index, result, ic, rows, read_set, reads, chrom_ids, window=1000,
     (buffer, offsets, lengths) triple), opt an `_abi.DraftOpt`.  The backbone pieces come from `index.draft_contigs` (not an assembler:
     one supporting read per call); `contig` is that piece sliced from `reads` (reverse-complemented on the reverse strand; A C G T, anything
     else N, as the device set holds it), `alt` the row's ins_seq, `read_idx` the window reads (`window_reads`).
+    reads may also be a resident `aligner.SeqSet` (read_set itself): the contig pieces (the drafts' qid, start, len, rc) are then cut on
+    the device in ONE `SeqSet.extract` call, and no host copy of the reads is needed.  The loci are equal between the two forms: both give
+    the letters as the set holds them.
     -> (list of dict(name, contig, alt, read_idx), the contigs' SeqSet in the same order -- `run_loci(..., contig_set=...)` --, the names
     of the calls without a draft)"""
     from . import telr_sv
@@ -84,15 +87,22 @@ def draft_loci(index, result, ic, rows, read_set, reads, chrom_ids, window=1000,
     drafts, cset = index.draft_contigs(result, ic, read_set, opt)
     wr = window_reads(index.result_arrays(result).alns, chrom_ids, rows, window) if len(rows) else []
 
+    cut = None
+    if hasattr(reads, "extract"):              # a resident set: every contig piece in one engine call
+        have = drafts[drafts["sig"] >= 0]
+        cut = iter(reads.extract(have["qid"], have["start"], have["len"], have["rc"] != 0))
     loci, skipped = [], []
     for k, row in enumerate(rows):
         d = drafts[k]
         if d["sig"] < 0:
             skipped.append(telr_sv.locus_name(row))
             continue
-        seq = as_packed(segment(reads, int(d["qid"]), int(d["start"]), int(d["len"])))
-        if d["rc"]:
-            seq = revcomp(seq)
+        if cut is not None:
+            seq = next(cut)
+        else:
+            seq = as_packed(segment(reads, int(d["qid"]), int(d["start"]), int(d["len"])))
+            if d["rc"]:
+                seq = revcomp(seq)
         loci.append(dict(name=telr_sv.locus_name(row), contig=seq.decode(), alt=row[7], read_idx=np.asarray(wr[k], np.int32)))
     return loci, cset, skipped
 

@@ -38,7 +38,11 @@ def call_insertions(index, result, tnames, qnames, reads, opt=None, sample="telr
     159-181).  Opt-in and NOT Sniffles: another definition of a call, whose agreement with Sniffles is not pinned.
     index: the aligner.Index the reads were mapped against; result: the raw handle of `index.map_raw`; tnames / qnames: target
     and read names by id; reads: the read sequences (a list of str / bytes, or the (buffer, offsets, lengths) triple given to
-    `seqset`); opt: an `_abi.InsOpt` (None = defaults).
+    `seqset`), or the resident `aligner.SeqSet` the result was mapped from: the ALT pieces (the representative signature's qid,
+    seg_start, seg_len and its record's strand) are then cut on the device in ONE `SeqSet.extract` call and only they come to the host.
+    For reads made only of upper-case A C G T N the rows are equal between the two forms; any other letter comes back as the set
+    holds it (lower case as upper case, U as T, anything else N), where host strings give the letter itself.
+    opt: an `_abi.InsOpt` (None = defaults).
     start = the call's position, end = start + 1, sv_length = the median length of the sized signatures, coverage = alt_count =
     the distinct supporting reads, ins_seq = the representative signature's segment of its read, on the reference strand.
     Rows are sorted by (target id, position), as `merge_rows` and `telr_assembly.window_reads` take them.
@@ -55,10 +59,17 @@ def call_insertions(index, result, tnames, qnames, reads, opt=None, sample="telr
     flags = _np_from(L.telr_result_alns(result), L.telr_result_count(result), ALN_DTYPE)["flags"] if len(ic.calls) else None
     gt = None if genotype is None or genotype is False else index.genotype_insertions(result, ic, None if genotype is True else genotype).gt
 
+    cut = None
+    if hasattr(reads, "extract"):              # a resident set: every ALT piece in one engine call
+        reps = [ic.sigs[c["rep"]] for c in ic.calls if c["rep"] >= 0]
+        cut = iter(reads.extract([int(s["qid"]) for s in reps], [int(s["seg_start"]) for s in reps], [int(s["seg_len"]) for s in reps],
+                                 [1 if int(flags[s["rec"]]) & F_REV else 0 for s in reps]))
     rows = []
     for k, c in enumerate(ic.calls):
         seq = b"N"
-        if c["rep"] >= 0:
+        if c["rep"] >= 0 and cut is not None:
+            seq = next(cut) or b"N"
+        elif c["rep"] >= 0:
             s = ic.sigs[c["rep"]]
             seq = segment(reads, int(s["qid"]), int(s["seg_start"]), int(s["seg_len"])) or b"N"
             if int(flags[s["rec"]]) & F_REV:
