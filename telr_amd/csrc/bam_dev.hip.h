@@ -24,8 +24,6 @@
 #include <unistd.h>
 #include <deque>
 
-#define BAM_BLK 65280            /* uncompressed bytes per BGZF block (as the host writer) */
-
 struct BamInfo { int32_t nm, md_len, cs_len, nI, nD; };
 struct BamArgs {
     const telr_aln *alns; int32_t nrec, n_mapped;
@@ -970,89 +968,6 @@ struct BamTimes { float ms[8]; };        // upload, scan+size, sort+scan, write,
 static BamTimes g_bam_times;
 extern "C" int telr_debug_bam_ms(float *out) { if (!out) return TELR_E_ARG; memcpy(out, g_bam_times.ms, sizeof(g_bam_times.ms)); return TELR_OK; }
 
-// the .bai of a coordinate-sorted record sequence: alns in sorted order through `order`, uncompressed start of every
-// record (sorted order, [nrec + 1]) and the file offset of every BGZF block ([nblk + 1])
-// Two steps, so that the long one needs nothing the coder produces: bai_build lays the whole index out with UNCOMPRESSED stream
-// offsets in the place of virtual file offsets (same order, and "same BGZF block" is "same 65,280-byte piece of the stream")
-// and notes where they stand; bai_finish, once the blocks' file offsets are known, rewrites those fields.
-static void bai_finish(std::string &bai, const std::vector<size_t> &fix, const uint64_t *coff, size_t nblk)
-{
-    auto voff = [&](uint64_t u) { size_t b = (size_t)(u / BAM_BLK); if (b >= nblk) return (uint64_t)(coff[nblk] << 16); return (uint64_t)(coff[b] << 16 | (u - (uint64_t)b * BAM_BLK)); };
-    for (size_t p : fix) { uint64_t u; memcpy(&u, &bai[p], 8); const uint64_t v = voff(u); memcpy(&bai[p], &v, 8); }
-}
-static void bai_build(const std::vector<telr_aln> &recs, const uint32_t *order, size_t nrec, size_t n_unmapped, const uint64_t *ustart,
-                      int32_t n_targets, const int32_t *t_len, std::string &bai, std::vector<size_t> &fix)
-{
-    auto put32 = [&](uint32_t v) { bai.append((const char*)&v, 4); };
-    auto put_off = [&](std::string &dst, size_t base, uint64_t u) { fix.push_back(base + dst.size()); dst.append((const char*)&u, 8); };      // base: where dst will start inside bai
-    auto voff = [&](uint64_t u) { return u; };
-    auto blk_of = [&](uint64_t u) { return u / BAM_BLK; };
-    fix.clear();
-    bai = "BAI\1"; put32((uint32_t)n_targets);
-    size_t i = 0;
-    const size_t n_mapped = nrec - n_unmapped;
-    struct Ch { uint32_t bin; uint64_t vb, ve; };
-    std::vector<Ch> chs;
-    for (int t = 0; t < n_targets; ++t) {
-        chs.clear();
-        const int n_lin = (t_len[t] >> 14) + 1;
-        std::vector<uint64_t> lin(n_lin, 0);
-        int max_lin = 0;
-        uint64_t ref_beg = 0, ref_end = 0, n_map = 0;
-        bool any = false;
-        while (i < n_mapped && recs[order[i]].tid == t) {
-            const telr_aln &a = recs[order[i]];
-            const uint64_t vb = voff(ustart[i]), ve = voff(ustart[i + 1]);
-            const int e = a.te > a.ts ? a.te : a.ts + 1;
-            chs.push_back(Ch{ (uint32_t)reg2bin(a.ts, e), vb, ve });
-            const int w0 = a.ts >> 14, w1 = (e - 1) >> 14;
-            for (int wv = w0; wv <= w1 && wv < n_lin; ++wv) { if (lin[wv] == 0 || vb < lin[wv]) lin[wv] = vb; if (wv + 1 > max_lin) max_lin = wv + 1; }
-            if (!any) { ref_beg = vb; any = true; }
-            ref_end = ve; ++n_map; ++i;
-        }
-        std::stable_sort(chs.begin(), chs.end(), [](const Ch &x, const Ch &y) { return x.bin < y.bin; });
-        // bins in ascending order, chunks of a bin merged while they end and start in the same BGZF block
-        std::string body; uint32_t nbin = 0;
-        for (size_t c0 = 0; c0 < chs.size(); ) {
-            size_t c1 = c0; std::vector<std::pair<uint64_t, uint64_t>> ch;
-            while (c1 < chs.size() && chs[c1].bin == chs[c0].bin) {
-                if (!ch.empty() && blk_of(ch.back().second) == blk_of(chs[c1].vb)) ch.back().second = chs[c1].ve; else ch.push_back(std::make_pair(chs[c1].vb, chs[c1].ve));
-                ++c1;
-            }
-            uint32_t bin = chs[c0].bin, nc = (uint32_t)ch.size();
-            body.append((const char*)&bin, 4); body.append((const char*)&nc, 4);
-            for (auto &c : ch) { put_off(body, bai.size() + 4, c.first); put_off(body, bai.size() + 4, c.second); }      // body goes in behind the 4-byte bin count
-            ++nbin; c0 = c1;
-        }
-        put32(nbin + (any ? 1 : 0));
-        bai += body;
-        if (any) {   // samtools' metadata pseudo-bin 37450
-            put32(37450u); put32(2u);
-            put_off(bai, 0, ref_beg); put_off(bai, 0, ref_end);
-            uint64_t zero = 0; bai.append((const char*)&n_map, 8); bai.append((const char*)&zero, 8);
-        }
-        for (int wv = 1; wv < max_lin; ++wv) if (lin[wv] == 0) lin[wv] = lin[wv - 1];
-        put32((uint32_t)max_lin);
-        // (a window before the first record of the reference keeps 0 = "from the start of the file", as it does with virtual offsets)
-        for (int wv = 0; wv < max_lin; ++wv) { if (lin[wv]) put_off(bai, 0, lin[wv]); else bai.append((const char*)&lin[wv], 8); }
-    }
-    uint64_t n_no_coor = n_unmapped;
-    bai.append((const char*)&n_no_coor, 8);
-}
-
-static std::string bam_header(int32_t n_targets, const char *const *tnames, const int32_t *t_len, const char *rg_id, const char *rg_sm, const char *rg_lb, const char *pg_line)
-{
-    std::string head, text = "@HD\tVN:1.6\tSO:coordinate\n";
-    char b[512];
-    for (int t = 0; t < n_targets; ++t) { snprintf(b, sizeof(b), "@SQ\tSN:%s\tLN:%d\n", tnames[t], t_len[t]); text += b; }
-    if (rg_id) { snprintf(b, sizeof(b), "@RG\tID:%s\tSM:%s\tLB:%s\n", rg_id, rg_sm ? rg_sm : rg_id, rg_lb ? rg_lb : "lib"); text += b; }
-    text += "@PG\tID:telr_amd\tPN:telr_amd\tVN:0.1.0\tCL:"; text += pg_line ? pg_line : "telr_map"; text += "\n";
-    auto put32 = [&](uint32_t v) { head.append((const char*)&v, 4); };
-    head += "BAM\1"; put32((uint32_t)text.size()); head += text; put32((uint32_t)n_targets);
-    for (int t = 0; t < n_targets; ++t) { uint32_t ln = (uint32_t)strlen(tnames[t]) + 1; put32(ln); head.append(tnames[t], ln); put32((uint32_t)t_len[t]); }
-    return head;
-}
-
 // ---- the output file, prepared ahead -----------------------------------------------------------------------------------
 // What a tmpfs file costs is the allocation of its pages and their way into the writer's page table (tools/ubench/shm_io.hip on
 // the MI355X box: pwrite into a fresh file 6.4-6.7 GB/s with one thread and LESS with more -- writes to one inode serialise --,
@@ -1620,10 +1535,15 @@ static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *
     float bai_ms = 0;
     // the index is laid out with stream offsets while the blocks are still being coded; their file offsets go in at the end
     std::vector<size_t> bai_fix;
-    if (write_index && !so) bai_th = std::thread([&] { auto tb0 = now(); bai_build(recs, h_order.data(), nrec, n_unmapped, h_ustart.data(), nt, tg->len.data(), bai, bai_fix); bai_ms = ms_since(tb0); });
+    // (sam_records.h: bai_build over offsets of the uncompressed stream, bai_finish below; the records are sorted here: always in file order)
+    if (write_index && !so) bai_th = std::thread([&] {
+        auto tb0 = now();
+        (void)bai_build(nrec - n_unmapped, [&](size_t i) { const telr_aln &a = recs[h_order[i]]; return BaiEntry{ a.tid, a.ts, a.te, h_ustart[i], h_ustart[i + 1] }; },
+                        [](uint64_t u) { return u / BAM_BLK; }, n_unmapped, nt, tg->len.data(), bai, &bai_fix);
+        bai_ms = ms_since(tb0);
+    });
     std::thread bai_starter;
     if (prog) bai_starter = std::thread([&] { if (producer.joinable()) producer.join(); });        // the block offsets are complete when the producer is
-    static const uint8_t eof_blk[28] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     if (so) {
         // slice mode: the image stays on the device (telr_bam_segment_write puts it at its place in the job's file once the
         // sizes of the slices before it are known); the records' coordinates and stream offsets go with it for the one index
@@ -1640,7 +1560,7 @@ static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *
         g_bam_times.ms[7] = ms_since(t_all);
         return rc;
     }
-    int rc = sink_to_file(ctx, d_c, cbytes, prog, eof_blk, 28, bam_path);
+    int rc = sink_to_file(ctx, d_c, cbytes, prog, BGZF_EOF, 28, bam_path);
     g_bam_times.ms[5] = ms_since(t0);
     if (bai_starter.joinable()) bai_starter.join();
     if (bai_th.joinable()) bai_th.join();
@@ -1709,7 +1629,6 @@ extern "C" int telr_bam_segment_write(telr_ctx *ctx, const telr_bam_segment *s, 
 {
     if (!ctx || !s || !path || file_off < 0 || s->ctx != ctx) return TELR_E_ARG;
     HIPCHK(hipSetDevice(ctx->device));
-    static const uint8_t eof_blk[28] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     const size_t tail = is_last ? 28 : 0, len = (size_t)s->cbytes + tail;
     int fd = open(path, O_RDWR);
     if (fd < 0) { ctx->err = std::string("cannot open ") + path; return TELR_E_ARG; }
@@ -1722,7 +1641,7 @@ extern "C" int telr_bam_segment_write(telr_ctx *ctx, const telr_bam_segment *s, 
         if (m != MAP_FAILED) { map = (uint8_t*)m; (void)madvise(map, map_len, 23 /* MADV_POPULATE_WRITE */); }
     }
     uint64_t total = 0;
-    rc = stream_to_file(ctx, s->d_img, s->cbytes, nullptr, eof_blk, tail, path, fd, map ? map + ((uint64_t)file_off - al) : nullptr, map ? len : 0, &total, nullptr, nullptr,
+    rc = stream_to_file(ctx, s->d_img, s->cbytes, nullptr, BGZF_EOF, tail, path, fd, map ? map + ((uint64_t)file_off - al) : nullptr, map ? len : 0, &total, nullptr, nullptr,
                         (uint64_t)file_off, true);
     if (map) munmap(map, map_len);
     close(fd);
@@ -1731,55 +1650,15 @@ extern "C" int telr_bam_segment_write(telr_ctx *ctx, const telr_bam_segment *s, 
 }
 // The .bai of a file whose records are described by arrays in FILE order (n mapped records: reference, start, end, virtual
 // offset of the first byte; v_end: the virtual offset behind the last of them; n_unmapped reads follow): what rank 0 writes
-// from the entries of all slices.  Same bins, chunk merging, linear index and metadata pseudo-bin as the one-rank writer.
+// from the entries of all slices.  The one index builder (sam_records.h), here over virtual offsets.
 extern "C" int telr_bai_write(const char *bai_path, int64_t n, const int32_t *tid, const int32_t *ts, const int32_t *te, const uint64_t *vb, uint64_t v_end,
                               int64_t n_unmapped, int32_t n_targets, const int32_t *t_len)
 {
     if (!bai_path || n < 0 || n_targets < 0 || (n && (!tid || !ts || !te || !vb)) || (n_targets && !t_len)) return TELR_E_ARG;
     std::string bai;
-    auto put32 = [&](uint32_t v) { bai.append((const char*)&v, 4); };
-    auto put64 = [&](std::string &d, uint64_t v) { d.append((const char*)&v, 8); };
-    bai = "BAI\1"; put32((uint32_t)n_targets);
-    int64_t i = 0;
-    struct Ch { uint32_t bin; uint64_t vb, ve; };
-    std::vector<Ch> chs;
-    for (int t = 0; t < n_targets; ++t) {
-        chs.clear();
-        const int n_lin = (t_len[t] >> 14) + 1;
-        std::vector<uint64_t> lin(n_lin, 0);
-        int max_lin = 0; uint64_t ref_beg = 0, ref_end = 0, n_map = 0; bool any = false;
-        while (i < n && tid[i] == t) {
-            const uint64_t b = vb[i], e_ = i + 1 < n ? vb[i + 1] : v_end;
-            const int e = te[i] > ts[i] ? te[i] : ts[i] + 1;
-            chs.push_back(Ch{ (uint32_t)reg2bin(ts[i], e), b, e_ });
-            const int w0 = ts[i] >> 14, w1 = (e - 1) >> 14;
-            for (int wv = w0; wv <= w1 && wv < n_lin; ++wv) { if (lin[wv] == 0 || b < lin[wv]) lin[wv] = b; if (wv + 1 > max_lin) max_lin = wv + 1; }
-            if (!any) { ref_beg = b; any = true; }
-            ref_end = e_; ++n_map; ++i;
-        }
-        if (i < n && tid[i] < t) return TELR_E_ARG;                 // not in file order
-        std::stable_sort(chs.begin(), chs.end(), [](const Ch &x, const Ch &y) { return x.bin < y.bin; });
-        std::string body; uint32_t nbin = 0;
-        for (size_t c0 = 0; c0 < chs.size(); ) {
-            size_t c1 = c0; std::vector<std::pair<uint64_t, uint64_t>> ch;
-            while (c1 < chs.size() && chs[c1].bin == chs[c0].bin) {
-                if (!ch.empty() && (ch.back().second >> 16) == (chs[c1].vb >> 16)) ch.back().second = chs[c1].ve; else ch.push_back(std::make_pair(chs[c1].vb, chs[c1].ve));
-                ++c1;
-            }
-            uint32_t bin = chs[c0].bin, nc = (uint32_t)ch.size();
-            body.append((const char*)&bin, 4); body.append((const char*)&nc, 4);
-            for (auto &c : ch) { put64(body, c.first); put64(body, c.second); }
-            ++nbin; c0 = c1;
-        }
-        put32(nbin + (any ? 1 : 0));
-        bai += body;
-        if (any) { put32(37450u); put32(2u); put64(bai, ref_beg); put64(bai, ref_end); put64(bai, n_map); put64(bai, 0); }
-        for (int wv = 1; wv < max_lin; ++wv) if (lin[wv] == 0) lin[wv] = lin[wv - 1];
-        put32((uint32_t)max_lin);
-        for (int wv = 0; wv < max_lin; ++wv) put64(bai, lin[wv]);
-    }
-    if (i != n) return TELR_E_ARG;
-    put64(bai, (uint64_t)n_unmapped);
+    const bool in_order = bai_build((size_t)n, [&](size_t i) { return BaiEntry{ tid[i], ts[i], te[i], vb[i], (int64_t)i + 1 < n ? vb[i + 1] : v_end }; },
+                                    [](uint64_t v) { return v >> 16; }, (uint64_t)n_unmapped, n_targets, t_len, bai, nullptr);
+    if (!in_order) return TELR_E_ARG;
     FILE *f = fopen(bai_path, "wb");
     if (!f) return TELR_E_ARG;
     const bool ok = fwrite(bai.data(), 1, bai.size(), f) == bai.size();

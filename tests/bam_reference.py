@@ -23,6 +23,9 @@ Choices of the writers that the specification leaves open, followed here because
     rules make the same number);
   * hard clips only on supplementary records without TELR_SAM_SOFTCLIP; a secondary keeps soft clips although its SEQ is `*`.
 Not modelled: `U` (the host writer reads it as T, the device as N; no input of the pipeline holds it).
+
+`sam_text` decodes such a stream to the SAM file telr_write_sam prints for the same records (tests/test_gpu_sam_text.py).  The text
+writer prints the read's own characters in SEQ where the stream has 4-bit codes: the two agree for reads of A C G T N in upper case.
 """
 import struct
 from collections import namedtuple
@@ -294,6 +297,63 @@ def bai_reference(stream, tlens):
                 R["linear"][w] = prev
             prev = R["linear"][w]
     return dict(refs=refs, n_no_coor=n_no_coor)
+
+
+# ---- the stream as SAM text ----------------------------------------------------------------------------------------------
+def sam_records(stream):
+    """the SAM lines (no newline) of the stream's records, in the stream's order.  Columns from the record's fixed part; tags
+    in the record's order (`i` -> :i:, `A` -> :A:, `Z` -> :Z:); SEQ `*` when l_seq is 0, QUAL `*` when it is 0 or the bytes are
+    0xff; a CG:B,I tag becomes the CIGAR column and is not printed (the text has no 65,535-operation limit)."""
+    raw = stream.raw
+    p = 8 + struct.unpack_from("<i", raw, 4)[0]
+    n_ref = struct.unpack_from("<i", raw, p)[0]; p += 4
+    tnames = []
+    for _ in range(n_ref):
+        ln = struct.unpack_from("<i", raw, p)[0]
+        tnames.append(raw[p + 4:p + 4 + ln - 1].decode()); p += 8 + ln
+    assert p == stream.head_len
+    lines = []
+    for r in stream.recs:
+        o = r["off"]
+        bs, refid, pos, lrn, mapq, _bin, ncig, flag, lseq, nref, npos, tlen = struct.unpack_from("<iiiBBHHHiiii", raw, o)
+        name = raw[o + 36:o + 36 + lrn - 1].decode()
+        ops = list(struct.unpack_from("<%dI" % ncig, raw, r["p_cig"]))
+        seq = "".join(SEQ_CODES[raw[r["p_seq"] + (x >> 1)] >> (0 if x & 1 else 4) & 15] for x in range(lseq))
+        qual = raw[r["p_qual"]:r["p_qual"] + lseq]
+        tags, t, e = [], r["p_tags"], o + 4 + bs
+        while t < e:
+            tag, ty = raw[t:t + 2].decode(), chr(raw[t + 2]); t += 3
+            if ty == "i":
+                tags.append("%s:i:%d" % (tag, struct.unpack_from("<i", raw, t)[0])); t += 4
+            elif ty == "A":
+                tags.append("%s:A:%s" % (tag, chr(raw[t]))); t += 1
+            elif ty == "Z":
+                z = raw.index(b"\0", t); tags.append("%s:Z:%s" % (tag, raw[t:z].decode())); t = z + 1
+            else:
+                assert (tag, ty, chr(raw[t])) == ("CG", "B", "I"), (tag, ty)
+                n = struct.unpack_from("<I", raw, t + 1)[0]
+                ops = list(struct.unpack_from("<%dI" % n, raw, t + 5)); t += 5 + 4 * n
+        assert t == e
+        cols = [name, "%d" % flag, tnames[refid] if refid >= 0 else "*", "%d" % (pos + 1), "%d" % mapq,
+                "".join("%d%s" % (c >> 4, CIGAR_OPS[c & 15]) for c in ops) or "*",
+                "*" if nref < 0 else "=" if nref == refid else tnames[nref], "%d" % (npos + 1), "%d" % tlen,
+                seq or "*", "*" if not lseq or qual == b"\xff" * lseq else bytes(b + 33 for b in qual).decode()]
+        lines.append("\t".join(cols + tags))
+    return lines
+
+
+def sam_text(stream, coordinate_sorted=True, keep=None):
+    """the SAM file telr_write_sam prints for the stream's records: the stream's own header text and one line per record.
+    coordinate_sorted: the stream's order.  Otherwise @HD says SO:unsorted GO:query and the lines stand in (read, rank) order,
+    which is the input order of the records, an unmapped read at its read's place.  keep(flag) -> bool drops lines."""
+    text = stream.raw[8:8 + struct.unpack_from("<i", stream.raw, 4)[0]].decode()
+    lines = list(zip(stream.recs, sam_records(stream)))
+    if not coordinate_sorted:
+        hd = "@HD\tVN:1.6\tSO:coordinate\n"
+        assert text.startswith(hd)
+        text = "@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + text[len(hd):]
+        lines.sort(key=lambda x: (x[0]["qid"], x[0]["idx"] if x[0]["idx"] is not None else -1))
+    return text + "".join(l + "\n" for r, l in lines if keep is None or keep(r["flag"]))
 
 
 # ---- reading files back (zlib + struct) ---------------------------------------------------------------------------------

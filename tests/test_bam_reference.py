@@ -110,6 +110,10 @@ def test_hand_derived_records(h):
     assert struct.unpack_from("<i", body, 0)[0] == len(body) - 4 and struct.unpack_from("<iii", body, 24) == (-1, -1, 0)
     q0 = 36 + 3 + 4 * len(ops) + (l_seq + 1) // 2
     assert body[q0:q0 + l_seq] == b"\xff" * l_seq and body[q0 + l_seq:] == tags
+    # the same record as SAM text: the table's own strings, SEQ spelled from its 4-bit codes
+    seq_txt = "".join({"1": "A", "2": "C", "4": "G", "8": "T", "f": "N"}[x] for x in seq_hex[:l_seq])
+    assert br.sam_records(s) == ["rd\t%d\ttg\t%d\t60\t%s\t*\t0\t0\t%s\t*\tNM:i:%d\tAS:i:-5\tMD:Z:%s\tcs:Z:%s\ttp:A:P\tcm:i:3\ts1:i:40\ts2:i:7"
+                                 % (16 if rev else 0, ts + 1, rec_cigar, seq_txt, nm, md, cs)]
 
 
 def test_hand_derived_tag_bytes_and_header():
@@ -122,6 +126,9 @@ def test_hand_derived_tag_bytes_and_header():
     want = (struct.pack("<iiiBBHHHiiii", 32 + 2 + 4 + 4 + 8 + 63, 0, 0, 2, 60, 4681, 1, 0, 8, -1, -1, 0) + b"r\0" + struct.pack("<I", 8 << 4) + bytes.fromhex("12411248") + b"\xff" * 8
             + b"NMi\1\0\0\0ASi\6\0\0\0MDZ3T4\0csZ:3*ta:4\0tpAPcmi\1\0\0\0s1i\x08\0\0\0s2i\0\0\0\0RGZg1\0")
     assert s.raw[s.head_len:] == want
+    line = "r\t0\tchr1\t1\t60\t8M\t*\t0\t0\tACGAACGT\t*\tNM:i:1\tAS:i:6\tMD:Z:3T4\tcs:Z::3*ta:4\ttp:A:P\tcm:i:1\ts1:i:8\ts2:i:0\tRG:Z:g1\n"
+    assert br.sam_text(s) == text + line
+    assert br.sam_text(s, coordinate_sorted=False) == "@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + text[text.index("@SQ"):] + line
 
 
 def test_hand_derived_sa_clips_secondary_and_unmapped():
@@ -144,8 +151,29 @@ def test_hand_derived_sa_clips_secondary_and_unmapped():
         assert order == ["NM", "AS", "tp", "cm", "s1"] and t["tp"] == ("A", "S") and sec[8] == 0 and sec[9] == b"" and cigar_text(sec[7]) == "8M7S"
         assert "SA" not in tags_of(z[10])[0]
         assert (un[3], un[4], un[7], un[8], un[9], un[10]) == (4680, 0, (), 3, bytes.fromhex("4f10"), b"")
+        # as SAM text: coordinate order, and the order of the reads with the unmapped one at its place
+        sq = "@SQ\tSN:t0\tLN:20\n@SQ\tSN:t1\tLN:20\n@PG\tID:telr_amd\tPN:telr_amd\tVN:0.1.0\tCL:x\n"
+        l_pri = "two\t0\tt0\t1\t60\t8M7S\t*\t0\t0\tACGTACGTTACGTAC\t*\tNM:i:0\tAS:i:0\tSA:Z:t1,3,-,7M8S,30,0;\ttp:A:P\tcm:i:0\ts1:i:0\ts2:i:0\n"
+        l_sec = "two\t256\tt0\t5\t0\t8M7S\t*\t0\t0\t*\t*\tNM:i:0\tAS:i:0\ttp:A:S\tcm:i:0\ts1:i:0\n"
+        l_z = "z\t0\tt1\t1\t60\t4M\t*\t0\t0\tACGT\t*\tNM:i:0\tAS:i:0\ttp:A:P\tcm:i:0\ts1:i:0\ts2:i:0\n"
+        l_sup = "two\t2064\tt1\t3\t30\t%s\t*\t0\t0\t%s\t*\tNM:i:0\tAS:i:0\tSA:Z:t0,1,+,8M7S,60,0;\ttp:A:P\tcm:i:0\ts1:i:0\ts2:i:0\n" % (clip, seq)
+        l_un = "lost\t4\t*\t0\t0\t*\t*\t0\t0\tGNA\t*\n"
+        assert br.sam_text(s) == "@HD\tVN:1.6\tSO:coordinate\n" + sq + l_pri + l_sec + l_z + l_sup + l_un
+        assert br.sam_text(s, coordinate_sorted=False) == "@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + sq + l_pri + l_sec + l_sup + l_un + l_z
+        assert br.sam_text(s, keep=lambda f: not f & 0x900) == "@HD\tVN:1.6\tSO:coordinate\n" + sq + l_pri + l_z + l_un
     s = br.bam_stream(al, np.array(cigs, np.uint32), reads, [T20, T20], names, ["t0", "t1"], br.SAM_NO_UNMAPPED, ("g", "g", "l"), "x")
     assert len(s.recs) == 4 and all(r[10].endswith(b"RGZg\0") for r in br.parse_records(s.raw))
+
+
+def test_hand_derived_reverse_primary_with_sa():
+    """a read whose first 7 bases lie on the reverse strand at t[1:8] with one mismatch (primary) and whose last 5 lie forward at
+    t[12:17] (supplementary).  The reverse strand of the read is TACGTCGTTCGT: 5 clipped bases, then CGTTCGT against CGTACGT."""
+    cigs = []
+    al = np.concatenate([aln(0, 0, 12, 0, 7, 1, "7M", F_PRIMARY | F_REV, cigs, mlen=6, blen=7), aln(0, 0, 12, 7, 12, 12, "5M", F_SUPPL, cigs, mapq=30, mlen=5, blen=5)])
+    s = br.bam_stream(al, np.array(cigs, np.uint32), ["ACGAACGACGTA"], [T20], ["rv"], ["tg"], br.SAM_MD | br.SAM_CS | br.SAM_SOFTCLIP, None, "x")
+    assert br.sam_records(s) == [
+        "rv\t16\ttg\t2\t60\t5S7M\t*\t0\t0\tTACGTCGTTCGT\t*\tNM:i:1\tAS:i:0\tMD:Z:3A3\tcs:Z::3*at:3\tSA:Z:tg,13,+,7S5M,30,0;\ttp:A:P\tcm:i:0\ts1:i:0\ts2:i:0",
+        "rv\t2048\ttg\t13\t30\t7S5M\t*\t0\t0\tACGAACGACGTA\t*\tNM:i:0\tAS:i:0\tMD:Z:5\tcs:Z::5\tSA:Z:tg,2,-,5S7M,60,1;\ttp:A:P\tcm:i:0\ts1:i:0\ts2:i:0"]
 
 
 def test_reg2bin_at_the_boundaries_of_every_level():
