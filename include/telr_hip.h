@@ -251,6 +251,15 @@ int  telr_seqset_has_qual(const telr_seqset *s);
  * summed) of 2^35 bytes or more in one call. */
 int  telr_seqset_extract(telr_ctx *ctx, const telr_seqset *s, int64_t n, const int32_t *idx, const int32_t *start, const int32_t *len,
                          const uint8_t *rc /* NULL = all forward */, char *out, const int64_t *out_off /* [n + 1] */);
+/* The same pieces as a NEW SET: sequence k of *out is bases [start[k], start[k] + len[k]) of parent[idx[k]],
+ * reverse-complemented when rc[k] != 0 (rc NULL = all forward); the mask bits are carried (an N stays an N), len[k] == 0 gives an empty
+ * sequence.  The set has the layout of any other set (64-base-aligned offsets) and is made on the device from the packed words of
+ * `parent` (the kernel telr_draft_contigs cuts its drafts with); no qualities are carried (as telr_seqset_subset).  n == 0 gives an
+ * empty set.  The set is the caller's (telr_seqset_free).  Checked on the host before any launch, with the codes of
+ * telr_seqset_extract: TELR_E_ARG for a negative n, an idx outside the set, a negative start or len, start + len beyond the sequence, a
+ * null pointer where n > 0; TELR_E_RANGE from 2^31 - 16 pieces on. */
+int  telr_seqset_pieces(telr_ctx *ctx, const telr_seqset *parent, int32_t n, const int32_t *idx, const int32_t *start, const int32_t *len,
+                        const uint8_t *rc /* NULL = all forward */, telr_seqset **out);
 
 /* ---- FASTA / FASTQ text -> the arrays above (host code; plain files, not gzip).  Replaces handing the file names to
  *      ngmlr / minimap2 (src/telr/TELR_alignment.py:31-51, 69-82).  Names end at the first white space. */
@@ -573,6 +582,49 @@ int  telr_draft_contigs(telr_ctx *ctx, const telr_result *r, int32_t n_targets, 
 int64_t telr_drafts_count(const telr_drafts *d);                      /* = n_calls */
 const telr_draft *telr_drafts_data(const telr_drafts *d);
 void telr_draft_contigs_free(telr_drafts *d);
+
+/* ---- the reference's TE copies, annotated on the device for the liftover (opt-in).  Stands where the reference masks
+ *      the reference genome with RepeatMasker and hands the BED to the liftover (src/telr/telr.py:132-159, TELR_te.py:391-469).  An OWN
+ *      definition and NOT RepeatMasker: the library is indexed, the reference is cut into overlapping tiles that are mapped to it as
+ *      queries, and the records become features by the interval rule below.  Hit sets differ from RepeatMasker's, above all for old,
+ *      diverged copies; agreement with it is unpinned.  tests/refte_ref.py states the definition in plain Python.
+ * Tiles (telr_tile_plan; host only, no device needed).  A target of length n gets no tile when n == 0, one when n <= tile, else
+ *      1 + ceil((n - tile) / stride); tile j = (tid, j * stride, min(tile, n - j * stride)), listed in (tid, start) order.  Every
+ *      interval of a target no longer than tile - stride + 1 lies whole inside at least one tile; no tile lies inside another.
+ *      *needed = the number of tiles; when it exceeds cap nothing is copied and TELR_E_RANGE is returned: call again with
+ *      cap >= *needed.  TELR_E_ARG: tile < 1, stride < 1 or > tile, tile >= 2^24 (the query limit of telr_map), a negative length, a
+ *      null pointer where it is needed.  TELR_E_RANGE from 2^31 - 16 tiles on.  The callers' defaults: tile 32,768, stride 16,384
+ *      (any library sequence up to 16 kb lies whole inside a tile).
+ * Features (telr_annotate_hits).  r = a result whose queries are the tiles (qid = the tile's index) and whose targets are the library
+ *      (tid = the family's index).
+ * Hit:     a record that is not TELR_F_SECONDARY, with mapq >= min_mapq and qe - qs >= min_len: tid = tiles[qid].tid,
+ *          start = tiles[qid].start + qs, end = tiles[qid].start + qe (qs / qe are on the forward query strand), family = rec.tid,
+ *          strand = 1 on TELR_F_REV else 0, score = dp_score.
+ * Order:   ascending by (tid, family, strand, start, end); hits with equal keys are interchangeable.
+ * Feature: inside a run of equal (tid, family, strand) hit i opens a new feature iff it is the run's first or
+ *          start_i >= M_i + join_gap, M_i = the maximum end of ALL earlier hits of the run (a running maximum, not the previous hit's
+ *          end).  join_gap 0: only true overlaps join, book-ended tandem copies stay apart; join_gap 1: `bedtools merge`.
+ *          Its fields: start of its first hit, maximum end, maximum score, n_hits.
+ * Output:  ascending by (tid, start, end, family, strand); the bytes are the same on every run.  No CIGAR is read.
+ * TELR_E_ARG (text in telr_last_error): a negative option, a qid outside [0, n_tiles), a record tid outside [0, n_families), a tile
+ *      outside its target, qe > tiles[qid].len, coordinates out of order.  TELR_E_RANGE from 2^31 - 16 records on.  No hit: zero
+ *      features, TELR_OK.  opt NULL = the defaults. */
+typedef struct telr_tile { int32_t tid, start, len; } telr_tile;
+int  telr_tile_plan(int32_t n_targets, const int32_t *target_len, int32_t tile, int32_t stride, telr_tile *out, int64_t cap, int64_t *needed);
+typedef struct telr_refte_opt {
+    int32_t min_len;   /* 100 */
+    int32_t min_mapq;  /* 0   */
+    int32_t join_gap;  /* 0   */
+    int32_t reserved;  /* 0   */
+} telr_refte_opt;
+typedef struct telr_te_feat { int32_t tid, start, end, family, strand, score, n_hits; } telr_te_feat;
+typedef struct telr_te_feats telr_te_feats;
+void telr_refte_opt_default(telr_refte_opt *o);
+int  telr_annotate_hits(telr_ctx *ctx, const telr_result *r, int64_t n_tiles, const telr_tile *tiles, int32_t n_targets,
+                        const int32_t *target_len, int32_t n_families, const telr_refte_opt *opt, telr_te_feats **out);
+int64_t telr_te_feats_count(const telr_te_feats *f);
+const telr_te_feat *telr_te_feats_data(const telr_te_feats *f);
+void telr_te_feats_free(telr_te_feats *f);
 
 /* ---- a BAM file as input (opt-in).  The reference accepts a BAM as `--reads`: parse_input skips the alignment
  *      (src/telr/TELR_input.py:300-305) and bam2fasta makes the read file with `samtools fasta`, first name wins (:329-361).  Here

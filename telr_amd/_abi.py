@@ -93,6 +93,28 @@ class Draft(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sig", "qid", "start", "len", "rc", "ins_off", "ins_len", "set_index")]
 
 
+class RefTeOpt(C.Structure):
+    """telr_refte_opt: the options of telr_annotate_hits (defaults: RefTeOpt.default())"""
+    _fields_ = [(n, C.c_int32) for n in ("min_len", "min_mapq", "join_gap", "reserved")]
+
+    @classmethod
+    def default(cls, **kw):
+        o = cls(100, 0, 0, 0)
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("RefTeOpt has no field %r" % k)
+            setattr(o, k, int(v))
+        return o
+
+
+class Tile(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tid", "start", "len")]
+
+
+class TeFeat(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tid", "start", "end", "family", "strand", "score", "n_hits")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "query_bases", "minimizers", "probes", "anchors", "chains", "dp_problems", "dp_cells",
@@ -120,3 +142,6 @@ GENO_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsGt._fields_])
 assert GENO_DTYPE.itemsize == C.sizeof(InsGt) == 16 and C.sizeof(GenoOpt) == 32
 DRAFT_DTYPE = _np.dtype([(n, _np.int32) for n, _ in Draft._fields_])
 assert DRAFT_DTYPE.itemsize == C.sizeof(Draft) == 32 and C.sizeof(DraftOpt) == 32
+TILE_DTYPE = _np.dtype([(n, _np.int32) for n, _ in Tile._fields_])
+TE_FEAT_DTYPE = _np.dtype([(n, _np.int32) for n, _ in TeFeat._fields_])
+assert TILE_DTYPE.itemsize == C.sizeof(Tile) == 12 and TE_FEAT_DTYPE.itemsize == C.sizeof(TeFeat) == 28 and C.sizeof(RefTeOpt) == 16

@@ -6,7 +6,8 @@ boundary (TELR_alignment.py:69-82 and the five other sites listed in include/tel
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._abi import IdxOpt, MapOpt, Counters, InsOpt, GenoOpt, DraftOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, DRAFT_DTYPE, N_STAGES, N_DPCLS
+from ._abi import IdxOpt, MapOpt, Counters, InsOpt, GenoOpt, DraftOpt, RefTeOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, DRAFT_DTYPE, TILE_DTYPE, \
+    TE_FEAT_DTYPE, TELR_E_RANGE, N_STAGES, N_DPCLS
 from .fasta import concat
 
 
@@ -138,6 +139,41 @@ class Engine:
         if rc != 0:
             raise _lib.TelrError("telr_debug_map_plan: %d" % rc, rc)
         return Engine.MAP_PLAN_MODES[int(out[0])], int(out[1]), [int(e) for e in ends[:int(out[2])]]
+
+    @staticmethod
+    def tile_plan(lengths, tile, stride):
+        """-> TILE_DTYPE array (tid, start, len): the overlapping tiles of targets of these lengths, in (tid, start) order (telr_tile_plan;
+        include/telr_hip.h has the definition; no device needed)"""
+        a = np.ascontiguousarray(lengths, dtype=np.int32)
+        L = _lib.lib()
+        need = C.c_int64(0)
+        rc = L.telr_tile_plan(len(a), a.ctypes.data, int(tile), int(stride), None, 0, C.byref(need))
+        if rc != 0 and not (rc == TELR_E_RANGE and need.value > 0):
+            raise _lib.TelrError("telr_tile_plan: %s" % L.telr_strerror(rc).decode(), rc)
+        out = np.zeros(need.value, TILE_DTYPE)
+        if need.value:
+            rc = L.telr_tile_plan(len(a), a.ctypes.data, int(tile), int(stride), out.ctypes.data, len(out), C.byref(need))
+            if rc != 0:
+                raise _lib.TelrError("telr_tile_plan: %s" % L.telr_strerror(rc).decode(), rc)
+        return out
+
+    def annotate_hits(self, r, tiles, target_len, n_families, opt=None):
+        """the records of a tile map as reference TE features (telr_annotate_hits; include/telr_hip.h has the definition, which is not
+        RepeatMasker's): r a raw result whose queries are `tiles` (a TILE_DTYPE array as tile_plan returns it) and whose targets are the
+        n_families library sequences; target_len the lengths of the tiled targets; opt an _abi.RefTeOpt (None: the defaults)
+        -> TE_FEAT_DTYPE array in (tid, start, end, family, strand) order"""
+        o = RefTeOpt.default() if opt is None else opt
+        tiles = np.ascontiguousarray(tiles, dtype=TILE_DTYPE)
+        tl = np.ascontiguousarray(target_len, dtype=np.int32)
+        h = C.c_void_p()
+        L = self.L
+        rc = L.telr_annotate_hits(self.h, r, len(tiles), tiles.ctypes.data, len(tl), tl.ctypes.data, int(n_families), C.byref(o), C.byref(h))
+        if rc != 0:
+            raise _lib.TelrError("telr_annotate_hits: %s [%s]" % (L.telr_strerror(rc).decode(), L.telr_last_error(self.h).decode()), rc)
+        try:
+            return _np_from(L.telr_te_feats_data(h), int(L.telr_te_feats_count(h)), TE_FEAT_DTYPE)
+        finally:
+            L.telr_te_feats_free(h)
 
     def debug_dp(self, queries, targets, mo, probs):
         """one DP pass (the map path's dp_pass) over a list of problems -- test tap.  probs: (np, 12) int32 rows
@@ -322,6 +358,29 @@ class SeqSet:
             raise _lib.TelrError("telr_seqset_extract: %s [%s]" % (L.telr_strerror(code).decode(), L.telr_last_error(self.eng.h).decode()), code)
         buf = out.tobytes()
         return [buf[int(off[k]):int(off[k + 1])] for k in range(n)]
+
+    def pieces(self, idx, start, length, rc=None, eng=None):
+        """new set whose sequence k is bases [start[k], start[k] + length[k]) of sequence idx[k], reverse-complemented where rc[k] != 0
+        (rc None: all forward), cut on the device from the packed form (telr_seqset_pieces): N stays N, no qualities are carried"""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        n = len(idx)
+        if len(start) != n or len(length) != n:
+            raise ValueError("pieces: one start and one length per index")
+        if rc is not None:
+            rc = np.ascontiguousarray(rc, dtype=np.uint8)
+            if len(rc) != n:
+                raise ValueError("pieces: one rc flag per index")
+        eng = self.eng if eng is None else eng
+        h = C.c_void_p()
+        code = eng.L.telr_seqset_pieces(eng.h, self.h, n, idx.ctypes.data, start.ctypes.data, length.ctypes.data,
+                                        None if rc is None else rc.ctypes.data, C.byref(h))
+        if code != 0:
+            raise _lib.TelrError("telr_seqset_pieces: %s [%s]" % (eng.L.telr_strerror(code).decode(), eng.L.telr_last_error(eng.h).decode()), code)
+        out = SeqSet.__new__(SeqSet)
+        out.eng = eng; out.h = h; out.len = length.copy(); out.n = n
+        return out
 
     def packed(self):
         """the set's two word arrays as torch int32 tensors ON THE DEVICE, zero-copy views of the library's memory (valid while

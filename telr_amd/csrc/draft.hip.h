@@ -252,14 +252,40 @@ extern "C" const telr_draft *telr_drafts_data(const telr_drafts *d) { return d ?
 extern "C" void telr_draft_contigs_free(telr_drafts *d) { delete d; }
 
 // an output set of the given lengths (seqset_alloc: layout, arrays, zeroed slack words, offsets uploaded); the words are the caller's to write
-static int draft_make_set(telr_ctx *ctx, const std::vector<int32_t> &lens, telr_seqset **out)
+static int draft_make_set(telr_ctx *ctx, const char *what, const std::vector<int32_t> &lens, telr_seqset **out)
 {
     telr_seqset *s = new telr_seqset();
     s->ctx = ctx; s->n = (int32_t)lens.size(); s->len = lens;
-    TRY(seqset_alloc(ctx, s, "telr_draft_contigs", true, ctx->stream));
+    TRY(seqset_alloc(ctx, s, what, true, ctx->stream));
     const hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->err = std::string("telr_draft_contigs: ") + hipGetErrorString(e); telr_seqset_free(s); return TELR_E_HIP; }
+    if (e != hipSuccess) { ctx->err = std::string(what) + ": " + hipGetErrorString(e); telr_seqset_free(s); return TELR_E_HIP; }
     *out = s;
+    return TELR_OK;
+}
+
+// A new set whose sequence k is piece k of `parent` (pieces[k].src = its first base in the parent's base layout, checked by the caller),
+// each at a 64-base-aligned offset, cut by k_draft_extract: the one way a set is made of pieces of another (telr_draft_contigs,
+// telr_seqset_pieces).  A piece of length 0 is an empty sequence; no pieces: an empty set.
+static int draft_cut_set(telr_ctx *ctx, const char *what, const telr_seqset *parent, const std::vector<int32_t> &lens, const std::vector<DraftPiece> &pieces, telr_seqset **out)
+{
+    hipStream_t st = ctx->stream;
+    telr_seqset *S = nullptr;
+    TRY(draft_make_set(ctx, what, lens, &S));
+    if (S->padded_bases > 0) {
+        const int32_t nd = (int32_t)pieces.size();
+        const int64_t nw = S->padded_bases / 16;
+        DraftPiece *d_piece = nullptr;
+        int rc_ = ctx_buf_t(ctx, "draft_piece", (size_t)nd, &d_piece);
+        if (rc_ != TELR_OK) { telr_seqset_free(S); return rc_; }
+        hipError_t e = hipMemcpyAsync(d_piece, pieces.data(), (size_t)nd * sizeof(DraftPiece), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_draft_extract, ins_grid(nw), dim3(256), 0, st, parent->d_seq2, parent->d_nmask, d_piece, S->d_boff, nd, nw, S->d_seq2, S->d_nmask);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { ctx->err = std::string(what) + ": " + hipGetErrorString(e); telr_seqset_free(S); return TELR_E_HIP; }
+    }
+    *out = S;
     return TELR_OK;
 }
 
@@ -401,21 +427,33 @@ extern "C" int telr_draft_contigs(telr_ctx *ctx, const telr_result *r, int32_t n
         lens.push_back(d.len); pieces.push_back(p);
     }
     telr_seqset *S = nullptr;
-    TRY(draft_make_set(ctx, lens, &S));
-    if (!pieces.empty()) {
-        const int32_t nd = (int32_t)pieces.size();
-        const int64_t nw = S->padded_bases / 16;
-        DraftPiece *d_piece = nullptr;
-        int rc_ = ctx_buf_t(ctx, "draft_piece", (size_t)nd, &d_piece);
-        if (rc_ != TELR_OK) { telr_seqset_free(S); return rc_; }
-        hipError_t e = hipMemcpyAsync(d_piece, pieces.data(), (size_t)nd * sizeof(DraftPiece), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_draft_extract, ins_grid(nw), dim3(256), 0, st, read_set->d_seq2, read_set->d_nmask, d_piece, S->d_boff, nd, nw, S->d_seq2, S->d_nmask);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { ctx->err = std::string("telr_draft_contigs: ") + hipGetErrorString(e); telr_seqset_free(S); return TELR_E_HIP; }
-    }
+    TRY(draft_cut_set(ctx, "telr_draft_contigs", read_set, lens, pieces, &S));
     *out = guard.release(); *out_set = S;
     return TELR_OK;
+}
+
+extern "C" int telr_seqset_pieces(telr_ctx *ctx, const telr_seqset *parent, int32_t n, const int32_t *idx, const int32_t *start, const int32_t *len,
+                                  const uint8_t *rc, telr_seqset **out)
+{
+    (void)hipGetLastError();
+    if (!ctx) return TELR_E_ARG;
+    auto bad = [&](const std::string &why) { ctx->err = "telr_seqset_pieces: " + why; return TELR_E_ARG; };
+    if (!parent || !out) return bad("null set or output");
+    if (n < 0) return bad("negative n");
+    if (n > 0 && (!idx || !start || !len)) return bad("null idx, start or len");
+    if (n >= 0x7ffffff0) { ctx->err = "telr_seqset_pieces: too many pieces"; return TELR_E_RANGE; }
+    std::vector<int32_t> lens((size_t)n);
+    std::vector<DraftPiece> pieces((size_t)n);
+    for (int32_t k = 0; k < n; ++k) {
+        const std::string who = "piece " + std::to_string(k);
+        if (idx[k] < 0 || idx[k] >= parent->n) return bad(who + ": idx outside the set");
+        if (start[k] < 0) return bad(who + ": negative start");
+        if (len[k] < 0) return bad(who + ": negative len");
+        if ((int64_t)start[k] + len[k] > parent->len[(size_t)idx[k]]) return bad(who + ": start + len beyond the sequence");
+        DraftPiece &p = pieces[(size_t)k];
+        p.src = parent->boff[(size_t)idx[k]] + start[k]; p.len = len[k]; p.rc = (rc && rc[k]) ? 1 : 0;
+        lens[(size_t)k] = len[k];
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    return draft_cut_set(ctx, "telr_seqset_pieces", parent, lens, pieces, out);
 }

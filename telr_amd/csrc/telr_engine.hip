@@ -3170,5 +3170,6 @@ extern "C" int telr_seqset_attach_qual(telr_ctx *ctx, telr_seqset *s, const char
 #include "inscall.hip.h"
 #include "genotype.hip.h"
 #include "draft.hip.h"
+#include "refte.hip.h"
 #include "bam_in.hip.h"
 #include "seq_extract.hip.h"

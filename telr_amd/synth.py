@@ -246,16 +246,21 @@ def make_stage1_dataset(seed=20261002, genome_len=23513712, n_reads=10000, total
     # reference TE copies: diverged, 5'-truncated copies over ~te_frac of the genome
     covered = 0
     te_copies = []                  # (start, end) of the reference's TE-derived stretches (reported, not used by the generator)
+    te_copy_info = []               # (start, end, family, strand, cut, divergence) of the same copies, in the order they were laid down (a later one may overwrite an earlier one)
     while covered < te_frac * genome_len:
-        f = lib[int(rng.integers(0, n_fam))]
+        fam = int(rng.integers(0, n_fam))
+        f = lib[fam]
         cut = int(rng.integers(0, max(1, len(f) // 2)))
-        cp = mutate(rng, f[cut:], float(rng.uniform(0, 0.15)), 0.0, 0.0)
-        if rng.integers(0, 2):
+        div = float(rng.uniform(0, 0.15))
+        cp = mutate(rng, f[cut:], div, 0.0, 0.0)
+        strand = int(rng.integers(0, 2))
+        if strand:
             cp = revcomp_arr(cp)
         p = int(rng.integers(0, genome_len - len(cp)))
         ref[p:p + len(cp)] = cp
         covered += len(cp)
         te_copies.append((p, p + len(cp)))
+        te_copy_info.append((p, p + len(cp), fam, strand, cut, div))
     hard_feats = []
     if hard:
         hard_feats = harden_sequence(np.random.default_rng([seed, 7]), ref, 0, gc, hard)
@@ -290,7 +295,7 @@ def make_stage1_dataset(seed=20261002, genome_len=23513712, n_reads=10000, total
     ln = np.concatenate([rA[2], rB[2]])
     off = np.cumsum(ln.astype(np.int64)) - ln
     truth = np.concatenate([np.c_[np.zeros(nA, np.int64), rA[3]], np.c_[np.ones(n_reads - nA, np.int64), rB[3]]])
-    return dict(ref=ref, library=lib, reads=(buf, off.astype(np.int64), ln.astype(np.int32)), insertions=ins, truth=truth, haps=haps, te_copies=te_copies, hard_features=hard_feats)
+    return dict(ref=ref, library=lib, reads=(buf, off.astype(np.int64), ln.astype(np.int32)), insertions=ins, truth=truth, haps=haps, te_copies=te_copies, te_copy_info=te_copy_info, hard_features=hard_feats)
 
 
 def make_loci_from_dataset(d, n_loci, seed=7, flank=(8000, 15000), reads_cap=60, window=1000):

@@ -13,7 +13,9 @@ here; the flow is that of its `main` (src/telr/telr.py:22-189) with this project
     calls                      telr_sv.call_insertions(..., reads=<the resident set>, genotype=True)      (not Sniffles)
     drafts                     telr_assembly.draft_loci(..., reads=<the resident set>)                     (not wtdbg2 / flye)
     asm10 index                Engine.index over the same resident reference
-    loci                       locus_pipeline.run_loci(..., read_set, contig_set, polish, ...)
+    reference TE copies        `--ref_te engine`: telr_te.annotate_reference on the resident reference (not RepeatMasker),
+                               kept as <out>/intermediate_files/<reference>.te.bed; `--ref_te FILE`: a BED6 of the caller's; default none
+    loci                       locus_pipeline.run_loci(..., read_set, contig_set, polish, ref_te_rows, ...)
     outputs                    locus_pipeline.write_outputs(..., sv_info=telr_sv.sv_info(rows))
 
 On neither route are the reads decoded to host text: the ALT sequences and the contigs are cut out of the resident packed set by
@@ -77,17 +79,26 @@ def get_args(argv=None):
     own.add_argument("--chain_skip", action="store_true", help="minimap2's own chaining scan (minimap2 aligner only)")
     own.add_argument("--seed_rescue", action="store_true", help="minimap2's high-occurrence seed rescue (minimap2 aligner only)")
     own.add_argument("--mm2_mapq", action="store_true", help="minimap2's own MAPQ (minimap2 aligner only)")
+    own.add_argument("--ref_te", type=str, default="none", help="the reference's own TE copies for the liftover: 'none', 'engine' (annotated on the device; not "
+                     "RepeatMasker) or a BED6 file with the columns RepeatMasker's GFF gives (default = 'none')")
     own.add_argument("--sample", type=str, help="sample name (default: the reads file's name without its extension)")
     p._action_groups.append(opt)
     a = p.parse_args(argv)
 
-    for path in (a.reads, a.reference, a.library):
+    for path in (a.reads, a.reference, a.library) + (() if a.ref_te in ("none", "engine") else (a.ref_te,)):
         try:
             open(path, "r").close()
         except Exception as e:
             print(e)
             _say("Can not open input file: " + path)
             sys.exit(1)
+    if a.ref_te not in ("none", "engine"):
+        from . import telr_te
+        try:
+            telr_te.read_te_bed(a.ref_te)
+        except (OSError, ValueError) as e:
+            print(e)
+            _exit("Please provide a valid BED6 file of the reference's TE copies (--ref_te), exiting...")
 
     def choice(name, default, allowed, what):
         v = getattr(a, name)
@@ -200,9 +211,21 @@ def draft_stage(ix, r, ic, rows, read_set, chrom_ids):
     return telr_assembly.draft_loci(ix, r, ic, rows, read_set, read_set, chrom_ids)
 
 
-def loci_stage(eng, ix10, tnames, ref_seq, loci, lib_names, lib_seqs, read_set, cset, args):
+def ref_te_stage(eng, ix, tnames, lib_names, lib_seqs, args, bed_path):
+    """--ref_te: the reference's TE copies as BED6 rows for the liftover -- annotated on the device and written to bed_path ('engine'), or read
+    from the caller's file"""
+    from . import telr_te
+    if args.ref_te == "engine":
+        rows = telr_te.annotate_reference(eng, ix.targets, tnames, lib_names, lib_seqs)
+        telr_te.write_te_bed(rows, bed_path)
+        return rows
+    return telr_te.read_te_bed(args.ref_te)
+
+
+def loci_stage(eng, ix10, tnames, ref_seq, loci, lib_names, lib_seqs, read_set, cset, args, ref_te_rows=None):
     from . import locus_pipeline
     return locus_pipeline.run_loci(eng, ix10, tnames, ref_seq, loci, lib_names, lib_seqs, presets=args.presets, read_set=read_set, contig_set=cset,
+                                   ref_te_rows=ref_te_rows,
                                    polish=None if args.polish == "none" else args.polish, polish_iterations=args.polish_iterations,
                                    flank_len=args.flank_len, gap=args.gap, overlap=args.overlap,
                                    af_params=(args.af_flank_interval, args.af_flank_offset, args.af_te_interval, args.af_te_offset))
@@ -286,8 +309,14 @@ def run(args, engine=None):
         io10, _ = preset("asm10")
         ix10 = eng.index(ix.targets, io10)
         done("index10", "asm10 index of the reference")
+        ref_te_rows = None
+        if args.ref_te != "none" and loci:          # (only the liftover of a locus reads them)
+            files["ref_te"] = os.path.join(inter, os.path.basename(args.reference) + ".te.bed") if args.ref_te == "engine" else args.ref_te
+            ref_te_rows = ref_te_stage(eng, ix, tnames, lib_names, lib_seqs, args, files["ref_te"])
+            counts["ref_te_features"] = len(ref_te_rows)
+            done("ref_te", "%d reference TE features (%s)" % (len(ref_te_rows), "annotated on the device" if args.ref_te == "engine" else "from " + args.ref_te))
         # 7. annotation, liftover, allele frequency
-        res = loci_stage(eng, ix10, tnames, lambda ch: by_name[ch], loci, lib_names, lib_seqs, read_set, cset, args) if loci else dict(EMPTY_RESULT)
+        res = loci_stage(eng, ix10, tnames, lambda ch: by_name[ch], loci, lib_names, lib_seqs, read_set, cset, args, ref_te_rows) if loci else dict(EMPTY_RESULT)
         counts["loci_annotated"] = len(set(a[0] for a in res["annotation"]))
         counts["loci_lifted"] = sum(1 for x in res["liftover"] if x["report"]["type"] == "non-reference")
         done("loci", "%d loci annotated, %d lifted over" % (counts["loci_annotated"], counts["loci_lifted"]))

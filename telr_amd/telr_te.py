@@ -10,6 +10,8 @@ between them (reference src/telr/TELR_te.py:21-262).
 Here S4 is ONE engine call for all loci (query i sees only its contig) and S5 is ONE call in which the
 library is sketched once and chains are ranked per contig (TELR_MF_PER_TARGET).  The RepeatMasker
 re-annotation that follows in the reference (:267-370) is a hand-off point and is not reproduced.
+`annotate_reference` is an opt-in stand-in for the RepeatMasker BED of the REFERENCE genome that the
+liftover consults (:391-469), made on the device; it is not RepeatMasker.
 """
 import numpy as np
 
@@ -59,6 +61,59 @@ def annotate_contig(backend, contig_names, contig_seqs, alt_seqs, lib_names, lib
     for c, s, e, fam, strand in merged:
         ann.append([c, s, e, fam, ".", strand if strand in ("+", "-") else "."])
     return iv.bed_sort(ann), seq2contig, te2contig
+
+
+# ---- the reference's TE copies on the device: a stand-in for the RepeatMasker BED below, NOT RepeatMasker ----------
+def annotate_reference(engine, target_set, tnames, lib_names, lib_seqs, tile=32768, stride=16384, opt=None):
+    """The reference genome's TE annotation as the BED6 rows `gff3tobed` hands to the liftover -- [chrom, start, end, family, ".", strand] in
+    `bed_sort` order -- made on the device from the resident reference `target_set` (a SeqSet; it is not decoded to text): the library is
+    indexed with the map-ont index options, the reference is cut into overlapping tiles (Engine.tile_plan, SeqSet.pieces) that are mapped
+    to it as queries with map-ont minus the long join and the secondaries (genome against consensus: no read errors, so the preset does
+    not follow -x), and the records become features by the interval rule of telr_annotate_hits (opt: an _abi.RefTeOpt).  A copy
+    interrupted by a nested element is two features, and the nested element is its own.  This is an own definition, not RepeatMasker:
+    the hit sets differ, above all for old, diverged copies."""
+    from ._abi import MF_CIGAR
+    tiles = engine.tile_plan(target_set.len, tile, stride)
+    if len(tiles) == 0 or len(lib_seqs) == 0:
+        return []
+    io, mo = preset("map-ont")
+    mo = mo.copy(); mo.bw_long = 0; mo.secondary = 0; mo.flags |= MF_CIGAR
+    tset = lib = r = None
+    try:
+        tset = target_set.pieces(tiles["tid"], tiles["start"], tiles["len"], eng=engine)
+        lib = engine.index(list(lib_seqs), io)
+        r = lib.map_raw(tset, mo)
+        feats = engine.annotate_hits(r, tiles, target_set.len, len(lib_seqs), opt)
+    finally:
+        if r is not None:
+            lib.free_raw(r)
+        if lib is not None:
+            lib.free(); lib.targets.free()
+        if tset is not None:
+            tset.free()
+    return iv.bed_sort([[tnames[f["tid"]], str(f["start"]), str(f["end"]), lib_names[f["family"]], ".", "-" if f["strand"] else "+"] for f in feats])
+
+
+def write_te_bed(rows, path):
+    """BED6 rows as the file `gff3tobed` writes"""
+    with open(path, "w") as fh:
+        fh.write("".join("\t".join(r) + "\n" for r in rows))
+
+
+def read_te_bed(path):
+    """-> the rows of a BED6 file with the columns of `gff3tobed`, in `bed_sort` order; a line with fewer than six columns or a start /
+    end that is no number raises ValueError"""
+    rows = []
+    with open(path) as fh:
+        for n, line in enumerate(fh, 1):
+            if not line.strip() or line.startswith("#"):
+                continue
+            c = line.rstrip("\n").split("\t")
+            if len(c) < 6:
+                raise ValueError("%s line %d: fewer than six columns" % (path, n))
+            int(c[1]); int(c[2])
+            rows.append(c[:6])
+    return iv.bed_sort(rows)
 
 
 # ---- RepeatMasker hand-off (reference src/telr/TELR_te.py:391-494, telr.py:132-144) ------------------------------------
