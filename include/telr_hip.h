@@ -288,6 +288,51 @@ void telr_index_free(telr_index *idx);
 /* number of minimizers / distinct minimizers, for reports */
 int  telr_index_stats(const telr_index *idx, int64_t *n_minimizers, int64_t *n_distinct);
 
+/* ---- references of any size: a multi-part index, merged on the device (opt-in).  An index holds its targets in one
+ *      31-bit coordinate space, so telr_index_build refuses a target set whose padded extent reaches 2^31 bases.  The way round it is
+ *      minimap2's own (`-I` / `--split-prefix`): cut the targets into parts that each fit, map the reads against every part, and run the
+ *      final selection again over each read's pooled records.  tests/part_merge_ref.py states the merge in plain Python integers.
+ * Parts (telr_part_plan; host only, no device needed).  Contiguous runs of targets in target order, chosen greedily: a part's extent
+ *      starts at 0 and advances target by target as telr_index_build lays targets out, g -> (g + len + 16384 + 63) & ~63; a target with
+ *      which the extent would REACH max_bases starts the next part.  max_bases 0 = the engine's own limit, 2^31 (a larger value is that
+ *      limit too).  part_of[t] = the part of target t, *n_parts their number; n_targets == 0 gives 0 parts.  Every part is accepted by
+ *      telr_index_build; no part would be with its successor's first target added.  TELR_E_RANGE: a target that alone reaches the limit
+ *      (telr_part_plan_error names it; the text of the calling thread's last telr_part_plan).  TELR_E_ARG: a negative length or
+ *      max_bases, a null pointer where it is needed.
+ * Merge (telr_merge_parts).  parts[p] = the result of mapping the SAME n_queries queries against the index of part p, with the same
+ *      options `mo`; tid_map[p][0 .. n_part_targets[p]) = the global id of every target of part p.
+ *   1. Pool.   For each query, its records from all parts; a record is (part, rank), rank = its index within that part's records
+ *              of the query.
+ *   2. Order.  The pool sorted by (dp_score descending, part ascending, rank ascending).
+ *   3. State.  Every record starts as its own parent.  A record that was PRIMARY or SUPPL in its part keeps its subsc and n_sub, one
+ *              that was SECONDARY starts with 0 for both.
+ *   4. Mask.   For i in order: the first earlier j that is still its own parent and for which
+ *              (float)overlap(qs, qe) > mask_level * (float)min(len_i, len_j) (float32, as the engine's selection) becomes i's parent;
+ *              then subsc[j] = max(subsc[j], score_i) and n_sub[j] += 1 -- unless i was j's secondary in the same part already (same
+ *              part, i was SECONDARY, i's part-level parent == j's rank): j counted it there.
+ *   5. Keep.   Own parents always.  A secondary iff mo->secondary, (float)dp_i >= (float)dp_parent * pri_ratio, and fewer than
+ *              best_n kept secondaries precede it.
+ *   6. Fields of a kept record: parent = the parent's index among the query's kept records; the first kept own parent is PRIMARY,
+ *              the others SUPPL, the rest SECONDARY, TELR_F_REV (and any other bit) carried; subsc = n_sub = 0 on secondaries; tid =
+ *              the global id; mapq by the formula telr_map uses (TELR_MF_MM2_MAPQ or not), computed on the host; cigar_off dense in
+ *              output order; every other field carried.
+ *   7. Output. Ordered by (qid, kept order).  An ordinary result: records on the host, the CIGAR words gathered on the device from
+ *              the parts' arrays (a part's resident copy, TELR_MF_KEEP_CIGARS, or one upload) into a resident array of its own --
+ *              complete, as after TELR_MF_KEEP_CIGARS -- and mirrored to the host once.  The bytes are the same on every run.
+ *      With one part the merge is the identity.  TELR_MF_PER_TARGET is TELR_E_ARG (per-target calls never compete across targets);
+ *      every other flag passes through.  Checked on the host before any launch, TELR_E_ARG with a text in telr_last_error and `out`
+ *      untouched: a part not ordered by qid, a qid outside [0, n_queries), a tid outside its map, cigar_off + n_cigar outside the
+ *      part's words, a parent outside the query's records in the part, flags without exactly one class bit, a null pointer where
+ *      it is needed.  TELR_E_RANGE from 2^31 - 16 pooled records on.  An empty part, zero parts, zero queries, zero records: valid.
+ * Caveats. The occurrence cut-off (mid_occ) is per part, as in minimap2: a repeat below it in a part but above it in the whole set is
+ *      seeded in the parts, so the merged result can hold secondaries the unsplit index would not.  All part indexes, the P part
+ *      results and the merged one live side by side: a read set for which that does not fit gets TELR_E_NOMEM. */
+int  telr_part_plan(int32_t n_targets, const int32_t *target_len, int64_t max_bases, int32_t *part_of /* [n_targets] */, int32_t *n_parts);
+const char *telr_part_plan_error(void);
+int  telr_merge_parts(telr_ctx *ctx, int32_t n_parts, const telr_result *const *parts,
+                      const int32_t *const *tid_map /* part-local tid -> global tid */, const int32_t *n_part_targets,
+                      int32_t n_queries, const telr_map_opt *mo, telr_result **out);
+
 /* ---- mapping (S1,S2,S7: all queries vs all targets; S3,S4,S6: query i vs the
  *      single target qtarget[i]; S5: TELR_MF_PER_TARGET) ------------------------
  * qtarget may be NULL (every query sees every target) or hold one target id
@@ -417,6 +462,11 @@ int  telr_bam_discard(telr_ctx *ctx);
 int  telr_write_bam_dev(telr_ctx *ctx, const telr_result *r, const telr_seqset *queries, const telr_index *idx,
                         const char *const *qnames, const char *const *tnames, int32_t flags, const char *rg_id, const char *rg_sm,
                         const char *rg_lb, const char *pg_line, const char *bam_path, int32_t write_index, int32_t level);
+/* the same with the target set itself in the index's place (the writer reads nothing of an index but its targets): for a result
+ * whose tids are those of a set no single index holds (telr_merge_parts).  telr_write_bam_dev is this call with the index's targets. */
+int  telr_write_bam_dev_targets(telr_ctx *ctx, const telr_result *r, const telr_seqset *queries, const telr_seqset *targets,
+                                const char *const *qnames, const char *const *tnames, int32_t flags, const char *rg_id, const char *rg_sm,
+                                const char *rg_lb, const char *pg_line, const char *bam_path, int32_t write_index, int32_t level);
 
 /* ---- pile-up consensus of the index's targets from the PRIMARY records of a result (neither secondary nor supplementary:
  *      `samtools view -F0x900`).  Stands where the reference pipes that view into `wtpoa-cns -d CNS -i -` to polish a locus'

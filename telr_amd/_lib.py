@@ -26,6 +26,7 @@ EXPORTS = [
     "telr_bam_in_read_names", "telr_bam_in_read_lens", "telr_bam_in_seqset", "telr_bam_in_result", "telr_bam_in_detach_seqset", "telr_bam_in_detach_result",
     "telr_bam_in_counters", "telr_bam_in_ascii", "telr_bam_in_phase_ms",
     "telr_seqset_extract", "telr_seqset_pieces",
+    "telr_part_plan", "telr_part_plan_error", "telr_merge_parts", "telr_write_bam_dev_targets",
     "telr_tile_plan", "telr_refte_opt_default", "telr_annotate_hits", "telr_te_feats_count", "telr_te_feats_data", "telr_te_feats_free",
 ]
 
@@ -130,6 +131,12 @@ def lib():
     L.telr_write_bam_qual.argtypes = L.telr_write_bam.argtypes + [vp, vp, i32]
     L.telr_write_bam_dev.restype = C.c_int
     L.telr_write_bam_dev.argtypes = [vp, vp, vp, vp, vp, vp, i32, cp, cp, cp, cp, cp, i32, i32]
+    L.telr_write_bam_dev_targets.restype = C.c_int
+    L.telr_write_bam_dev_targets.argtypes = L.telr_write_bam_dev.argtypes
+    L.telr_part_plan.restype = C.c_int; L.telr_part_plan.argtypes = [i32, vp, i64, vp, C.POINTER(i32)]
+    L.telr_part_plan_error.restype = cp; L.telr_part_plan_error.argtypes = []
+    L.telr_merge_parts.restype = C.c_int; L.telr_merge_parts.argtypes = [vp, i32, vp, vp, vp, i32, C.POINTER(MapOpt), C.POINTER(vp)]
+    L.telr_debug_merge_ms.restype = C.c_int; L.telr_debug_merge_ms.argtypes = [vp]
     L.telr_fasta_load.restype = C.c_int; L.telr_fasta_load.argtypes = [cp, C.POINTER(vp)]
     L.telr_fasta_count.restype = i32; L.telr_fasta_count.argtypes = [vp]
     L.telr_fasta_bases.restype = i64; L.telr_fasta_bases.argtypes = [vp]

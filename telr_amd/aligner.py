@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 from . import _lib
 from ._abi import IdxOpt, MapOpt, Counters, InsOpt, GenoOpt, DraftOpt, RefTeOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, DRAFT_DTYPE, TILE_DTYPE, \
-    TE_FEAT_DTYPE, TELR_E_RANGE, N_STAGES, N_DPCLS
+    TE_FEAT_DTYPE, TELR_E_ARG, TELR_E_RANGE, MF_PER_TARGET, MF_KEEP_CIGARS, N_STAGES, N_DPCLS
 from .fasta import concat
 
 
@@ -81,6 +81,24 @@ class Engine:
 
     def index(self, targets, io):
         return Index(self, targets, io)
+
+    @staticmethod
+    def part_plan(lengths, max_bases=0):
+        """-> part_of (int32, one part number per target): how targets of these lengths are cut into parts that each fit an index of at
+        most max_bases bases of padded extent (0: the engine's own limit, 2^31) -- contiguous runs in target order, chosen greedily
+        (telr_part_plan; include/telr_hip.h has the definition; no device needed)"""
+        a = np.ascontiguousarray(lengths, dtype=np.int32)
+        L = _lib.lib()
+        part_of = np.zeros(max(len(a), 1), np.int32); n = C.c_int32(0)
+        rc = L.telr_part_plan(len(a), a.ctypes.data, int(max_bases), part_of.ctypes.data, C.byref(n))
+        if rc != 0:
+            raise _lib.TelrError("telr_part_plan: %s [%s]" % (L.telr_strerror(rc).decode(), L.telr_part_plan_error().decode()), rc)
+        return part_of[:len(a)]
+
+    def index_parts(self, targets, io, max_part_bases=0, like=None):
+        """a multi-part index over targets of any total size -> PartIndex.  like: another PartIndex over the same
+        targets (and the same max_part_bases), whose resident target set and subsets are used again"""
+        return PartIndex(self, targets, io, max_part_bases, like)
 
     def load_bam(self, path, keep_qual=False):
         """a BAM file as stage-1 input, inflated and parsed on the device (telr_bam_load; include/telr_hip.h has the definition)
@@ -706,8 +724,10 @@ class Index:
         qa, ta = self._cstr_array(qnames), self._cstr_array(tnames)
         flags = (1 if md else 0) | (2 if cs else 0) | (4 if softclip else 0) | (0 if unmapped else 8)
         rg_id, rg_sm, rg_lb = (None, None, None) if rg is None else tuple(x.encode() for x in rg)
-        self.eng._chk(self.eng.L.telr_write_bam_dev(self.eng.h, r, queries.h, self.h, qa, ta, flags, rg_id, rg_sm, rg_lb,
-                                                    cmdline.encode(), path.encode(), 1 if index else 0, level), "telr_write_bam_dev")
+        self._write_bam_dev(r, queries, qa, ta, flags, rg_id, rg_sm, rg_lb, cmdline.encode(), path.encode(), 1 if index else 0, level)
+
+    def _write_bam_dev(self, r, queries, *rest):
+        self.eng._chk(self.eng.L.telr_write_bam_dev(self.eng.h, r, queries.h, self.h, *rest), "telr_write_bam_dev")
 
     def bam_prepare(self, path, est_bytes):
         """start creating the output file in the background (call before map_raw; see telr_bam_prepare)"""
@@ -865,3 +885,105 @@ class Index:
             self.free()
         except Exception:
             pass
+
+
+class PartIndex(Index):
+    """An index over a target set of any total size: one Index per part (Engine.part_plan), the reads mapped against every part in turn
+    and the per-part results merged on the device (telr_merge_parts; include/telr_hip.h has the definition).  `targets` is the full
+    resident set and the merged result carries global target ids, so call_insertions, genotype_insertions, draft_contigs,
+    depth_medians, result_arrays, write_bam_device and the text writers work as on an Index.  Not for a multi-part index: qtarget /
+    MF_PER_TARGET, write_bam_slice, consensus, the debug taps.  All part indexes are resident together, and during a map the part
+    results and the merged one live side by side."""
+
+    def __init__(self, eng, targets, io, max_part_bases=0, like=None):
+        self.eng = eng
+        self.io = io
+        self.h = None
+        self.parts = []
+        self.max_part_bases = int(max_part_bases)
+        if like is not None:
+            if not isinstance(like, PartIndex) or like.max_part_bases != self.max_part_bases:
+                raise ValueError("index_parts: like= must be a PartIndex cut with the same max_part_bases")
+            self.targets, self.part_of, self.part_sets, self._owner = like.targets, like.part_of, like.part_sets, like
+        else:
+            self.targets = targets if isinstance(targets, SeqSet) else SeqSet(eng, targets)
+            self.part_of = Engine.part_plan(self.targets.len, self.max_part_bases)
+            self._owner = None
+            self.part_sets = []
+        n_parts = int(self.part_of.max()) + 1 if len(self.part_of) else 0
+        self.tid_maps = [np.ascontiguousarray(np.flatnonzero(self.part_of == p), dtype=np.int32) for p in range(n_parts)]
+        try:
+            if like is None:
+                for m in self.tid_maps:
+                    self.part_sets.append(self.targets.subset(m))
+            for sub in self.part_sets:
+                self.parts.append(Index(eng, sub, io))
+        except BaseException:
+            self.free()
+            raise
+
+    @property
+    def n_parts(self):
+        return len(self.parts)
+
+    def stats(self):
+        a = [ix.stats() for ix in self.parts]
+        return sum(x[0] for x in a), sum(x[1] for x in a)
+
+    def map_raw(self, queries, mo, qtarget=None):
+        """-> opaque handle of the merged result (caller frees with free_raw); its CIGAR words are resident on the device"""
+        if qtarget is not None or (mo.flags & MF_PER_TARGET):
+            raise _lib.TelrError("PartIndex.map_raw: qtarget / TELR_MF_PER_TARGET are not for a multi-part index", TELR_E_ARG)
+        q = queries if isinstance(queries, SeqSet) else SeqSet(self.eng, queries)
+        mp = mo.copy(); mp.flags |= MF_KEEP_CIGARS
+        raws = []
+        try:
+            for ix in self.parts:
+                raws.append(ix.map_raw(q, mp))
+            return self.merge_raw(raws, q.n, mo)
+        finally:
+            for r in raws:
+                self.free_raw(r)
+
+    def merge_raw(self, raws, n_queries, mo):
+        """telr_merge_parts over one raw result per part (in part order) -> the merged handle; the part results stay the caller's"""
+        n = len(raws)
+        if n != len(self.parts):
+            raise ValueError("merge_raw: one result per part")
+        ra = (C.c_void_p * max(1, n))(*[r.value if isinstance(r, C.c_void_p) else r for r in raws])
+        ma = (C.c_void_p * max(1, n))(*[m.ctypes.data for m in self.tid_maps])
+        nt = np.ascontiguousarray([len(m) for m in self.tid_maps], dtype=np.int32)
+        out = C.c_void_p()
+        L = self.eng.L
+        rc = L.telr_merge_parts(self.eng.h, n, ra, ma, nt.ctypes.data if n else None, int(n_queries), C.byref(mo), C.byref(out))
+        if rc != 0:
+            raise _lib.TelrError("telr_merge_parts: %s [%s]" % (L.telr_strerror(rc).decode(), L.telr_last_error(self.eng.h).decode()), rc)
+        return out
+
+    def _write_bam_dev(self, r, queries, *rest):
+        """the writer reads nothing of an index but its targets: the full set stands in (telr_write_bam_dev_targets)"""
+        self.eng._chk(self.eng.L.telr_write_bam_dev_targets(self.eng.h, r, queries.h, self.targets.h, *rest), "telr_write_bam_dev_targets")
+
+    def _not_here(self, what):
+        raise _lib.TelrError("%s is not for a multi-part index" % what, TELR_E_ARG)
+
+    def write_bam_slice(self, *a, **k):
+        self._not_here("write_bam_slice")
+
+    def consensus(self, *a, **k):
+        self._not_here("consensus")
+
+    def debug_dump(self):
+        self._not_here("debug_dump")
+
+    def debug_mid_occ(self, mo):
+        self._not_here("debug_mid_occ")
+
+    def free(self):
+        for ix in getattr(self, "parts", []):
+            ix.free()
+        self.parts = []
+        if getattr(self, "_owner", None) is None:
+            for s in getattr(self, "part_sets", []):
+                s.free()
+            self.part_sets = []

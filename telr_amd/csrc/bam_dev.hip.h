@@ -1278,25 +1278,25 @@ struct telr_bam_segment {
     int64_t n_unmapped = 0;
 };
 struct BamSliceOpt { const uint8_t *emit; int32_t with_header; telr_bam_segment *seg; };
-static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *queries, const telr_index *idx, const char *const *qnames,
+static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *queries, const telr_seqset *tg, const char *const *qnames,
                         const char *const *tnames, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb, const char *pg_line,
                         const char *bam_path, int32_t write_index, int32_t level, const BamSliceOpt *so = nullptr);
 // one writer at a time per process, whole-file and slice calls alike: the call's timing / size records (g_bam_*), the NOMEM retry size and
 // the code tables are process-wide
 static std::mutex g_bam_mu;
-extern "C" int telr_write_bam_dev(telr_ctx *ctx, const telr_result *r, const telr_seqset *queries, const telr_index *idx, const char *const *qnames,
-                                  const char *const *tnames, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb, const char *pg_line,
-                                  const char *bam_path, int32_t write_index, int32_t level)
+extern "C" int telr_write_bam_dev_targets(telr_ctx *ctx, const telr_result *r, const telr_seqset *queries, const telr_seqset *targets, const char *const *qnames,
+                                          const char *const *tnames, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb, const char *pg_line,
+                                          const char *bam_path, int32_t write_index, int32_t level)
 {
     std::lock_guard<std::mutex> writer_lock(g_bam_mu);
     (void)hipGetLastError();          // a failed allocation of an EARLIER call leaves its error with the thread: not this call's
-    int rc = bam_dev_impl(ctx, r, queries, idx, qnames, tnames, flags, rg_id, rg_sm, rg_lb, pg_line, bam_path, write_index, level);
+    int rc = bam_dev_impl(ctx, r, queries, targets, qnames, tnames, flags, rg_id, rg_sm, rg_lb, pg_line, bam_path, write_index, level);
     if (rc == TELR_E_NOMEM) {
         (void)hipGetLastError();
         mem_note(ctx, "telr_write_bam_dev: out of memory");
         ctx_release_map_scratch(ctx, g_bam_need);
         mem_note(ctx, "telr_write_bam_dev: after giving back scratch");
-        rc = bam_dev_impl(ctx, r, queries, idx, qnames, tnames, flags, rg_id, rg_sm, rg_lb, pg_line, bam_path, write_index, level);
+        rc = bam_dev_impl(ctx, r, queries, targets, qnames, tnames, flags, rg_id, rg_sm, rg_lb, pg_line, bam_path, write_index, level);
     }
     if (rc != TELR_OK && bam_path) {
         // no partial (or merely pre-sized) file at the output path: callers test for the file's existence (TELR_alignment.py:110-114)
@@ -1305,11 +1305,18 @@ extern "C" int telr_write_bam_dev(telr_ctx *ctx, const telr_result *r, const tel
     }
     return rc;
 }
-static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *queries, const telr_index *idx, const char *const *qnames,
+// the index supplies nothing but its targets
+extern "C" int telr_write_bam_dev(telr_ctx *ctx, const telr_result *r, const telr_seqset *queries, const telr_index *idx, const char *const *qnames,
+                                  const char *const *tnames, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb, const char *pg_line,
+                                  const char *bam_path, int32_t write_index, int32_t level)
+{
+    return telr_write_bam_dev_targets(ctx, r, queries, idx ? idx->targets : nullptr, qnames, tnames, flags, rg_id, rg_sm, rg_lb, pg_line, bam_path, write_index, level);
+}
+static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *queries, const telr_seqset *tg, const char *const *qnames,
                         const char *const *tnames, int32_t flags, const char *rg_id, const char *rg_sm, const char *rg_lb, const char *pg_line,
                         const char *bam_path, int32_t write_index, int32_t level, const BamSliceOpt *so)
 {
-    if (!ctx || !r || !queries || !idx || !idx->targets || !qnames || !tnames || (!bam_path && !so)) return TELR_E_ARG;
+    if (!ctx || !r || !queries || !tg || !qnames || !tnames || (!bam_path && !so)) return TELR_E_ARG;
     if (level < 0) return TELR_E_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     auto now = [] { return std::chrono::steady_clock::now(); };
@@ -1319,7 +1326,6 @@ static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *
     g_bam_need = (uint64_t)queries->total_bases * (level == 0 ? 6 : 9) + (uint64_t)r->ncig * 4 + (256u << 20);      // refined below once the stream's size is known
     result_wait(r);
     hipStream_t st = ctx->stream;
-    const telr_seqset *tg = idx->targets;
     const int32_t nq = queries->n, nt = tg->n;
     const size_t n_mapped = r->alns.size();
     for (const telr_aln &a : r->alns) if (a.qid < 0 || a.qid >= nq || a.tid < 0 || a.tid >= nt) return TELR_E_ARG;
@@ -1587,11 +1593,11 @@ extern "C" int telr_write_bam_slice(telr_ctx *ctx, const telr_result *r, const t
     (void)hipGetLastError();
     telr_bam_segment *S = new telr_bam_segment();
     BamSliceOpt so{ emit, with_header, S };
-    int rc = bam_dev_impl(ctx, r, queries, idx, qnames, tnames, flags, rg_id, rg_sm, rg_lb, pg_line, nullptr, 0, level, &so);
+    int rc = bam_dev_impl(ctx, r, queries, idx ? idx->targets : nullptr, qnames, tnames, flags, rg_id, rg_sm, rg_lb, pg_line, nullptr, 0, level, &so);
     if (rc == TELR_E_NOMEM) {
         (void)hipGetLastError();
         ctx_release_map_scratch(ctx, g_bam_need);
-        rc = bam_dev_impl(ctx, r, queries, idx, qnames, tnames, flags, rg_id, rg_sm, rg_lb, pg_line, nullptr, 0, level, &so);
+        rc = bam_dev_impl(ctx, r, queries, idx ? idx->targets : nullptr, qnames, tnames, flags, rg_id, rg_sm, rg_lb, pg_line, nullptr, 0, level, &so);
     }
     if (rc != TELR_OK) { delete S; return rc; }
     *out = S;

@@ -23,7 +23,7 @@
 #include <stdint.h>
 
 #define TELR_NEG      (-(1 << 28))
-#define TELR_TPAD     16384         // padding between targets in global coordinates (tests/sketch_edges.py mirrors it: TPAD)
+#include "part_plan.h"              // TELR_TPAD, the padding between targets in global coordinates, and index_extent_next
 #define SK_TILE       1024          // minimizer slots per sketch tile
 #define SK_THREADS    256
 #define DP_DMAX       4096          // widest band (diagonals) the DP kernel accepts

@@ -850,7 +850,7 @@ static int index_build_impl(telr_ctx *ctx, const telr_seqset *tg, const telr_idx
     ix->ctx = ctx; ix->targets = tg; ix->io = *io;
     ix->goff.resize(n + 1);
     uint64_t g = 0;
-    for (int i = 0; i < n; ++i) { ix->goff[i] = (uint32_t)g; g = (g + (uint64_t)tg->len[i] + TELR_TPAD + 63) & ~63ULL; if (g >= (1ULL << 31)) return TELR_E_RANGE; }
+    for (int i = 0; i < n; ++i) { ix->goff[i] = (uint32_t)g; g = index_extent_next(g, (uint64_t)tg->len[i]); if (g >= PART_INDEX_LIMIT) return TELR_E_RANGE; }
     ix->goff[n] = (uint32_t)g;
     HIPCHK(hipMalloc(&ix->d_goff, (n + 1) * 4));
     // (a null-stream copy on purpose: with the copy moved to the context's stream every later telr_map call on configs[2] ran 7 %
@@ -3173,3 +3173,4 @@ extern "C" int telr_seqset_attach_qual(telr_ctx *ctx, telr_seqset *s, const char
 #include "refte.hip.h"
 #include "bam_in.hip.h"
 #include "seq_extract.hip.h"
+#include "part_merge.hip.h"

@@ -13,6 +13,10 @@ here; the flow is that of its `main` (src/telr/telr.py:22-189) with this project
     calls                      telr_sv.call_insertions(..., reads=<the resident set>, genotype=True)      (not Sniffles)
     drafts                     telr_assembly.draft_loci(..., reads=<the resident set>)                     (not wtdbg2 / flye)
     asm10 index                Engine.index over the same resident reference
+    a reference above 2^31     `--index_part_bases N`: the reference is cut into parts of at most N bases of padded extent, each
+                               with an index of its own (Engine.index_parts); the reads are mapped against every part and the records merged
+                               on the device.  With 0 (the default) the run is what it was, and goes this way only when the reference does
+                               not fit one index (about 2.1 Gbp).  The BAM route maps nothing and is unaffected.
     reference TE copies        `--ref_te engine`: telr_te.annotate_reference on the resident reference (not RepeatMasker),
                                kept as <out>/intermediate_files/<reference>.te.bed; `--ref_te FILE`: a BED6 of the caller's; default none
     loci                       locus_pipeline.run_loci(..., read_set, contig_set, polish, ref_te_rows, ...)
@@ -25,7 +29,9 @@ reference's bam2fasta leaves behind on the BAM route, is therefore not written; 
 Different from the reference on purpose: every value it prints a message for ends the run with status 1 (the reference goes on after
 four of its messages: -p below 1, a negative --af_flank_offset or --af_te_offset, --af_te_interval below 1); a reads file of any
 extension other than `.bam` goes to the reader (gzip included).  Not built: the ALT pre-screen, merge_rows on the
-caller's rows, the RepeatMasker route for families, the N-rank path, gzip on the BAM route.
+caller's rows, the RepeatMasker route for families, the N-rank path, gzip on the BAM route.  On a multi-part reference: the occurrence
+cut-off of the seeding is per part, as with minimap2 -I (secondaries the unsplit index would not report), all parts are resident together,
+and `--ref_te engine` maps the tiles to the library, not to the reference, so it runs as it is.
 """
 import argparse
 import os
@@ -81,6 +87,8 @@ def get_args(argv=None):
     own.add_argument("--mm2_mapq", action="store_true", help="minimap2's own MAPQ (minimap2 aligner only)")
     own.add_argument("--ref_te", type=str, default="none", help="the reference's own TE copies for the liftover: 'none', 'engine' (annotated on the device; not "
                      "RepeatMasker) or a BED6 file with the columns RepeatMasker's GFF gives (default = 'none')")
+    own.add_argument("--index_part_bases", type=int, default=0, help="cut the reference into index parts of at most N bases (padded extent) and merge the "
+                     "per-part records on the device; 0: one index, parts only when the reference does not fit one (default = 0)")
     own.add_argument("--sample", type=str, help="sample name (default: the reads file's name without its extension)")
     p._action_groups.append(opt)
     a = p.parse_args(argv)
@@ -131,6 +139,8 @@ def get_args(argv=None):
     number("overlap", 20, lambda v: True, "")
     if a.device < 0:
         _exit("Please provide a valid device number, exiting...")
+    if a.index_part_bases < 0:
+        _exit("Please provide a valid number of bases per index part (0 or a positive integer), exiting...")
     if (a.chain_skip or a.seed_rescue or a.mm2_mapq) and a.aligner != "minimap2":
         _exit("--chain_skip, --seed_rescue and --mm2_mapq are options of the minimap2 aligner, exiting...")
     a.out = os.path.abspath("." if a.out is None else a.out)
@@ -161,6 +171,24 @@ def aligner_preset(args):
 def make_engine(device):
     from .aligner import Engine
     return Engine(device)
+
+
+def index_stage(eng, targets, io, part_bases, like=None):
+    """the index of a stage over the reference -> (index, number of parts).  part_bases 0: Engine.index as ever, unless the planner says
+    that the reference needs more than one part; part_bases > 0: always Engine.index_parts.  like: the stage-1 index, whose resident
+    targets (and parts) the asm10 index is built over"""
+    from .aligner import Engine, PartIndex
+    if like is not None:
+        if isinstance(like, PartIndex):
+            ix = eng.index_parts(None, io, max_part_bases=like.max_part_bases, like=like)
+            return ix, ix.n_parts
+        return eng.index(like.targets, io), 1
+    if part_bases == 0:
+        part_of = Engine.part_plan([len(s) for s in targets])
+        if len(part_of) == 0 or int(part_of[-1]) == 0:
+            return eng.index(targets, io), 1
+    ix = eng.index_parts(targets, io, max_part_bases=part_bases)
+    return ix, ix.n_parts
 
 
 def load_reads(eng, ix, args, tnames, bam_path):
@@ -276,8 +304,8 @@ def run(args, engine=None):
         done("inputs", "%d reference sequences, %d library sequences" % (len(tnames), len(lib_names)))
         # 2. the stage-1 index
         io, _ = preset(aligner_preset(args)[0])
-        ix = eng.index(tseqs, io)
-        done("index", "stage-1 index (%s)" % aligner_preset(args)[0])
+        ix, n_parts = index_stage(eng, tseqs, io, args.index_part_bases)
+        done("index", "stage-1 index (%s), %d part%s" % (aligner_preset(args)[0], n_parts, "" if n_parts == 1 else "s"))
         # 3. the reads: mapped here, or taken from the BAM
         if is_bam(args.reads):
             qnames, read_set, r, release = load_bam(eng, ix, args, tnames, [len(s) for s in tseqs])
@@ -307,8 +335,8 @@ def run(args, engine=None):
             eng.release_scratch()                   # stage 1 will not run again: its mapping scratch goes back to the device
         # 6. the asm10 index over the same resident reference
         io10, _ = preset("asm10")
-        ix10 = eng.index(ix.targets, io10)
-        done("index10", "asm10 index of the reference")
+        ix10, n_parts10 = index_stage(eng, None, io10, args.index_part_bases, like=ix)
+        done("index10", "asm10 index of the reference, %d part%s" % (n_parts10, "" if n_parts10 == 1 else "s"))
         ref_te_rows = None
         if args.ref_te != "none" and loci:          # (only the liftover of a locus reads them)
             files["ref_te"] = os.path.join(inter, os.path.basename(args.reference) + ".te.bed") if args.ref_te == "engine" else args.ref_te
