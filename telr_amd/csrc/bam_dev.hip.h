@@ -75,13 +75,6 @@ struct ByteW {
     __device__ __forceinline__ void flush() { for (int i = 0; i < k; ++i) p[i] = (uint8_t)(acc >> (8 * i)); k = 0; acc = 0; }
 };
 __device__ __forceinline__ int d_wave_sum(int v) { for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s); return v; }
-// inclusive prefix sum over the wave
-__device__ __forceinline__ int d_wave_incl(int v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(v, o); if (lane >= o) v += y; }
-    return v;
-}
 
 // 32 bases x .. x+31 of a sequence (first base at base offset b0 of the packed arrays, L bases) read on strand `rev`
 // (1: the reverse complement, x counted from its own start), first base in the low bits; n = ambiguity bits.
@@ -1334,13 +1327,9 @@ static int bam_dev_impl(telr_ctx *ctx, const telr_result *r, const telr_seqset *
     // ... unless the result kept them there (TELR_MF_KEEP_CIGARS): the mirrored array is used in place
     uint32_t *d_cig;
     static const bool no_twin = ab_on("bam_no_twin");
-    const bool twin = r->d_cig && !r->twin_off && r->twin_n == r->ncig && !no_twin;
+    bool twin;
+    TRY(result_dev_cigars(ctx, r, "bam_cig", !no_twin, &d_cig, &twin, 1));
     g_bam_twin = twin ? 1 : 0;
-    if (twin) { d_cig = r->d_cig; HIPCHK(hipDeviceSynchronize()); }      // its last pieces were copied on other streams
-    else {
-        TRY(ctx_buf_t(ctx, "bam_cig", r->ncig + 1, &d_cig));
-        if (r->ncig) HIPCHK(hipMemcpyAsync(d_cig, r->cig, r->ncig * 4, hipMemcpyHostToDevice, st));
-    }
     // ---- 1. records (+ pseudo records of the unmapped reads, in query order), names, header
     std::vector<telr_aln> recs(r->alns);
     size_t n_unmapped = 0;

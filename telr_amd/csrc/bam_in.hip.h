@@ -185,8 +185,7 @@ static __device__ __forceinline__ CigWalk bam_cigar_walk(const uint8_t *__restri
         const uint64_t heads = __ballot(head);
         const int64_t L = m >= 0 ? (int64_t)len : 0;
         if (m == 0) acc0 += L; else if (m == 1) acc1 += L; else if (m == 2) acc2 += L;
-        int64_t P = L;                                          // inclusive prefix sum over the lanes
-        for (int o = 1; o < 64; o <<= 1) { const int64_t y = __shfl_up(P, o); if (lane >= o) P += y; }
+        const int64_t P = d_wave_incl<int64_t>(L, lane);
         const int64_t tot = __shfl(P, 63);
         if (!heads) { carry_sum += tot; continue; }
         const int fh = __ffsll((long long)heads) - 1;
@@ -755,7 +754,7 @@ extern "C" int telr_bam_load(telr_ctx *ctx, const char *path, int32_t keep_qual,
         TRY(ctx_buf_t(ctx, "bamin_reads", (size_t)nq, &d_reads));
         HIPCHK(hipMemcpyAsync(d_reads, reads.data(), (size_t)nq * sizeof(BamRead), hipMemcpyHostToDevice, st));
         const int64_t nw = S->padded_bases / 16;
-        hipLaunchKernelGGL(k_bam_seq, ins_grid(nw), dim3(256), 0, st, d_stream, d_reads, S->d_boff, nq, nw, S->d_seq2, S->d_nmask);
+        hipLaunchKernelGGL(k_bam_seq, grid256(nw), dim3(256), 0, st, d_stream, d_reads, S->d_boff, nq, nw, S->d_seq2, S->d_nmask);
         HIPCHK(hipGetLastError());
         if (keep_qual && !any_ff) {
             int32_t *d_over;
@@ -763,7 +762,7 @@ extern "C" int telr_bam_load(telr_ctx *ctx, const char *path, int32_t keep_qual,
             HIPCHK(hipMemsetAsync(d_over, 0, (size_t)nq * 4, st));
             HIPCHK(hipMalloc(&S->d_qual, (size_t)S->padded_bases + 64));
             HIPCHK(hipMemsetAsync(S->d_qual + S->padded_bases, 0, 64, st));
-            hipLaunchKernelGGL(k_bam_qual, ins_grid(S->padded_bases / 4), dim3(256), 0, st, d_stream, d_reads, S->d_boff, nq, S->padded_bases / 4, (uint32_t*)S->d_qual, d_over);
+            hipLaunchKernelGGL(k_bam_qual, grid256(S->padded_bases / 4), dim3(256), 0, st, d_stream, d_reads, S->d_boff, nq, S->padded_bases / 4, (uint32_t*)S->d_qual, d_over);
             HIPCHK(hipGetLastError());
             std::vector<int32_t> over((size_t)nq);
             HIPCHK(hipMemcpyAsync(over.data(), d_over, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
@@ -813,7 +812,7 @@ extern "C" int telr_bam_in_ascii(const telr_bam_in *in, char *buf, int64_t *off)
     TRY(ctx_buf_t(ctx, "bamin_coff", (size_t)S->n + 1, &d_coff));
     HIPCHK(hipMemcpyAsync(d_coff, coff.data(), ((size_t)S->n + 1) * 8, hipMemcpyHostToDevice, st));
     const int64_t nq4 = S->padded_bases / 4;
-    hipLaunchKernelGGL(k_bam_ascii, ins_grid(nq4), dim3(256), 0, st, S->d_seq2, S->d_nmask, S->d_boff, S->d_len, d_coff, S->n, nq4, d_text);
+    hipLaunchKernelGGL(k_bam_ascii, grid256(nq4), dim3(256), 0, st, S->d_seq2, S->d_nmask, S->d_boff, S->d_len, d_coff, S->n, nq4, d_text);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(buf, d_text, (size_t)S->total_bases, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

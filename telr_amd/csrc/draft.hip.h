@@ -34,9 +34,7 @@ __global__ void __launch_bounds__(256) k_draft_span(const telr_ins_sig *__restri
     int32_t f = 0, c = 0;
     if (s.kind == 0 || s.kind == 1) {
         const int64_t lo = s.pos > reach ? (int64_t)s.pos - reach : 0, hi = (int64_t)s.pos + reach < 0x7fffffffLL ? (int64_t)s.pos + reach : 0x7fffffffLL;
-        const uint64_t t = (uint64_t)(uint32_t)s.tid << 32;
-        const int64_t b0 = geno_bound<false>(ckeys, ncall, t | (uint64_t)lo), b1 = geno_bound<true>(ckeys, ncall, t | (uint64_t)hi);
-        f = (int32_t)b0; c = b1 > b0 ? (int32_t)(b1 - b0) : 0;
+        d_span(ckeys, ncall, s.tid, lo, hi, &f, &c);
     }
     first[j] = f; cnt[j] = c;
 }
@@ -48,13 +46,8 @@ __global__ void __launch_bounds__(256) k_draft_pairs(const int64_t *__restrict__
 {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= np) return;
-    int32_t lo = 0, hi = ns;                              // first signature with off > p
-    while (lo < hi) { const int32_t mid = lo + ((hi - lo) >> 1); if (off[mid] <= p) lo = mid + 1; else hi = mid; }
-    const int32_t j = lo - 1, k = first[j] + (int32_t)(p - off[j]), q = sigs[j].qid;
-    int64_t a = read_off[k], b = read_off[k + 1];
-    const int64_t end = b;
-    while (a < b) { const int64_t mid = a + ((b - a) >> 1); if (reads[mid] < q) a = mid + 1; else b = mid; }
-    psig[p] = j; pcall[p] = (a < end && reads[a] == q) ? k : ~k;
+    const int32_t j = d_pair_owner(off, ns, p), k = first[j] + (int32_t)(p - off[j]), q = sigs[j].qid;
+    psig[p] = j; pcall[p] = d_in_list(reads, read_off[k], read_off[k + 1], q) ? k : ~k;
 }
 
 // One wave walks the n CIGAR words at c from the state (ts, qs): lo = the smallest strand coordinate among the states at reference
@@ -73,7 +66,7 @@ static __device__ __forceinline__ void draft_walk(const uint32_t *__restrict__ c
         next = i < n - 64 ? c[i + 64] : 0u;               // the next step's words are on their way while this step's are summed
         const int32_t op = (int32_t)(word & 15u);
         const int64_t len = (int64_t)(word >> 4), r = (op == 0 || op == 2) ? len : 0, q = (op == 0 || op == 1) ? len : 0;
-        const int64_t ri = geno_wave_incl(r, lane), qi = geno_wave_incl(q, lane), p = rbase + ri - r, u = qbase + qi - q;
+        const int64_t ri = d_wave_incl<int64_t>(r, lane), qi = d_wave_incl<int64_t>(q, lane), p = rbase + ri - r, u = qbase + qi - q;
         if (WANT_LO && !flo) {
             const uint64_t m = __ballot(i < n && p <= xlo && xlo <= p + r);
             if (m) { lo = __shfl(u + (op == 0 ? xlo - p : 0), __builtin_ctzll(m)); flo = true; }
@@ -186,29 +179,6 @@ __global__ void __launch_bounds__(256) k_draft_select(const telr_ins_sig *__rest
     out[k] = d;
 }
 
-// 16 bases from base offset S of a packed array (S >= -15: what lies before the array reads as zero)
-static __device__ __forceinline__ uint32_t draft_window2(const uint32_t *__restrict__ p, int64_t S)
-{
-    const int64_t sw = S >> 4;
-    const int sh = (int)(S & 15) * 2;
-    const uint32_t a = sw >= 0 ? p[sw] : 0u;
-    if (sh == 0) return a;
-    return (uint32_t)((((uint64_t)p[sw + 1] << 32) | a) >> sh);
-}
-static __device__ __forceinline__ uint32_t draft_window1(const uint32_t *__restrict__ p, int64_t S)
-{
-    const int64_t sw = S >> 5;
-    const int sh = (int)(S & 31);
-    const uint32_t a = sw >= 0 ? p[sw] : 0u;
-    if (sh <= 16) return (a >> sh) & 0xffffu;
-    return (uint32_t)((((uint64_t)p[sw + 1] << 32) | a) >> sh) & 0xffffu;
-}
-static __device__ __forceinline__ uint32_t draft_rev16x2(uint32_t x)      // the sixteen 2-bit codes of a word in reverse order
-{
-    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
-    x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
-    return __builtin_bswap32(x);
-}
 static __device__ __forceinline__ uint32_t draft_spread16(uint32_t v)     // bit i -> bit 2i
 {
     v = (v | v << 8) & 0x00FF00FFu; v = (v | v << 4) & 0x0F0F0F0Fu; v = (v | v << 2) & 0x33333333u; v = (v | v << 1) & 0x55555555u;
@@ -231,8 +201,8 @@ __global__ void __launch_bounds__(256) k_draft_extract(const uint32_t *__restric
     uint32_t code = 0, m16 = 0;
     if (kb > 0) {
         const int64_t S = P.rc ? P.src + P.len - 16 - j0 : P.src + j0;
-        code = draft_window2(par2, S); m16 = draft_window1(parn, S);
-        if (P.rc) { code = ~draft_rev16x2(code); m16 = __brev(m16) >> 16; }
+        code = d_window2(par2, S); m16 = d_window1(parn, S);
+        if (P.rc) { code = ~d_rev16x2(code); m16 = __brev(m16) >> 16; }
         const uint32_t keep = kb == 16 ? 0xffffu : (1u << kb) - 1u;
         m16 &= keep;
         code &= draft_spread16(keep & ~m16) * 3u;         // an N keeps its mask bit and code 0, as the packers write it
@@ -279,7 +249,7 @@ static int draft_cut_set(telr_ctx *ctx, const char *what, const telr_seqset *par
         if (rc_ != TELR_OK) { telr_seqset_free(S); return rc_; }
         hipError_t e = hipMemcpyAsync(d_piece, pieces.data(), (size_t)nd * sizeof(DraftPiece), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_draft_extract, ins_grid(nw), dim3(256), 0, st, parent->d_seq2, parent->d_nmask, d_piece, S->d_boff, nd, nw, S->d_seq2, S->d_nmask);
+            hipLaunchKernelGGL(k_draft_extract, grid256(nw), dim3(256), 0, st, parent->d_seq2, parent->d_nmask, d_piece, S->d_boff, nd, nw, S->d_seq2, S->d_nmask);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -311,33 +281,13 @@ extern "C" int telr_draft_contigs(telr_ctx *ctx, const telr_result *r, int32_t n
     if (n_sig >= 0x7ffffff0LL) { ctx->err = "telr_draft_contigs: too many signatures"; return TELR_E_RANGE; }
     // the calls: 64-bit (tid, pos) keys, strictly ascending; the supporter lists ascending and distinct
     std::vector<uint64_t> ckeys((size_t)n_calls);
-    for (int64_t k = 0; k < n_calls; ++k) {
-        const telr_ins_call &c = calls[k];
-        if (c.tid < 0 || c.tid >= n_targets) return bad("call " + std::to_string(k) + ": tid outside n_targets");
-        if (c.pos < 0) return bad("call " + std::to_string(k) + ": negative pos");
-        ckeys[k] = ((uint64_t)(uint32_t)c.tid << 32) | (uint32_t)c.pos;
-        if (k > 0 && ckeys[k] <= ckeys[k - 1]) return bad("call " + std::to_string(k) + ": calls not strictly ascending by (tid, pos)");
-    }
-    if (n_calls > 0) {
-        if (read_off[0] != 0) return bad("read_off[0] is not 0");
-        for (int64_t k = 0; k < n_calls; ++k) {
-            if (read_off[k + 1] < read_off[k]) return bad("call " + std::to_string(k) + ": read offsets descend");
-            if (read_off[k + 1] > read_off[k] && !reads) return bad("null reads");
-            for (int64_t j = read_off[k]; j < read_off[k + 1]; ++j) {
-                if (reads[j] < 0 || reads[j] >= read_set->n) return bad("call " + std::to_string(k) + ": read id outside the read set");
-                if (j > read_off[k] && reads[j] <= reads[j - 1]) return bad("call " + std::to_string(k) + ": read list not ascending");
-            }
-        }
-    }
-    // the records: what telr_call_insertions refuses is refused here, and every record's read is a sequence of the set with its length
+    std::string why;
+    if (!call_list_check(n_calls, calls, read_off, reads, n_targets, read_set->n, ckeys.data(), nullptr, &why)) return bad(why);
+    // the records: the shared refusals (record_checks.h), and every record's read is a sequence of the set with its length
     std::vector<DraftRec> recs(n);
     for (size_t i = 0; i < n; ++i) {
         const telr_aln &a = r->alns[i];
-        if (a.tid < 0 || a.tid >= n_targets) return bad("record " + std::to_string(i) + ": tid outside n_targets");
-        if (a.qid < 0 || a.qlen < 0 || a.qs < 0 || a.qe < a.qs || a.qe > a.qlen || a.ts < 0 || a.te < a.ts)
-            return bad("record " + std::to_string(i) + ": coordinates");
-        if (a.n_cigar < 0 || a.cigar_off < 0 || (uint64_t)a.cigar_off + (uint64_t)a.n_cigar > (uint64_t)r->ncig)
-            return bad("record " + std::to_string(i) + ": CIGAR range outside the result's array");
+        if (!record_check(a, i, n_targets, r->ncig, &why)) return bad(why);
         if (a.qid >= read_set->n) return bad("record " + std::to_string(i) + ": qid outside the read set");
         if (a.qlen != read_set->len[a.qid]) return bad("record " + std::to_string(i) + ": qlen is not the length of its read in the read set");
         DraftRec &e = recs[i];
@@ -381,7 +331,7 @@ extern "C" int telr_draft_contigs(telr_ctx *ctx, const telr_result *r, int32_t n
         HIPCHK(hipMemcpyAsync(d_sig, sigs, (size_t)ns * sizeof(telr_ins_sig), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_calls, calls, (size_t)nc * sizeof(telr_ins_call), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_ckeys, ckeys.data(), (size_t)nc * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_draft_span, ins_grid((int64_t)ns), dim3(256), 0, st, d_sig, ns, d_ckeys, nc, O.reach, d_first, d_cnt);
+        hipLaunchKernelGGL(k_draft_span, grid256((int64_t)ns), dim3(256), 0, st, d_sig, ns, d_ckeys, nc, O.reach, d_first, d_cnt);
         HIPCHK(hipGetLastError());
         TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt, ns, d_off, d_tot, 0, nullptr, nullptr)));
         HIPCHK(hipMemcpyAsync(&P, d_tot, 8, hipMemcpyDeviceToHost, st));
@@ -389,14 +339,8 @@ extern "C" int telr_draft_contigs(telr_ctx *ctx, const telr_result *r, int32_t n
         if (P >= 0x7ffffff0LL) { ctx->err = "telr_draft_contigs: too many (signature, call) pairs"; return TELR_E_RANGE; }
     }
     if (P > 0) {
-        // the CIGAR array: the result's own device copy when it kept one (TELR_MF_KEEP_CIGARS), else uploaded
-        const bool twin = r->d_cig && !r->twin_off && r->twin_n == r->ncig;
         uint32_t *d_cig;
-        if (twin) { d_cig = r->d_cig; HIPCHK(hipDeviceSynchronize()); }
-        else {
-            TRY(ctx_buf_t(ctx, "draft_cig", r->ncig, &d_cig));
-            if (r->ncig) HIPCHK(hipMemcpyAsync(d_cig, r->cig, r->ncig * 4, hipMemcpyHostToDevice, st));
-        }
+        TRY(result_dev_cigars(ctx, r, "draft_cig", true, &d_cig, nullptr));
         const int64_t nreads = read_off[n_calls];
         DraftRec *d_rec; int64_t *d_roff; int32_t *d_reads, *d_psig, *d_pcall; DraftCand *d_cand; telr_draft *d_out;
         TRY(ctx_buf_t(ctx, "draft_rec", n, &d_rec));
@@ -409,7 +353,7 @@ extern "C" int telr_draft_contigs(telr_ctx *ctx, const telr_result *r, int32_t n
         HIPCHK(hipMemcpyAsync(d_rec, recs.data(), n * sizeof(DraftRec), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_roff, read_off, ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
         if (nreads) HIPCHK(hipMemcpyAsync(d_reads, reads, (size_t)nreads * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_draft_pairs, ins_grid(P), dim3(256), 0, st, d_off, ns, d_first, P, d_sig, d_roff, d_reads, d_psig, d_pcall);
+        hipLaunchKernelGGL(k_draft_pairs, grid256(P), dim3(256), 0, st, d_off, ns, d_first, P, d_sig, d_roff, d_reads, d_psig, d_pcall);
         hipLaunchKernelGGL(k_draft_walk, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, st, d_sig, d_calls, d_rec, d_cig, d_psig, d_pcall, P, O.flank, O.min_flank, O.max_len, d_cand);
         hipLaunchKernelGGL(k_draft_select, dim3((unsigned)(((int64_t)nc + 3) / 4)), dim3(256), 0, st, d_sig, ns, d_calls, nc, d_rec, d_first, d_cnt, d_off, d_cand, O.reach, d_out);
         HIPCHK(hipGetLastError());

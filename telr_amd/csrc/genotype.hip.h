@@ -13,7 +13,7 @@
 //   sort           radix.hip.h over the bits the three fields can hold: the clean pair of a (call, read) run sorts first, so the
 //                  run's first pair is clean iff any is;
 //   k_geno_flags   run heads that are no supporter (binary search in the call's read list) -> reference / ambiguous flags; two
-//                  scans give the counts as differences at the calls' bounds (k_geno_bounds) and the places of the read lists.
+//                  scans give the counts as differences at the calls' bounds (k_geno_cstart) and the places of the read lists.
 #pragma once
 
 struct GenoRec { int32_t qid, tid, ts, te, n_cigar, pad; int64_t cigar_off; };      // an eligible record
@@ -30,19 +30,6 @@ static __host__ __device__ __forceinline__ int32_t geno_gt(int32_t alt, int32_t 
     return a >= hom_pct * n ? 2 : a >= het_pct * n ? 1 : 0;
 }
 
-// first i in [0, n) with k[i] >= v (UPPER: > v)
-template <bool UPPER>
-static __device__ __forceinline__ int64_t geno_bound(const uint64_t *__restrict__ k, int64_t n, uint64_t v)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const uint64_t x = k[mid];
-        if (UPPER ? x <= v : x < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // the calls record a spans: the keys in [(tid, ts + flank) -- (tid, 0) when ts is 0: the max(0, .) rule --, (tid, te - flank)]
 __global__ void __launch_bounds__(256) k_geno_span(const GenoRec *__restrict__ recs, int32_t ne, const uint64_t *__restrict__ ckeys, int32_t ncall, int32_t flank,
                                                    int32_t *__restrict__ first, int32_t *__restrict__ cnt)
@@ -52,11 +39,7 @@ __global__ void __launch_bounds__(256) k_geno_span(const GenoRec *__restrict__ r
     const GenoRec R = recs[a];
     const int64_t lo = R.ts == 0 ? 0 : (int64_t)R.ts + flank, hi = (int64_t)R.te - flank;
     int32_t f = 0, c = 0;
-    if (hi >= lo && lo <= 0x7fffffffLL) {
-        const uint64_t t = (uint64_t)(uint32_t)R.tid << 32;
-        const int64_t b0 = geno_bound<false>(ckeys, ncall, t | (uint64_t)lo), b1 = geno_bound<true>(ckeys, ncall, t | (uint64_t)hi);
-        f = (int32_t)b0; c = b1 > b0 ? (int32_t)(b1 - b0) : 0;
-    }
+    if (hi >= lo && lo <= 0x7fffffffLL) d_span(ckeys, ncall, R.tid, lo, hi, &f, &c);
     first[a] = f; cnt[a] = c;
 }
 
@@ -66,17 +49,8 @@ __global__ void __launch_bounds__(256) k_geno_pairs(const int64_t *__restrict__ 
 {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= np) return;
-    int32_t lo = 0, hi = ne;                              // first record with off > p
-    while (lo < hi) { const int32_t mid = lo + ((hi - lo) >> 1); if (off[mid] <= p) lo = mid + 1; else hi = mid; }
-    const int32_t a = lo - 1;
+    const int32_t a = d_pair_owner(off, ne, p);
     prec[p] = a; pcall[p] = first[a] + (int32_t)(p - off[a]);
-}
-
-static __device__ __forceinline__ int64_t geno_wave_incl(int64_t v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int64_t x = __shfl_up(v, o); if (lane >= o) v += x; }
-    return v;
 }
 
 // the window indel of every pair -> its sort key ((call << qbits | read) << 1) | unclean
@@ -100,7 +74,7 @@ __global__ void __launch_bounds__(256) k_geno_window(const GenoRec *__restrict__
         next = i < n - 64 ? c[i + 64] : 0u;               // the next step's words are on their way while this step's are summed
         const int32_t op = (int32_t)(word & 15u);
         const int64_t len = (int64_t)(word >> 4), r = (op == 0 || op == 2) ? len : 0;
-        const int64_t ri = geno_wave_incl(r, lane), p = rbase + ri - r;
+        const int64_t ri = d_wave_incl<int64_t>(r, lane), p = rbase + ri - r;
         if (op == 1) { if (wlo <= p && p <= whi) sum += len; }
         else if (op == 2) {
             const int64_t e = (p + len < whi ? p + len : whi) - (p > wlo ? p : wlo);
@@ -126,20 +100,17 @@ __global__ void __launch_bounds__(256) k_geno_flags(const uint64_t *__restrict__
         if (j == 0 || (keys[j - 1] >> 1) != (key >> 1)) {
             const int32_t q = (int32_t)((key >> 1) & ((1ULL << qbits) - 1ULL));
             const int64_t k = (int64_t)(key >> (qbits + 1));
-            int64_t lo = read_off[k], hi = read_off[k + 1];
-            const int64_t end = hi;
-            while (lo < hi) { const int64_t mid = lo + ((hi - lo) >> 1); if (reads[mid] < q) lo = mid + 1; else hi = mid; }
-            if (!(lo < end && reads[lo] == q)) { if (key & 1ULL) af = 1; else rf = 1; }
+            if (!d_in_list(reads, read_off[k], read_off[k + 1], q)) { if (key & 1ULL) af = 1; else rf = 1; }
         }
     }
     rflag[j] = rf; aflag[j] = af;
 }
 // cstart[k] = the first sorted pair of call k or a later one (cstart[ncall] = np)
-__global__ void __launch_bounds__(256) k_geno_bounds(const uint64_t *__restrict__ keys, int64_t np, int qbits, int32_t ncall, int32_t *__restrict__ cstart)
+__global__ void __launch_bounds__(256) k_geno_cstart(const uint64_t *__restrict__ keys, int64_t np, int qbits, int32_t ncall, int32_t *__restrict__ cstart)
 {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k > ncall) return;
-    cstart[k] = k == ncall ? (int32_t)np : (int32_t)geno_bound<false>(keys, np, (uint64_t)k << (qbits + 1));
+    cstart[k] = k == ncall ? (int32_t)np : (int32_t)d_bound<false>(keys, np, (uint64_t)k << (qbits + 1));
 }
 __global__ void __launch_bounds__(256) k_geno_calls(const int32_t *__restrict__ cstart, int32_t ncall, const int32_t *__restrict__ rx, const int32_t *__restrict__ ax,
                                                     const int32_t *__restrict__ support, int32_t het_pct, int32_t hom_pct, telr_ins_gt *__restrict__ gt,
@@ -199,35 +170,14 @@ extern "C" int telr_genotype_insertions(telr_ctx *ctx, const telr_result *r, int
     // the calls: 64-bit (tid, pos) keys, strictly ascending; the supporter lists ascending and distinct
     std::vector<uint64_t> ckeys((size_t)n_calls);
     std::vector<int32_t> support((size_t)n_calls);
-    for (int64_t k = 0; k < n_calls; ++k) {
-        const telr_ins_call &c = calls[k];
-        if (c.tid < 0 || c.tid >= n_targets) return bad("call " + std::to_string(k) + ": tid outside n_targets");
-        if (c.pos < 0) return bad("call " + std::to_string(k) + ": negative pos");
-        ckeys[k] = ((uint64_t)(uint32_t)c.tid << 32) | (uint32_t)c.pos;
-        if (k > 0 && ckeys[k] <= ckeys[k - 1]) return bad("call " + std::to_string(k) + ": calls not strictly ascending by (tid, pos)");
-        support[k] = c.support;
-    }
-    if (n_calls > 0) {
-        if (read_off[0] != 0) return bad("read_off[0] is not 0");
-        for (int64_t k = 0; k < n_calls; ++k) {
-            if (read_off[k + 1] < read_off[k]) return bad("call " + std::to_string(k) + ": read offsets descend");
-            if (read_off[k + 1] > read_off[k] && !reads) return bad("null reads");
-            for (int64_t j = read_off[k]; j < read_off[k + 1]; ++j) {
-                if (reads[j] < 0) return bad("call " + std::to_string(k) + ": negative read id");
-                if (j > read_off[k] && reads[j] <= reads[j - 1]) return bad("call " + std::to_string(k) + ": read list not ascending");
-            }
-        }
-    }
+    std::string why;
+    if (!call_list_check(n_calls, calls, read_off, reads, n_targets, -1, ckeys.data(), support.data(), &why)) return bad(why);
     // the eligible records
     std::vector<GenoRec> er;
     int32_t max_qid = 0;
     for (size_t i = 0; i < n; ++i) {
         const telr_aln &a = r->alns[i];
-        if (a.tid < 0 || a.tid >= n_targets) return bad("record " + std::to_string(i) + ": tid outside n_targets");
-        if (a.qid < 0 || a.qlen < 0 || a.qs < 0 || a.qe < a.qs || a.qe > a.qlen || a.ts < 0 || a.te < a.ts)
-            return bad("record " + std::to_string(i) + ": coordinates");
-        if (a.n_cigar < 0 || a.cigar_off < 0 || (uint64_t)a.cigar_off + (uint64_t)a.n_cigar > (uint64_t)r->ncig)
-            return bad("record " + std::to_string(i) + ": CIGAR range outside the result's array");
+        if (!record_check(a, i, n_targets, r->ncig, &why)) return bad(why);
         if ((a.flags & TELR_F_SECONDARY) || a.mapq < O.min_mapq) continue;
         GenoRec e;
         e.qid = a.qid; e.tid = a.tid; e.ts = a.ts; e.te = a.te; e.n_cigar = a.n_cigar; e.pad = 0; e.cigar_off = a.cigar_off;
@@ -253,7 +203,7 @@ extern "C" int telr_genotype_insertions(telr_ctx *ctx, const telr_result *r, int
     TRY(ctx_buf_t(ctx, "geno_tot", 4, &d_tot));
     HIPCHK(hipMemcpyAsync(d_rec, er.data(), ne * sizeof(GenoRec), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_ckeys, ckeys.data(), (size_t)nc * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_geno_span, ins_grid((int64_t)ne), dim3(256), 0, st, d_rec, (int32_t)ne, d_ckeys, nc, O.flank, d_first, d_cnt);
+    hipLaunchKernelGGL(k_geno_span, grid256((int64_t)ne), dim3(256), 0, st, d_rec, (int32_t)ne, d_ckeys, nc, O.flank, d_first, d_cnt);
     HIPCHK(hipGetLastError());
     TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt, (int32_t)ne, d_off, d_tot, 0, nullptr, nullptr)));
     int64_t tot[2];
@@ -262,14 +212,8 @@ extern "C" int telr_genotype_insertions(telr_ctx *ctx, const telr_result *r, int
     const int64_t P = tot[0];
     if (P == 0) { *out = guard.release(); return TELR_OK; }
     if (P >= 0x7ffffff0LL) { ctx->err = "telr_genotype_insertions: too many (call, record) pairs"; return TELR_E_RANGE; }
-    // the CIGAR array: the result's own device copy when it kept one (TELR_MF_KEEP_CIGARS), else uploaded
-    const bool twin = r->d_cig && !r->twin_off && r->twin_n == r->ncig;
     uint32_t *d_cig;
-    if (twin) { d_cig = r->d_cig; HIPCHK(hipDeviceSynchronize()); }
-    else {
-        TRY(ctx_buf_t(ctx, "geno_cig", r->ncig, &d_cig));
-        if (r->ncig) HIPCHK(hipMemcpyAsync(d_cig, r->cig, r->ncig * 4, hipMemcpyHostToDevice, st));
-    }
+    TRY(result_dev_cigars(ctx, r, "geno_cig", true, &d_cig, nullptr));
     const int64_t nreads = read_off[n_calls];
     int32_t *d_pcall, *d_prec, *d_support, *d_reads; int64_t *d_roff; uint64_t *d_keys, *d_tkeys; uint32_t *d_hist;
     TRY(ctx_buf_t(ctx, "geno_pcall", (size_t)P, &d_pcall));
@@ -279,12 +223,12 @@ extern "C" int telr_genotype_insertions(telr_ctx *ctx, const telr_result *r, int
     TRY(ctx_buf_t(ctx, "geno_roff", (size_t)nc + 1, &d_roff));
     TRY(ctx_buf_t(ctx, "geno_keys", (size_t)P, &d_keys));
     TRY(ctx_buf_t(ctx, "geno_tkeys", (size_t)P, &d_tkeys));
-    TRY(ctx_buf_t(ctx, "geno_hist", (size_t)RS_BINS * (((size_t)P + RS_TILE - 1) / RS_TILE) + RS_BINS, &d_hist));
+    TRY(ctx_buf_t(ctx, "geno_hist", rs_hist_words((size_t)P), &d_hist));
     HIPCHK(hipMemcpyAsync(d_support, support.data(), (size_t)nc * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_roff, read_off, ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
     if (nreads) HIPCHK(hipMemcpyAsync(d_reads, reads, (size_t)nreads * 4, hipMemcpyHostToDevice, st));
-    const int qb = std::max(1, ins_bits((uint64_t)max_qid)), cb = ins_bits((uint64_t)nc - 1);
-    const dim3 gP = ins_grid(P), gP1 = ins_grid(P + 1), gC1 = ins_grid((int64_t)nc + 1);
+    const int qb = std::max(1, bits_of((uint64_t)max_qid)), cb = bits_of((uint64_t)nc - 1);
+    const dim3 gP = grid256(P), gP1 = grid256(P + 1), gC1 = grid256((int64_t)nc + 1);
     hipLaunchKernelGGL(k_geno_pairs, gP, dim3(256), 0, st, d_off, (int32_t)ne, d_first, P, d_pcall, d_prec);
     hipLaunchKernelGGL(k_geno_window, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, st, d_rec, d_cig, d_ckeys, d_pcall, d_prec, P, O.flank, O.max_window_indel, qb, d_keys);
     HIPCHK(hipGetLastError());
@@ -298,7 +242,7 @@ extern "C" int telr_genotype_insertions(telr_ctx *ctx, const telr_result *r, int
     TRY(ctx_buf_t(ctx, "geno_ax", (size_t)P + 1, &d_ax));
     TRY(ctx_buf_t(ctx, "geno_cstart", (size_t)nc + 1, &d_cstart));
     hipLaunchKernelGGL(k_geno_flags, gP1, dim3(256), 0, st, d_keys, P, qb, d_roff, d_reads, d_rflag, d_aflag);
-    hipLaunchKernelGGL(k_geno_bounds, gC1, dim3(256), 0, st, d_keys, P, qb, nc, d_cstart);
+    hipLaunchKernelGGL(k_geno_cstart, gC1, dim3(256), 0, st, d_keys, P, qb, nc, d_cstart);
     HIPCHK(hipGetLastError());
     TRY((dev_qscan<int32_t, int32_t>(ctx, d_rflag, (int32_t)P, d_rx, d_tot, 0, nullptr, nullptr)));
     TRY((dev_qscan<int32_t, int32_t>(ctx, d_aflag, (int32_t)P, d_ax, d_tot + 1, 0, nullptr, nullptr)));

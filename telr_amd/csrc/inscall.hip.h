@@ -28,13 +28,6 @@ struct telr_ins_calls {
     std::vector<int32_t> reads;
 };
 
-static __device__ __forceinline__ int32_t ins_wave_incl(int32_t v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int32_t x = __shfl_up(v, o); if (lane >= o) v += x; }
-    return v;
-}
-
 template <bool EMIT>
 __global__ void __launch_bounds__(256) k_ins_cigar(const InsRec *__restrict__ recs, int32_t ne, const uint32_t *__restrict__ cig, int32_t min_len,
                                                    int32_t *__restrict__ cnt, const int64_t *__restrict__ off, telr_ins_sig *__restrict__ out)
@@ -55,7 +48,7 @@ __global__ void __launch_bounds__(256) k_ins_cigar(const InsRec *__restrict__ re
         const uint64_t m = __ballot(hit);
         if (EMIT) {
             const int32_t r = (op == 0 || op == 2) ? len : 0, q = (op == 0 || op == 1) ? len : 0;
-            const int32_t ri = ins_wave_incl(r, lane), qi = ins_wave_incl(q, lane);
+            const int32_t ri = d_wave_incl<int32_t>(r, lane), qi = d_wave_incl<int32_t>(q, lane);
             if (hit) {
                 const int32_t rank = __builtin_popcountll(m & ((1ULL << lane) - 1ULL));
                 const int32_t qb = qbase + qi - q;          // query bases of the record before the run, on the record's strand
@@ -107,38 +100,15 @@ __global__ void __launch_bounds__(256) k_ins_query(const InsRec *__restrict__ re
     if (!EMIT) cnt[a] = n;
 }
 
-// the key of a sort round, gathered through the permutation the rounds before left
-enum { INS_K_KLM, INS_K_REC, INS_K_TP, INS_K_CQU, INS_K_RM, INS_K_LQ, INS_K_CU };
-__global__ void __launch_bounds__(256) k_ins_key(int mode, const telr_ins_sig *__restrict__ sig, const int32_t *__restrict__ cid, const uint32_t *__restrict__ perm,
-                                                 int64_t n, int b0, int b1, uint64_t *__restrict__ keys)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t p = perm[i];
-    const telr_ins_sig s = sig[p];
-    const uint64_t uns = s.kind == 2 ? 1u : 0u;
-    uint64_t k = 0;
-    switch (mode) {
-    case INS_K_KLM: k = ((((uint64_t)s.kind << 31) | (uint32_t)s.len) << b0) | (uint32_t)(s.mate + 1); break;      // b0: bits of a record number + 1
-    case INS_K_REC: k = (uint32_t)s.rec; break;
-    case INS_K_TP:  k = ((uint64_t)(uint32_t)s.tid << 32) | (uint32_t)s.pos; break;
-    case INS_K_CQU: k = ((((uint64_t)(uint32_t)cid[p] << b0) | (uint32_t)s.qid) << 1) | uns; break;                    // b0: bits of a read number
-    case INS_K_RM:  k = ((uint64_t)(uint32_t)s.rec << b0) | (uint32_t)(s.mate + 1); break;
-    case INS_K_LQ:  k = ((uint64_t)(uint32_t)s.len << b0) | (uint32_t)s.qid; break;
-    case INS_K_CU:  k = ((uint64_t)(uint32_t)cid[p] << 1) | uns; break;
-    }
-    keys[i] = k;
-}
-__global__ void __launch_bounds__(256) k_ins_iota(uint32_t *__restrict__ perm, int64_t n)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) perm[i] = (uint32_t)i;
-}
-__global__ void __launch_bounds__(256) k_ins_gather(const telr_ins_sig *__restrict__ in, const uint32_t *__restrict__ perm, int64_t n, telr_ins_sig *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = in[perm[i]];
-}
+// the keys of the sort rounds (stage2_common.hip.h: perm_sort_round); rb / qb: the bits of a record number + 1 / of a read number
+struct InsKeyKLM { int rb; __device__ uint64_t operator()(const telr_ins_sig &s, uint32_t) const { return ((((uint64_t)s.kind << 31) | (uint32_t)s.len) << rb) | (uint32_t)(s.mate + 1); } };
+struct InsKeyREC { __device__ uint64_t operator()(const telr_ins_sig &s, uint32_t) const { return (uint32_t)s.rec; } };
+struct InsKeyTP  { __device__ uint64_t operator()(const telr_ins_sig &s, uint32_t) const { return ((uint64_t)(uint32_t)s.tid << 32) | (uint32_t)s.pos; } };
+struct InsKeyRM  { int rb; __device__ uint64_t operator()(const telr_ins_sig &s, uint32_t) const { return ((uint64_t)(uint32_t)s.rec << rb) | (uint32_t)(s.mate + 1); } };
+struct InsKeyLQ  { int qb; __device__ uint64_t operator()(const telr_ins_sig &s, uint32_t) const { return ((uint64_t)(uint32_t)s.len << qb) | (uint32_t)s.qid; } };
+// with the cluster id of the signature (cid, by the signature's index); unsized (a clipped end) sorts behind sized
+struct InsKeyCQU { const int32_t *cid; int qb; __device__ uint64_t operator()(const telr_ins_sig &s, uint32_t p) const { return ((((uint64_t)(uint32_t)cid[p] << qb) | (uint32_t)s.qid) << 1) | (s.kind == 2 ? 1u : 0u); } };
+struct InsKeyCU  { const int32_t *cid; __device__ uint64_t operator()(const telr_ins_sig &s, uint32_t p) const { return ((uint64_t)(uint32_t)cid[p] << 1) | (s.kind == 2 ? 1u : 0u); } };
 // head[i] = signature i starts a cluster, sized[i] = it carries a length; both with a trailing 0 for the scans
 __global__ void __launch_bounds__(256) k_ins_heads(const telr_ins_sig *__restrict__ sig, int64_t n, int32_t dist, int32_t *__restrict__ head, int32_t *__restrict__ sized)
 {
@@ -212,19 +182,6 @@ __global__ void __launch_bounds__(256) k_ins_reads(const telr_ins_sig *__restric
     if (cflag[c]) reads[qx[c] + (dx[j] - dx[cstart[c]])] = sig[p].qid;
 }
 
-struct InsSort { uint64_t *keys, *tkeys; uint32_t *perm, *tperm, *hist; };
-static int ins_bits(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
-static inline dim3 ins_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-// one stable round: sorts the permutation by `nbits` bits of the keys of `mode`
-static int ins_sort_round(telr_ctx *ctx, InsSort &S, int mode, const telr_ins_sig *sig, const int32_t *cid, int64_t n, int b0, int nbits)
-{
-    hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(k_ins_key, ins_grid(n), dim3(256), 0, st, mode, sig, cid, S.perm, n, b0, 0, S.keys);
-    if (radix_sort_passes<uint64_t, true>(S.keys, S.perm, S.tkeys, S.tperm, n, nbits, S.hist, st)) { std::swap(S.keys, S.tkeys); std::swap(S.perm, S.tperm); }
-    HIPCHK(hipGetLastError());
-    return TELR_OK;
-}
-
 extern "C" void telr_ins_opt_default(telr_ins_opt *o)
 {
     if (!o) return;
@@ -255,13 +212,10 @@ extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t
     // the eligible records, grouped by read (a mapped result is in read order already)
     std::vector<InsRec> er;
     int32_t max_qid = 0; bool in_order = true;
+    std::string why;
     for (size_t i = 0; i < n; ++i) {
         const telr_aln &a = r->alns[i];
-        if (a.tid < 0 || a.tid >= n_targets) return bad("record " + std::to_string(i) + ": tid outside n_targets");
-        if (a.qid < 0 || a.qlen < 0 || a.qs < 0 || a.qe < a.qs || a.qe > a.qlen || a.ts < 0 || a.te < a.ts)
-            return bad("record " + std::to_string(i) + ": coordinates");
-        if (a.n_cigar < 0 || a.cigar_off < 0 || (uint64_t)a.cigar_off + (uint64_t)a.n_cigar > (uint64_t)r->ncig)
-            return bad("record " + std::to_string(i) + ": CIGAR range outside the result's array");
+        if (!record_check(a, i, n_targets, r->ncig, &why)) return bad(why);
         if ((a.flags & TELR_F_SECONDARY) || a.mapq < O.min_mapq) continue;
         InsRec e;
         e.qid = a.qid; e.tid = a.tid; e.ts = a.ts; e.te = a.te; e.qlen = a.qlen; e.rev = (a.flags & TELR_F_REV) ? 1 : 0;
@@ -286,14 +240,8 @@ extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     result_wait(r);
-    // the CIGAR array: the result's own device copy when it kept one (TELR_MF_KEEP_CIGARS), else uploaded
-    const bool twin = r->d_cig && !r->twin_off && r->twin_n == r->ncig;
     uint32_t *d_cig;
-    if (twin) { d_cig = r->d_cig; HIPCHK(hipDeviceSynchronize()); }
-    else {
-        TRY(ctx_buf_t(ctx, "ins_cig", r->ncig, &d_cig));
-        if (r->ncig) HIPCHK(hipMemcpyAsync(d_cig, r->cig, r->ncig * 4, hipMemcpyHostToDevice, st));
-    }
+    TRY(result_dev_cigars(ctx, r, "ins_cig", true, &d_cig, nullptr));
     InsRec *d_rec; int32_t *d_cnt0, *d_cnt1; int64_t *d_off0, *d_off1, *d_tot;
     TRY(ctx_buf_t(ctx, "ins_rec", ne, &d_rec));
     TRY(ctx_buf_t(ctx, "ins_cnt0", ne + 1, &d_cnt0));
@@ -302,7 +250,7 @@ extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t
     TRY(ctx_buf_t(ctx, "ins_off1", ne + 1, &d_off1));
     TRY(ctx_buf_t(ctx, "ins_tot", 4, &d_tot));
     HIPCHK(hipMemcpyAsync(d_rec, er.data(), ne * sizeof(InsRec), hipMemcpyHostToDevice, st));
-    const dim3 gw((unsigned)((ne + 3) / 4)), gl = ins_grid((int64_t)ne);
+    const dim3 gw((unsigned)((ne + 3) / 4)), gl = grid256((int64_t)ne);
     hipLaunchKernelGGL((k_ins_cigar<false>), gw, dim3(256), 0, st, d_rec, (int32_t)ne, d_cig, O.min_len, d_cnt0, (const int64_t*)nullptr, (telr_ins_sig*)nullptr);
     hipLaunchKernelGGL((k_ins_query<false>), gl, dim3(256), 0, st, d_rec, (int32_t)ne, O.min_len, O.min_clip, O.max_ref_gap, d_cnt1, (const int64_t*)nullptr, (telr_ins_sig*)nullptr);
     HIPCHK(hipGetLastError());
@@ -321,20 +269,15 @@ extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t
     hipLaunchKernelGGL((k_ins_query<true>), gl, dim3(256), 0, st, d_rec, (int32_t)ne, O.min_len, O.min_clip, O.max_ref_gap, d_cnt1, d_off1, d_raw + tot[0]);
     HIPCHK(hipGetLastError());
     // sort by (tid, pos, rec, kind, len, mate): least significant group first
-    InsSort S;
-    const size_t ntiles = ((size_t)N + RS_TILE - 1) / RS_TILE;
-    TRY(ctx_buf_t(ctx, "ins_keys", (size_t)N, &S.keys));
-    TRY(ctx_buf_t(ctx, "ins_tkeys", (size_t)N, &S.tkeys));
-    TRY(ctx_buf_t(ctx, "ins_perm", (size_t)N, &S.perm));
-    TRY(ctx_buf_t(ctx, "ins_tperm", (size_t)N, &S.tperm));
-    TRY(ctx_buf_t(ctx, "ins_hist", (size_t)RS_BINS * ntiles + RS_BINS, &S.hist));
-    const int rb = ins_bits((uint64_t)n), qb = ins_bits((uint64_t)max_qid), tb = ins_bits((uint64_t)n_targets - 1);
-    const dim3 gN = ins_grid(N), gN1 = ins_grid(N + 1);
-    hipLaunchKernelGGL(k_ins_iota, gN, dim3(256), 0, st, S.perm, N);
-    TRY(ins_sort_round(ctx, S, INS_K_KLM, d_raw, nullptr, N, rb, 33 + rb));
-    TRY(ins_sort_round(ctx, S, INS_K_REC, d_raw, nullptr, N, 0, rb));
-    TRY(ins_sort_round(ctx, S, INS_K_TP, d_raw, nullptr, N, 0, 32 + tb));
-    hipLaunchKernelGGL(k_ins_gather, gN, dim3(256), 0, st, d_raw, S.perm, N, d_sig);
+    PermSort S;
+    TRY(S.alloc(ctx, "ins_", (size_t)N));
+    const int rb = bits_of((uint64_t)n), qb = bits_of((uint64_t)max_qid), tb = bits_of((uint64_t)n_targets - 1);
+    const dim3 gN = grid256(N), gN1 = grid256(N + 1);
+    perm_iota(ctx, S, N);
+    TRY(perm_sort_round(ctx, S, d_raw, N, InsKeyKLM{rb}, 33 + rb));
+    TRY(perm_sort_round(ctx, S, d_raw, N, InsKeyREC{}, rb));
+    TRY(perm_sort_round(ctx, S, d_raw, N, InsKeyTP{}, 32 + tb));
+    perm_gather(ctx, S, d_raw, N, d_sig);
     // clusters
     int32_t *d_head, *d_hx, *d_sized, *d_sx, *d_cid, *d_cstart, *d_dflag, *d_sdflag, *d_dx, *d_sdx;
     TRY(ctx_buf_t(ctx, "ins_head", (size_t)N + 1, &d_head));
@@ -355,10 +298,10 @@ extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t
     int32_t nc = 0;
     HIPCHK(hipMemcpyAsync(&nc, d_hx + N, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    const int cb = ins_bits((uint64_t)nc - 1);
+    const int cb = bits_of((uint64_t)nc - 1);
     // the distinct reads of every cluster
-    hipLaunchKernelGGL(k_ins_iota, gN, dim3(256), 0, st, S.perm, N);
-    TRY(ins_sort_round(ctx, S, INS_K_CQU, d_sig, d_cid, N, qb, cb + qb + 1));
+    perm_iota(ctx, S, N);
+    TRY(perm_sort_round(ctx, S, d_sig, N, InsKeyCQU{d_cid, qb}, cb + qb + 1));
     uint32_t *d_permd;
     TRY(ctx_buf_t(ctx, "ins_permd", (size_t)N, &d_permd));
     HIPCHK(hipMemcpyAsync(d_permd, S.perm, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
@@ -367,17 +310,17 @@ extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t
     TRY((dev_qscan<int32_t, int32_t>(ctx, d_dflag, (int32_t)N, d_dx, nullptr, 0, nullptr, nullptr)));
     TRY((dev_qscan<int32_t, int32_t>(ctx, d_sdflag, (int32_t)N, d_sdx, nullptr, 0, nullptr, nullptr)));
     // the representative: (cluster, unsized, len, read, rec, mate)
-    hipLaunchKernelGGL(k_ins_iota, gN, dim3(256), 0, st, S.perm, N);
-    TRY(ins_sort_round(ctx, S, INS_K_RM, d_sig, d_cid, N, rb, 2 * rb));
-    TRY(ins_sort_round(ctx, S, INS_K_LQ, d_sig, d_cid, N, qb, 31 + qb));
-    TRY(ins_sort_round(ctx, S, INS_K_CU, d_sig, d_cid, N, 0, cb + 1));
+    perm_iota(ctx, S, N);
+    TRY(perm_sort_round(ctx, S, d_sig, N, InsKeyRM{rb}, 2 * rb));
+    TRY(perm_sort_round(ctx, S, d_sig, N, InsKeyLQ{qb}, 31 + qb));
+    TRY(perm_sort_round(ctx, S, d_sig, N, InsKeyCU{d_cid}, cb + 1));
     // calls
     int32_t *d_cflag, *d_qcnt, *d_cx; int64_t *d_qx;
     TRY(ctx_buf_t(ctx, "ins_cflag", (size_t)nc + 1, &d_cflag));
     TRY(ctx_buf_t(ctx, "ins_qcnt", (size_t)nc + 1, &d_qcnt));
     TRY(ctx_buf_t(ctx, "ins_cx", (size_t)nc + 1, &d_cx));
     TRY(ctx_buf_t(ctx, "ins_qx", (size_t)nc + 1, &d_qx));
-    const dim3 gC1 = ins_grid((int64_t)nc + 1);
+    const dim3 gC1 = grid256((int64_t)nc + 1);
     hipLaunchKernelGGL(k_ins_cluster, gC1, dim3(256), 0, st, d_cstart, nc, d_dx, d_sdx, O.min_support, O.min_sized, d_cflag, d_qcnt);
     HIPCHK(hipGetLastError());
     TRY((dev_qscan<int32_t, int32_t>(ctx, d_cflag, nc, d_cx, d_tot, 0, nullptr, nullptr)));

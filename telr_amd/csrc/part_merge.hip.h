@@ -252,7 +252,7 @@ extern "C" int telr_merge_parts(telr_ctx *ctx, int32_t n_parts, const telr_resul
     std::vector<char> twin((size_t)P);
     for (int p = 0; p < P; ++p) {
         const telr_result *r = parts[p];
-        twin[p] = r->d_cig && !r->twin_off && r->twin_n == r->ncig && !no_twin;
+        twin[p] = !no_twin && result_cigars_resident(r);
         if (twin[p]) any_twin = true; else up_words += (r->ncig + 3) & ~(size_t)3;
     }
     if (any_twin) HIPCHK(hipDeviceSynchronize());        // the last pieces of a mapped result's device copy were made on other streams

@@ -163,7 +163,8 @@ __global__ void __launch_bounds__(RS_T) k_rs_scatter(const K *__restrict__ keys,
 }
 
 // Sorts keys[0 .. n) (and vals) by bits [0, nbits) of the key; the result ends in `keys` / `vals` or in `tkeys` / `tvals` (returned:
-// 1 = in the temporaries).  hist: 256 * ceil(n / 2048) + 256 counters.  n < 2^32.
+// 1 = in the temporaries).  hist: rs_hist_words(n) counters.  n < 2^32.
+static inline size_t rs_hist_words(size_t n) { return (size_t)RS_BINS * ((n + RS_TILE - 1) / RS_TILE) + RS_BINS; }      // 256 * ceil(n / 2048) + 256
 template <typename K, bool HAS_V>
 static int radix_sort_passes(K *keys, uint32_t *vals, K *tkeys, uint32_t *tvals, int64_t n, int nbits, uint32_t *hist, hipStream_t st)
 {

@@ -1,0 +1,55 @@
+// record_checks.h — what the call stages (telr_call_insertions, telr_genotype_insertions, telr_draft_contigs)
+// refuse in a result's records and in a call list, stated once.  These checks are all that stands between a caller's arrays and the
+// kernels that index with them.  Plain C++: no HIP call and no type of the engine's own, so they are pinned on a CPU and run under the
+// sanitizers from a stand-alone program (tools/record_checks_check.cpp).  The reason comes back in a std::string; the entry's name in
+// front of it ("telr_call_insertions: " ...) and the TELR_E_RANGE limits on the counts stay with the callers.
+//
+// Two neighbours are separate contracts on purpose.  cons_first_bad_record (pileup.hip.h) answers yes or no without a reason, walks
+// every op of every CIGAR against the query and target lengths and runs on the host's threads.  part_merge_check (part_plan.h) holds a
+// part's records to that part's own word count, its tid map and the query order, in its own words.
+#ifndef TELR_RECORD_CHECKS_H
+#define TELR_RECORD_CHECKS_H
+#include <cstdint>
+#include <string>
+#include "../../include/telr_hip.h"
+
+// Record i of a result of ncig CIGAR words against n_targets targets: true, or false with "record i: <what>" in *why.  The first
+// fault in the order tid, coordinates, CIGAR range is the one reported.  One call per record, from the caller's own loop.
+static inline bool record_check(const telr_aln &a, size_t i, int32_t n_targets, uint64_t ncig, std::string *why)
+{
+    const char *what = nullptr;
+    if (a.tid < 0 || a.tid >= n_targets) what = "tid outside n_targets";
+    else if (a.qid < 0 || a.qlen < 0 || a.qs < 0 || a.qe < a.qs || a.qe > a.qlen || a.ts < 0 || a.te < a.ts) what = "coordinates";
+    else if (a.n_cigar < 0 || a.cigar_off < 0 || (uint64_t)a.cigar_off + (uint64_t)a.n_cigar > ncig) what = "CIGAR range outside the result's array";
+    if (what) *why = "record " + std::to_string(i) + ": " + what;
+    return !what;
+}
+
+// A call list as telr_call_insertions returns it: (tid, pos) strictly ascending, read_off from 0 and ascending, every supporter list
+// ascending and distinct with ids in [0, n_reads) -- n_reads < 0: no upper bound.  Fills ckeys[k] = tid << 32 | pos and, when support
+// is not null, support[k]; both hold n_calls elements.  True, or false with the reason in *why (ckeys / support then hold a prefix).
+static inline bool call_list_check(int64_t n_calls, const telr_ins_call *calls, const int64_t *read_off, const int32_t *reads, int32_t n_targets, int64_t n_reads,
+                                   uint64_t *ckeys, int32_t *support, std::string *why)
+{
+    auto bad = [&](int64_t k, const char *what) { *why = "call " + std::to_string(k) + ": " + what; return false; };
+    for (int64_t k = 0; k < n_calls; ++k) {
+        const telr_ins_call &c = calls[k];
+        if (c.tid < 0 || c.tid >= n_targets) return bad(k, "tid outside n_targets");
+        if (c.pos < 0) return bad(k, "negative pos");
+        ckeys[k] = ((uint64_t)(uint32_t)c.tid << 32) | (uint32_t)c.pos;
+        if (k > 0 && ckeys[k] <= ckeys[k - 1]) return bad(k, "calls not strictly ascending by (tid, pos)");
+        if (support) support[k] = c.support;
+    }
+    if (n_calls <= 0) return true;
+    if (read_off[0] != 0) { *why = "read_off[0] is not 0"; return false; }
+    for (int64_t k = 0; k < n_calls; ++k) {
+        if (read_off[k + 1] < read_off[k]) return bad(k, "read offsets descend");
+        if (read_off[k + 1] > read_off[k] && !reads) { *why = "null reads"; return false; }
+        for (int64_t j = read_off[k]; j < read_off[k + 1]; ++j) {
+            if (n_reads < 0 ? reads[j] < 0 : (reads[j] < 0 || reads[j] >= n_reads)) return bad(k, n_reads < 0 ? "negative read id" : "read id outside the read set");
+            if (j > read_off[k] && reads[j] <= reads[j - 1]) return bad(k, "read list not ascending");
+        }
+    }
+    return true;
+}
+#endif /* TELR_RECORD_CHECKS_H */

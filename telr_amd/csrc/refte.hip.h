@@ -30,7 +30,7 @@
 #pragma once
 #include "tile_plan.h"
 
-struct RtHit { int32_t tid, start, end, family, strand, score; };      // the first five fields as telr_te_feat has them: one key kernel
+struct RtHit { int32_t tid, start, end, family, strand, score; };      // the first five fields as telr_te_feat has them: one set of key functors
 
 struct telr_te_feats { std::vector<telr_te_feat> f; };
 
@@ -58,29 +58,11 @@ __global__ void __launch_bounds__(256) k_rt_hits(const telr_aln *__restrict__ al
     hits[off[i]] = h;
 }
 
-// the key of a sort round, gathered through the permutation the rounds before left; cb / fb: the bits of a coordinate / a family index
-enum { RT_K_SE, RT_K_TFS, RT_K_FS, RT_K_T };
-template <typename T>
-__global__ void __launch_bounds__(256) k_rt_key(int mode, const T *__restrict__ v, const uint32_t *__restrict__ perm, int64_t n, int cb, int fb, uint64_t *__restrict__ keys)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const T s = v[perm[i]];
-    uint64_t k = 0;
-    switch (mode) {
-    case RT_K_SE:  k = ((uint64_t)(uint32_t)s.start << cb) | (uint32_t)s.end; break;
-    case RT_K_TFS: k = ((((uint64_t)(uint32_t)s.tid << fb) | (uint32_t)s.family) << 1) | (uint32_t)s.strand; break;
-    case RT_K_FS:  k = ((uint64_t)(uint32_t)s.family << 1) | (uint32_t)s.strand; break;
-    case RT_K_T:   k = (uint32_t)s.tid; break;
-    }
-    keys[i] = k;
-}
-template <typename T>
-__global__ void __launch_bounds__(256) k_rt_gather(const T *__restrict__ in, const uint32_t *__restrict__ perm, int64_t n, T *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = in[perm[i]];
-}
+// the keys of the sort rounds (stage2_common.hip.h: perm_sort_round), of a hit or of a feature; cb / fb: the bits of a coordinate / a family index
+struct RtKeySE  { int cb; template <typename T> __device__ uint64_t operator()(const T &s, uint32_t) const { return ((uint64_t)(uint32_t)s.start << cb) | (uint32_t)s.end; } };
+struct RtKeyTFS { int fb; template <typename T> __device__ uint64_t operator()(const T &s, uint32_t) const { return ((((uint64_t)(uint32_t)s.tid << fb) | (uint32_t)s.family) << 1) | (uint32_t)s.strand; } };
+struct RtKeyFS  { template <typename T> __device__ uint64_t operator()(const T &s, uint32_t) const { return ((uint64_t)(uint32_t)s.family << 1) | (uint32_t)s.strand; } };
+struct RtKeyT   { template <typename T> __device__ uint64_t operator()(const T &s, uint32_t) const { return (uint32_t)s.tid; } };
 
 // over the sorted hits: head[i] = hit i is the first of its (tid, family, strand) run; end[i], score[i] = its fields
 __global__ void __launch_bounds__(256) k_rt_runs(const RtHit *__restrict__ hits, int64_t n, int32_t *__restrict__ head, int32_t *__restrict__ end, int32_t *__restrict__ score)
@@ -228,15 +210,6 @@ static int rt_segmax(telr_ctx *ctx, const int32_t *head, const T *val, int64_t n
     return TELR_OK;
 }
 
-template <typename T>
-static int rt_sort_round(telr_ctx *ctx, InsSort &S, int mode, const T *v, int64_t n, int cb, int fb, int nbits)
-{
-    hipLaunchKernelGGL((k_rt_key<T>), ins_grid(n), dim3(256), 0, ctx->stream, mode, v, S.perm, n, cb, fb, S.keys);
-    if (radix_sort_passes<uint64_t, true>(S.keys, S.perm, S.tkeys, S.tperm, n, nbits, S.hist, ctx->stream)) { std::swap(S.keys, S.tkeys); std::swap(S.perm, S.tperm); }
-    HIPCHK(hipGetLastError());
-    return TELR_OK;
-}
-
 extern "C" int telr_tile_plan(int32_t n_targets, const int32_t *target_len, int32_t tile, int32_t stride, telr_tile *out, int64_t cap, int64_t *needed)
 {
     return tile_plan(n_targets, target_len, tile, stride, out, cap, needed);
@@ -276,7 +249,7 @@ extern "C" int telr_annotate_hits(telr_ctx *ctx, const telr_result *r, int64_t n
     TRY(ctx_buf_t(ctx, "rt_off", (size_t)n + 1, &d_off));
     HIPCHK(hipMemcpyAsync(d_aln, r->alns.data(), (size_t)n * sizeof(telr_aln), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_tiles, tiles, (size_t)n_tiles * sizeof(telr_tile), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_rt_elig, ins_grid(n + 1), dim3(256), 0, st, d_aln, n, O.min_len, O.min_mapq, d_elig);
+    hipLaunchKernelGGL(k_rt_elig, grid256(n + 1), dim3(256), 0, st, d_aln, n, O.min_len, O.min_mapq, d_elig);
     HIPCHK(hipGetLastError());
     TRY((dev_qscan<int32_t, int32_t>(ctx, d_elig, (int32_t)n, d_off, nullptr, 0, nullptr, nullptr)));
     int32_t nh = 0;
@@ -287,21 +260,16 @@ extern "C" int telr_annotate_hits(telr_ctx *ctx, const telr_result *r, int64_t n
     RtHit *d_raw, *d_hit;
     TRY(ctx_buf_t(ctx, "rt_raw", (size_t)N, &d_raw));
     TRY(ctx_buf_t(ctx, "rt_hit", (size_t)N, &d_hit));
-    hipLaunchKernelGGL(k_rt_hits, ins_grid(n), dim3(256), 0, st, d_aln, n, d_tiles, d_elig, d_off, d_raw);
+    hipLaunchKernelGGL(k_rt_hits, grid256(n), dim3(256), 0, st, d_aln, n, d_tiles, d_elig, d_off, d_raw);
     // sort by (tid, family, strand, start, end): least significant group first
-    InsSort S;
-    const size_t ntiles = ((size_t)N + RS_TILE - 1) / RS_TILE;
-    TRY(ctx_buf_t(ctx, "rt_keys", (size_t)N, &S.keys));
-    TRY(ctx_buf_t(ctx, "rt_tkeys", (size_t)N, &S.tkeys));
-    TRY(ctx_buf_t(ctx, "rt_perm", (size_t)N, &S.perm));
-    TRY(ctx_buf_t(ctx, "rt_tperm", (size_t)N, &S.tperm));
-    TRY(ctx_buf_t(ctx, "rt_hist", (size_t)RS_BINS * ntiles + RS_BINS, &S.hist));
-    const int cb = ins_bits((uint64_t)max_end), fb = ins_bits((uint64_t)(n_families > 0 ? n_families - 1 : 0)), tb = ins_bits((uint64_t)(n_targets > 0 ? n_targets - 1 : 0));
-    const dim3 gN = ins_grid(N), gN1 = ins_grid(N + 1);
-    hipLaunchKernelGGL(k_ins_iota, gN, dim3(256), 0, st, S.perm, N);
-    TRY(rt_sort_round<RtHit>(ctx, S, RT_K_SE, d_raw, N, cb, fb, 2 * cb));
-    TRY(rt_sort_round<RtHit>(ctx, S, RT_K_TFS, d_raw, N, cb, fb, tb + fb + 1));
-    hipLaunchKernelGGL((k_rt_gather<RtHit>), gN, dim3(256), 0, st, d_raw, S.perm, N, d_hit);
+    PermSort S;
+    TRY(S.alloc(ctx, "rt_", (size_t)N));
+    const int cb = bits_of((uint64_t)max_end), fb = bits_of((uint64_t)(n_families > 0 ? n_families - 1 : 0)), tb = bits_of((uint64_t)(n_targets > 0 ? n_targets - 1 : 0));
+    const dim3 gN = grid256(N), gN1 = grid256(N + 1);
+    perm_iota(ctx, S, N);
+    TRY(perm_sort_round(ctx, S, d_raw, N, RtKeySE{cb}, 2 * cb));
+    TRY(perm_sort_round(ctx, S, d_raw, N, RtKeyTFS{fb}, tb + fb + 1));
+    perm_gather(ctx, S, d_raw, N, d_hit);
     // the running maximum of end over the runs, the feature heads, their scan
     int32_t *d_head, *d_end, *d_score, *d_emax, *d_smax, *d_fh, *d_fx, *d_fstart;
     TRY(ctx_buf_t(ctx, "rt_head", (size_t)N, &d_head));
@@ -328,13 +296,13 @@ extern "C" int telr_annotate_hits(telr_ctx *ctx, const telr_result *r, int64_t n
     telr_te_feat *d_fraw, *d_feat;
     TRY(ctx_buf_t(ctx, "rt_fraw", (size_t)nf, &d_fraw));
     TRY(ctx_buf_t(ctx, "rt_feat", (size_t)nf, &d_feat));
-    const dim3 gF = ins_grid((int64_t)nf);
+    const dim3 gF = grid256((int64_t)nf);
     hipLaunchKernelGGL(k_rt_feats, gF, dim3(256), 0, st, d_hit, d_fstart, nf, d_emax, d_smax, d_fraw);
-    hipLaunchKernelGGL(k_ins_iota, gF, dim3(256), 0, st, S.perm, (int64_t)nf);
-    TRY(rt_sort_round<telr_te_feat>(ctx, S, RT_K_FS, d_fraw, nf, cb, fb, fb + 1));
-    TRY(rt_sort_round<telr_te_feat>(ctx, S, RT_K_SE, d_fraw, nf, cb, fb, 2 * cb));
-    TRY(rt_sort_round<telr_te_feat>(ctx, S, RT_K_T, d_fraw, nf, cb, fb, tb));
-    hipLaunchKernelGGL((k_rt_gather<telr_te_feat>), gF, dim3(256), 0, st, d_fraw, S.perm, (int64_t)nf, d_feat);
+    perm_iota(ctx, S, nf);
+    TRY(perm_sort_round(ctx, S, d_fraw, nf, RtKeyFS{}, fb + 1));
+    TRY(perm_sort_round(ctx, S, d_fraw, nf, RtKeySE{cb}, 2 * cb));
+    TRY(perm_sort_round(ctx, S, d_fraw, nf, RtKeyT{}, tb));
+    perm_gather(ctx, S, d_fraw, nf, d_feat);
     HIPCHK(hipGetLastError());
     F->f.resize((size_t)nf);
     HIPCHK(hipMemcpyAsync(F->f.data(), d_feat, (size_t)nf * sizeof(telr_te_feat), hipMemcpyDeviceToHost, st));

@@ -7,8 +7,8 @@
 //             device text, so no store straddles two pieces; one DraftPiece (first base in the set's layout, len, rc) per piece and
 //             the scanned unit offsets go up
 //   device    k_seq_extract    one lane per unit: its piece from a binary search in the scanned offsets (as k_draft_extract), the
-//             16 2-bit codes and 16 mask bits at the piece's base offset by the funnel shifts of draft.hip.h (draft_window2 /
-//             draft_window1), for rc read from the other end, base-reversed and complemented; four dwords of letters, one 16-byte store
+//             16 2-bit codes and 16 mask bits at the piece's base offset by the funnel shifts of stage2_common.hip.h (d_window2 /
+//             d_window1), for rc read from the other end, base-reversed and complemented; four dwords of letters, one 16-byte store
 //   host      the slotted text comes back in one copy (pinned) and is compacted into the caller's dense buffer
 // Every store position is the lane's own index; there is no atomic; the bytes are the same on every run.  The set is not copied.
 #pragma once
@@ -40,8 +40,8 @@ __global__ void __launch_bounds__(256) k_seq_extract(const uint32_t *__restrict_
     const int64_t j0 = (u - uoff[d]) * 16;
     const int kb = P.len - j0 >= 16 ? 16 : (int)(P.len - j0);      // 1 .. 16: a slot has no unit behind its piece
     const int64_t S = P.rc ? P.src + P.len - 16 - j0 : P.src + j0;      // >= -15: what lies before the set reads as zero
-    uint32_t code = draft_window2(seq2, S), m16 = draft_window1(nmask, S);
-    if (P.rc) { code = ~draft_rev16x2(code); m16 = __brev(m16) >> 16; }
+    uint32_t code = d_window2(seq2, S), m16 = d_window1(nmask, S);
+    if (P.rc) { code = ~d_rev16x2(code); m16 = __brev(m16) >> 16; }
     uint4 o;
     o.x = sx_letters4(code & 0xffu, m16 & 0xfu);
     o.y = sx_letters4(code >> 8 & 0xffu, m16 >> 4 & 0xfu);
@@ -97,7 +97,7 @@ extern "C" int telr_seqset_extract(telr_ctx *ctx, const telr_seqset *s, int64_t 
     TRY(ctx_hbuf_t(ctx, "sx_text_host", (size_t)nu * 16, &h_text));
     HIPCHK(hipMemcpyAsync(d_piece, pieces.data(), (size_t)n * sizeof(DraftPiece), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_uoff, uoff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_seq_extract, ins_grid(nu), dim3(256), 0, st, s->d_seq2, s->d_nmask, d_piece, d_uoff, (int32_t)n, nu, d_text);
+    hipLaunchKernelGGL(k_seq_extract, grid256(nu), dim3(256), 0, st, s->d_seq2, s->d_nmask, d_piece, d_uoff, (int32_t)n, nu, d_text);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_text, d_text, (size_t)nu * 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

@@ -1,0 +1,147 @@
+// What the stages on top of a mapped telr_result share: the CIGAR array on the device, the launch and bit-count
+// helpers, the wave and search inlines of the span / pair kernels, the funnel shifts of the piece cutters, and the stable permutation
+// sort over radix.hip.h.  Included by telr_engine.hip once telr_result is defined (telr_depth_medians is a caller), so before
+// every feature header (inscall, genotype, draft, refte, bam_in, seq_extract, part_merge, pileup, bam_dev): none of them takes a name
+// from a sibling.  The host-side record and call-list checks of the call stages are record_checks.h.
+#pragma once
+#include "record_checks.h"
+
+// ---- the result's CIGAR words on the device ---------------------------------------------------------------------------------------
+// The device copy a result kept (TELR_MF_KEEP_CIGARS, telr_result_from_device_cigars, telr_merge_parts) is complete iff this holds.
+static inline bool result_cigars_resident(const telr_result *r) { return r->d_cig && !r->twin_off && r->twin_n == r->ncig; }
+
+// *d_cig = the result's own device copy when it is complete and the caller allows it, else the host array uploaded on the context's
+// stream into the context buffer `tag` of ncig + slack words.  Call it after result_wait(r).  *resident (nullable) says which.
+static int result_dev_cigars(telr_ctx *ctx, const telr_result *r, const char *tag, bool allow_resident, uint32_t **d_cig, bool *resident, size_t slack = 0)
+{
+    const bool res = allow_resident && result_cigars_resident(r);
+    if (resident) *resident = res;
+    // the last pieces of a mapped result's device copy were made on other streams than the caller's: a device-wide wait, not a stream's
+    if (res) { *d_cig = r->d_cig; HIPCHK(hipDeviceSynchronize()); return TELR_OK; }
+    TRY(ctx_buf_t(ctx, tag, r->ncig + slack, d_cig));
+    if (r->ncig) HIPCHK(hipMemcpyAsync(*d_cig, r->cig, r->ncig * 4, hipMemcpyHostToDevice, ctx->stream));
+    return TELR_OK;
+}
+
+// ---- small helpers ----------------------------------------------------------------------------------------------------------------
+static inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }      // one lane per element, 256 per workgroup
+static inline int bits_of(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
+
+// inclusive prefix sum over the wave
+template <typename T>
+static __device__ __forceinline__ T d_wave_incl(T v, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const T x = __shfl_up(v, o); if (lane >= o) v += x; }
+    return v;
+}
+
+// first i in [0, n) with k[i] >= v (UPPER: > v)
+template <bool UPPER>
+static __device__ __forceinline__ int64_t d_bound(const uint64_t *__restrict__ k, int64_t n, uint64_t v)
+{
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        const uint64_t x = k[mid];
+        if (UPPER ? x <= v : x < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// the calls with (tid, pos) keys in [(tid, lo), (tid, hi)], 0 <= lo and hi < 2^32: a contiguous run of the ascending keys
+static __device__ __forceinline__ void d_span(const uint64_t *__restrict__ ckeys, int32_t ncall, int32_t tid, int64_t lo, int64_t hi, int32_t *first, int32_t *cnt)
+{
+    const uint64_t t = (uint64_t)(uint32_t)tid << 32;
+    const int64_t b0 = d_bound<false>(ckeys, ncall, t | (uint64_t)lo), b1 = d_bound<true>(ckeys, ncall, t | (uint64_t)hi);
+    *first = (int32_t)b0; *cnt = b1 > b0 ? (int32_t)(b1 - b0) : 0;
+}
+// off = exclusive scan of n counts (off[n] = the pairs): pair p belongs to the last element with off <= p
+static __device__ __forceinline__ int32_t d_pair_owner(const int64_t *__restrict__ off, int32_t n, int64_t p)
+{
+    int32_t lo = 0, hi = n;                               // first element with off > p
+    while (lo < hi) { const int32_t mid = lo + ((hi - lo) >> 1); if (off[mid] <= p) lo = mid + 1; else hi = mid; }
+    return lo - 1;
+}
+// is q among the ascending reads[lo .. hi)
+static __device__ __forceinline__ bool d_in_list(const int32_t *__restrict__ reads, int64_t lo, int64_t hi, int32_t q)
+{
+    const int64_t end = hi;
+    while (lo < hi) { const int64_t mid = lo + ((hi - lo) >> 1); if (reads[mid] < q) lo = mid + 1; else hi = mid; }
+    return lo < end && reads[lo] == q;
+}
+
+// ---- 2-bit packed bases: the funnel shifts of the piece cutters (k_draft_extract, k_seq_extract) -------------------------------------
+// 16 bases from base offset S of a packed array (S >= -15: what lies before the array reads as zero)
+static __device__ __forceinline__ uint32_t d_window2(const uint32_t *__restrict__ p, int64_t S)
+{
+    const int64_t sw = S >> 4;
+    const int sh = (int)(S & 15) * 2;
+    const uint32_t a = sw >= 0 ? p[sw] : 0u;
+    if (sh == 0) return a;
+    return (uint32_t)((((uint64_t)p[sw + 1] << 32) | a) >> sh);
+}
+static __device__ __forceinline__ uint32_t d_window1(const uint32_t *__restrict__ p, int64_t S)
+{
+    const int64_t sw = S >> 5;
+    const int sh = (int)(S & 31);
+    const uint32_t a = sw >= 0 ? p[sw] : 0u;
+    if (sh <= 16) return (a >> sh) & 0xffffu;
+    return (uint32_t)((((uint64_t)p[sw + 1] << 32) | a) >> sh) & 0xffffu;
+}
+static __device__ __forceinline__ uint32_t d_rev16x2(uint32_t x)      // the sixteen 2-bit codes of a word in reverse order
+{
+    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+    x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
+    return __builtin_bswap32(x);
+}
+
+// ---- stable permutation sort --------------------------------------------------------------------------------------------------------
+// LSD over a composite key, least significant group first: a permutation is carried from round to round, the keys of a round are
+// gathered through it.  A key is a functor of the feature's own: uint64_t operator()(const T &element, uint32_t its_index).
+struct PermSort {
+    uint64_t *keys, *tkeys; uint32_t *perm, *tperm, *hist;
+    // the buffers <prefix>keys, tkeys, perm, tperm, hist of the context, for up to n elements
+    int alloc(telr_ctx *ctx, const std::string &prefix, size_t n)
+    {
+        TRY(ctx_buf_t(ctx, (prefix + "keys").c_str(), n, &keys));
+        TRY(ctx_buf_t(ctx, (prefix + "tkeys").c_str(), n, &tkeys));
+        TRY(ctx_buf_t(ctx, (prefix + "perm").c_str(), n, &perm));
+        TRY(ctx_buf_t(ctx, (prefix + "tperm").c_str(), n, &tperm));
+        return ctx_buf_t(ctx, (prefix + "hist").c_str(), rs_hist_words(n), &hist);
+    }
+};
+__global__ void __launch_bounds__(256) k_perm_iota(uint32_t *__restrict__ perm, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) perm[i] = (uint32_t)i;
+}
+template <typename T, typename KEY>
+__global__ void __launch_bounds__(256) k_perm_key(const T *__restrict__ v, const uint32_t *__restrict__ perm, int64_t n, KEY key, uint64_t *__restrict__ keys)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t p = perm[i];
+    keys[i] = key(v[p], p);
+}
+template <typename T>
+__global__ void __launch_bounds__(256) k_perm_gather(const T *__restrict__ in, const uint32_t *__restrict__ perm, int64_t n, T *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = in[perm[i]];
+}
+static inline void perm_iota(telr_ctx *ctx, PermSort &S, int64_t n) { hipLaunchKernelGGL(k_perm_iota, grid256(n), dim3(256), 0, ctx->stream, S.perm, n); }
+template <typename T>
+static inline void perm_gather(telr_ctx *ctx, const PermSort &S, const T *in, int64_t n, T *out)
+{
+    hipLaunchKernelGGL((k_perm_gather<T>), grid256(n), dim3(256), 0, ctx->stream, in, S.perm, n, out);
+}
+// one stable round: sorts the permutation by `nbits` bits of the elements' keys
+template <typename T, typename KEY>
+static int perm_sort_round(telr_ctx *ctx, PermSort &S, const T *v, int64_t n, KEY key, int nbits)
+{
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL((k_perm_key<T, KEY>), grid256(n), dim3(256), 0, st, v, S.perm, n, key, S.keys);
+    if (radix_sort_passes<uint64_t, true>(S.keys, S.perm, S.tkeys, S.tperm, n, nbits, S.hist, st)) { std::swap(S.keys, S.tkeys); std::swap(S.perm, S.tperm); }
+    HIPCHK(hipGetLastError());
+    return TELR_OK;
+}

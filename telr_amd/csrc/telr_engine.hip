@@ -881,7 +881,7 @@ static int index_build_impl(telr_ctx *ctx, const telr_seqset *tg, const telr_idx
     if (nmz > 0 && !sort_lib) {
         const int passes = (2 * k + 7) / 8;
         uint64_t *d_tk; TRY(ctx_buf_t(ctx, "ix_rs_keys", (size_t)nmz, &d_tk));
-        TRY(ctx_buf_t(ctx, "ix_rs_hist", (size_t)RS_BINS * ((nmz + RS_TILE - 1) / RS_TILE) + RS_BINS, &d_rshist));
+        TRY(ctx_buf_t(ctx, "ix_rs_hist", rs_hist_words((size_t)nmz), &d_rshist));
         // an even number of passes ends where it began: the hashes start in the final arrays (d_h2, pos) then, else in the temporaries (d_tk, d_y)
         uint64_t *k0 = passes % 2 == 0 ? d_h2 : d_tk; uint32_t *v0 = passes % 2 == 0 ? d_y2 : d_y;
         hipLaunchKernelGGL(k_ix_hash_keys, dim3((nmz + 255) / 256), dim3(256), 0, ctx->stream, d_x, d_y, (int64_t)nmz, k0, v0);
@@ -1174,6 +1174,7 @@ static void result_wait(const telr_result *r)
     if (r) { for (hipEvent_t e : r->up_events) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); } r->up_events.clear(); }
 }
 extern "C" int telr_result_wait(const telr_result *r) { if (!r) return TELR_E_ARG; result_wait(r); return TELR_OK; }
+#include "stage2_common.hip.h"      // what every stage on top of a result shares, telr_depth_medians below and the feature headers at the end of this file
 // CIGAR buffers of freed results are kept (at most two) and handed to the next telr_map call: a fresh
 // 200 MB allocation costs ~20 ms of page faults and another ~20 ms of munmap per call.
 // result CIGAR buffers are PINNED host memory (the stitched CIGARs are copied device -> result in one DMA)
@@ -3046,10 +3047,7 @@ extern "C" int telr_depth_medians(telr_ctx *ctx, const telr_result *r, int32_t n
     TRY(ctx_buf_t(ctx, "dm_tlen", (size_t)n_targets, &d_tlen));
     TRY(ctx_buf_t(ctx, "dm_recs", recs.size(), &d_recs));
     result_wait(r);
-    // the CIGAR array: the result's own device copy when it kept one (TELR_MF_KEEP_CIGARS), else uploaded
-    const bool twin = r->d_cig && !r->twin_off && r->twin_n == r->ncig;
-    if (twin) { d_cig = r->d_cig; HIPCHK(hipDeviceSynchronize()); }      // (its last pieces were copied on other streams, as in telr_write_bam_dev)
-    else TRY(ctx_buf_t(ctx, "dm_cig", r->ncig, &d_cig));
+    TRY(result_dev_cigars(ctx, r, "dm_cig", true, &d_cig, nullptr));
     TRY(ctx_buf_t(ctx, "dm_ivt", (size_t)n_iv, &d_ivt));
     TRY(ctx_buf_t(ctx, "dm_ivs", (size_t)n_iv, &d_ivs));
     TRY(ctx_buf_t(ctx, "dm_ive", (size_t)n_iv, &d_ive));
@@ -3058,7 +3056,6 @@ extern "C" int telr_depth_medians(telr_ctx *ctx, const telr_result *r, int32_t n
     HIPCHK(hipMemcpyAsync(d_toff, toff.data(), (size_t)(n_targets + 1) * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_tlen, target_len, (size_t)n_targets * 4, hipMemcpyHostToDevice, st));
     if (!recs.empty()) HIPCHK(hipMemcpyAsync(d_recs, recs.data(), recs.size() * sizeof(DepthRec), hipMemcpyHostToDevice, st));
-    if (r->ncig && !twin) HIPCHK(hipMemcpyAsync(d_cig, r->cig, r->ncig * 4, hipMemcpyHostToDevice, st));
     if (n_iv) {
         HIPCHK(hipMemcpyAsync(d_ivt, iv_tid, (size_t)n_iv * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_ivs, iv_start, (size_t)n_iv * 4, hipMemcpyHostToDevice, st));

@@ -452,6 +452,28 @@ def cases(seed=11):
     return poa_cases(rng) + pile_cases(rng)
 
 
+def resident_case(seed=23):
+    """four records on two short targets, for the consumers of a result's CIGAR array that take it resident on the device or
+    upload it (telr_consensus_build, telr_depth_medians): a record without ops, one of a single op, one of 65 words (two steps
+    of a 64-words-per-step walk) and one of 64 words exactly; every read differs from its target, so the votes show"""
+    rng = np.random.default_rng(seed)
+    t0, t1 = rseq(rng, 700), rseq(rng, 400)
+    b = Builder([t0, t1])
+    b.rec(0, 5, "", [], left=rseq(rng, 40))
+    x = t1[30:150]
+    b.rec(1, 30, x[:60] + other(x[60]) + x[61:], [M(120)])
+    seg = t0[100:270]
+    piece, cig = edit(seg, subs={2: other(seg[2])}, ins={5 + 10 * k: "A" for k in range(16)}, dels={10 + 10 * k: 1 for k in range(16)})
+    assert len(cig) == 65
+    b.rec(0, 100, piece, cig)
+    seg = t0[300:465]
+    piece, cig = edit(seg, subs={2: other(seg[2])}, ins={5 + 10 * k: "C" for k in range(16)}, dels={10 + 10 * k: 1 for k in range(15)})
+    cig = cig[:-1] + [M((cig[-1] >> 4) - 2), M(2)]                  # (63 words as merged: the last M run as two words)
+    assert len(cig) == 64 and cig[-2] >> 4 > 0
+    b.rec(0, 300, piece, cig, rev=True)
+    return b.case("resident_or_uploaded", poa=False)
+
+
 def run_all(engine, cs=None):
     """every case through telr_poa_build / telr_consensus_build against tor_poa / tor_consensus at each of its min_depth
     values -> (comparisons, list of differences)"""

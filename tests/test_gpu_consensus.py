@@ -51,6 +51,31 @@ def test_hip_consensus_equals_oracle(engine, seed, pname):
     assert got[3] != drafts[3] and got[3].upper() == got[3]
 
 
+def test_resident_cigars_and_uploaded_cigars_give_the_same(engine):
+    """telr_consensus_build takes the CIGAR array where the result holds it: uploaded from the host array (result_from_arrays) or in
+    place on the device (result_from_device_cigars).  Records of 0, 1, 65 and 64 words: the same consensus bytes either way"""
+    import torch
+    import consensus_edges as ce
+    c = ce.resident_case()
+    io, _ = preset("map-ont")
+    ix = engine.index(c["targets"], io)
+    qset = engine.seqset(c["reads"])
+    got = []
+    try:
+        for resident in (False, True):
+            r = (ix.result_from_device_cigars(c["alns"], torch.from_numpy(c["cigars"].view(np.int32).copy()).to("cuda:0")) if resident
+                 else ix.result_from_arrays(c["alns"], c["cigars"]))
+            try:
+                got.append([ix.consensus(r, qset, min_depth=md) for md in (1, 2)])
+            finally:
+                ix.free_raw(r)
+    finally:
+        qset.free(); ix.free()
+    assert got[0] == got[1]
+    assert all(a != t for a, t in zip(got[0][0], c["targets"]))      # every target took a vote against its draft
+    assert got[0][1] == list(c["targets"])                          # and at a depth no column has, none
+
+
 def test_polish_consensus_moves_the_drafts_to_the_truth(engine):
     truths, drafts, reads = _loci(7, n_loci=8, depth=40)
     out = telr_assembly.polish_consensus(engine, ["c%d" % i for i in range(8)], drafts, reads, presets="ont", iterations=2)

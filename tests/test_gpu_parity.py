@@ -161,6 +161,33 @@ def test_depth_medians(engine):
         gix.free_raw(r)
 
 
+def test_depth_medians_resident_cigars_and_uploaded_cigars_give_the_same(engine):
+    """telr_depth_medians takes the CIGAR array where the result holds it: uploaded from the host array (result_from_arrays) or in
+    place on the device (result_from_device_cigars).  Records of 0, 1, 65 and 64 words: the same medians either way, the oracle's"""
+    import torch
+    from oracle import binding as ob
+    import consensus_edges as ce
+    c = ce.resident_case()
+    io, _ = preset("map-ont")
+    ix = engine.index(c["targets"], io)
+    iv_t = np.array([0, 0, 0, 0, 1, 1], np.int32)
+    iv_s = np.array([0, 100, 300, 104, 30, 0], np.int32); iv_e = np.array([699, 280, 464, 111, 149, 399], np.int32)
+    got = []
+    try:
+        for resident in (False, True):
+            r = (ix.result_from_device_cigars(c["alns"], torch.from_numpy(c["cigars"].view(np.int32).copy()).to("cuda:0")) if resident
+                 else ix.result_from_arrays(c["alns"], c["cigars"]))
+            try:
+                got.append(ix.depth_medians(r, iv_t, iv_s, iv_e))
+            finally:
+                ix.free_raw(r)
+    finally:
+        ix.free()
+    np.testing.assert_array_equal(got[0], got[1])
+    np.testing.assert_array_equal(got[0], ob.depth_medians(c["alns"], c["cigars"], [len(t) for t in c["targets"]], iv_t, iv_s, iv_e))
+    assert got[0][1] == 1 and got[0][2] == 1 and got[0][4] == 1 and got[0][0] == 0
+
+
 def test_wide_bands(engine):
     """Anchor-free stretches force long gap-fill segments: register kernel with 2/4/8 diagonal pairs
     per lane, the LDS kernel and (asm10, bw=10000) very wide bands."""

@@ -1,5 +1,10 @@
 """The insertion caller's definition (tests/inscall_ref.py, the checker of telr_call_insertions) against hand-derived answers, one
-case per rule, and against the known answer of the bundled reads: one non-reference insertion at chr2L:~33,017."""
+case per rule, and against the known answer of the bundled reads: one non-reference insertion at chr2L:~33,017;
+tools/record_checks_check.cpp (the record and call-list refusals the call stages share) under ASan and UBSan."""
+import os
+import shutil
+import subprocess
+
 import pytest
 
 import inscall_cases as cases
@@ -7,6 +12,7 @@ import inscall_ref as ref
 from telr_amd.fasta import read_fasta
 from telr_amd.presets import preset
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HAND = cases.hand_cases()
 
 
@@ -57,3 +63,16 @@ def test_bundled_reads_give_the_known_insertion(fixture_records, name):
     # the cluster at the end of the reference has six clipped reads and no sized one: still one call at min_support 6
     calls6 = ref.calls(sigs, dict(min_support=6, min_sized=1))
     assert len(calls6) == 1 and calls6[0]["pos"] == c["pos"]
+
+
+def test_record_checks_check_under_sanitizers(tmp_path):
+    """tools/record_checks_check.cpp = record_checks.h (what telr_call_insertions, telr_genotype_insertions and telr_draft_contigs refuse
+    in a result's records and in a call list, with the full texts) as a program of its own, compiled with -fsanitize=address,undefined"""
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "record_checks_check")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tools", "record_checks_check.cpp"), "-o", exe])
+    p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    print(p.stdout)
+    assert p.returncode == 0 and "checks ok" in p.stdout, p.stdout
