@@ -803,10 +803,27 @@ __device__ __forceinline__ void d_seed_rescue(const SeedArgs &A, const int q, co
 // aligner against every contig (TELR_te.py:68-78,119-132,504-506; TELR_assembly.py:199-212): a minimizer's occurrences are
 // counted inside the target and compared with THAT target's cut-off (tmid), so a TE k-mer shared by hundreds of contigs
 // is not masked as repetitive.
-// the minimizers of query q, taken in turn by `nthr` threads (this one is `tid`)
+// the minimizers of query q, taken in turn by `nthr` threads (this one is `tid`).
+// MODE 1 (the key writer: k_seed<1> and the fill of the fused sort) is bound by the latency of its dependent loads -- mz_cnt, then
+// the minimizer's header, then one occurrence after the other -- while its workgroup waits at the barrier in front of the sort.  A
+// thread therefore takes SEED_PROBE_BATCH minimizers a round (g = gb + tid + u * nthr: consecutive threads still read consecutive
+// entries) and issues their loads LEVEL BY LEVEL: the tile offsets the indices need, every mz_cnt, then the headers of the minimizers
+// that have anchors; an occurrence list is read four occurrences at a time.  Every key goes where the one-by-one walk puts it.
+// SEED_PROBE_BATCH = 1 issues every load in the order of the one-minimizer loop (the A/B partner inside one tree).  MODE 0 (the
+// probes) keeps one minimizer a round: it runs at the rate the part delivers scattered lines, and four probes in flight per thread
+// made it 4 % slower alone (profiles/seed_batch_trace_*.txt).
+#ifndef SEED_PROBE_BATCH
+#define SEED_PROBE_BATCH 4
+#endif
+// the value of a load is in its register from here on: no instruction, only a place the compiler may not move the first use behind
+#define SEED_ARRIVED(v_) asm volatile("" : "+v"(v_))
+#define SEED_TILE_WIN 8            /* tile offsets read ahead per round (SEED_PROBE_BATCH > 1): ~190 minimizers a tile, nthr * U indices a round */
 template <int MODE>
 __device__ __forceinline__ void d_seed_query(const SeedArgs &A, const int q, const int tid, const int nthr)
 {
+    constexpr int U = MODE == 1 ? SEED_PROBE_BATCH : 1;
+    constexpr int OG = U > 1 ? 4 : 1;                                        // MODE 1: occurrences read per group
+    static_assert(U >= 1 && U <= 8, "SEED_PROBE_BATCH");
     const int m0 = A.q_mzoff[q], m1 = A.q_mzoff[q + 1];
     const int tf = A.qtarget ? A.qtarget[q] : -1;
     const bool pt = tf < 0 && A.per_target && A.tmid;
@@ -817,50 +834,93 @@ __device__ __forceinline__ void d_seed_query(const SeedArgs &A, const int q, con
     // staged input: minimizer g of the query lives in tile t at slot g - tile_off[t]; g only grows, so t is advanced, not searched
     int t = A.tile_off ? A.q_tile0[q] : 0, t_lo = 0, t_hi = 0;
     if (A.tile_off) { t_lo = A.tile_off[t]; t_hi = A.tile_off[t + 1]; }
+    const int t_end = A.tile_off && U > 1 ? A.q_tile0[q + 1] : 0;           // tile_off[t_end] = m1: the last offset a read-ahead may touch
     const int64_t wbase = MODE == 1 && !A.lds_keys ? A.q_aoff[q] : 0;       // where the query's anchors start in the key array
     __shared__ int32_t s_wtot[16];                                           // MODE 0 (one block of at most 1,024 threads per query): the waves' totals
     int32_t carry = 0;                                                       // MODE 0: anchors of the minimizers before this round's
-    for (int gb = m0; gb < m1; gb += nthr) {
-      int32_t cnt_out = 0;
-      const int g = gb + tid;
-      if (g < m1) do {
-        int64_t gi = g;
-        if (A.tile_off) {
-            while (g >= t_hi) { ++t; t_lo = t_hi; t_hi = A.tile_off[t + 1]; }
-            gi = (int64_t)t * SK_TILE + (g - t_lo);
-        }
-        uint64_t x = A.mz_x[gi];
-        uint32_t o0 = 0, o1 = 0;
-        if (MODE == 0) {
-            uint32_t off = 0, n = 0;
-            if (!d_ht_lookup(A.I, x >> 8, off, n)) n = 0;
-            A.mz_ent[g] = (int32_t)off; A.mz_n[g] = (int32_t)n;
-            o0 = off; o1 = off + n;
+    for (int gb = m0; gb + tid < m1; gb += U * nthr) {
+      // this round's minimizers; a slot of the round past the query's end reads where slot 0 reads and is dropped
+      int g[U]; bool live[U]; int64_t gi[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) { g[u] = gb + tid + u * nthr; live[u] = g[u] < m1; gi[u] = live[u] ? g[u] : g[0]; }
+      if (A.tile_off) {
+        if constexpr (U == 1) {
+            while (g[0] >= t_hi) { ++t; t_lo = t_hi; t_hi = A.tile_off[t + 1]; }
+            gi[0] = (int64_t)t * SK_TILE + (g[0] - t_lo);
         } else {
-            if (A.mz_cnt[g] == 0) break;
-            o0 = (uint32_t)A.mz_ent[g]; o1 = o0 + (uint32_t)A.mz_n[g];
+            // the offsets behind t_hi in one go; every index then walks them in registers from the round's first tile
+            int32_t nxt[SEED_TILE_WIN];
+#pragma unroll
+            for (int j = 0; j < SEED_TILE_WIN; ++j) nxt[j] = A.tile_off[min(t + 2 + j, t_end)];
+            int tu = t, lo = t_lo, hi = t_hi;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (live[u]) {
+                    tu = t; lo = t_lo; hi = t_hi;
+#pragma unroll
+                    for (int j = 0; j < SEED_TILE_WIN; ++j) if (g[u] >= hi) { ++tu; lo = hi; hi = nxt[j]; }
+                    while (g[u] >= hi) { ++tu; lo = hi; hi = A.tile_off[tu + 1]; }      // (a run of empty tiles longer than the window)
+                    gi[u] = (int64_t)tu * SK_TILE + (g[u] - lo);
+                } else gi[u] = gi[0];
+            }
+            t = tu; t_lo = lo; t_hi = hi;                                    // the round's last live index: the next round starts behind it
         }
+      }
+      uint64_t x[U]; uint32_t o0[U], o1[U]; uint32_t y[U]; int32_t aoff[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) { x[u] = 0; o0[u] = o1[u] = 0; y[u] = 0; aoff[u] = 0; }
+      if (MODE == 0) {
+        x[0] = A.mz_x[gi[0]];
+        uint32_t off = 0, n = 0;
+        if (!d_ht_lookup(A.I, x[0] >> 8, off, n)) n = 0;
+        A.mz_ent[g[0]] = (int32_t)off; A.mz_n[g[0]] = (int32_t)n;
+        o0[0] = off; o1[0] = off + n;
+      } else {
+        int32_t c[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) c[u] = A.mz_cnt[live[u] ? g[u] : g[0]];
+        // every count before the first header load: left to itself the compiler tests count u + 1 behind the branch that holds the
+        // header loads of minimizer u, and the wait for that count then waits for those loads as well
+#pragma unroll
+        for (int u = 0; u < U; ++u) SEED_ARRIVED(c[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) live[u] = live[u] && c[u] != 0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (live[u]) {
+                x[u] = A.mz_x[gi[u]];
+                o0[u] = (uint32_t)A.mz_ent[g[u]]; o1[u] = (uint32_t)A.mz_n[g[u]];
+                if (U > 1) { y[u] = A.mz_y[gi[u]]; aoff[u] = A.mz_aoff[g[u]]; }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) o1[u] += o0[u];                           // (behind the last header load: no value is used between the loads)
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+      int32_t cnt_out = 0;
+      if (live[u]) do {
         // one occurrence: o0 IS the occurrence (k_ht_build), not an index into `pos`
-        const bool single = o1 - o0 == 1u;
-        const uint32_t pos1 = o0;
+        const bool single = o1[u] - o0[u] == 1u;
+        const uint32_t pos1 = o0[u];
 #define SEED_POS(i_) (single ? pos1 : A.I.pos[i_])
         if (pt) {
             // occurrences are sorted by global position, i.e. grouped by target: one run per target
-            int32_t total = 0; int64_t w = MODE == 1 ? wbase + A.mz_aoff[g] : 0;
+            int32_t total = 0; int64_t w = MODE == 1 ? wbase + (U > 1 ? aoff[u] : A.mz_aoff[g[u]]) : 0;
             uint64_t kf = 0, kr = 0; int32_t qz = 0;
             if (MODE == 1) {
-                const uint32_t y = A.mz_y[gi];
-                const int32_t span = (int32_t)(x & 0xff), qpos = (int32_t)(y >> 1); qz = (int32_t)(y & 1);
+                const uint32_t yy = U > 1 ? y[u] : A.mz_y[gi[u]];
+                const int32_t span = (int32_t)(x[u] & 0xff), qpos = (int32_t)(yy >> 1); qz = (int32_t)(yy & 1);
                 kf = (uint64_t)qpos << 8 | (uint64_t)span;
                 kr = (1ULL << 63) | (uint64_t)(qlen - (qpos + 1 - span) - 1) << 8 | (uint64_t)span;
             }
-            uint32_t o = o0;
-            while (o < o1) {
+            uint32_t o = o0[u];
+            while (o < o1[u]) {
                 const int t = d_tid_of(A.I.goff, A.n_targets, SEED_POS(o) >> 1);
                 const uint32_t gend = A.I.goff[t + 1];
                 uint32_t e = o + 1;
                 // (a run is one to three occurrences as a rule; a satellite's thousands inside one contig are stepped over by bisection)
-                for (int lin = 0; e < o1 && (SEED_POS(e) >> 1) < gend; ) { ++e; if (++lin == 8) { e = d_occ_lower(A.I.pos, e, o1, gend); break; } }
+                for (int lin = 0; e < o1[u] && (SEED_POS(e) >> 1) < gend; ) { ++e; if (++lin == 8) { e = d_occ_lower(A.I.pos, e, o1[u], gend); break; } }
                 if ((int32_t)(e - o) <= A.tmid[t]) {
                     total += (int32_t)(e - o);
                     if (MODE == 1) for (uint32_t z = o; z < e; ++z) { const uint32_t py = SEED_POS(z); d_put_key(A, w++, ((int)(py & 1) == qz ? kf : kr) | (uint64_t)(py >> 1) << 32); }
@@ -871,13 +931,13 @@ __device__ __forceinline__ void d_seed_query(const SeedArgs &A, const int q, con
             break;
         }
         int32_t cnt = 0;
-        uint32_t a0 = o0, a1 = o1;           // the occurrences that count: all, or those inside the query's target
-        if (o1 > o0) {
+        uint32_t a0 = o0[u], a1 = o1[u];     // the occurrences that count: all, or those inside the query's target
+        if (o1[u] > o0[u]) {
             if (tf >= 0) {
                 // Round 6: the target's piece of the list by bisection (the list is sorted by position).  A linear sweep met lists of
                 // 10^5-10^6 entries on the hard genome -- a satellite shared by the contigs of 150 loci, S6 -- once per query minimizer.
                 if (single) { const uint32_t gp = pos1 >> 1; if (gp < g0 || gp >= g1) a1 = a0; }
-                else { a0 = d_occ_lower(A.I.pos, o0, o1, g0); a1 = d_occ_lower(A.I.pos, a0, o1, g1); }
+                else { a0 = d_occ_lower(A.I.pos, o0[u], o1[u], g0); a1 = d_occ_lower(A.I.pos, a0, o1[u], g1); }
             }
             cnt = (int32_t)(a1 - a0);
             // (seed rescue, MODE 1: a minimizer above the cut-off that still has its count was rescued by MODE 0)
@@ -885,18 +945,23 @@ __device__ __forceinline__ void d_seed_query(const SeedArgs &A, const int q, con
         }
         cnt_out = cnt;
         if (MODE == 1 && cnt > 0) {
-            uint32_t y = A.mz_y[gi];
-            int32_t span = (int32_t)(x & 0xff), qpos = (int32_t)(y >> 1), qz = (int32_t)(y & 1);
+            const uint32_t yy = U > 1 ? y[u] : A.mz_y[gi[u]];
+            int32_t span = (int32_t)(x[u] & 0xff), qpos = (int32_t)(yy >> 1), qz = (int32_t)(yy & 1);
             uint64_t kf = (uint64_t)qpos << 8 | (uint64_t)span;
             uint64_t kr = (1ULL << 63) | (uint64_t)(qlen - (qpos + 1 - span) - 1) << 8 | (uint64_t)span;
-            int64_t w = wbase + A.mz_aoff[g];
-            for (uint32_t o = a0; o < a1; ++o) {
-                const uint32_t py = SEED_POS(o);
-                d_put_key(A, w++, ((int)(py & 1) == qz ? kf : kr) | (uint64_t)(py >> 1) << 32);
+            int64_t w = wbase + (U > 1 ? aoff[u] : A.mz_aoff[g[u]]);
+            // OG independent occurrence loads, then their keys, every key at the place the one-by-one walk gives it
+            for (uint32_t o = a0; o < a1; o += OG, w += OG) {
+                uint32_t py[OG];
+#pragma unroll
+                for (int j = 0; j < OG; ++j) py[j] = SEED_POS(min(o + (uint32_t)j, a1 - 1u));
+#pragma unroll
+                for (int j = 0; j < OG; ++j) if (o + (uint32_t)j < a1) d_put_key(A, w + j, ((int)(py[j] & 1) == qz ? kf : kr) | (uint64_t)(py[j] >> 1) << 32);
             }
         }
       } while (0);
-      if (MODE == 0 && g < m1) A.mz_cnt[g] = cnt_out;
+      if (MODE == 0 && g[u] < m1) A.mz_cnt[g[u]] = cnt_out;
+      }
     }
     if (MODE == 0) {
         // the counts -> offsets from the query's first anchor, in a pass of its own behind the probes (with the scan inside the probing
