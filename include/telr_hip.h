@@ -705,14 +705,42 @@ void telr_te_feats_free(telr_te_feats *f);
  *      s2 (integer types c C s S i I, truncated to 32 bits; the last occurrence wins), else 0; n_sub = n_ambi = 0; mapq, tid = refID,
  *      tlen from the header.  flags: 0x100 -> TELR_F_SECONDARY, 0x800 -> TELR_F_SUPPL, neither -> TELR_F_PRIMARY, 0x10 -> TELR_F_REV.
  *      Order: qid, then class (neither; 0x800; 0x100), then file order; parent = the record's index within its read, 0 for a
- *      secondary; CIGAR words packed in that order.  2^31 - 16 or more members, records or reads: TELR_E_RANGE.  A file that does
- *      not fit into device memory next to its inflated stream: TELR_E_NOMEM (both live in the context's scratch until
- *      telr_release_scratch).
+ *      secondary; CIGAR words packed in that order.  2^31 - 16 or more members, records or reads: TELR_E_RANGE.  telr_bam_load
+ *      holds the file next to its inflated stream in device memory; one that does not fit there: TELR_E_NOMEM (both live in the
+ *      context's scratch until telr_release_scratch).  telr_bam_load_chunked has no such limit.
  * counters: members, records, mapped, kept, reads, orphans, len_mismatch, no_cigar, no_eof.  The set and the result belong to the
  *      handle (telr_bam_in_free frees them) until detached; after that they are the caller's (telr_seqset_free / telr_result_free)
- *      and the handle's accessors stay valid while they live.  Not read: .bai, CRAM, SAM, the header text beyond its length. */
+ *      and the handle's accessors stay valid while they live.  Not read: .bai, CRAM, SAM, the header text beyond its length.
+ * Chunked (telr_bam_load_chunked): the same result -- names, targets, counters, records, CIGAR words, the set's words and qualities,
+ *      byte for byte -- for every accepted file and every chunk_bytes >= 1, with transient device memory that depends on the chunk and
+ *      not on the file.  The file stays mapped on the host.  It is cut into chunks (telr_bam_chunk_plan: a chunk is a run of whole
+ *      members in file order; it closes before the member whose ISIZE would take its sum of ISIZE above chunk_bytes and always holds
+ *      at least one member; members of ISIZE 0 are members like any other); every chunk is uploaded, inflated and parsed in turn,
+ *      chunk k + 1 inflating while chunk k is parsed.  The bytes of a chunk behind its last complete record (or all of it while the
+ *      header is incomplete) are carried in front of the next chunk; a record or header longer than a chunk makes that carry grow
+ *      and is no error.  Two passes: the first collects every record's fields and names, the host decides, the second inflates
+ *      again and writes CIGAR words, bases and qualities where they stay.  Beyond the result and the set, the device holds two chunk
+ *      slots (the chunk's file bytes and its buffer: carry + inflated members), the per-record tables of one chunk and fixed tables.
+ *      chunk_bytes: n > 0 that size; 0 the engine's own: free device memory (telr_device_mem) / 16, at least 1 MiB, at most 1 GiB;
+ *      TELR_BAM_CHUNK_FIT: telr_bam_load's whole-file path when file size + sum of ISIZE is below half the free device memory, else
+ *      as 0 (one hop of the member headers serves the decision and the load).
+ *      Errors: framing (the hop over the whole file, before any upload) first, as in telr_bam_load; all others in chunk order, and
+ *      within a chunk inflate (lowest block), header, record chain, records (lowest record); a quality above 93 in the second pass,
+ *      lowest record.  Block and record numbers are the file's.  A file with one fault gives telr_bam_load's code and text (texts
+ *      open with "telr_bam_load:" on either path); with several faults the chunk order may name another one than the whole-file
+ *      order (there: inflate of every block, then the header, the chain, every record).  A failed load leaves nothing allocated
+ *      beyond the context's scratch.
+ *      telr_bam_in_chunk_info: chunks, passes run (1 when nothing is kept and there is no read), the largest chunk buffer (bytes
+ *      allocated for one slot: carry room + inflated members; at most 64 KiB above the largest carry + the largest chunk's members,
+ *      so at most max(chunk_bytes, 65,536) + largest carry + 64 KiB), the largest carry (bytes); all 0 after a whole-file load. */
+#define TELR_BAM_CHUNK_FIT (-1)
 typedef struct telr_bam_in telr_bam_in;
 int  telr_bam_load(telr_ctx *ctx, const char *path, int32_t keep_qual, telr_bam_in **out);
+int  telr_bam_load_chunked(telr_ctx *ctx, const char *path, int32_t keep_qual, int64_t chunk_bytes, telr_bam_in **out);
+/* host only, no device needed.  first_member_of_chunk[c] for c < min(*n_chunks, cap).  TELR_E_ARG: a null pointer, a negative count
+ * or ISIZE, chunk_bytes < 1; TELR_E_RANGE: more chunks than cap (the first cap are written and *n_chunks is exact: call again) */
+int  telr_bam_chunk_plan(int64_t n_members, const int32_t *isize, int64_t chunk_bytes, int64_t *first_member_of_chunk, int64_t cap, int64_t *n_chunks);
+int  telr_bam_in_chunk_info(const telr_bam_in *in, int64_t *out /* [4] */);
 void telr_bam_in_free(telr_bam_in *in);
 int32_t telr_bam_in_target_count(const telr_bam_in *in);
 const char *const *telr_bam_in_target_names(const telr_bam_in *in);
@@ -727,7 +755,10 @@ telr_result *telr_bam_in_detach_result(telr_bam_in *in);
 int  telr_bam_in_counters(const telr_bam_in *in, int64_t *out /* [9] */);
 /* the `bam2fasta` text, decoded on demand on the device: buf[off[q] .. off[q] + len[q]) = read q, off[q] = the bases before it */
 int  telr_bam_in_ascii(const telr_bam_in *in, char *buf, int64_t *off);
-/* wall-clock milliseconds of the load's phases: host hop, upload, inflate, chain, parse, names on the host, sequences, total */
+/* wall-clock milliseconds of the load's phases: host hop, upload, inflate, chain, parse, names on the host, sequences, total.
+ * After telr_bam_load_chunked they are sums over the chunks (upload, inflate: both passes, device time between events on the second
+ * stream; chain: device time; parse: host time of pass 1 behind the chain; sequences: the whole second pass); upload and inflate
+ * overlap with the others, so total (wall clock) is no longer the sum of the rest */
 int  telr_bam_in_phase_ms(const telr_bam_in *in, float *out /* [8] */);
 
 /* ---- window reads (a12) -------------------------------------------------------

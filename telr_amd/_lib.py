@@ -24,7 +24,7 @@ EXPORTS = [
     "telr_draft_opt_default", "telr_draft_contigs", "telr_drafts_count", "telr_drafts_data", "telr_draft_contigs_free",
     "telr_bam_load", "telr_bam_in_free", "telr_bam_in_target_count", "telr_bam_in_target_names", "telr_bam_in_target_lens", "telr_bam_in_read_count",
     "telr_bam_in_read_names", "telr_bam_in_read_lens", "telr_bam_in_seqset", "telr_bam_in_result", "telr_bam_in_detach_seqset", "telr_bam_in_detach_result",
-    "telr_bam_in_counters", "telr_bam_in_ascii", "telr_bam_in_phase_ms",
+    "telr_bam_in_counters", "telr_bam_in_ascii", "telr_bam_in_phase_ms", "telr_bam_load_chunked", "telr_bam_chunk_plan", "telr_bam_in_chunk_info",
     "telr_seqset_extract", "telr_seqset_pieces",
     "telr_part_plan", "telr_part_plan_error", "telr_merge_parts", "telr_write_bam_dev_targets",
     "telr_tile_plan", "telr_refte_opt_default", "telr_annotate_hits", "telr_te_feats_count", "telr_te_feats_data", "telr_te_feats_free",
@@ -117,6 +117,9 @@ def lib():
     L.telr_bam_in_counters.restype = C.c_int; L.telr_bam_in_counters.argtypes = [vp, vp]
     L.telr_bam_in_ascii.restype = C.c_int; L.telr_bam_in_ascii.argtypes = [vp, vp, vp]
     L.telr_bam_in_phase_ms.restype = C.c_int; L.telr_bam_in_phase_ms.argtypes = [vp, vp]
+    L.telr_bam_load_chunked.restype = C.c_int; L.telr_bam_load_chunked.argtypes = [vp, cp, i32, i64, C.POINTER(vp)]
+    L.telr_bam_chunk_plan.restype = C.c_int; L.telr_bam_chunk_plan.argtypes = [i64, vp, i64, vp, i64, C.POINTER(i64)]
+    L.telr_bam_in_chunk_info.restype = C.c_int; L.telr_bam_in_chunk_info.argtypes = [vp, vp]
     L.telr_debug_bgzf_inflate.restype = C.c_int; L.telr_debug_bgzf_inflate.argtypes = [vp, cp, vp, i64, C.POINTER(i64)]
     L.telr_debug_seqset_qual.restype = i64; L.telr_debug_seqset_qual.argtypes = [vp, vp, i64]
     L.telr_window_reads.restype = C.c_int; L.telr_window_reads.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, i64, vp]

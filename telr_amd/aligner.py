@@ -10,6 +10,7 @@ from ._abi import IdxOpt, MapOpt, Counters, InsOpt, GenoOpt, DraftOpt, RefTeOpt,
     TE_FEAT_DTYPE, TELR_E_ARG, TELR_E_RANGE, MF_PER_TARGET, MF_KEEP_CIGARS, N_STAGES, N_DPCLS
 from .fasta import concat
 
+BAM_CHUNK_FIT = -1        # TELR_BAM_CHUNK_FIT (include/telr_hip.h): Engine.load_bam decides between the whole-file and the chunked load
 
 def _np_from(ptr, n, dtype):
     if n == 0 or not ptr:
@@ -100,10 +101,25 @@ class Engine:
         targets (and the same max_part_bases), whose resident target set and subsets are used again"""
         return PartIndex(self, targets, io, max_part_bases, like)
 
-    def load_bam(self, path, keep_qual=False):
+    @staticmethod
+    def bam_chunk_plan(isize, chunk_bytes):
+        """-> first_member_of_chunk (int64): how a file whose BGZF members inflate to these ISIZE is cut into chunks of at most
+        chunk_bytes inflated bytes (telr_bam_chunk_plan; include/telr_hip.h has the definition; no device needed)"""
+        a = np.ascontiguousarray(isize, dtype=np.int32)
+        L = _lib.lib()
+        first = np.zeros(max(len(a), 1), np.int64); n = C.c_int64(0)
+        rc = L.telr_bam_chunk_plan(len(a), a.ctypes.data, int(chunk_bytes), first.ctypes.data, len(a), C.byref(n))
+        if rc != 0:
+            raise _lib.TelrError("telr_bam_chunk_plan: %s" % L.telr_strerror(rc).decode(), rc)
+        return first[:int(n.value)]
+
+    def load_bam(self, path, keep_qual=False, chunk_bytes=None):
         """a BAM file as stage-1 input, inflated and parsed on the device (telr_bam_load; include/telr_hip.h has the definition)
-        -> BamInput.  keep_qual: attach the reads' base qualities to the read set when every sequence-bearing record has them"""
-        return BamInput(self, path, keep_qual)
+        -> BamInput.  keep_qual: attach the reads' base qualities to the read set when every sequence-bearing record has them.
+        chunk_bytes: None = the whole file at once (it must fit into device memory next to its inflated stream); n > 0 = in chunks of
+        at most n inflated bytes, 0 = in chunks of the engine's own size (telr_bam_load_chunked: a file of any size, the same result);
+        BAM_CHUNK_FIT = the whole file when it fits into half the free device memory, else as 0"""
+        return BamInput(self, path, keep_qual, chunk_bytes)
 
     def stage_ms(self):
         a = np.zeros(N_STAGES, np.float32)
@@ -465,18 +481,26 @@ class BamInput:
     """what Engine.load_bam returns: tnames / tlens (the header's references), qnames (the reads, in file order of their first
     sequence-bearing record), read_set (a SeqSet resident on the device, qualities attached when kept), result (a raw result handle with
     its CIGARs resident: Index.call_insertions, genotype_insertions, draft_contigs, write_bam_device, result_arrays, ...), counters
-    (dict: members, records, mapped, kept, reads, orphans, len_mismatch, no_cigar, no_eof) and phase_ms (dict)"""
+    (dict: members, records, mapped, kept, reads, orphans, len_mismatch, no_cigar, no_eof), phase_ms (dict) and chunk_info (dict: chunks,
+    passes, largest_buffer, largest_carry; all 0 after a whole-file load)"""
     COUNTERS = ("members", "records", "mapped", "kept", "reads", "orphans", "len_mismatch", "no_cigar", "no_eof")
     PHASES = ("host_hop", "upload", "inflate", "chain", "parse", "names_host", "sequences", "total")
+    CHUNK_INFO = ("chunks", "passes", "largest_buffer", "largest_carry")
 
-    def __init__(self, eng, path, keep_qual=False):
+    def __init__(self, eng, path, keep_qual=False, chunk_bytes=None):
         L = eng.L
         self.eng = eng
         h = C.c_void_p()
-        rc = L.telr_bam_load(eng.h, str(path).encode(), 1 if keep_qual else 0, C.byref(h))
+        if chunk_bytes is None:
+            rc = L.telr_bam_load(eng.h, str(path).encode(), 1 if keep_qual else 0, C.byref(h))
+        else:
+            rc = L.telr_bam_load_chunked(eng.h, str(path).encode(), 1 if keep_qual else 0, int(chunk_bytes), C.byref(h))
         if rc != 0:
             raise _lib.TelrError("telr_bam_load: %s [%s]" % (L.telr_strerror(rc).decode(), L.telr_last_error(eng.h).decode()), rc)
         self.h = h
+        ci = np.zeros(len(self.CHUNK_INFO), np.int64)
+        L.telr_bam_in_chunk_info(h, ci.ctypes.data)
+        self.chunk_info = dict(zip(self.CHUNK_INFO, (int(x) for x in ci)))
         nt, nq = int(L.telr_bam_in_target_count(h)), int(L.telr_bam_in_read_count(h))
         self.tnames = [x.decode("latin-1") for x in _cstrs(L.telr_bam_in_target_names(h), nt)]
         self.tlens = _np_from(L.telr_bam_in_target_lens(h), nt, np.int32)

@@ -13,6 +13,7 @@
 //             k_bam_seq / k_bam_qual   the reads' 2-bit words, mask words and Phred bytes in the set's layout
 //             k_bam_ascii      the set as text, on demand
 // Every store position is a scan's or the lane's own index; there is no atomic; the bytes are the same on every run.
+// telr_bam_load_chunked (bam_in_chunked.hip.h) runs the same kernels and the same host decision chunk by chunk, for a file of any size.
 //
 // The window is in LDS, not in the member's global output: a match copy reads what the symbol before it wrote, and the turn-around
 // of an LDS store -> load inside one wave is some hundred cycles where a global one is a microsecond or more.  64 KiB of window +
@@ -118,9 +119,11 @@ static __device__ __forceinline__ uint32_t bi_ld32(const uint8_t *__restrict__ s
 }
 static __device__ __forceinline__ uint32_t bi_ld16(const uint8_t *__restrict__ s, int64_t p) { return (uint32_t)s[p] | (uint32_t)s[p + 1] << 8; }
 
-// res[0] = records, res[1] = 0 | 1 (record res[0] runs past the stream) | 2 (its block_size is below 32) | 3 (more records than `cap`)
-__global__ void __launch_bounds__(64) k_bam_chain(const uint8_t *__restrict__ stream, int64_t total, int64_t start, int64_t *__restrict__ offs, int64_t cap,
-                                                  int64_t *__restrict__ res)
+// res[0] = records, res[1] = 0 | 1 (record res[0] runs past the stream) | 2 (its block_size is below 32) | 3 (more records than `cap`);
+// PART (a chunk's buffer, bam_in_chunked.hip.h): res[2] = where the walk ended -- behind the last complete record
+template <bool PART>
+static __device__ __forceinline__ void bam_chain_walk(const uint8_t *__restrict__ stream, int64_t total, int64_t start, int64_t *__restrict__ offs, int64_t cap,
+                                                      int64_t *__restrict__ res)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int64_t p = start, n = 0, st = 0;
@@ -134,6 +137,17 @@ __global__ void __launch_bounds__(64) k_bam_chain(const uint8_t *__restrict__ st
         p += 4 + (int64_t)bs;
     }
     res[0] = n; res[1] = st;
+    if (PART) res[2] = p;
+}
+__global__ void __launch_bounds__(64) k_bam_chain(const uint8_t *__restrict__ stream, int64_t total, int64_t start, int64_t *__restrict__ offs, int64_t cap,
+                                                  int64_t *__restrict__ res)
+{
+    bam_chain_walk<false>(stream, total, start, offs, cap, res);
+}
+__global__ void __launch_bounds__(64) k_bam_chain_part(const uint8_t *__restrict__ stream, int64_t total, int64_t start, int64_t *__restrict__ offs, int64_t cap,
+                                                       int64_t *__restrict__ res)
+{
+    bam_chain_walk<true>(stream, total, start, offs, cap, res);
 }
 
 enum { BREC_OK = 0, BREC_FIELDS = 1, BREC_TAGS = 2, BREC_REF = 3, BREC_CLIP = 4, BREC_OP = 5, BREC_RANGE = 6 };
@@ -359,11 +373,9 @@ static __device__ __forceinline__ int32_t bam_read_of(const int64_t *__restrict_
     return lo - 1;
 }
 // one lane per 2-bit word (16 bases) of the set's layout; the mask words from lane pairs (nw is even: reads are padded to 64 bases)
-__global__ void __launch_bounds__(256) k_bam_seq(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
-                                                 int64_t nw, uint32_t *__restrict__ out2, uint32_t *__restrict__ outn)
+static __device__ __forceinline__ void bam_seq_word(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
+                                                    int64_t w, uint32_t *__restrict__ out2, uint32_t *__restrict__ outn)
 {
-    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (w >= nw) return;
     const int64_t b0 = w * 16;
     const int32_t q = bam_read_of(boff, n, b0);
     const BamRead R = reads[q];
@@ -378,12 +390,25 @@ __global__ void __launch_bounds__(256) k_bam_seq(const uint8_t *__restrict__ str
     const uint32_t other = __shfl_xor(m16, 1);
     if (!(w & 1)) outn[w >> 1] = m16 | (other << 16);
 }
-// one lane per 4 Phred bytes of the set's base layout (zero behind a read's end); over[q] = 1 for a read with a value above 93 (the same 1 from whichever lane meets one)
-__global__ void __launch_bounds__(256) k_bam_qual(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
-                                                  int64_t nw, uint32_t *__restrict__ out4, int32_t *__restrict__ over)
+__global__ void __launch_bounds__(256) k_bam_seq(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
+                                                 int64_t nw, uint32_t *__restrict__ out2, uint32_t *__restrict__ outn)
 {
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (w >= nw) return;
+    bam_seq_word(stream, reads, boff, n, w, out2, outn);
+}
+// a chunk's reads (bam_in_chunked.hip.h): words [w0, w1) of the set's layout, both multiples of 4; reads / boff start at the chunk's first read
+__global__ void __launch_bounds__(256) k_bam_seq_part(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
+                                                      int64_t w0, int64_t w1, uint32_t *__restrict__ out2, uint32_t *__restrict__ outn)
+{
+    const int64_t w = w0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= w1) return;
+    bam_seq_word(stream, reads, boff, n, w, out2, outn);
+}
+// one lane per 4 Phred bytes of the set's base layout (zero behind a read's end); over[q] = 1 for a read with a value above 93 (the same 1 from whichever lane meets one)
+static __device__ __forceinline__ void bam_qual_word(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
+                                                     int64_t w, uint32_t *__restrict__ out4, int32_t *__restrict__ over)
+{
     const int64_t b0 = w * 4;
     const int32_t q = bam_read_of(boff, n, b0);
     const BamRead R = reads[q];
@@ -398,6 +423,20 @@ __global__ void __launch_bounds__(256) k_bam_qual(const uint8_t *__restrict__ st
     }
     out4[w] = v;
     if (big) over[q] = 1;
+}
+__global__ void __launch_bounds__(256) k_bam_qual(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
+                                                  int64_t nw, uint32_t *__restrict__ out4, int32_t *__restrict__ over)
+{
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= nw) return;
+    bam_qual_word(stream, reads, boff, n, w, out4, over);
+}
+__global__ void __launch_bounds__(256) k_bam_qual_part(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
+                                                       int64_t w0, int64_t w1, uint32_t *__restrict__ out4, int32_t *__restrict__ over)
+{
+    const int64_t w = w0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= w1) return;
+    bam_qual_word(stream, reads, boff, n, w, out4, over);
 }
 // the set as text: one lane per 4 bases of the padded layout, stored where the compact text has them (coff[q] = bases before read q)
 __global__ void __launch_bounds__(256) k_bam_ascii(const uint32_t *__restrict__ seq2, const uint32_t *__restrict__ nmask, const int64_t *__restrict__ boff,
@@ -432,6 +471,7 @@ struct telr_bam_in {
     bool set_owned = true, res_owned = true;
     int64_t counters[9] = {0};
     float phase_ms[BIN_NPHASE] = {0};
+    int64_t chunk_info[4] = {0};       // telr_bam_load_chunked: chunks, passes, largest chunk buffer, largest carry
 };
 struct BamInClock {
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
@@ -450,11 +490,17 @@ static const char *infl_text(int st)
     return st >= 0 && st <= 9 ? T[st] : "?";
 }
 
-// the file -> its inflated stream in the context's scratch ("bamin_stream"; valid until the next load on the context)
-static int bam_in_inflate(telr_ctx *ctx, const char *what, const char *path, uint8_t **d_stream_out, int64_t *total_out, int64_t *n_members, int64_t *no_eof, float *phase)
+// the mapped file and its member table (host only): what the whole-file load and the chunked load both start from
+struct BamInHop {
+    BamInFile F;
+    std::vector<BgzfMember> mem; std::vector<int32_t> isz;      // mem[k].off: file offset of member k's deflate bytes
+    int64_t total = 0, no_eof = 0;                              // sum of ISIZE; 1 without the EOF marker
+    float ms = 0;
+};
+static int bam_in_hop(telr_ctx *ctx, const char *what, const char *path, BamInHop &H)
 {
     BamInClock clk;
-    BamInFile F;
+    BamInFile &F = H.F;
     F.fd = open(path, O_RDONLY);
     struct stat sb;
     if (F.fd < 0 || fstat(F.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { ctx->err = std::string(what) + ": cannot open " + path; return TELR_E_IO; }
@@ -462,7 +508,7 @@ static int bam_in_inflate(telr_ctx *ctx, const char *what, const char *path, uin
     if (F.n) { void *m = mmap(nullptr, F.n, PROT_READ, MAP_PRIVATE, F.fd, 0); if (m == MAP_FAILED) { F.n = 0; ctx->err = std::string(what) + ": cannot map " + path; return TELR_E_IO; } F.p = (const uint8_t*)m; }
     const uint8_t *d = F.p; const size_t size = F.n;
     // hop the member headers
-    std::vector<BgzfMember> mem; std::vector<int32_t> isz;
+    std::vector<BgzfMember> &mem = H.mem; std::vector<int32_t> &isz = H.isz;
     size_t p = 0;
     while (p < size) {
         const size_t k = mem.size();
@@ -490,11 +536,23 @@ static int bam_in_inflate(telr_ctx *ctx, const char *what, const char *path, uin
     }
     const size_t nm = mem.size();
     if (nm >= 0x7ffffff0u) { ctx->err = std::string(what) + ": too many BGZF members"; return TELR_E_RANGE; }
-    *n_members = (int64_t)nm;
-    *no_eof = (size >= 28 && !memcmp(d + size - 28, BGZF_EOF28, 28)) ? 0 : 1;
-    int64_t total = 0;
-    for (size_t k = 0; k < nm; ++k) total += mem[k].isize;
-    phase[BIN_HOP] = clk.lap();
+    H.no_eof = (size >= 28 && !memcmp(d + size - 28, BGZF_EOF28, 28)) ? 0 : 1;
+    H.total = 0;
+    for (size_t k = 0; k < nm; ++k) H.total += mem[k].isize;
+    H.ms = clk.lap();
+    return TELR_OK;
+}
+
+// the file -> its inflated stream in the context's scratch ("bamin_stream"; valid until the next load on the context)
+static int bam_in_inflate(telr_ctx *ctx, const char *what, const BamInHop &H, uint8_t **d_stream_out, int64_t *total_out, int64_t *n_members, int64_t *no_eof, float *phase)
+{
+    BamInClock clk;
+    const uint8_t *d = H.F.p; const size_t size = H.F.n;
+    const std::vector<BgzfMember> &mem = H.mem; const std::vector<int32_t> &isz = H.isz;
+    const size_t nm = mem.size();
+    const int64_t total = H.total;
+    *n_members = (int64_t)nm; *no_eof = H.no_eof;
+    phase[BIN_HOP] = H.ms;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     uint8_t *d_file, *d_stream; BgzfMember *d_mem; int32_t *d_isz, *d_status; int64_t *d_ooff; CrcTabs *d_tabs;
@@ -537,7 +595,9 @@ extern "C" int telr_debug_bgzf_inflate(telr_ctx *ctx, const char *path, uint8_t 
     (void)hipGetLastError();
     if (!ctx || !path || !n) return TELR_E_ARG;
     uint8_t *d_stream; int64_t total, nm, ne; float ph[BIN_NPHASE];
-    TRY(bam_in_inflate(ctx, "telr_debug_bgzf_inflate", path, &d_stream, &total, &nm, &ne, ph));
+    BamInHop H;
+    TRY(bam_in_hop(ctx, "telr_debug_bgzf_inflate", path, H));
+    TRY(bam_in_inflate(ctx, "telr_debug_bgzf_inflate", H, &d_stream, &total, &nm, &ne, ph));
     *n = total;
     if (total && total <= cap && out) HIPCHK(hipMemcpy(out, d_stream, (size_t)total, hipMemcpyDeviceToHost));
     return TELR_OK;
@@ -587,16 +647,122 @@ extern "C" void telr_bam_in_free(telr_bam_in *in)
     delete in;
 }
 
-extern "C" int telr_bam_load(telr_ctx *ctx, const char *path, int32_t keep_qual, telr_bam_in **out)
+// ---- what the host decides from the records' fields and names (both loads: the whole file's records, in file order) ----
+// the first of recs[0 .. n) that breaks a rule; its number in the text is base + its index
+static int bam_in_rec_fault(telr_ctx *ctx, const BamRec *recs, int64_t n, int64_t base)
 {
-    (void)hipGetLastError();
-    if (!ctx) return TELR_E_ARG;
-    if (!path || !out) { ctx->err = "telr_bam_load: null path or output"; return TELR_E_ARG; }
+    for (int64_t k = 0; k < n; ++k) {
+        const int s = recs[k].status;
+        if (s == BREC_OK) continue;
+        static const char *const why[] = { "", "fields run past the record", "malformed tags", "refID or pos outside the header's references",
+                                           "a clip inside the CIGAR", "CIGAR op code above 8", "CIGAR lengths beyond the record's coordinate bits" };
+        ctx->err = "telr_bam_load: record " + std::to_string(base + k) + ": " + why[s >= 1 && s <= 6 ? s : 0];
+        return s == BREC_RANGE ? TELR_E_RANGE : TELR_E_ARG;
+    }
+    return TELR_OK;
+}
+struct BamInDecided {
+    std::vector<BamRead> reads; std::vector<int32_t> rlen, first_rec;      // read q: where its bases are, its length, its record
+    bool any_ff = false;                                                   // a sequence-bearing record without QUAL
+    std::vector<int32_t> kept_rec; std::vector<int64_t> kept_off;          // the kept records in the result's order; their first CIGAR word
+    int64_t ncig = 0;
+    std::unique_ptr<telr_result> R;                                        // alns filled in, no CIGAR array yet
+};
+// names -> read numbers (first name wins), which records are kept, their order, their result records; B: qnames and counters 1 .. 7
+static int bam_in_decide(telr_ctx *ctx, telr_bam_in *B, const std::vector<BamRec> &recs, const std::vector<char> &names, const std::vector<int64_t> &noff, BamInDecided &D)
+{
+    const int64_t nrec = (int64_t)recs.size();
+    std::unordered_map<std::string, int32_t> qid_of;
+    std::vector<BamRead> &reads = D.reads; std::vector<int32_t> &rlen = D.rlen, &first_rec = D.first_rec;
+    int64_t n_mapped = 0, n_nocig = 0;
+    auto name_of = [&](int64_t k) { return std::string(names.data() + noff[(size_t)k], (size_t)(noff[(size_t)k + 1] - noff[(size_t)k])); };
+    auto mapped_of = [](const BamRec &r) { return !(r.flag & 4) && r.refid >= 0; };
+    for (int64_t k = 0; k < nrec; ++k) {
+        const BamRec &r = recs[(size_t)k];
+        const bool mapped = mapped_of(r);
+        if (mapped) { ++n_mapped; if (r.n_norm == 0) ++n_nocig; }
+        const int64_t qlen = (int64_t)r.clip5 + r.sm + r.si + r.clip3;
+        if ((r.flag & 0x900) || r.lseq <= 0 || (mapped && r.lseq != qlen)) continue;
+        if (r.qual0 == 0xff) D.any_ff = true;
+        auto ins = qid_of.emplace(name_of(k), (int32_t)reads.size());
+        if (!ins.second) continue;
+        if (reads.size() >= 0x7ffffff0u) { ctx->err = "telr_bam_load: too many reads"; return TELR_E_RANGE; }
+        BamRead R; R.seq_off = r.seq_off; R.qual_off = r.seq_off + ((int64_t)r.lseq + 1) / 2; R.len = r.lseq; R.rev = (r.flag & 0x10) ? 1 : 0;
+        reads.push_back(R); rlen.push_back(r.lseq); first_rec.push_back((int32_t)k);
+        B->qnames.push_back(ins.first->first);
+    }
+    const int32_t nq = (int32_t)reads.size();
+    struct Kept { int32_t qid, cls, rec; };
+    std::vector<Kept> kept;
+    int64_t n_orphan = 0, n_lenmis = 0;
+    for (int64_t k = 0; k < nrec; ++k) {
+        const BamRec &r = recs[(size_t)k];
+        if (!mapped_of(r) || r.n_norm == 0) continue;
+        auto it = qid_of.find(name_of(k));
+        if (it == qid_of.end()) { ++n_orphan; continue; }
+        if ((int64_t)r.clip5 + r.sm + r.si + r.clip3 != rlen[(size_t)it->second]) { ++n_lenmis; continue; }
+        Kept x; x.qid = it->second; x.cls = (r.flag & 0x100) ? 2 : (r.flag & 0x800) ? 1 : 0; x.rec = (int32_t)k;
+        kept.push_back(x);
+    }
+    std::sort(kept.begin(), kept.end(), [](const Kept &a, const Kept &b) { return a.qid != b.qid ? a.qid < b.qid : a.cls != b.cls ? a.cls < b.cls : a.rec < b.rec; });
+    const size_t nk = kept.size();
+    D.R.reset(new telr_result());
+    telr_result *R = D.R.get();
+    R->ctx = ctx;
+    R->alns.resize(nk);
+    D.kept_rec.resize(nk); D.kept_off.resize(nk);
+    int64_t ncig = 0; int32_t within = 0;
+    for (size_t i = 0; i < nk; ++i) {
+        const BamRec &r = recs[(size_t)kept[i].rec];
+        within = (i > 0 && kept[i - 1].qid == kept[i].qid) ? within + 1 : 0;
+        telr_aln &a = R->alns[i];
+        const bool rev = (r.flag & 0x10) != 0;
+        const int32_t qlen = r.clip5 + r.sm + r.si + r.clip3, blen = r.sm + r.si + r.sd;
+        a.qid = kept[i].qid; a.tid = r.refid; a.qlen = qlen; a.tlen = B->tlens[(size_t)r.refid];
+        a.qs = rev ? r.clip3 : r.clip5; a.qe = rev ? qlen - r.clip5 : qlen - r.clip3;
+        a.ts = r.pos; a.te = r.pos + r.sm + r.sd;
+        a.blen = blen;
+        if (r.has_nm) { const int32_t m = (int32_t)((uint32_t)blen - (uint32_t)r.nm); a.mlen = m > 0 ? m : 0; } else a.mlen = r.sm;
+        a.score = r.s1; a.subsc = r.s2; a.dp_score = r.as; a.cnt = r.cm; a.n_sub = 0; a.n_ambi = 0;
+        a.parent = kept[i].cls == 2 ? 0 : within;
+        a.n_cigar = r.n_norm; a.cigar_off = ncig;
+        a.flags = (kept[i].cls == 2 ? TELR_F_SECONDARY : kept[i].cls == 1 ? TELR_F_SUPPL : TELR_F_PRIMARY) | (rev ? TELR_F_REV : 0);
+        a.mapq = r.mapq;
+        D.kept_rec[i] = kept[i].rec; D.kept_off[i] = ncig;
+        ncig += r.n_norm;
+    }
+    D.ncig = ncig;
+    B->counters[1] = nrec; B->counters[2] = n_mapped; B->counters[3] = (int64_t)nk; B->counters[4] = nq;
+    B->counters[5] = n_orphan; B->counters[6] = n_lenmis; B->counters[7] = n_nocig;
+    return TELR_OK;
+}
+// the result's CIGAR arrays for ncig words: the host mirror and the device array the emit pass writes
+static int bam_in_result_arrays(telr_ctx *ctx, telr_result *R, int64_t ncig)
+{
+    R->cig = cig_alloc((size_t)ncig + 1);
+    if (!R->cig) { ctx->err = "telr_bam_load: host CIGAR array"; return TELR_E_NOMEM; }
+    R->cap = (size_t)ncig + 1; R->ncig = (size_t)ncig;
+    if (hipMalloc(&R->d_cig, ((size_t)ncig + 1) * 4) != hipSuccess) { (void)hipGetLastError(); R->d_cig = nullptr; ctx->err = "telr_bam_load: device CIGAR array"; return TELR_E_NOMEM; }
+    R->d_cap = (size_t)ncig + 1;
+    return TELR_OK;
+}
+
+// a finished load: the handle takes the set and the result, and its name tables are made
+static void bam_in_finish(telr_bam_in *B, telr_seqset *S, telr_result *R)
+{
+    for (auto &s : B->tnames) B->tname_ptr.push_back(s.c_str());
+    for (auto &s : B->qnames) B->qname_ptr.push_back(s.c_str());
+    B->tname_ptr.push_back(nullptr); B->qname_ptr.push_back(nullptr);
+    B->set = S; B->res = R;
+}
+
+static int bam_load_whole(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual, telr_bam_in **out)
+{
     BamInClock wall, clk;
     std::unique_ptr<telr_bam_in, void (*)(telr_bam_in*)> B(new telr_bam_in(), telr_bam_in_free);
     B->ctx = ctx;
     uint8_t *d_stream; int64_t total = 0;
-    TRY(bam_in_inflate(ctx, "telr_bam_load", path, &d_stream, &total, &B->counters[0], &B->counters[8], B->phase_ms));
+    TRY(bam_in_inflate(ctx, "telr_bam_load", H, &d_stream, &total, &B->counters[0], &B->counters[8], B->phase_ms));
     hipStream_t st = ctx->stream;
     clk.lap();
     // the header: small, parsed on the host
@@ -656,88 +822,24 @@ extern "C" int telr_bam_load(telr_ctx *ctx, const char *path, int32_t keep_qual,
     }
     B->phase_ms[BIN_PARSE] = clk.lap();
     // ---- host: the first record in file order that breaks a rule; names -> read numbers; which records are kept, and where
-    for (int64_t k = 0; k < nrec; ++k) {
-        const int s = recs[(size_t)k].status;
-        if (s == BREC_OK) continue;
-        static const char *const why[] = { "", "fields run past the record", "malformed tags", "refID or pos outside the header's references",
-                                           "a clip inside the CIGAR", "CIGAR op code above 8", "CIGAR lengths beyond the record's coordinate bits" };
-        ctx->err = "telr_bam_load: record " + std::to_string(k) + ": " + why[s >= 1 && s <= 6 ? s : 0];
-        return s == BREC_RANGE ? TELR_E_RANGE : TELR_E_ARG;
-    }
-    std::unordered_map<std::string, int32_t> qid_of;
-    std::vector<BamRead> reads; std::vector<int32_t> rlen, first_rec;
-    bool any_ff = false;
-    int64_t n_mapped = 0, n_nocig = 0;
-    auto name_of = [&](int64_t k) { return std::string(names.data() + noff[(size_t)k], (size_t)(noff[(size_t)k + 1] - noff[(size_t)k])); };
-    auto mapped_of = [](const BamRec &r) { return !(r.flag & 4) && r.refid >= 0; };
-    for (int64_t k = 0; k < nrec; ++k) {
-        const BamRec &r = recs[(size_t)k];
-        const bool mapped = mapped_of(r);
-        if (mapped) { ++n_mapped; if (r.n_norm == 0) ++n_nocig; }
-        const int64_t qlen = (int64_t)r.clip5 + r.sm + r.si + r.clip3;
-        if ((r.flag & 0x900) || r.lseq <= 0 || (mapped && r.lseq != qlen)) continue;
-        if (r.qual0 == 0xff) any_ff = true;
-        auto ins = qid_of.emplace(name_of(k), (int32_t)reads.size());
-        if (!ins.second) continue;
-        if (reads.size() >= 0x7ffffff0u) { ctx->err = "telr_bam_load: too many reads"; return TELR_E_RANGE; }
-        BamRead R; R.seq_off = r.seq_off; R.qual_off = r.seq_off + ((int64_t)r.lseq + 1) / 2; R.len = r.lseq; R.rev = (r.flag & 0x10) ? 1 : 0;
-        reads.push_back(R); rlen.push_back(r.lseq); first_rec.push_back((int32_t)k);
-        B->qnames.push_back(ins.first->first);
-    }
+    TRY(bam_in_rec_fault(ctx, recs.data(), nrec, 0));
+    BamInDecided D;
+    TRY(bam_in_decide(ctx, B.get(), recs, names, noff, D));
+    std::vector<BamRead> &reads = D.reads; std::vector<int32_t> &first_rec = D.first_rec;
+    const bool any_ff = D.any_ff;
     const int32_t nq = (int32_t)reads.size();
-    struct Kept { int32_t qid, cls, rec; };
-    std::vector<Kept> kept;
-    int64_t n_orphan = 0, n_lenmis = 0;
-    for (int64_t k = 0; k < nrec; ++k) {
-        const BamRec &r = recs[(size_t)k];
-        if (!mapped_of(r) || r.n_norm == 0) continue;
-        auto it = qid_of.find(name_of(k));
-        if (it == qid_of.end()) { ++n_orphan; continue; }
-        if ((int64_t)r.clip5 + r.sm + r.si + r.clip3 != rlen[(size_t)it->second]) { ++n_lenmis; continue; }
-        Kept x; x.qid = it->second; x.cls = (r.flag & 0x100) ? 2 : (r.flag & 0x800) ? 1 : 0; x.rec = (int32_t)k;
-        kept.push_back(x);
-    }
-    std::sort(kept.begin(), kept.end(), [](const Kept &a, const Kept &b) { return a.qid != b.qid ? a.qid < b.qid : a.cls != b.cls ? a.cls < b.cls : a.rec < b.rec; });
-    const size_t nk = kept.size();
-    std::unique_ptr<telr_result> R(new telr_result());
-    R->ctx = ctx;
-    R->alns.resize(nk);
-    std::vector<int32_t> kept_rec(nk); std::vector<int64_t> kept_off(nk);
-    int64_t ncig = 0; int32_t within = 0;
-    for (size_t i = 0; i < nk; ++i) {
-        const BamRec &r = recs[(size_t)kept[i].rec];
-        within = (i > 0 && kept[i - 1].qid == kept[i].qid) ? within + 1 : 0;
-        telr_aln &a = R->alns[i];
-        const bool rev = (r.flag & 0x10) != 0;
-        const int32_t qlen = r.clip5 + r.sm + r.si + r.clip3, blen = r.sm + r.si + r.sd;
-        a.qid = kept[i].qid; a.tid = r.refid; a.qlen = qlen; a.tlen = B->tlens[(size_t)r.refid];
-        a.qs = rev ? r.clip3 : r.clip5; a.qe = rev ? qlen - r.clip5 : qlen - r.clip3;
-        a.ts = r.pos; a.te = r.pos + r.sm + r.sd;
-        a.blen = blen;
-        if (r.has_nm) { const int32_t m = (int32_t)((uint32_t)blen - (uint32_t)r.nm); a.mlen = m > 0 ? m : 0; } else a.mlen = r.sm;
-        a.score = r.s1; a.subsc = r.s2; a.dp_score = r.as; a.cnt = r.cm; a.n_sub = 0; a.n_ambi = 0;
-        a.parent = kept[i].cls == 2 ? 0 : within;
-        a.n_cigar = r.n_norm; a.cigar_off = ncig;
-        a.flags = (kept[i].cls == 2 ? TELR_F_SECONDARY : kept[i].cls == 1 ? TELR_F_SUPPL : TELR_F_PRIMARY) | (rev ? TELR_F_REV : 0);
-        a.mapq = r.mapq;
-        kept_rec[i] = kept[i].rec; kept_off[i] = ncig;
-        ncig += r.n_norm;
-    }
-    B->counters[1] = nrec; B->counters[2] = n_mapped; B->counters[3] = (int64_t)nk; B->counters[4] = nq;
-    B->counters[5] = n_orphan; B->counters[6] = n_lenmis; B->counters[7] = n_nocig;
+    const size_t nk = D.kept_rec.size();
+    const int64_t ncig = D.ncig;
+    std::unique_ptr<telr_result> R(std::move(D.R));
     B->phase_ms[BIN_NAMES_HOST] = clk.lap();
     // ---- the result: CIGAR words written on the device where the result keeps them, mirrored to the host once
-    R->cig = cig_alloc((size_t)ncig + 1);
-    if (!R->cig) { ctx->err = "telr_bam_load: host CIGAR array"; return TELR_E_NOMEM; }
-    R->cap = (size_t)ncig + 1; R->ncig = (size_t)ncig;
-    if (hipMalloc(&R->d_cig, ((size_t)ncig + 1) * 4) != hipSuccess) { (void)hipGetLastError(); R->d_cig = nullptr; ctx->err = "telr_bam_load: device CIGAR array"; return TELR_E_NOMEM; }
-    R->d_cap = (size_t)ncig + 1;
+    TRY(bam_in_result_arrays(ctx, R.get(), ncig));
     if (nk) {
         int32_t *d_krec; int64_t *d_koff;
         TRY(ctx_buf_t(ctx, "bamin_krec", nk, &d_krec));
         TRY(ctx_buf_t(ctx, "bamin_koff", nk, &d_koff));
-        HIPCHK(hipMemcpyAsync(d_krec, kept_rec.data(), nk * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_koff, kept_off.data(), nk * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_krec, D.kept_rec.data(), nk * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_koff, D.kept_off.data(), nk * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_bam_cig, dim3((unsigned)((nk + 3) / 4)), dim3(256), 0, st, d_stream, d_recs, d_krec, d_koff, (int64_t)nk, R->d_cig);
         HIPCHK(hipGetLastError());
         if (ncig) HIPCHK(hipMemcpyAsync(R->cig, R->d_cig, (size_t)ncig * 4, hipMemcpyDeviceToHost, st));
@@ -746,7 +848,7 @@ extern "C" int telr_bam_load(telr_ctx *ctx, const char *path, int32_t keep_qual,
     R->twin_n = R->ncig; R->twin_off = false;
     // ---- the reads
     telr_seqset *S = new telr_seqset();
-    S->ctx = ctx; S->n = nq; S->len = rlen;
+    S->ctx = ctx; S->n = nq; S->len = D.rlen;
     TRY(seqset_alloc(ctx, S, "telr_bam_load", true, st));          // (frees S on failure)
     std::unique_ptr<telr_seqset, void (*)(telr_seqset*)> Sg(S, telr_seqset_free);
     if (nq) {
@@ -774,13 +876,19 @@ extern "C" int telr_bam_load(telr_ctx *ctx, const char *path, int32_t keep_qual,
     }
     HIPCHK(hipStreamSynchronize(st));
     B->phase_ms[BIN_SEQ] = clk.lap();
-    B->phase_ms[BIN_TOTAL] = wall.lap();
-    for (auto &s : B->tnames) B->tname_ptr.push_back(s.c_str());
-    for (auto &s : B->qnames) B->qname_ptr.push_back(s.c_str());
-    B->tname_ptr.push_back(nullptr); B->qname_ptr.push_back(nullptr);
-    B->set = Sg.release(); B->res = R.release();
+    B->phase_ms[BIN_TOTAL] = wall.lap() + H.ms;
+    bam_in_finish(B.get(), Sg.release(), R.release());
     *out = B.release();
     return TELR_OK;
+}
+extern "C" int telr_bam_load(telr_ctx *ctx, const char *path, int32_t keep_qual, telr_bam_in **out)
+{
+    (void)hipGetLastError();
+    if (!ctx) return TELR_E_ARG;
+    if (!path || !out) { ctx->err = "telr_bam_load: null path or output"; return TELR_E_ARG; }
+    BamInHop H;
+    TRY(bam_in_hop(ctx, "telr_bam_load", path, H));
+    return bam_load_whole(ctx, H, keep_qual, out);
 }
 
 extern "C" int32_t telr_bam_in_target_count(const telr_bam_in *in) { return in ? (int32_t)in->tnames.size() : 0; }
@@ -794,6 +902,7 @@ extern "C" telr_result *telr_bam_in_result(const telr_bam_in *in) { return in ? 
 extern "C" telr_seqset *telr_bam_in_detach_seqset(telr_bam_in *in) { if (!in || !in->set_owned) return nullptr; in->set_owned = false; return in->set; }
 extern "C" telr_result *telr_bam_in_detach_result(telr_bam_in *in) { if (!in || !in->res_owned) return nullptr; in->res_owned = false; return in->res; }
 extern "C" int telr_bam_in_counters(const telr_bam_in *in, int64_t *out) { if (!in || !out) return TELR_E_ARG; memcpy(out, in->counters, sizeof(in->counters)); return TELR_OK; }
+extern "C" int telr_bam_in_chunk_info(const telr_bam_in *in, int64_t *out) { if (!in || !out) return TELR_E_ARG; memcpy(out, in->chunk_info, sizeof(in->chunk_info)); return TELR_OK; }
 extern "C" int telr_bam_in_phase_ms(const telr_bam_in *in, float *out) { if (!in || !out) return TELR_E_ARG; memcpy(out, in->phase_ms, sizeof(in->phase_ms)); return TELR_OK; }
 // the reads as text: buf[off[q] .. off[q] + len[q]) = read q (A C G T N), off[q] = the bases before it; decoded on the device from the set
 extern "C" int telr_bam_in_ascii(const telr_bam_in *in, char *buf, int64_t *off)

@@ -1,0 +1,379 @@
+// bam_in_chunked.hip.h -- telr_bam_load_chunked: the load of bam_in.hip.h for a file of any size.  The file is cut into
+// chunks of whole BGZF members (bam_chunk_plan.h); every chunk is uploaded, inflated and parsed in turn, so that the transient device
+// memory depends on the chunk and not on the file.  The kernels are those of bam_in.hip.h; the result is the whole-file load's.
+//
+// Two passes.  Which records are kept and where their words and bases go depends on the whole file (a supplementary record may come
+// any number of chunks before its primary, the first name wins across chunks, orphans and len_mismatch need the primary's length):
+//   pass 1    per chunk: upload, k_bgzf_inflate, k_bam_chain_part, k_bam_rec, k_bam_names; fields and names go to the host, as in the
+//             whole-file load
+//   host      bam_in_decide: the same code as the whole-file load, on the same arrays
+//   pass 2    per chunk: upload and inflate again, then k_bam_cig, k_bam_seq_part, k_bam_qual_part straight into the final arrays at their
+//             final offsets.  The reads first met in one chunk have consecutive numbers: one contiguous stretch of the set's layout.
+// So every store position stays a scan's result or the lane's own index, there is no atomic and no provisional array to gather from;
+// the price is a second inflate.
+//
+// A chunk's buffer.  slot = [ room | the chunk's inflated members | 64 ].  The members are inflated to a fixed place behind `room`, so the
+// inflate of chunk k + 1 can run before chunk k's record chain has said how long the carry is; the carry -- the bytes of chunk k behind
+// its last complete record, or all of it while the header is incomplete -- is then copied to the END of the next slot's room and the
+// chunk's kernels see  buf = slot + room - carry,  carry + members bytes long.  A carry longer than the room (a record or a header
+// longer than a chunk grows it over several chunks) makes the slot grow; that is no error.  Offsets into `buf` are the same in both
+// passes: same carry, same members.
+//
+// Overlap.  Two slots.  Chunk k + 1 is uploaded and inflated on a second stream while chunk k is chained and parsed on the context's
+// stream; the host waits for chunk k's results at the end of every chunk (it needs them), which also orders the slots' reuse.
+#include "bam_chunk_plan.h"
+
+#define BAMC_AUTO_DIV  16               /* chunk_bytes 0: free device memory / 16 ... */
+#define BAMC_AUTO_MAX  (1LL << 30)      /* ... at most 1 GiB ... */
+#define BAMC_AUTO_MIN  (1LL << 20)      /* ... at least 1 MiB */
+#define BAMC_ROOM      (65536 - 64)     /* a slot's carry room is a multiple of this: with the 64 bytes behind the members a slot is never
+                                           more than 64 KiB above carry + members */
+
+struct BamChunkSlot {
+    char nm_file[32], nm_buf[32], nm_mem[32], nm_ooff[32], nm_status[32];
+    uint8_t *d_file = nullptr, *d_buf = nullptr;
+    size_t room = 0;
+    BgzfMember *d_mem = nullptr; int64_t *d_ooff = nullptr; int32_t *d_status = nullptr;
+    std::vector<BgzfMember> h_mem; std::vector<int64_t> h_ooff; std::vector<int32_t> h_status;      // alive while their copies may run
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;      // before the upload, behind it, behind the inflate
+};
+struct BamChunked {
+    telr_ctx *ctx; const BamInHop &H;
+    hipStream_t s_main, s_io;
+    std::vector<int64_t> first;          // [nch + 1] the chunks' first members
+    int64_t nch = 0;
+    size_t max_payload = 0, max_cbytes = 0, max_members = 0, max_alloc = 0;      // max_alloc: the largest slot buffer of the load
+    BamChunkSlot slot[2];
+    CrcTabs *d_tabs = nullptr;
+    hipEvent_t ec0 = nullptr, ec1 = nullptr;      // around a chunk's record chain
+    float ms_upload = 0, ms_inflate = 0, ms_chain = 0;
+    BamChunked(telr_ctx *c, const BamInHop &h) : ctx(c), H(h), s_main(c->stream), s_io(c->side[0]) {}
+    ~BamChunked()
+    {
+        (void)hipStreamSynchronize(s_io); (void)hipStreamSynchronize(s_main);      // nothing of a failed load is left running
+        for (BamChunkSlot &s : slot) for (hipEvent_t e : { s.e0, s.e1, s.e2 }) if (e) (void)hipEventDestroy(e);
+        if (ec0) (void)hipEventDestroy(ec0);
+        if (ec1) (void)hipEventDestroy(ec1);
+    }
+    int64_t payload(int64_t k) const { int64_t s = 0; for (int64_t m = first[(size_t)k]; m < first[(size_t)k + 1]; ++m) s += H.mem[(size_t)m].isize; return s; }
+};
+
+// a slot's carry room of at least `need` bytes; the `keep` bytes of members behind the room move with it
+static int bamc_room(BamChunked &C, BamChunkSlot &s, size_t need, size_t keep)
+{
+    telr_ctx *ctx = C.ctx;
+    if (s.room >= need && s.d_buf) return TELR_OK;
+    const size_t room = std::max<size_t>((need + BAMC_ROOM - 1) / BAMC_ROOM, 1) * BAMC_ROOM, bytes = room + C.max_payload + 64;
+    C.max_alloc = std::max(C.max_alloc, bytes);
+    HIPCHK(hipStreamSynchronize(C.s_io)); HIPCHK(hipStreamSynchronize(C.s_main));
+    DBuf &b = ctx->bufs[s.nm_buf];
+    void *p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    if (keep && s.d_buf) {
+        const hipError_t e = hipMemcpy((uint8_t*)p + room, s.d_buf + s.room, keep, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) { (void)hipFree(p); HIPCHK(e); }
+    }
+    if (b.p) HIPCHK(hipFree(b.p));
+    b.p = p; b.bytes = bytes;
+    s.d_buf = (uint8_t*)p; s.room = room;
+    return TELR_OK;
+}
+
+static int bamc_setup(BamChunked &C, int64_t chunk_bytes)
+{
+    telr_ctx *ctx = C.ctx;
+    const std::vector<BgzfMember> &mem = C.H.mem;
+    const int64_t nm = (int64_t)mem.size();
+    int64_t nch = 0;
+    int rc = bam_chunk_plan(nm, C.H.isz.data(), chunk_bytes, nullptr, 0, &nch);
+    if (rc != TELR_OK && rc != TELR_E_RANGE) { ctx->err = "telr_bam_load_chunked: chunk plan"; return rc; }
+    C.first.assign((size_t)nch + 1, nm);
+    if (nch) TRY(bam_chunk_plan(nm, C.H.isz.data(), chunk_bytes, C.first.data(), nch, &nch));
+    C.nch = nch;
+    for (int64_t k = 0; k < nch; ++k) {
+        const int64_t m0 = C.first[(size_t)k], m1 = C.first[(size_t)k + 1];
+        C.max_payload = std::max(C.max_payload, (size_t)C.payload(k));
+        C.max_cbytes = std::max(C.max_cbytes, (size_t)(mem[(size_t)m1 - 1].off + mem[(size_t)m1 - 1].clen - mem[(size_t)m0].off));
+        C.max_members = std::max(C.max_members, (size_t)(m1 - m0));
+    }
+    for (int i = 0; i < 2; ++i) {
+        BamChunkSlot &s = C.slot[i];
+        snprintf(s.nm_file, sizeof(s.nm_file), "bamin_c%d_file", i); snprintf(s.nm_buf, sizeof(s.nm_buf), "bamin_c%d_buf", i);
+        snprintf(s.nm_mem, sizeof(s.nm_mem), "bamin_c%d_mem", i); snprintf(s.nm_ooff, sizeof(s.nm_ooff), "bamin_c%d_ooff", i);
+        snprintf(s.nm_status, sizeof(s.nm_status), "bamin_c%d_status", i);
+        TRY(ctx_buf_t(ctx, s.nm_file, ((C.max_cbytes + 3) & ~(size_t)3) + BGZF_INCH + 16, &s.d_file));
+        TRY(ctx_buf_t(ctx, s.nm_mem, C.max_members + 1, &s.d_mem));
+        TRY(ctx_buf_t(ctx, s.nm_ooff, C.max_members + 1, &s.d_ooff));
+        TRY(ctx_buf_t(ctx, s.nm_status, C.max_members + 1, &s.d_status));
+        // (the buffer of an earlier load is not taken over: its room and its members' place are this load's)
+        s.d_buf = nullptr; s.room = 0;
+        TRY(bamc_room(C, s, 0, 0));
+        HIPCHK(hipEventCreate(&s.e0)); HIPCHK(hipEventCreate(&s.e1)); HIPCHK(hipEventCreate(&s.e2));
+    }
+    HIPCHK(hipEventCreate(&C.ec0)); HIPCHK(hipEventCreate(&C.ec1));
+    TRY(ctx_buf_t(ctx, "bamin_crctabs", 1, &C.d_tabs));
+    { static CrcTabs T; static bool made = false; if (!made) { crc_tabs_make(T); made = true; } HIPCHK(hipMemcpyAsync(C.d_tabs, &T, sizeof(T), hipMemcpyHostToDevice, C.s_main)); }
+    HIPCHK(hipStreamSynchronize(C.s_main));
+    return TELR_OK;
+}
+
+// chunk k: its slice of the file and its member table (offsets relative to the slice) go up, its members are inflated behind the slot's room
+static int bamc_issue(BamChunked &C, int64_t k)
+{
+    telr_ctx *ctx = C.ctx;
+    BamChunkSlot &s = C.slot[k & 1];
+    const std::vector<BgzfMember> &mem = C.H.mem;
+    const int64_t m0 = C.first[(size_t)k], m1 = C.first[(size_t)k + 1], n = m1 - m0;
+    const int64_t f0 = mem[(size_t)m0].off, f1 = mem[(size_t)m1 - 1].off + mem[(size_t)m1 - 1].clen;
+    s.h_mem.assign(mem.begin() + m0, mem.begin() + m1); s.h_ooff.resize((size_t)n); s.h_status.resize((size_t)n);
+    int64_t o = 0;
+    for (int64_t j = 0; j < n; ++j) { s.h_mem[(size_t)j].off -= f0; s.h_ooff[(size_t)j] = o; o += s.h_mem[(size_t)j].isize; }
+    const size_t cb = (size_t)(f1 - f0);
+    HIPCHK(hipEventRecord(s.e0, C.s_io));
+    if (cb) HIPCHK(hipMemcpyAsync(s.d_file, C.H.F.p + f0, cb, hipMemcpyHostToDevice, C.s_io));
+    HIPCHK(hipMemsetAsync(s.d_file + cb, 0, ((cb + 3) & ~(size_t)3) - cb + BGZF_INCH + 16, C.s_io));
+    HIPCHK(hipMemcpyAsync(s.d_mem, s.h_mem.data(), (size_t)n * sizeof(BgzfMember), hipMemcpyHostToDevice, C.s_io));
+    HIPCHK(hipMemcpyAsync(s.d_ooff, s.h_ooff.data(), (size_t)n * 8, hipMemcpyHostToDevice, C.s_io));
+    HIPCHK(hipMemsetAsync(s.d_buf + s.room + o, 0, 64, C.s_io));
+    HIPCHK(hipEventRecord(s.e1, C.s_io));
+    hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)n), dim3(64), 0, C.s_io, s.d_file, s.d_mem, s.d_ooff, C.d_tabs, s.d_buf + s.room, s.d_status);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(s.h_status.data(), s.d_status, (size_t)n * 4, hipMemcpyDeviceToHost, C.s_io));
+    HIPCHK(hipEventRecord(s.e2, C.s_io));
+    return TELR_OK;
+}
+// chunk k is inflated; the lowest block that failed is the error (its number is the file's)
+static int bamc_wait(BamChunked &C, int64_t k)
+{
+    telr_ctx *ctx = C.ctx;
+    BamChunkSlot &s = C.slot[k & 1];
+    HIPCHK(hipEventSynchronize(s.e2));
+    float a = 0, b = 0;
+    HIPCHK(hipEventElapsedTime(&a, s.e0, s.e1)); HIPCHK(hipEventElapsedTime(&b, s.e1, s.e2));
+    C.ms_upload += a; C.ms_inflate += b;
+    for (size_t j = 0; j < s.h_status.size(); ++j)
+        if (s.h_status[j] != INFL_OK) { ctx->err = "telr_bam_load: block " + std::to_string(C.first[(size_t)k] + (int64_t)j) + ": " + infl_text(s.h_status[j]); return TELR_E_ARG; }
+    return TELR_OK;
+}
+// the `len` bytes at src (chunk k's buffer) become chunk k + 1's carry: the end of its slot's room
+static int bamc_carry(BamChunked &C, int64_t k, const uint8_t *src, int64_t len)
+{
+    telr_ctx *ctx = C.ctx;
+    BamChunkSlot &d = C.slot[(k + 1) & 1];
+    TRY(bamc_room(C, d, (size_t)len, (size_t)C.payload(k + 1)));
+    if (len) HIPCHK(hipMemcpyAsync(d.d_buf + d.room - len, src, (size_t)len, hipMemcpyDeviceToDevice, C.s_main));
+    HIPCHK(hipStreamSynchronize(C.s_main));
+    return TELR_OK;
+}
+
+static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual, int64_t chunk_bytes, telr_bam_in **out)
+{
+    BamInClock wall, clk;
+    std::unique_ptr<telr_bam_in, void (*)(telr_bam_in*)> B(new telr_bam_in(), telr_bam_in_free);
+    B->ctx = ctx;
+    B->counters[0] = (int64_t)H.mem.size(); B->counters[8] = H.no_eof;
+    B->phase_ms[BIN_HOP] = H.ms;
+    HIPCHK(hipSetDevice(ctx->device));
+    BamChunked C(ctx, H);
+    TRY(bamc_setup(C, chunk_bytes));
+    hipStream_t st = C.s_main;
+    const int64_t nch = C.nch, nrun = std::max<int64_t>(nch, 1);      // (a file without members: one empty chunk, for the header's error)
+    // ---- pass 1: every chunk's records and names
+    std::vector<BamRec> recs; std::vector<int64_t> noff(1, 0), noff_k; std::vector<char> names;
+    std::vector<int64_t> rec0((size_t)nrun + 1, 0), carry_in((size_t)nrun + 1, 0), cut((size_t)nrun, 0);
+    bool hdr = false;
+    int64_t carry = 0, max_carry = 0;
+    int32_t n_ref = 0;
+    float ms_parse = 0;
+    if (nch) TRY(bamc_issue(C, 0));
+    for (int64_t k = 0; k < nrun; ++k) {
+        const bool last = k + 1 >= nrun;
+        if (nch) TRY(bamc_wait(C, k));
+        BamChunkSlot &s = C.slot[k & 1];
+        const int64_t buflen = carry + (nch ? C.payload(k) : 0);
+        uint8_t *buf = s.d_buf + s.room - carry;
+        carry_in[(size_t)k] = carry; max_carry = std::max(max_carry, carry);
+        int64_t from = 0;
+        if (!hdr) {
+            // the header: small, parsed on the host; incomplete in a chunk that is not the last: the whole buffer is carried on
+            std::vector<uint8_t> h;
+            int64_t have = std::min<int64_t>(buflen, 1 << 16), need = 0;
+            for (;;) {
+                h.resize((size_t)have + 1);
+                if (have) HIPCHK(hipMemcpy(h.data(), buf, (size_t)have, hipMemcpyDeviceToHost));
+                const int rc = bam_in_header(ctx, h.data(), have, last ? buflen : INT64_MAX / 2, B.get(), &from, &need);
+                if (rc == TELR_OK) { hdr = true; break; }
+                if (rc != 1) return rc;
+                if (have == buflen) break;
+                have = std::min<int64_t>(buflen, std::max<int64_t>(need, have * 4));
+            }
+            n_ref = (int32_t)B->tnames.size();
+        }
+        int64_t nrec_k = 0, p_end = 0, *d_offs = nullptr, *d_res = nullptr;
+        if (hdr) {
+            const int64_t cap = (buflen - from) / 36 + 1;
+            TRY(ctx_buf_t(ctx, "bamin_offs", (size_t)cap + 1, &d_offs));
+            TRY(ctx_buf_t(ctx, "bamin_res", 3, &d_res));
+            HIPCHK(hipEventRecord(C.ec0, st));
+            hipLaunchKernelGGL(k_bam_chain_part, dim3(1), dim3(64), 0, st, buf, buflen, from, d_offs, cap, d_res);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(C.ec1, st));
+        }
+        if (k + 1 < nch) TRY(bamc_issue(C, k + 1));          // (the host is busy with the upload while the chain walks)
+        if (hdr) {
+            int64_t res[3] = {0, 0, 0};
+            HIPCHK(hipMemcpyAsync(res, d_res, 24, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            float ms = 0; HIPCHK(hipEventElapsedTime(&ms, C.ec0, C.ec1)); C.ms_chain += ms;
+            clk.lap();
+            const int64_t base = rec0[(size_t)k];
+            if (res[1] == 1 && last) { ctx->err = "telr_bam_load: record " + std::to_string(base + res[0]) + ": runs past the stream"; return TELR_E_ARG; }
+            if (res[1] == 2) { ctx->err = "telr_bam_load: record " + std::to_string(base + res[0]) + ": block_size below 32"; return TELR_E_ARG; }
+            if (res[1] == 3 || base + res[0] >= 0x7ffffff0LL) { ctx->err = "telr_bam_load: too many records"; return TELR_E_RANGE; }
+            nrec_k = res[0]; p_end = res[2];
+            if (nrec_k) {
+                BamRec *d_recs; int32_t *d_nlen; int64_t *d_noff, *d_ntot; uint8_t *d_names; int64_t ntot = 0;
+                TRY(ctx_buf_t(ctx, "bamin_recs", (size_t)nrec_k, &d_recs));
+                TRY(ctx_buf_t(ctx, "bamin_nlen", (size_t)nrec_k + 1, &d_nlen));
+                TRY(ctx_buf_t(ctx, "bamin_noff", (size_t)nrec_k + 2, &d_noff));
+                TRY(ctx_buf_t(ctx, "bamin_ntot", 2, &d_ntot));
+                const dim3 grid((unsigned)((nrec_k + 3) / 4));
+                hipLaunchKernelGGL(k_bam_rec, grid, dim3(256), 0, st, buf, d_offs, nrec_k, n_ref, d_recs, d_nlen);
+                HIPCHK(hipGetLastError());
+                TRY((dev_qscan<int32_t, int64_t>(ctx, d_nlen, (int32_t)nrec_k, d_noff, d_ntot, 0, nullptr, nullptr)));
+                HIPCHK(hipMemcpyAsync(&ntot, d_ntot, 8, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                TRY(ctx_buf_t(ctx, "bamin_names", (size_t)ntot + 1, &d_names));
+                hipLaunchKernelGGL(k_bam_names, grid, dim3(256), 0, st, buf, d_offs, nrec_k, d_nlen, d_noff, d_names);
+                HIPCHK(hipGetLastError());
+                const size_t nb = names.size();
+                recs.resize((size_t)(base + nrec_k)); noff_k.resize((size_t)nrec_k + 1); names.resize(nb + (size_t)ntot);
+                HIPCHK(hipMemcpyAsync(recs.data() + base, d_recs, (size_t)nrec_k * sizeof(BamRec), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(noff_k.data(), d_noff, ((size_t)nrec_k + 1) * 8, hipMemcpyDeviceToHost, st));
+                if (ntot) HIPCHK(hipMemcpyAsync(names.data() + nb, d_names, (size_t)ntot, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                for (int64_t i = 1; i <= nrec_k; ++i) noff.push_back((int64_t)nb + noff_k[(size_t)i]);
+                TRY(bam_in_rec_fault(ctx, recs.data() + base, nrec_k, base));
+            }
+            ms_parse += clk.lap();
+        }
+        rec0[(size_t)k + 1] = rec0[(size_t)k] + nrec_k;
+        cut[(size_t)k] = p_end;
+        carry = buflen - p_end;
+        if (!last) TRY(bamc_carry(C, k, buf + p_end, carry));
+    }
+    B->phase_ms[BIN_CHAIN] = C.ms_chain; B->phase_ms[BIN_PARSE] = ms_parse;
+    // ---- host: names -> read numbers; which records are kept, and where (the whole-file load's code)
+    clk.lap();
+    names.push_back(0);
+    BamInDecided D;
+    TRY(bam_in_decide(ctx, B.get(), recs, names, noff, D));
+    const int32_t nq = (int32_t)D.reads.size();
+    const size_t nk = D.kept_rec.size();
+    std::unique_ptr<telr_result> R(std::move(D.R));
+    std::vector<size_t> order(nk);                             // the kept records in file order: chunk by chunk
+    for (size_t i = 0; i < nk; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return D.kept_rec[a] < D.kept_rec[b]; });
+    B->phase_ms[BIN_NAMES_HOST] = clk.lap();
+    // ---- the result's arrays and the set, final from the start
+    TRY(bam_in_result_arrays(ctx, R.get(), D.ncig));
+    telr_seqset *S = new telr_seqset();
+    S->ctx = ctx; S->n = nq; S->len = D.rlen;
+    TRY(seqset_alloc(ctx, S, "telr_bam_load", true, st));          // (frees S on failure)
+    std::unique_ptr<telr_seqset, void (*)(telr_seqset*)> Sg(S, telr_seqset_free);
+    const bool with_qual = nq && keep_qual && !D.any_ff;
+    if (with_qual) {
+        HIPCHK(hipMalloc(&S->d_qual, (size_t)S->padded_bases + 64));
+        HIPCHK(hipMemsetAsync(S->d_qual + S->padded_bases, 0, 64, st));
+    }
+    // ---- pass 2: inflate again; the kept records' words and the reads' bases go where they stay
+    int64_t passes = 1;
+    if (nq || nk) {
+        passes = 2;
+        for (BamChunkSlot &s : C.slot) TRY(bamc_room(C, s, (size_t)max_carry, 0));
+        std::vector<BamRec> h_recs; std::vector<int32_t> h_idx, h_over; std::vector<int64_t> h_off; std::vector<BamRead> h_reads;
+        size_t ki = 0; int32_t q = 0;
+        TRY(bamc_issue(C, 0));
+        for (int64_t k = 0; k < nch; ++k) {
+            TRY(bamc_wait(C, k));
+            BamChunkSlot &s = C.slot[k & 1];
+            const uint8_t *buf = s.d_buf + s.room - carry_in[(size_t)k];
+            const int64_t r0 = rec0[(size_t)k], r1 = rec0[(size_t)k + 1];
+            h_recs.clear(); h_idx.clear(); h_off.clear();
+            for (; ki < nk && D.kept_rec[order[ki]] < r1; ++ki) {
+                h_idx.push_back((int32_t)h_recs.size()); h_recs.push_back(recs[(size_t)D.kept_rec[order[ki]]]); h_off.push_back(D.kept_off[order[ki]]);
+            }
+            if (!h_recs.empty()) {
+                const size_t n = h_recs.size();
+                BamRec *d_recs; int32_t *d_krec; int64_t *d_koff;
+                TRY(ctx_buf_t(ctx, "bamin_recs", n, &d_recs));
+                TRY(ctx_buf_t(ctx, "bamin_krec", n, &d_krec));
+                TRY(ctx_buf_t(ctx, "bamin_koff", n, &d_koff));
+                HIPCHK(hipMemcpyAsync(d_recs, h_recs.data(), n * sizeof(BamRec), hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(d_krec, h_idx.data(), n * 4, hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(d_koff, h_off.data(), n * 8, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(k_bam_cig, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, buf, d_recs, d_krec, d_koff, (int64_t)n, R->d_cig);
+                HIPCHK(hipGetLastError());
+            }
+            const int32_t q0 = q;
+            while (q < nq && D.first_rec[(size_t)q] < r1) ++q;
+            const int32_t nqk = q - q0;
+            int32_t *d_over = nullptr;
+            if (nqk) {
+                BamRead *d_reads;
+                TRY(ctx_buf_t(ctx, "bamin_reads", (size_t)nqk, &d_reads));
+                HIPCHK(hipMemcpyAsync(d_reads, D.reads.data() + q0, (size_t)nqk * sizeof(BamRead), hipMemcpyHostToDevice, st));
+                const int64_t b0 = S->boff[(size_t)q0], b1 = S->boff[(size_t)q];
+                hipLaunchKernelGGL(k_bam_seq_part, grid256((b1 - b0) / 16), dim3(256), 0, st, buf, d_reads, S->d_boff + q0, nqk, b0 / 16, b1 / 16, S->d_seq2, S->d_nmask);
+                HIPCHK(hipGetLastError());
+                if (with_qual) {
+                    TRY(ctx_buf_t(ctx, "bamin_over", (size_t)nqk, &d_over));
+                    HIPCHK(hipMemsetAsync(d_over, 0, (size_t)nqk * 4, st));
+                    hipLaunchKernelGGL(k_bam_qual_part, grid256((b1 - b0) / 4), dim3(256), 0, st, buf, d_reads, S->d_boff + q0, nqk, b0 / 4, b1 / 4, (uint32_t*)S->d_qual, d_over);
+                    HIPCHK(hipGetLastError());
+                    h_over.resize((size_t)nqk);
+                    HIPCHK(hipMemcpyAsync(h_over.data(), d_over, (size_t)nqk * 4, hipMemcpyDeviceToHost, st));
+                }
+            }
+            if (k + 1 < nch) TRY(bamc_issue(C, k + 1));
+            HIPCHK(hipStreamSynchronize(st));
+            if (d_over)          // (reads are numbered in file order of their records: the first one found is the lowest record)
+                for (int32_t j = 0; j < nqk; ++j) if (h_over[(size_t)j]) {
+                    ctx->err = "telr_bam_load: record " + std::to_string(D.first_rec[(size_t)(q0 + j)]) + ": a base quality above 93"; return TELR_E_ARG;
+                }
+            if (k + 1 < nch) TRY(bamc_carry(C, k, buf + cut[(size_t)k], carry_in[(size_t)k + 1]));
+        }
+        if (D.ncig) HIPCHK(hipMemcpyAsync(R->cig, R->d_cig, (size_t)D.ncig * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    R->twin_n = R->ncig; R->twin_off = false;
+    B->phase_ms[BIN_SEQ] = clk.lap();
+    B->phase_ms[BIN_UPLOAD] = C.ms_upload; B->phase_ms[BIN_INFLATE] = C.ms_inflate;
+    B->phase_ms[BIN_TOTAL] = wall.lap() + H.ms;
+    B->chunk_info[0] = nch; B->chunk_info[1] = passes; B->chunk_info[2] = (int64_t)C.max_alloc; B->chunk_info[3] = max_carry;
+    bam_in_finish(B.get(), Sg.release(), R.release());
+    *out = B.release();
+    return TELR_OK;
+}
+
+extern "C" int telr_bam_chunk_plan(int64_t n_members, const int32_t *isize, int64_t chunk_bytes, int64_t *first_member_of_chunk, int64_t cap, int64_t *n_chunks)
+{
+    return bam_chunk_plan(n_members, isize, chunk_bytes, first_member_of_chunk, cap, n_chunks);
+}
+
+extern "C" int telr_bam_load_chunked(telr_ctx *ctx, const char *path, int32_t keep_qual, int64_t chunk_bytes, telr_bam_in **out)
+{
+    (void)hipGetLastError();
+    if (!ctx) return TELR_E_ARG;
+    if (!path || !out) { ctx->err = "telr_bam_load_chunked: null path or output"; return TELR_E_ARG; }
+    if (chunk_bytes < TELR_BAM_CHUNK_FIT) { ctx->err = "telr_bam_load_chunked: chunk_bytes below TELR_BAM_CHUNK_FIT"; return TELR_E_ARG; }
+    BamInHop H;
+    TRY(bam_in_hop(ctx, "telr_bam_load", path, H));
+    if (chunk_bytes <= 0) {
+        int64_t fr = 0;
+        TRY(telr_device_mem(ctx, &fr, nullptr));
+        if (chunk_bytes == TELR_BAM_CHUNK_FIT && (int64_t)H.F.n + H.total < fr / 2) return bam_load_whole(ctx, H, keep_qual, out);
+        chunk_bytes = std::min<int64_t>(std::max<int64_t>(fr / BAMC_AUTO_DIV, BAMC_AUTO_MIN), BAMC_AUTO_MAX);
+    }
+    return bam_load_chunked(ctx, H, keep_qual, chunk_bytes, out);
+}

@@ -3169,5 +3169,6 @@ extern "C" int telr_seqset_attach_qual(telr_ctx *ctx, telr_seqset *s, const char
 #include "draft.hip.h"
 #include "refte.hip.h"
 #include "bam_in.hip.h"
+#include "bam_in_chunked.hip.h"
 #include "seq_extract.hip.h"
 #include "part_merge.hip.h"

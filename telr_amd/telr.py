@@ -9,7 +9,10 @@ here; the flow is that of its `main` (src/telr/telr.py:22-189) with this project
     stage-1 index              Engine.index with the aligner's preset (`--aligner nglmr`: ngmlr-ont / ngmlr-pacbio, `minimap2`: map-ont / map-pb)
     reads route                fasta.load -> Engine.seqset -> Index.map_raw (TELR_MF_CIGAR | TELR_MF_KEEP_CIGARS) -> the sorted BAM + .bai
                                with the device writer into <out>/intermediate_files/<sample>_sort.bam
-    BAM route (`-i x.bam`)     Engine.load_bam, BamInput.check_targets against the reference
+    BAM route (`-i x.bam`)     Engine.load_bam, BamInput.check_targets against the reference.  `--bam_chunk_mb N`: in chunks of N MiB of
+                               inflated bytes (a file of any size); 0 (the default): the whole file at once when it and
+                               its inflated stream fit into half the free device memory, else in chunks of the engine's own size --
+                               one hop of the member headers decides and is handed on.  The outputs do not depend on the choice.
     calls                      telr_sv.call_insertions(..., reads=<the resident set>, genotype=True)      (not Sniffles)
     drafts                     telr_assembly.draft_loci(..., reads=<the resident set>)                     (not wtdbg2 / flye)
     asm10 index                Engine.index over the same resident reference
@@ -89,6 +92,8 @@ def get_args(argv=None):
                      "RepeatMasker) or a BED6 file with the columns RepeatMasker's GFF gives (default = 'none')")
     own.add_argument("--index_part_bases", type=int, default=0, help="cut the reference into index parts of at most N bases (padded extent) and merge the "
                      "per-part records on the device; 0: one index, parts only when the reference does not fit one (default = 0)")
+    own.add_argument("--bam_chunk_mb", type=int, default=0, help="load a BAM of reads in chunks of at most N MiB of inflated bytes; 0: the whole file at once "
+                     "when it fits into half the free device memory next to its inflated stream, else chunks of the engine's own size (default = 0)")
     own.add_argument("--sample", type=str, help="sample name (default: the reads file's name without its extension)")
     p._action_groups.append(opt)
     a = p.parse_args(argv)
@@ -141,6 +146,8 @@ def get_args(argv=None):
         _exit("Please provide a valid device number, exiting...")
     if a.index_part_bases < 0:
         _exit("Please provide a valid number of bases per index part (0 or a positive integer), exiting...")
+    if a.bam_chunk_mb < 0:
+        _exit("Please provide a valid BAM chunk size in MiB (0 or a positive integer), exiting...")
     if (a.chain_skip or a.seed_rescue or a.mm2_mapq) and a.aligner != "minimap2":
         _exit("--chain_skip, --seed_rescue and --mm2_mapq are options of the minimap2 aligner, exiting...")
     a.out = os.path.abspath("." if a.out is None else a.out)
@@ -219,7 +226,8 @@ def load_reads(eng, ix, args, tnames, bam_path):
 
 def load_bam(eng, ix, args, tnames, tlens):
     """the BAM route: the file inflated and parsed on the device, its references checked against the reference's -> the same four"""
-    bi = eng.load_bam(args.reads, keep_qual=args.keep_qual)
+    from .aligner import BAM_CHUNK_FIT
+    bi = eng.load_bam(args.reads, keep_qual=args.keep_qual, chunk_bytes=args.bam_chunk_mb << 20 if args.bam_chunk_mb > 0 else BAM_CHUNK_FIT)
     try:
         bi.check_targets(tnames, tlens)
     except BaseException:

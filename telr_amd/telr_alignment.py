@@ -40,14 +40,15 @@ def wait_release():
 atexit.register(wait_release)
 
 
-def bam_input(bam, out, sample_name, engine=None, index=None, keep_qual=False):
+def bam_input(bam, out, sample_name, engine=None, index=None, keep_qual=False, chunk_bytes=None):
     """The `.bam` branch of parse_input (TELR_input.py:300-305, 329-361): the alignment is skipped and the reads come out of the BAM.
     The file is loaded on the device (Engine.load_bam); <out>/<sample_name>.telr.fasta is written as bam2fasta writes it (first
     record of a name wins) and the BamInput is returned: its read_set and result are what alignment() + a re-read of the BAM would
     have left on the device.  index: an Index whose targets the file's references must equal (names, lengths, order; ValueError).
-    A coordinate-sorted file needs no sort_index_bam; another order is accepted as it is."""
+    A coordinate-sorted file needs no sort_index_bam; another order is accepted as it is.  chunk_bytes: as Engine.load_bam takes it
+    (None: the whole file at once; 0 or n: in chunks, a file of any size)."""
     eng = engine or (index.eng if index is not None else Engine(0))
-    bi = eng.load_bam(bam, keep_qual=keep_qual)
+    bi = eng.load_bam(bam, keep_qual=keep_qual, chunk_bytes=chunk_bytes)
     if index is not None:
         names = getattr(index, "tnames", None)
         if names is not None:
