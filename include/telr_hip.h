@@ -761,6 +761,50 @@ int  telr_bam_in_ascii(const telr_bam_in *in, char *buf, int64_t *off);
  * overlap with the others, so total (wall clock) is no longer the sum of the rest */
 int  telr_bam_in_phase_ms(const telr_bam_in *in, float *out /* [8] */);
 
+/* ---- a FASTA / FASTQ file -- plain, gzip or BGZF -- as a read set, parsed and packed on the device (opt-in).  The
+ *      text is never held as host text: it goes to the device in chunks (inflated there for BGZF, by one host thread running zlib for
+ *      gzip) and becomes names, lengths, 2-bit words, mask words and Phred bytes in the set's layout.  tests/reads_in_ref.py states
+ *      the definition in plain Python.
+ * Container, by content: BGZF -- the file opens 1f 8b 08 and telr_bam_load's framing accepts the whole file (every member a BC subfield
+ *      and ISIZE <= 65,536; empty members anywhere; no EOF marker: no_eof = 1, accepted); gzip -- any other file that opens 1f 8b: one
+ *      or several RFC 1952 members of any size, zlib checks each CRC and ISIZE; plain -- a file that opens '@' or '>'; an empty file is
+ *      an empty set; anything else TELR_E_ARG.
+ * Text:  lines end in "\n", the last one may lack it; one "\r" directly before the "\n", or at the end of the text, belongs to the
+ *      terminator.  The first byte decides the kind.  FASTQ ('@'): lines in fours -- line 4k starts with '@', line 4k + 1 holds the
+ *      bases, line 4k + 2 starts with '+' (the rest of it is ignored), line 4k + 3 holds as many quality characters; anything else
+ *      (an empty line where '@' is due, a trailing empty line, a record on more lines, 1 - 3 lines at the end) is TELR_E_ARG naming
+ *      the lowest offending record.  FASTA ('>'): a line that starts with '>' opens a record, every other line adds its bytes without
+ *      the terminator, an empty line adds nothing, a header alone is a record of length 0.  A name: the bytes behind the '@' / '>' up
+ *      to the first space, tab, "\r" or the line's end; it may be empty.  Bases as in telr_seqset_create: A C G T U in either case are
+ *      codes 0 1 2 3 3, any other byte sets the mask bit and has code 0, padding up to 64 bases has code 0 and mask 0.
+ * Qualities:  keep_qual on a FASTQ: the set carries byte - 33; a character outside 33 .. 126 is TELR_E_ARG naming the lowest record.
+ *      Without keep_qual only the quality line's length is checked.  A FASTA with keep_qual gives a set without qualities.
+ * Limits:  a record above INT32_MAX bases, or 2^31 - 16 records or more: TELR_E_RANGE.
+ * Errors:  every text opens with "telr_reads_load:"; "record N: ..." for grammar and qualities (the lowest record; in one record
+ *      grammar first), "block K: ..." for a BGZF member (telr_bam_load's texts), "gzip: ..." for what zlib reports.  They are found in
+ *      chunk order; a file with one fault gives the same code and text at every chunk_bytes.  A failed load leaves nothing allocated
+ *      beyond the context's scratch.
+ * Chunks:  chunk_bytes: n > 0 that many bytes of text at the most (BGZF: telr_bam_chunk_plan over the members' ISIZE; gzip and plain:
+ *      consecutive chunk_bytes of text, of which those below 4 KiB that close no record are gathered on the host up to 4 KiB);
+ *      0 the engine's own size, as in telr_bam_load_chunked; negative: TELR_E_ARG.  The result does not depend on it.  One pass: each
+ *      chunk's words are written as a piece and the pieces are copied end to end into the set at the end, so the transient device
+ *      memory is one more copy of the finished set's arrays (with keep_qual that includes a byte per base) plus two chunk slots.
+ * counters: container (0 plain, 1 gzip, 2 BGZF), fastq (1 / 0), members (BGZF or gzip members; 0 for plain), text_bytes, lines,
+ *      records, bases, no_eof.  chunk_info: chunks, the largest chunk buffer (bytes), the largest carry, peak transient device bytes.
+ *      phase_ms: host hop, upload, inflate (gzip: the zlib thread's time), lines, records, names, pack, join, total (wall clock; upload
+ *      and inflate overlap with the rest). */
+typedef struct telr_reads_in telr_reads_in;
+int  telr_reads_load(telr_ctx *ctx, const char *path, int32_t keep_qual, int64_t chunk_bytes, telr_reads_in **out);
+void telr_reads_in_free(telr_reads_in *in);
+int32_t telr_reads_in_count(const telr_reads_in *in);
+const char *const *telr_reads_in_names(const telr_reads_in *in);
+const int32_t *telr_reads_in_lens(const telr_reads_in *in);
+telr_seqset *telr_reads_in_seqset(const telr_reads_in *in);
+telr_seqset *telr_reads_in_detach_seqset(telr_reads_in *in);      /* NULL when detached before */
+int  telr_reads_in_counters(const telr_reads_in *in, int64_t *out /* [8] */);
+int  telr_reads_in_chunk_info(const telr_reads_in *in, int64_t *out /* [4] */);
+int  telr_reads_in_phase_ms(const telr_reads_in *in, float *out /* [9] */);
+
 /* ---- window reads (a12) -------------------------------------------------------
  * Replaces the per-locus `pysam.AlignmentFile(bam).fetch(chr, bp-1000, bp+1000)` loop of prep_assembly_inputs
  * (src/telr/TELR_assembly.py:384-415, read_type="all"): for every window w = (win_tid, [win_lo, win_hi)) the ascending,

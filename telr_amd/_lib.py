@@ -26,6 +26,8 @@ EXPORTS = [
     "telr_bam_in_read_names", "telr_bam_in_read_lens", "telr_bam_in_seqset", "telr_bam_in_result", "telr_bam_in_detach_seqset", "telr_bam_in_detach_result",
     "telr_bam_in_counters", "telr_bam_in_ascii", "telr_bam_in_phase_ms", "telr_bam_load_chunked", "telr_bam_chunk_plan", "telr_bam_in_chunk_info",
     "telr_seqset_extract", "telr_seqset_pieces",
+    "telr_reads_load", "telr_reads_in_free", "telr_reads_in_count", "telr_reads_in_names", "telr_reads_in_lens", "telr_reads_in_seqset", "telr_reads_in_detach_seqset",
+    "telr_reads_in_counters", "telr_reads_in_chunk_info", "telr_reads_in_phase_ms",
     "telr_part_plan", "telr_part_plan_error", "telr_merge_parts", "telr_write_bam_dev_targets",
     "telr_tile_plan", "telr_refte_opt_default", "telr_annotate_hits", "telr_te_feats_count", "telr_te_feats_data", "telr_te_feats_free",
 ]
@@ -120,6 +122,13 @@ def lib():
     L.telr_bam_load_chunked.restype = C.c_int; L.telr_bam_load_chunked.argtypes = [vp, cp, i32, i64, C.POINTER(vp)]
     L.telr_bam_chunk_plan.restype = C.c_int; L.telr_bam_chunk_plan.argtypes = [i64, vp, i64, vp, i64, C.POINTER(i64)]
     L.telr_bam_in_chunk_info.restype = C.c_int; L.telr_bam_in_chunk_info.argtypes = [vp, vp]
+    L.telr_reads_load.restype = C.c_int; L.telr_reads_load.argtypes = [vp, cp, i32, i64, C.POINTER(vp)]
+    L.telr_reads_in_free.restype = None; L.telr_reads_in_free.argtypes = [vp]
+    L.telr_reads_in_count.restype = i32; L.telr_reads_in_count.argtypes = [vp]
+    for fn in ("telr_reads_in_names", "telr_reads_in_lens", "telr_reads_in_seqset", "telr_reads_in_detach_seqset"):
+        getattr(L, fn).restype = vp; getattr(L, fn).argtypes = [vp]
+    for fn in ("telr_reads_in_counters", "telr_reads_in_chunk_info", "telr_reads_in_phase_ms"):
+        getattr(L, fn).restype = C.c_int; getattr(L, fn).argtypes = [vp, vp]
     L.telr_debug_bgzf_inflate.restype = C.c_int; L.telr_debug_bgzf_inflate.argtypes = [vp, cp, vp, i64, C.POINTER(i64)]
     L.telr_debug_seqset_qual.restype = i64; L.telr_debug_seqset_qual.argtypes = [vp, vp, i64]
     L.telr_window_reads.restype = C.c_int; L.telr_window_reads.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, i64, vp]

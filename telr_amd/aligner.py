@@ -121,6 +121,12 @@ class Engine:
         BAM_CHUNK_FIT = the whole file when it fits into half the free device memory, else as 0"""
         return BamInput(self, path, keep_qual, chunk_bytes)
 
+    def load_reads(self, path, keep_qual=False, chunk_bytes=0):
+        """a FASTA / FASTQ file -- plain, gzip or BGZF, decided by content -- as a resident read set, parsed and packed on the device
+        in chunks (telr_reads_load; include/telr_hip.h has the definition) -> ReadsInput.  keep_qual: a FASTQ's qualities stay with
+        the set.  chunk_bytes: at most that many bytes of text per chunk, 0 = the engine's own size; the result does not depend on it"""
+        return ReadsInput(self, path, keep_qual, chunk_bytes)
+
     def stage_ms(self):
         a = np.zeros(N_STAGES, np.float32)
         self.L.telr_stage_ms(self.h, a.ctypes.data)
@@ -550,6 +556,54 @@ class BamInput:
             self.eng.L.telr_result_free(self.result); self.result = None
         if getattr(self, "h", None):
             self.eng.L.telr_bam_in_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ReadsInput:
+    """what Engine.load_reads returns: read_set (a SeqSet resident on the device, qualities attached when kept), qnames (list of str),
+    names_c (the C array of names for the writers, valid while this object lives), n_bases, kind ("fastq", "fasta", or None for an
+    empty text), container ("plain", "gzip", "bgzf"), counters, chunk_info and phase_ms (dicts)"""
+    COUNTERS = ("container", "fastq", "members", "text_bytes", "lines", "records", "bases", "no_eof")
+    CHUNK_INFO = ("chunks", "largest_buffer", "largest_carry", "peak_transient_bytes")
+    PHASES = ("host_hop", "upload", "inflate", "lines", "records", "names", "pack", "join", "total")
+    CONTAINERS = ("plain", "gzip", "bgzf")
+
+    def __init__(self, eng, path, keep_qual=False, chunk_bytes=0):
+        L = eng.L
+        self.eng = eng
+        h = C.c_void_p()
+        rc = L.telr_reads_load(eng.h, str(path).encode(), 1 if keep_qual else 0, int(chunk_bytes), C.byref(h))
+        if rc != 0:
+            raise _lib.TelrError("telr_reads_load: %s [%s]" % (L.telr_strerror(rc).decode(), L.telr_last_error(eng.h).decode()), rc)
+        self.h = h
+        n = int(L.telr_reads_in_count(h))
+        c = np.zeros(len(self.COUNTERS), np.int64); ci = np.zeros(len(self.CHUNK_INFO), np.int64); ph = np.zeros(len(self.PHASES), np.float32)
+        L.telr_reads_in_counters(h, c.ctypes.data); L.telr_reads_in_chunk_info(h, ci.ctypes.data); L.telr_reads_in_phase_ms(h, ph.ctypes.data)
+        self.counters = dict(zip(self.COUNTERS, (int(x) for x in c)))
+        self.chunk_info = dict(zip(self.CHUNK_INFO, (int(x) for x in ci)))
+        self.phase_ms = dict(zip(self.PHASES, (float(x) for x in ph)))
+        self.n_bases = self.counters["bases"]
+        self.container = self.CONTAINERS[self.counters["container"]]
+        self.kind = None if self.counters["text_bytes"] == 0 else "fastq" if self.counters["fastq"] else "fasta"
+        self.names_c = C.cast(L.telr_reads_in_names(h), C.POINTER(C.c_char_p * max(1, n))).contents if n else (C.c_char_p * 1)()
+        self.qnames = [self.names_c[i].decode("latin-1") for i in range(n)]
+        rs = SeqSet.__new__(SeqSet)
+        rs.eng = eng; rs.len = _np_from(L.telr_reads_in_lens(h), n, np.int32); rs.n = n
+        rs.h = C.c_void_p(L.telr_reads_in_detach_seqset(h))
+        self.read_set = rs
+
+    def free(self):
+        """the handle and its names; the read set is the caller's (read_set.free())"""
+        if getattr(self, "h", None):
+            self.names_c = None
+            self.eng.L.telr_reads_in_free(self.h); self.h = None
+
+    close = free
 
     def __del__(self):
         try:

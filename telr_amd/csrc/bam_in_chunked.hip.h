@@ -47,6 +47,7 @@ struct BamChunked {
     CrcTabs *d_tabs = nullptr;
     hipEvent_t ec0 = nullptr, ec1 = nullptr;      // around a chunk's record chain
     float ms_upload = 0, ms_inflate = 0, ms_chain = 0;
+    const char *what = "telr_bam_load";      // opens a failed block's error text (telr_reads_load runs the same slots: reads_in.hip.h)
     BamChunked(telr_ctx *c, const BamInHop &h) : ctx(c), H(h), s_main(c->stream), s_io(c->side[0]) {}
     ~BamChunked()
     {
@@ -152,7 +153,7 @@ static int bamc_wait(BamChunked &C, int64_t k)
     HIPCHK(hipEventElapsedTime(&a, s.e0, s.e1)); HIPCHK(hipEventElapsedTime(&b, s.e1, s.e2));
     C.ms_upload += a; C.ms_inflate += b;
     for (size_t j = 0; j < s.h_status.size(); ++j)
-        if (s.h_status[j] != INFL_OK) { ctx->err = "telr_bam_load: block " + std::to_string(C.first[(size_t)k] + (int64_t)j) + ": " + infl_text(s.h_status[j]); return TELR_E_ARG; }
+        if (s.h_status[j] != INFL_OK) { ctx->err = std::string(C.what) + ": block " + std::to_string(C.first[(size_t)k] + (int64_t)j) + ": " + infl_text(s.h_status[j]); return TELR_E_ARG; }
     return TELR_OK;
 }
 // the `len` bytes at src (chunk k's buffer) become chunk k + 1's carry: the end of its slot's room

@@ -160,3 +160,17 @@ def load(path):
         if getattr(e, "code", None) != TELR_E_ARG:
             raise
         return None
+
+
+def load_reads(path, engine, keep_qual=False, chunk_bytes=0):
+    """a reads file parsed and packed on the device (Engine.load_reads: gzip, BGZF or plain text, by content) -> ReadsInput, or None
+    where the loader refuses the file (TELR_E_ARG: a grammar it is stricter about than read_fasta, a container it does not know): the
+    caller then does what it does without it, as after `load`.  Every other error is raised."""
+    from . import _lib
+    from ._abi import TELR_E_ARG
+    try:
+        return engine.load_reads(path, keep_qual=keep_qual, chunk_bytes=chunk_bytes)
+    except _lib.TelrError as e:
+        if getattr(e, "code", None) != TELR_E_ARG:
+            raise
+        return None

@@ -9,6 +9,10 @@ here; the flow is that of its `main` (src/telr/telr.py:22-189) with this project
     stage-1 index              Engine.index with the aligner's preset (`--aligner nglmr`: ngmlr-ont / ngmlr-pacbio, `minimap2`: map-ont / map-pb)
     reads route                fasta.load -> Engine.seqset -> Index.map_raw (TELR_MF_CIGAR | TELR_MF_KEEP_CIGARS) -> the sorted BAM + .bai
                                with the device writer into <out>/intermediate_files/<sample>_sort.bam
+    gzip / BGZF reads          a reads file ending `.gz`: fasta.load_reads -> Engine.load_reads: the container is decided
+                               by content, the text is inflated (BGZF: on the device; gzip: one zlib thread), parsed and packed on the device
+                               in chunks (`--reads_chunk_mb N`; 0, the default: the engine's own size) and never becomes host text.  A file
+                               whose grammar the device parser refuses goes to fasta.read_fasta as before.  Same outputs either way.
     BAM route (`-i x.bam`)     Engine.load_bam, BamInput.check_targets against the reference.  `--bam_chunk_mb N`: in chunks of N MiB of
                                inflated bytes (a file of any size); 0 (the default): the whole file at once when it and
                                its inflated stream fit into half the free device memory, else in chunks of the engine's own size --
@@ -31,7 +35,7 @@ reference's bam2fasta leaves behind on the BAM route, is therefore not written; 
 
 Different from the reference on purpose: every value it prints a message for ends the run with status 1 (the reference goes on after
 four of its messages: -p below 1, a negative --af_flank_offset or --af_te_offset, --af_te_interval below 1); a reads file of any
-extension other than `.bam` goes to the reader (gzip included).  Not built: the ALT pre-screen, merge_rows on the
+extension other than `.bam` is read as reads (a `.gz` on the device, see above; one it refuses, and every plain file, by the readers).  Not built: the ALT pre-screen, merge_rows on the
 caller's rows, the RepeatMasker route for families, the N-rank path, gzip on the BAM route.  On a multi-part reference: the occurrence
 cut-off of the seeding is per part, as with minimap2 -I (secondaries the unsplit index would not report), all parts are resident together,
 and `--ref_te engine` maps the tiles to the library, not to the reference, so it runs as it is.
@@ -94,6 +98,8 @@ def get_args(argv=None):
                      "per-part records on the device; 0: one index, parts only when the reference does not fit one (default = 0)")
     own.add_argument("--bam_chunk_mb", type=int, default=0, help="load a BAM of reads in chunks of at most N MiB of inflated bytes; 0: the whole file at once "
                      "when it fits into half the free device memory next to its inflated stream, else chunks of the engine's own size (default = 0)")
+    own.add_argument("--reads_chunk_mb", type=int, default=0, help="parse a gzip or BGZF reads file on the device in chunks of at most N MiB of text; "
+                     "0: chunks of the engine's own size (default = 0)")
     own.add_argument("--sample", type=str, help="sample name (default: the reads file's name without its extension)")
     p._action_groups.append(opt)
     a = p.parse_args(argv)
@@ -148,6 +154,8 @@ def get_args(argv=None):
         _exit("Please provide a valid number of bases per index part (0 or a positive integer), exiting...")
     if a.bam_chunk_mb < 0:
         _exit("Please provide a valid BAM chunk size in MiB (0 or a positive integer), exiting...")
+    if a.reads_chunk_mb < 0:
+        _exit("Please provide a valid reads chunk size in MiB (0 or a positive integer), exiting...")
     if (a.chain_skip or a.seed_rescue or a.mm2_mapq) and a.aligner != "minimap2":
         _exit("--chain_skip, --seed_rescue and --mm2_mapq are options of the minimap2 aligner, exiting...")
     a.out = os.path.abspath("." if a.out is None else a.out)
@@ -206,8 +214,12 @@ def load_reads(eng, ix, args, tnames, bam_path):
     name, rg, cmd = aligner_preset(args)
     _, mo = preset(name, chain_skip=args.chain_skip, seed_rescue=args.seed_rescue, mm2_mapq=args.mm2_mapq)
     mo.flags |= MF_CIGAR | MF_KEEP_CIGARS
-    qf = fasta.load(args.reads)
-    if qf is not None:
+    ri = fasta.load_reads(args.reads, eng, args.keep_qual, getattr(args, "reads_chunk_mb", 0) << 20) if str(args.reads).endswith(".gz") else None
+    qf = fasta.load(args.reads) if ri is None else None
+    if ri is not None:                              # gzip or BGZF: parsed and packed on the device, never host text
+        qnames, qset = ri.qnames, ri.read_set
+        ri.free()
+    elif qf is not None:
         qnames = list(qf.names)
         qset = eng.seqset(qf.triple, qual=qf.qual if args.keep_qual else None)
         qf.close()                                  # the host copy is not needed again: every later piece comes from the set

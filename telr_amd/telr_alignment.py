@@ -17,7 +17,7 @@ import threading
 import time
 
 from .aligner import Engine
-from .fasta import read_fasta, load
+from .fasta import read_fasta, load, load_reads
 from .presets import preset
 from ._abi import MF_KEEP_CIGARS
 
@@ -90,13 +90,17 @@ def alignment(bam, read, reference, out, sample_name, thread, method, presets, e
     io, mo = preset(name, chain_skip=chain_skip, seed_rescue=seed_rescue, mm2_mapq=mm2_mapq)
     tm = {}                                       # seconds per phase of the last call: alignment.last_timings
     t0 = time.time()
-    tf, qf = load(reference), load(read)          # None for gzip: the Python reader
+    tf = load(reference)                          # None for gzip: the Python reader
+    ri = load_reads(read, eng, keep_qual) if str(read).endswith(".gz") else None          # gzip / BGZF reads: parsed and packed on the device (None: refused)
+    qf = load(read) if ri is None else None
     if tf is not None:
         tn, ts = tf.names_c, tf.triple
     else:
         tn, ts = read_fasta(reference)
     qq = None
-    if qf is not None:
+    if ri is not None:
+        qn, qs, n_bases = ri.names_c, None, ri.n_bases
+    elif qf is not None:
         qn, qs, n_bases = qf.names_c, qf.triple, int(qf.triple[2].sum())
         if keep_qual:
             qq = qf.qual
@@ -109,10 +113,11 @@ def alignment(bam, read, reference, out, sample_name, thread, method, presets, e
     tm["parse_files"] = time.time() - t0; t0 = time.time()
     ix = eng.index(ts, io)
     tm["pack_reference_build_index"] = time.time() - t0; t0 = time.time()
-    qset = eng.seqset(qs, qual=qq)
+    qset = ri.read_set if ri is not None else eng.seqset(qs, qual=qq)
+    has_qual = qq is not None or (ri is not None and qset.has_qual)
     tm["pack_upload_reads"] = time.time() - t0; t0 = time.time()
     # about 0.85 bytes of BAM per read base with --cs --MD, 0.6 without cs, at level 1; qualities add their entropy (0.45 measured for ONT-shaped ones, at most 0.82: 6.55 bits)
-    ix.bam_prepare(bam, int(((0.95 if with_cs else 0.7) + (0.85 if qq is not None else 0)) * n_bases) + (64 << 20))
+    ix.bam_prepare(bam, int(((0.95 if with_cs else 0.7) + (0.85 if has_qual else 0)) * n_bases) + (64 << 20))
     mo.flags |= MF_KEEP_CIGARS                   # the CIGAR array stays on the device as well: the BAM writer reads it there
     r = None
     try:
@@ -142,7 +147,7 @@ def alignment(bam, read, reference, out, sample_name, thread, method, presets, e
             for f in files:
                 if f is not None:
                     f.close()
-        th = threading.Thread(target=_drop, args=((tf, qf), qset, ix), daemon=False)
+        th = threading.Thread(target=_drop, args=((tf, qf, ri), qset, ix), daemon=False)
         _release_threads.append(th)
         th.start()
     tm["release"] = time.time() - t0
