@@ -59,6 +59,8 @@ def lib():
         L.tor_debug_dp.argtypes = [vp, vp, vp, vp, C.POINTER(MapOpt), vp, i32, vp, vp, i64]
         L.tor_debug_backtrack.restype = i32
         L.tor_debug_backtrack.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(MapOpt), vp, vp, vp, vp, vp, vp, vp, i64, vp]
+        L.tor_debug_chain.restype = i32
+        L.tor_debug_chain.argtypes = [i32, vp, vp, C.POINTER(MapOpt), vp, vp]
         L.tor_depth_medians.argtypes = [vp, i64, vp, i32, vp, i32, vp, vp, vp, vp]
         L.tor_consensus.restype = i64; L.tor_consensus.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, vp, i64, vp, vp]
         L.tor_poa.restype = i64; L.tor_poa.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, i32, vp, i64, vp, vp]
@@ -246,3 +248,16 @@ def debug_backtrack(keys, q_aoff, f, p, qlen, goff, tlen, mo):
     nch, nk, npb = (int(v) for v in n_out)
     return dict(chains=chains[:nch].copy(), ch_off=ch_off, ch_aoff=ch_aoff[:nch + 1].copy(), canch=canch[:int(ch_aoff[nch])].copy(),
                 kept=kept[:nk].copy(), prob_off=prob_off[:nk + 1].copy(), probs=probs[:npb].copy())
+
+
+def debug_chain(keys, q_aoff, mo):
+    """the oracle's chaining scores (chain_dp per query, as map() runs it under `mo`) of sorted anchor lists: same input and output as
+    Engine.debug_chain -> (f, p) int32 arrays (p relative to the query's first anchor, -1 for none)"""
+    K = np.ascontiguousarray(keys, dtype=np.uint64)
+    O = np.ascontiguousarray(q_aoff, dtype=np.int32)
+    if len(O) < 1 or int(O[0]) != 0 or int(O[-1]) != len(K) or np.any(np.diff(O) < 0):
+        raise ValueError("q_aoff must hold nq + 1 ascending offsets from 0 to len(keys)")
+    f = np.zeros(len(K), np.int32); p = np.zeros(len(K), np.int32)
+    if lib().tor_debug_chain(len(O) - 1, O.ctypes.data, K.ctypes.data, C.byref(mo), f.ctypes.data, p.ctypes.data) != 0:
+        raise ValueError("tor_debug_chain: bad offsets")
+    return f, p

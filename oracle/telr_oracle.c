@@ -1314,6 +1314,21 @@ int32_t tor_debug_backtrack(int32_t nq, const int32_t *q_aoff, const uint64_t *k
     return rc;
 }
 
+/* The chaining scores of caller-supplied anchor lists (the tap the engine's telr_debug_chain is held to): chain_dp on each query's
+ * sorted anchors keys[q_aoff[q] .. q_aoff[q + 1]) under `mo` (the default look-back loop, or the scan under TELR_MF_CHAIN_SKIP), as
+ * tor_map runs it.  Out: f and p of every anchor, p relative to the query's first anchor, -1 for none.  Returns 0, or -1 when the
+ * offsets do not ascend from 0. */
+int32_t tor_debug_chain(int32_t nq, const int32_t *q_aoff, const uint64_t *keys, const telr_map_opt *mo, int32_t *f, int32_t *p)
+{
+    if (nq < 0 || (nq > 0 && q_aoff[0] != 0)) return -1;
+    for (int32_t qi = 0; qi < nq; ++qi) if (q_aoff[qi + 1] < q_aoff[qi]) return -1;
+    for (int32_t qi = 0; qi < nq; ++qi) {
+        const int64_t a0 = q_aoff[qi];
+        chain_dp(keys + a0, q_aoff[qi + 1] - a0, mo, f + a0, p + a0);
+    }
+    return 0;
+}
+
 /* ------------------------------------------------------------------------- */
 /* 7. the mapping driver                                                      */
 typedef struct tor_result {
