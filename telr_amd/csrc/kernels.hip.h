@@ -1786,13 +1786,99 @@ __device__ __forceinline__ void d_chain_any(const uint64_t *__restrict__ keys, c
         else d_chain_run_lazy<R, SKIP>(keys, base, n, pdelta, o, f, p);
     }
 }
+// THE ISLAND WALK.  A sorted list falls into islands that chain independently (ISLANDS, below), and a read's list is mostly small
+// ones: random k-mer matches and repeat hits, one to a few anchors each.  The loops above take one anchor per trip whatever the
+// number of lanes its push can reach, so a singleton costs as much as an anchor of the read's true chain.  The wave of k_chain walks
+// its list by WINDOWS of 64 anchors instead, one per lane, starting at an island head:
+//   * one ballot of "reference word minus the previous anchor's > max_gap" (the strand is bit 31) gives the heads inside the window.
+//     Where the list ends inside the window all of it is whole islands; otherwise everything before the last head among lanes
+//     1..63 is, e anchors;
+//   * those islands are chained SIDE BY SIDE: in sub-step t every island pushes its t-th anchor to its own later lanes.  Lane l with
+//     head(l) + t < l fetches that lane's reference word, query position and 2 f + 2 through the LDS crossbar (ds_bpermute: a
+//     source lane per lane, which v_readlane cannot give) and scores the link with d_chain_push's rule.  The source is final by then
+//     (it took every earlier push in the sub-steps before), pushes reach a lane in ascending j, so ">=" keeps the largest index
+//     among ties, and every predecessor lies at most 63 back: inside every look-back, no far part.  The sub-steps number the
+//     largest island of the window less one; a window of singletons takes none;
+//   * where no island ends inside the window, forward ballots find the end of the island at the window's start and the loops above
+//     run on it as k_chain_isl runs them (d_chain_any: the push loop or the lazy look-back by d_chain_dense of that run, pdelta = its
+//     start).
+// Same f, same p.  Every loop is bounded: the sub-steps by 63, the forward scan by n.  `pack` == 0 (TELR_AB=chain_no_pack): the whole
+// list is one run, as before.
+template <int R, bool SKIP>
+__device__ __forceinline__ void d_chain_walk(const uint64_t *__restrict__ keys, const int64_t base, const int n,
+                                             const ChainOpt &o, int32_t *__restrict__ f, int32_t *__restrict__ p, const bool pack)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t *a = keys + base;
+    const uint32_t max_gap = (uint32_t)o.max_gap, ddc = o.bw < o.max_gap ? (uint32_t)(o.max_gap - 1 - o.bw) : 0u;
+    const uint32_t gap_q8 = (uint32_t)o.chain_gap_q8, skip_q8 = (uint32_t)o.chain_skip_q8;
+    const uint64_t upto = (2ULL << lane) - 1ULL;            // lanes 0 .. lane
+    const int lane4 = lane << 2;
+    int pos = 0;
+    while (pos < n) {
+        int end = n;                                        // of the run that goes to the loops for whole runs
+        if (pack) {
+            const int i = pos + lane;
+            const uint64_t k = i < n ? a[i] : 0;
+            const uint32_t gi = (uint32_t)(k >> 32);
+            const uint32_t gprev = (uint32_t)__shfl_up((int)gi, 1);
+            const uint64_t heads = __ballot(i < n && gi - gprev > max_gap) | 1ULL;
+            int e = n - pos;                                // the list ends inside the window: all of it
+            if (e > 64) { const uint64_t hh = heads & ~1ULL; e = hh ? 63 - __clzll((long long)hh) : 0; }
+            if (e > 0) {
+                const uint32_t qi = (uint32_t)A_Q(k), sp1 = (uint32_t)A_SPAN(k) - 1u;
+                int32_t B = 2 * A_SPAN(k) + 1, bp4 = 0;
+                // the source lane of this sub-step, times four (ds_bpermute addresses bytes): the island's head first.  Lanes
+                // beyond e hold a part of the next island: they take nothing (and no lane below e reads them).
+                int src4 = lane < e ? (63 - __clzll((long long)(heads & upto))) << 2 : lane4;
+                for (;;) {
+                    const bool act = src4 < lane4;
+                    if (__ballot(act) == 0) break;
+                    const uint32_t gj1 = (uint32_t)__builtin_amdgcn_ds_bpermute(src4, (int)gi) + 1u;
+                    const uint32_t qj1 = (uint32_t)__builtin_amdgcn_ds_bpermute(src4, (int)qi) + 1u;
+                    const int32_t fj2p2 = (__builtin_amdgcn_ds_bpermute(src4, B) & ~1) + 2;
+                    bool ok;
+                    const int32_t v2 = d_chain_link<SKIP>(gi, qi, sp1, gj1, qj1, fj2p2, max_gap, ddc, gap_q8, skip_q8, ok);
+                    if (act && ok && v2 >= B) { B = v2; bp4 = src4; }
+                    src4 += 4;
+                }
+                if (lane < e) { f[base + i] = B >> 1; p[base + i] = (B & 1) ? -1 : pos + (bp4 >> 2); }
+                pos += e;
+                continue;
+            }
+            // the island at pos fills the window and goes on: its end is the first head behind the window
+            for (int c = pos + 64; c < n; c += 256) {
+                uint64_t hm[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int ii = c + 64 * u + lane;
+                    bool h = false;
+                    if (ii < n) h = (uint32_t)(a[ii] >> 32) - (uint32_t)(a[ii - 1] >> 32) > max_gap;
+                    hm[u] = __ballot(h);
+                }
+                int at = -1;
+#pragma unroll
+                for (int u = 3; u >= 0; --u) if (hm[u]) at = c + 64 * u + __ffsll((long long)hm[u]) - 1;
+                if (at >= 0) { end = at; break; }
+            }
+        }
+        d_chain_any<R, SKIP, 2>(keys, base + pos, end - pos, pos, o, f, p, false);
+        pos = end;
+    }
+}
 template <int R, bool SKIP, int MODE = 2>
 __global__ void __launch_bounds__(64) k_chain(const uint64_t *__restrict__ keys, const int32_t *__restrict__ q_aoff, int32_t nq,
-                                              ChainOpt o, int32_t *__restrict__ f, int32_t *__restrict__ p, const int32_t *__restrict__ q_order, int32_t skip_mw)
+                                              ChainOpt o, int32_t *__restrict__ f, int32_t *__restrict__ p, const int32_t *__restrict__ q_order, int32_t skip_mw, int32_t pack)
 {
     if ((int)blockIdx.x >= nq) return;
     const int q = q_order ? q_order[blockIdx.x] : blockIdx.x;    // longest reads first: the kernel ends with the short ones
-    d_chain_any<R, SKIP, MODE>(keys, q_aoff[q], q_aoff[q + 1] - q_aoff[q], 0, o, f, p, skip_mw != 0);
+    const int64_t base = q_aoff[q]; const int n = q_aoff[q + 1] - q_aoff[q];
+    if constexpr (MODE != 2) d_chain_any<R, SKIP, MODE>(keys, base, n, 0, o, f, p, false);       // (a pinned loop: whole lists)
+    else {
+        // a run that k_chain_mw takes is left to it: decided on the whole list, before the walk
+        if (skip_mw && d_chain_is_mw(d_chain_dense(keys + base, n, o), n, o)) return;
+        d_chain_walk<R, SKIP>(keys, base, n, o, f, p, pack != 0);
+    }
 }
 // the long dense runs of a call, R waves each (beside k_chain, on a stream of its own): `list` = the range's over-size queries
 // (every run of o.mw_n > SEGSORT_CAP anchors is one of them), or every query when list == nullptr (tests with small thresholds)

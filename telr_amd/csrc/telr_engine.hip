@@ -100,7 +100,8 @@ struct telr_ctx {
 //                            after all forward kernels), no_avx2 (scalar host packer), fasta_copy (no in-place use of the mapped file),
 //                            bam_no_populate, bam_no_twin (BAM writer: no pre-faulted mapping / CIGARs uploaded again), scan_lib /
 //                            index_sort_lib (rocPRIM's scan / its sort of the index build), chain_lazy, chain_no_mw (the lazy far
-//                            look-back everywhere / no second kernel for the long dense runs)
+//                            look-back everywhere / no second kernel for the long dense runs), chain_no_pack (k_chain chains a
+//                            whole list as one run: no windows of small islands side by side)
 //   TELR_TRACE=tok[,tok...]  stderr traces: host (wall-clock marks of every batch's host side), mem (device memory at the points
 //                            where the engine runs out of it or gives it back), fasta (phases of telr_fasta_load)
 // The others are operational: TELR_DEBUG, TELR_HOST_THREADS, TELR_PACK_THREADS, TELR_BATCH_MBP / TELR_BATCH_KBP (range size),
@@ -1721,12 +1722,13 @@ static int chain_dispatch(telr_ctx *ctx, hipStream_t st, const telr_map_opt *mo,
     const int Rr = mo->chain_lookback / 64;
     const bool mw_all = dense_v[2] <= SEGSORT_CAP;            // (small thresholds: every query is looked at, not only the over-size list)
     static const bool no_islands = ab_on("no_islands");       // A/B: one wave per query whatever the call's shape
+    static const bool chain_no_pack = ab_on("chain_no_pack"); // A/B: k_chain takes a whole list as one run (kernels.hip.h: THE ISLAND WALK)
     const bool islands = nq <= CHAIN_ISL_NQ && na > 0 && !no_islands;
     const bool mw = !(mo->flags & TELR_MF_CHAIN_SKIP) && !chain_push && !chain_lazy && !chain_no_mw && Rr >= 2 && na > 0 && !islands && dense_v[2] > 0 && (mw_all || n_over > 0);
     co.dense_n = dense_v[0]; co.dense_span = dense_v[1]; co.mw_n = mw ? dense_v[2] : 0;
-#define CHAIN_LAUNCH(RR, SK) do { if (chain_push) hipLaunchKernelGGL((k_chain<RR, SK, 0>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, 0); \
-                                  else if (chain_lazy) hipLaunchKernelGGL((k_chain<RR, SK, 1>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, 0); \
-                                  else hipLaunchKernelGGL((k_chain<RR, SK, 2>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, mw ? 1 : 0); } while (0)
+#define CHAIN_LAUNCH(RR, SK) do { if (chain_push) hipLaunchKernelGGL((k_chain<RR, SK, 0>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, 0, 0); \
+                                  else if (chain_lazy) hipLaunchKernelGGL((k_chain<RR, SK, 1>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, 0, 0); \
+                                  else hipLaunchKernelGGL((k_chain<RR, SK, 2>), dim3(nq), dim3(64), 0, st, d_skeys, d_qaoff, nq, co, d_f, d_p, d_qorder, mw ? 1 : 0, chain_no_pack ? 0 : 1); } while (0)
 #define CHAIN_MW(RR, SK) hipLaunchKernelGGL((k_chain_mw<RR, SK>), dim3(mw_all ? nq : n_over), dim3(64 * RR), 0, ctx->side[0], d_skeys, d_qaoff, mw_all ? nq : n_over, mw_all ? (const int32_t*)nullptr : (const int32_t*)d_overlist, co, d_f, d_p)
     const bool skip = co.chain_skip_q8 != 0;
     if (mo->flags & TELR_MF_CHAIN_SKIP) {
