@@ -845,6 +845,27 @@ int  telr_debug_dp_class_table(int32_t *out /* [TELR_N_DPCLS][6] */);
  * out[1] bases per range at most, out[2] number of ranges; range_end (nullable, n entries suffice): the end of every range */
 int  telr_debug_map_plan(const int32_t *len, int32_t n, int32_t max_len, double per_base, int has_qtarget, int vote, int debug,
                          int pipe_nomem, int64_t *out /* [3] */, int32_t *range_end);
+/* ---- test taps behind the banded DP: CIGAR stitching, the per-chain sums and the retry pass, as telr_map runs them ----
+ * telr_debug_stitch: the stitch and chain-sum kernels on hand-made per-problem results.  Chain k owns the problems
+ * [p_off[k], p_off[k + 1]) (at least one each) and reads its first one forwards when has_left[k]; prob: five ints per problem
+ * {score, bi, bj, mlen, mcols}; the CIGAR words (len << 4 | op, op 0..2) of problem x are cig[cig_off[x] .. cig_off[x + 1]) in
+ * storage order: end to start of the DP problem, as the trace-back leaves them.  cx_scale as in telr_map_opt (0: no rounding).
+ * chain_out: nine ints per chain {dp, mlen, blen, l_bi, l_bj, r_bi, r_bj, n_cigar, first op in cig_out}.
+ * TELR_E_RANGE when cig_cap ops do not hold the stitched CIGARs. */
+int  telr_debug_stitch(telr_ctx *ctx, int32_t n_chain, const int32_t *p_off, const int32_t *has_left, const int32_t *prob,
+                       const int64_t *cig_off, const uint32_t *cig, int32_t cx_scale, int32_t *chain_out, uint32_t *cig_out,
+                       int64_t cig_cap);
+/* telr_debug_align: both DP passes, stitching and the records' numbers of a caller's chains.  chains: seven ints per chain {qid,
+ * tid, rev, qs, qe, rs, re}, the query interval on the chain's strand; chain k owns the rows [prob_off[k], prob_off[k + 1]) of
+ * probs, twelve ints each {qid, q_off, tid, t_off, m, n, dlo, dhi, kind, qstep, tstep, qcomp} with the bands telr_map builds:
+ * [kind 1]? (kind 0 | 3 | 5)+ [kind 2]? on the chain's sequences and strand, the kind-1 row (left extension) exactly when qs > 0
+ * and rs > 0, the kind-2 row (right extension) exactly when qe < qlen and re < tlen.  chain_out: nine ints per chain {qs, qe, ts,
+ * te, mlen, blen, dp_score, n_cigar, first op in cig_out} as in a record; prob_out: nine ints per problem {DP class of the first
+ * pass, retry flag, score, bi, bj, mlen, mcols, CIGAR ops, cells} after the retry pass; *n_retry: problems on the retry list;
+ * acc_out: the per-class accounts (telr_last_dp_classes) and, last, the sum of the target window bases. */
+int  telr_debug_align(telr_ctx *ctx, const telr_seqset *queries, const telr_seqset *targets, const telr_map_opt *mo, int32_t n_chain,
+                      const int32_t *chains, const int32_t *prob_off, const int32_t *probs, int32_t *chain_out, int32_t *prob_out,
+                      uint32_t *cig_out, int64_t cig_cap, int32_t *n_retry, int64_t *acc_out /* [TELR_N_DPCLS*4 + 1] */);
 
 #ifdef __cplusplus
 }

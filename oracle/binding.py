@@ -57,6 +57,8 @@ def lib():
                               C.POINTER(i32), C.POINTER(i32)]
         L.tor_debug_dp.restype = i32
         L.tor_debug_dp.argtypes = [vp, vp, vp, vp, C.POINTER(MapOpt), vp, i32, vp, vp, i64]
+        L.tor_debug_dp_cells.restype = i32
+        L.tor_debug_dp_cells.argtypes = [vp, vp, vp, vp, C.POINTER(MapOpt), vp, i32, vp, vp, i64, vp]
         L.tor_debug_backtrack.restype = i32
         L.tor_debug_backtrack.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(MapOpt), vp, vp, vp, vp, vp, vp, vp, i64, vp]
         L.tor_debug_chain.restype = i32
@@ -208,19 +210,20 @@ def consensus(alns, cigars, queries, targets, min_depth=3, poa=False, stats=Fals
 def debug_dp(queries, targets, mo, probs):
     """the oracle's DP of each problem of a telr_debug_dp list (band_dp / longgap_fill / band_dp_fallback).
     queries, targets: lists of ASCII sequences; probs: (np, 12) int32 rows as Engine.debug_dp takes them.
-    -> dict of per-problem arrays score, bi, bj, touched, and cigars (a list of uint32 arrays, start to end)"""
+    -> dict of per-problem arrays score, bi, bj, touched, cells, and cigars (a list of uint32 arrays, start to end)"""
     qb, qo, _ = concat(queries)
     tb, to, _ = concat(targets)
     P = np.ascontiguousarray(probs, dtype=np.int32).reshape(-1, 12)
     npb = len(P)
-    res = np.zeros((npb, 6), np.int32)
+    res = np.zeros((npb, 6), np.int32); cells = np.zeros(npb, np.int64)
     cap = int((6 * (P[:, 4].astype(np.int64) + P[:, 5]) + 16).sum()) + 16
     cig = np.zeros(cap, np.uint32)
-    rc = lib().tor_debug_dp(qb.ctypes.data, qo.ctypes.data, tb.ctypes.data, to.ctypes.data, C.byref(mo), P.ctypes.data, npb,
-                            res.ctypes.data, cig.ctypes.data, cap)
+    rc = lib().tor_debug_dp_cells(qb.ctypes.data, qo.ctypes.data, tb.ctypes.data, to.ctypes.data, C.byref(mo), P.ctypes.data, npb,
+                                  res.ctypes.data, cig.ctypes.data, cap, cells.ctypes.data)
     if rc != 0:
         raise ValueError("tor_debug_dp: bad problem list")
     out = {k: res[:, i].copy() for i, k in enumerate(("score", "bi", "bj", "touched"))}
+    out["cells"] = cells
     out["cigars"] = [cig[res[x, 5]:res[x, 5] + res[x, 4]].copy() for x in range(npb)]
     return out
 

@@ -1055,10 +1055,11 @@ int32_t tor_ext(const char *q, int m, const char *t, int n, const telr_map_opt *
 /* debug entry: a list of DP problems as the engine's test tap takes them (telr_debug_dp).  probs: np x 12 int32
  * {qid, q_off, tid, t_off, m, n, dlo, dhi, kind, qstep, tstep, qcomp} over two ASCII sequence sets; kinds 0 (band_dp),
  * 1 / 2 (band_dp with z-drop), 3 (band_dp_fallback; convex cost: its closing gap at the convex price, as align_chain does),
- * 5 (longgap_fill).  res: np x 6 {score, bi, bj, touched, CIGAR ops, first op in cig}; CIGARs start to end.
- * Returns 0, or -1 on a bad kind or when cig_cap is too small. */
-int32_t tor_debug_dp(const char *qascii, const int64_t *qoff, const char *tascii, const int64_t *toff, const telr_map_opt *mo,
-                     const int32_t *probs, int32_t np, int32_t *res, uint32_t *cig, int64_t cig_cap)
+ * 5 (longgap_fill).  res: np x 6 {score, bi, bj, touched, CIGAR ops, first op in cig}; CIGARs start to end; cells (nullable): np
+ * int64, dp_res_t.cells of every problem.  Returns 0, or -1 on a bad kind or when cig_cap is too small.
+ * tor_debug_dp is the entry without the cells column: its res layout is what earlier bindings allocate, so it stays as it is. */
+int32_t tor_debug_dp_cells(const char *qascii, const int64_t *qoff, const char *tascii, const int64_t *toff, const telr_map_opt *mo,
+                           const int32_t *probs, int32_t np, int32_t *res, uint32_t *cig, int64_t cig_cap, int64_t *cells)
 {
     convex_t CX; const int cx = (mo->cx_scale > 0 || (mo->flags & MFX_CONVEX)) && convex_of(mo, &CX);
     u32v_t rc = {0, 0, 0};
@@ -1084,10 +1085,16 @@ int32_t tor_debug_dp(const char *qascii, const int64_t *qoff, const char *tascii
         if ((kind != 0 && kind != 1 && kind != 2 && kind != 3 && kind != 5) || w + rc.n > cig_cap) { free(rc.a); return -1; }
         int32_t *o = res + (size_t)x * 6;
         o[0] = r.score; o[1] = r.bi; o[2] = r.bj; o[3] = r.touched; o[4] = (int32_t)rc.n; o[5] = (int32_t)w;
+        if (cells) cells[x] = r.cells;
         for (int64_t z = rc.n - 1; z >= 0; --z) cig[w++] = rc.a[z];
     }
     free(rc.a);
     return 0;
+}
+int32_t tor_debug_dp(const char *qascii, const int64_t *qoff, const char *tascii, const int64_t *toff, const telr_map_opt *mo,
+                     const int32_t *probs, int32_t np, int32_t *res, uint32_t *cig, int64_t cig_cap)
+{
+    return tor_debug_dp_cells(qascii, qoff, tascii, toff, mo, probs, np, res, cig, cig_cap, NULL);
 }
 
 /* The DP problems of one chain, in the order align_chain runs them (and tor_debug_backtrack reports them): the left extension

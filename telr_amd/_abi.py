@@ -130,6 +130,12 @@ MF_SEED_RESCUE = 0x2000         # minimap2's high-occurrence seed rescue (mm_see
 MF_MM2_MAPQ = 0x20000           # minimap2's MAPQ (mm_set_mapq without the second-best DP score) instead of the Li-2018 formula
 N_STAGES = 16
 N_DPCLS = 25
+# the rows of the two test taps behind the DP (include/telr_hip.h: telr_debug_stitch, telr_debug_align)
+STITCH_PROB_COLUMNS = ("score", "bi", "bj", "mlen", "mcols")
+STITCH_CHAIN_COLUMNS = ("dp", "mlen", "blen", "l_bi", "l_bj", "r_bi", "r_bj", "n_cigar", "cig_first")
+ALIGN_CHAIN_IN_COLUMNS = ("qid", "tid", "rev", "qs", "qe", "rs", "re")
+ALIGN_CHAIN_COLUMNS = ("qs", "qe", "ts", "te", "mlen", "blen", "dp_score", "n_cigar", "cig_first")
+ALIGN_PROB_COLUMNS = ("cls", "retried", "score", "bi", "bj", "mlen", "mcols", "nops", "cells")
 
 import numpy as _np
 

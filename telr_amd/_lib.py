@@ -30,6 +30,7 @@ EXPORTS = [
     "telr_reads_in_counters", "telr_reads_in_chunk_info", "telr_reads_in_phase_ms",
     "telr_part_plan", "telr_part_plan_error", "telr_merge_parts", "telr_write_bam_dev_targets",
     "telr_tile_plan", "telr_refte_opt_default", "telr_annotate_hits", "telr_te_feats_count", "telr_te_feats_data", "telr_te_feats_free",
+    "telr_debug_stitch", "telr_debug_align",
 ]
 
 _lib = None
@@ -197,6 +198,9 @@ def lib():
     L.telr_debug_dp_class_table.restype = C.c_int; L.telr_debug_dp_class_table.argtypes = [vp]
     L.telr_debug_map_plan.restype = C.c_int; L.telr_debug_map_plan.argtypes = [vp, i32, i32, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.telr_debug_dp.restype = C.c_int; L.telr_debug_dp.argtypes = [vp, vp, vp, C.POINTER(MapOpt), vp, i32, vp, vp, vp, i64]
+    L.telr_debug_stitch.restype = C.c_int; L.telr_debug_stitch.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i64]
+    L.telr_debug_align.restype = C.c_int
+    L.telr_debug_align.argtypes = [vp, vp, vp, C.POINTER(MapOpt), i32, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i32), vp]
     L.telr_debug_chain.restype = C.c_int; L.telr_debug_chain.argtypes = [vp, i32, vp, vp, C.POINTER(MapOpt), vp, vp]
     L.telr_debug_backtrack.restype = C.c_int
     L.telr_debug_backtrack.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(MapOpt), vp, vp, vp, vp, vp, vp, vp, i64, vp]

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 from . import _lib
 from ._abi import IdxOpt, MapOpt, Counters, InsOpt, GenoOpt, DraftOpt, RefTeOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, DRAFT_DTYPE, TILE_DTYPE, \
-    TE_FEAT_DTYPE, TELR_E_ARG, TELR_E_RANGE, MF_PER_TARGET, MF_KEEP_CIGARS, N_STAGES, N_DPCLS
+    TE_FEAT_DTYPE, TELR_E_ARG, TELR_E_RANGE, MF_PER_TARGET, MF_KEEP_CIGARS, N_STAGES, N_DPCLS, STITCH_CHAIN_COLUMNS, ALIGN_CHAIN_COLUMNS, ALIGN_PROB_COLUMNS
 from .fasta import concat
 
 BAM_CHUNK_FIT = -1        # TELR_BAM_CHUNK_FIT (include/telr_hip.h): Engine.load_bam decides between the whole-file and the chunked load
@@ -231,6 +231,48 @@ class Engine:
         out["tb_off"] = tb
         out["cigars"] = [cig[res[x, 7]:res[x, 7] + res[x, 6]].copy() for x in range(npb)]
         return out
+
+    def debug_stitch(self, p_off, has_left, prob, cigars, cx_scale=0):
+        """CIGAR stitching and the per-chain sums (the map path's stitch_count and k_stitch_write) on hand-made per-problem
+        results -- test tap.  p_off: n_chain + 1 problem offsets; has_left: per chain; prob: (np, 5) int32 rows STITCH_PROB_COLUMNS;
+        cigars: per problem its words (len << 4 | op) in storage order, as the trace-back leaves them (end to start of the DP problem).
+        -> dict of per-chain arrays dp, mlen, blen, l_bi, l_bj, r_bi, r_bj, n_cigar, and cigars (a list of uint32 arrays)"""
+        O = np.ascontiguousarray(p_off, dtype=np.int32)
+        HL = np.ascontiguousarray(has_left, dtype=np.int32)
+        P = np.ascontiguousarray(prob, dtype=np.int32).reshape(-1, 5)
+        if len(O) < 1 or len(HL) != len(O) - 1 or len(cigars) != len(P) or (len(O) > 1 and int(O[-1]) != len(P)):
+            raise _lib.TelrError("telr_debug_stitch: p_off must hold n_chain + 1 offsets ending at the problem count", TELR_E_ARG)
+        co = np.zeros(len(P) + 1, np.int64)
+        co[1:] = np.cumsum([len(c) for c in cigars])
+        raw = np.ascontiguousarray(np.concatenate([np.asarray(c, np.uint32) for c in cigars]) if len(cigars) else np.zeros(0), dtype=np.uint32)
+        nk, cap = len(O) - 1, len(raw) + 1
+        out = np.zeros((nk, len(STITCH_CHAIN_COLUMNS)), np.int32); cig = np.zeros(cap, np.uint32)
+        self._chk(self.L.telr_debug_stitch(self.h, nk, O.ctypes.data, HL.ctypes.data, P.ctypes.data, co.ctypes.data, raw.ctypes.data, int(cx_scale),
+                                           out.ctypes.data, cig.ctypes.data, cap), "telr_debug_stitch")
+        r = {k: out[:, i].copy() for i, k in enumerate(STITCH_CHAIN_COLUMNS[:-1])}
+        r["cigars"] = [cig[out[k, 8]:out[k, 8] + out[k, 7]].copy() for k in range(nk)]
+        return r
+
+    def debug_align(self, queries, targets, mo, chains, prob_off, probs):
+        """both DP passes, stitching and the records' numbers (the map path's dp_passes, stitch_count, k_stitch_write and
+        chain_numbers) of a caller's chains -- test tap.  chains: (n_chain, 7) int32 rows ALIGN_CHAIN_IN_COLUMNS (the query interval on
+        the chain's strand); prob_off: n_chain + 1 offsets into probs, (np, 12) rows as debug_dp takes them; queries / targets: SeqSet.
+        -> dict: `chains` {ALIGN_CHAIN_COLUMNS but the last: arrays}, `cigars` (a list of uint32 arrays), `probs` {ALIGN_PROB_COLUMNS:
+        arrays}, n_retry, and acc, the (N_DPCLS * 4 + 1) int64 accounts of the call"""
+        Cn = np.ascontiguousarray(chains, dtype=np.int32).reshape(-1, 7)
+        O = np.ascontiguousarray(prob_off, dtype=np.int32)
+        P = np.ascontiguousarray(probs, dtype=np.int32).reshape(-1, 12)
+        if len(O) != len(Cn) + 1 or (len(Cn) and int(O[-1]) != len(P)):
+            raise _lib.TelrError("telr_debug_align: prob_off must hold n_chain + 1 offsets ending at the problem count", TELR_E_ARG)
+        nk, npb = len(Cn), len(P)
+        cap = int((P[:, 4].astype(np.int64) + P[:, 5] + 2).sum()) + 16
+        co = np.zeros((nk, len(ALIGN_CHAIN_COLUMNS)), np.int32); po = np.zeros((npb, len(ALIGN_PROB_COLUMNS)), np.int32)
+        cig = np.zeros(cap, np.uint32); acc = np.zeros(N_DPCLS * 4 + 1, np.int64); n_retry = C.c_int32(0)
+        self._chk(self.L.telr_debug_align(self.h, queries.h, targets.h, C.byref(mo), nk, Cn.ctypes.data, O.ctypes.data, P.ctypes.data, co.ctypes.data,
+                                          po.ctypes.data, cig.ctypes.data, cap, C.byref(n_retry), acc.ctypes.data), "telr_debug_align")
+        return dict(chains={k: co[:, i].copy() for i, k in enumerate(ALIGN_CHAIN_COLUMNS[:-1])},
+                    cigars=[cig[co[k, 8]:co[k, 8] + co[k, 7]].copy() for k in range(nk)],
+                    probs={k: po[:, i].copy() for i, k in enumerate(ALIGN_PROB_COLUMNS)}, n_retry=int(n_retry.value), acc=acc)
 
     def debug_chain(self, keys, q_aoff, mo):
         """the chaining stage of map() on sorted anchor lists -- test tap.  keys: uint64 anchors in the engine's layout (strand << 63 |

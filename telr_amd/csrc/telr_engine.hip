@@ -2131,7 +2131,7 @@ static telr_aln *kept_records(telr_ctx *ctx, int NT, const telr_seqset *qs, cons
 
 // banded DP: narrow-band pass, then a wide-band pass for the problems whose path touched a band edge -> d_res, d_rawcig, *n_retry
 static int dp_passes(telr_ctx *ctx, hipStream_t st, const telr_seqset *qs, const telr_seqset *tg, const telr_map_opt *mo, DpProb *d_probs, int np,
-                     DpRes **d_res_out, uint32_t **d_rawcig, int32_t *n_retry_out)
+                     DpRes **d_res_out, uint32_t **d_rawcig, int32_t *n_retry_out, const int32_t **d_retry_out = nullptr)
 {
     DpRes *d_res; int32_t *d_retry, *d_rcnt, *d_rlist;
     *d_rawcig = nullptr;
@@ -2162,6 +2162,7 @@ static int dp_passes(telr_ctx *ctx, hipStream_t st, const telr_seqset *qs, const
         HIPCHK(hipGetLastError());
     }
     *d_res_out = d_res; *n_retry_out = n_retry;
+    if (d_retry_out) *d_retry_out = d_retry;            // (test tap: the first pass's flags)
     return TELR_OK;
 }
 
@@ -2956,6 +2957,33 @@ extern "C" int telr_debug_backtrack(telr_ctx *ctx, int32_t nq, const int32_t *q_
     }
     return TELR_OK;
 }
+// One row {qid, q_off, tid, t_off, m, n, dlo, dhi, kind, qstep, tstep, qcomp} of a test tap's problem list as the DpProb the map path
+// would have built (k_segments_w); -> why it is refused, or nullptr.  tb_off / cig_off / chain are the caller's.
+static const char *debug_prob_row(const telr_seqset *qs, const telr_seqset *tg, const telr_map_opt *mo, const int32_t *p, DpProb *out)
+{
+    const auto even_lo = [](int lo) { return lo - (lo & 1); };
+    const int qid = p[0], q_off = p[1], tid = p[2], t_off = p[3], m = p[4], n = p[5], dlo = p[6], dhi = p[7], kind = p[8], qstep = p[9], tstep = p[10], qcomp = p[11];
+    if (qid < 0 || qid >= qs->n || tid < 0 || tid >= tg->n) return "sequence id";
+    if (m < 1 || n < 1 || (qstep != 1 && qstep != -1) || (tstep != 1 && tstep != -1) || (qcomp != 0 && qcomp != 1)) return "lengths or steps";
+    const int64_t qlo = qstep > 0 ? q_off : (int64_t)q_off - m + 1, tlo = tstep > 0 ? t_off : (int64_t)t_off - n + 1;
+    if (qlo < 0 || qlo + m > qs->len[qid] || tlo < 0 || tlo + n > tg->len[tid]) return "window outside its sequence";
+    if (dlo & 1) return "dlo must be even";
+    const int D = dhi - dlo + 1, dl = n - m;
+    if (kind == 0 || kind == 3) {        // fill: W diagonals of slack on either side of the corner-to-corner range
+        const int W = dhi - (dl > 0 ? dl : 0);
+        if (W < 0 || dlo != even_lo((dl < 0 ? dl : 0) - W)) return "fill band";
+        if (kind == 0 ? D > DP_DMAX : D <= DP_DMAX) return "fill band width (kind 3 = wider than DP_DMAX)";
+    } else if (kind == 1 || kind == 2 || kind == 5) {      // the extension band
+        if (dlo != even_lo(-mo->ext_band) || dhi != mo->ext_band) return "extension band";
+        if (kind == 5 && !(mo->bw_long > mo->bw && (dl > mo->bw || -dl > mo->bw))) return "long-gap fill needs bw_long > bw and |n - m| > bw";
+        if (kind != 5 && (m > mo->ext_max || n > m + mo->ext_band)) return "extension window";
+    } else return "kind";
+    DpProb &P = *out;
+    P.qi0 = qs->boff[qid] + q_off; P.ti0 = tg->boff[tid] + t_off; P.tb_off = P.cig_off = 0;
+    P.m = m; P.n = n; P.dlo = dlo; P.dhi = dhi; P.qstep = (int8_t)qstep; P.tstep = (int8_t)tstep; P.qcomp = (int8_t)qcomp; P.kind = (int8_t)kind;
+    P.chain = 0; P.pad[0] = P.pad[1] = 0;
+    return nullptr;
+}
 // One DP pass over a caller's list of problems (test tap: every class of dp_pass against the oracle, problem by problem).
 // probs: np x 12 int32 {qid, q_off, tid, t_off, m, n, dlo, dhi, kind, qstep, tstep, qcomp}, q_off / t_off = the sequence offset
 // of DP base 0 (a window runs down from it when its step is -1); kinds 0 (fill), 1 / 2 (left / right z-drop extension),
@@ -2969,31 +2997,12 @@ extern "C" int telr_debug_dp(telr_ctx *ctx, const telr_seqset *qs, const telr_se
     if (!ctx || !qs || !tg || !mo || (np > 0 && (!probs || !res || !tb_off || !cig)) || np < 0 || np > (1 << 20)) return TELR_E_ARG;
     TRY(check_map_opt(ctx, mo));
     if (np == 0) return TELR_OK;
-    const auto even_lo = [](int lo) { return lo - (lo & 1); };
     std::vector<DpProb> hp((size_t)np);
     for (int x = 0; x < np; ++x) {
-        const int32_t *p = probs + (size_t)x * 12;
-        const int qid = p[0], q_off = p[1], tid = p[2], t_off = p[3], m = p[4], n = p[5], dlo = p[6], dhi = p[7], kind = p[8], qstep = p[9], tstep = p[10], qcomp = p[11];
-        auto bad = [&](const char *why) { ctx->err = "telr_debug_dp: problem " + std::to_string(x) + ": " + why; return TELR_E_ARG; };
-        if (qid < 0 || qid >= qs->n || tid < 0 || tid >= tg->n) return bad("sequence id");
-        if (m < 1 || n < 1 || (qstep != 1 && qstep != -1) || (tstep != 1 && tstep != -1) || (qcomp != 0 && qcomp != 1)) return bad("lengths or steps");
-        const int64_t qlo = qstep > 0 ? q_off : (int64_t)q_off - m + 1, tlo = tstep > 0 ? t_off : (int64_t)t_off - n + 1;
-        if (qlo < 0 || qlo + m > qs->len[qid] || tlo < 0 || tlo + n > tg->len[tid]) return bad("window outside its sequence");
-        if (dlo & 1) return bad("dlo must be even");
-        const int D = dhi - dlo + 1, dl = n - m;
-        if (kind == 0 || kind == 3) {        // fill: W diagonals of slack on either side of the corner-to-corner range
-            const int W = dhi - (dl > 0 ? dl : 0);
-            if (W < 0 || dlo != even_lo((dl < 0 ? dl : 0) - W)) return bad("fill band");
-            if (kind == 0 ? D > DP_DMAX : D <= DP_DMAX) return bad("fill band width (kind 3 = wider than DP_DMAX)");
-        } else if (kind == 1 || kind == 2 || kind == 5) {      // the extension band
-            if (dlo != even_lo(-mo->ext_band) || dhi != mo->ext_band) return bad("extension band");
-            if (kind == 5 && !(mo->bw_long > mo->bw && (dl > mo->bw || -dl > mo->bw))) return bad("long-gap fill needs bw_long > bw and |n - m| > bw");
-            if (kind != 5 && (m > mo->ext_max || n > m + mo->ext_band)) return bad("extension window");
-        } else return bad("kind");
-        DpProb &P = hp[(size_t)x];
-        P.qi0 = qs->boff[qid] + q_off; P.ti0 = tg->boff[tid] + t_off; P.tb_off = P.cig_off = 0;
-        P.m = m; P.n = n; P.dlo = dlo; P.dhi = dhi; P.qstep = (int8_t)qstep; P.tstep = (int8_t)tstep; P.qcomp = (int8_t)qcomp; P.kind = (int8_t)kind;
-        P.chain = x; P.pad[0] = P.pad[1] = 0;
+        if (const char *why = debug_prob_row(qs, tg, mo, probs + (size_t)x * 12, &hp[(size_t)x])) {
+            ctx->err = "telr_debug_dp: problem " + std::to_string(x) + ": " + why; return TELR_E_ARG;
+        }
+        hp[(size_t)x].chain = x;
     }
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -3022,6 +3031,165 @@ extern "C" int telr_debug_dp(telr_ctx *ctx, const telr_seqset *qs, const telr_se
         tb_off[x] = P.tb_off;
         for (int k = R.nops - 1; k >= 0; --k) cig[w++] = raw[(size_t)P.cig_off + k];        // the trace-back writes end -> start
     }
+    return TELR_OK;
+}
+
+// The stitch and chain-sum kernels on hand-made per-problem results (test tap: stitch_count -- k_stitch_count, the offset scan,
+// k_chain_stats -- and k_stitch_write as the map path launches them; no DP, no telr_result).  Chain k owns problems
+// [p_off[k], p_off[k + 1]) (at least one) and reads its first one forwards when has_left[k]; prob: np x 5 {score, bi, bj, mlen,
+// mcols}; the CIGAR words of problem x (len << 4 | op, op 0..2, len >= 1) are cig[cig_off[x] .. cig_off[x + 1]) in STORAGE order, as
+// the trace-back leaves them in the raw buffer (end to start of the DP problem).  Out: chain_out n_chain x 9 {dp, mlen, blen, l_bi,
+// l_bj, r_bi, r_bj, n_cigar, first op in cig_out}, and the stitched CIGARs in cig_out[cig_cap].
+extern "C" int telr_debug_stitch(telr_ctx *ctx, int32_t n_chain, const int32_t *p_off, const int32_t *has_left, const int32_t *prob,
+                                 const int64_t *cig_off, const uint32_t *cig, int32_t cx_scale, int32_t *chain_out, uint32_t *cig_out, int64_t cig_cap)
+{
+    (void)hipGetLastError();
+    if (!ctx || n_chain < 0 || n_chain > (1 << 20) || !p_off || cig_cap < 0 || (n_chain > 0 && (!has_left || !prob || !cig_off || !chain_out))) return TELR_E_ARG;
+    if (cx_scale < 0 || cx_scale > 64) { ctx->err = "telr_debug_stitch: cx_scale 0..64"; return TELR_E_ARG; }
+    if (p_off[0] != 0) { ctx->err = "telr_debug_stitch: p_off[0] must be 0"; return TELR_E_ARG; }
+    if (n_chain == 0) return TELR_OK;
+    for (int k = 0; k < n_chain; ++k) {
+        if (p_off[k + 1] <= p_off[k] || p_off[k + 1] > (1 << 22)) { ctx->err = "telr_debug_stitch: chain " + std::to_string(k) + ": p_off must ascend (a chain has a problem) up to 2^22"; return TELR_E_ARG; }
+        if (has_left[k] != 0 && has_left[k] != 1) { ctx->err = "telr_debug_stitch: chain " + std::to_string(k) + ": has_left must be 0 or 1"; return TELR_E_ARG; }
+    }
+    const int nk = n_chain, np = p_off[nk];
+    if (cig_off[0] != 0) { ctx->err = "telr_debug_stitch: cig_off[0] must be 0"; return TELR_E_ARG; }
+    for (int x = 0; x < np; ++x) if (cig_off[x + 1] < cig_off[x] || cig_off[x + 1] - cig_off[x] > (1 << 24)) { ctx->err = "telr_debug_stitch: problem " + std::to_string(x) + ": cig_off must not descend"; return TELR_E_ARG; }
+    const int64_t nraw = cig_off[np];
+    if (nraw > 0 && (!cig || !cig_out)) return TELR_E_ARG;
+    int64_t len_sum = 0;
+    for (int64_t z = 0; z < nraw; ++z) {
+        if ((cig[z] & 0xf) > 2 || (cig[z] >> 4) == 0) { ctx->err = "telr_debug_stitch: CIGAR word " + std::to_string(z) + ": op 0..2 and a length"; return TELR_E_ARG; }
+        len_sum += cig[z] >> 4;
+    }
+    if (len_sum >= (1 << 28)) { ctx->err = "telr_debug_stitch: the op lengths must sum to less than 2^28 (a merged op holds them)"; return TELR_E_ARG; }
+    std::vector<DpProb> hp((size_t)np); std::vector<DpRes> hr((size_t)np); std::vector<KeptLite> hl((size_t)nk);
+    memset(hp.data(), 0, (size_t)np * sizeof(DpProb)); memset(hl.data(), 0, (size_t)nk * sizeof(KeptLite));
+    for (int k = 0; k < nk; ++k) {
+        hl[(size_t)k].qs = hl[(size_t)k].rs = has_left[k];          // (stitch_count: a left extension when the chain starts inside both sequences)
+        int64_t a[5] = { 0, 0, 0, 0, 0 };
+        for (int x = p_off[k]; x < p_off[k + 1]; ++x) {
+            const int32_t *v = prob + (size_t)x * 5;
+            if (v[1] < 0 || v[2] < 0 || v[3] < 0 || v[4] < 0) { ctx->err = "telr_debug_stitch: problem " + std::to_string(x) + ": bi, bj, mlen, mcols must not be negative"; return TELR_E_ARG; }
+            a[0] += v[0] < 0 ? -(int64_t)v[0] : v[0];
+            for (int f = 1; f < 5; ++f) a[f] += v[f];
+            DpProb &P = hp[(size_t)x]; P.cig_off = cig_off[x]; P.chain = k; P.m = P.n = 1; P.qstep = P.tstep = 1;
+            DpRes &R = hr[(size_t)x]; R.score = v[0]; R.bi = v[1]; R.bj = v[2]; R.mlen = v[3]; R.mcols = v[4]; R.nops = (int32_t)(cig_off[x + 1] - cig_off[x]); R.cells = 0; R.tbases = 0;
+        }
+        if (a[0] >= (1 << 30) || a[1] + a[2] >= (1 << 30) || a[3] >= (1 << 30)) { ctx->err = "telr_debug_stitch: chain " + std::to_string(k) + ": the sums must stay below 2^30"; return TELR_E_ARG; }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DpProb *d_probs; DpRes *d_res; uint32_t *d_rawcig, *d_fin;
+    TRY(ctx_buf_t(ctx, "dbg_probs", (size_t)np, &d_probs));
+    TRY(ctx_buf_t(ctx, "dbg_res", (size_t)np, &d_res));
+    TRY(ctx_buf_t(ctx, "dbg_rawcig", (size_t)nraw + 16, &d_rawcig));
+    HIPCHK(hipMemcpyAsync(d_probs, hp.data(), (size_t)np * sizeof(DpProb), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_res, hr.data(), (size_t)np * sizeof(DpRes), hipMemcpyHostToDevice, st));
+    if (nraw) HIPCHK(hipMemcpyAsync(d_rawcig, cig, (size_t)nraw * 4, hipMemcpyHostToDevice, st));
+    telr_map_opt mo; memset(&mo, 0, sizeof(mo)); mo.cx_scale = cx_scale;
+    const std::vector<int32_t> h_poff(p_off, p_off + nk + 1);
+    StitchOut so;
+    TRY(stitch_count(ctx, st, host_threads(), &mo, hl.data(), nk, h_poff, d_probs, np, d_res, d_rawcig, &so));
+    const int64_t tot = so.h_foff[nk];
+    if (tot > cig_cap) { ctx->err = "telr_debug_stitch: cig_cap too small"; return TELR_E_RANGE; }
+    TRY(ctx_buf_t(ctx, "dbg_stitched", (size_t)tot + 1, &d_fin));
+    HIPCHK(hipMemsetAsync(d_fin, 0xff, ((size_t)tot + 1) * 4, st));          // an op nobody writes shows
+    hipLaunchKernelGGL(k_stitch_write, dim3((np + 31) / 32), dim3(256), 0, st, np, so.d_sp, d_probs, d_res, so.d_sv, d_rawcig, so.d_foff, d_fin);
+    HIPCHK(hipGetLastError());
+    if (tot) HIPCHK(hipMemcpyAsync(cig_out, d_fin, (size_t)tot * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < nk; ++k) {
+        const ChainStat &S = so.h_cs[k];
+        const int32_t w[9] = { S.dp, S.mlen, S.blen, S.l_bi, S.l_bj, S.r_bi, S.r_bj, (int32_t)(so.h_foff[k + 1] - so.h_foff[k]), (int32_t)so.h_foff[k] };
+        memcpy(chain_out + (size_t)k * 9, w, sizeof(w));
+    }
+    return TELR_OK;
+}
+
+// From a problem list to the records' numbers (test tap: dp_passes -- both passes --, stitch_count, k_stitch_write and chain_numbers
+// as the map path runs them; no telr_result).  chains: n_chain x 7 {qid, tid, rev, qs, qe, rs, re}, the query interval on the
+// chain's strand; chain k owns the rows [prob_off[k], prob_off[k + 1]) of probs (telr_debug_dp rows, checked as there), which are
+// [kind 1]? (kind 0 | 3 | 5)+ [kind 2]? on the chain's sequences and strand, the kind-1 row there exactly when qs > 0 and rs > 0, the
+// kind-2 row exactly when qe < qlen and re < tlen.  Out: chain_out n_chain x 9 {qs, qe, ts, te, mlen, blen, dp_score, n_cigar, first
+// op in cig_out} (qs / qe on the forward read, as in a record); prob_out np x 9 {class of the first pass, retry flag, score, bi, bj,
+// mlen, mcols, nops, cells} after the retry merge; the stitched CIGARs; *n_retry; acc_out[TELR_N_DPCLS * 4 + 1] of k_dp_account.
+extern "C" int telr_debug_align(telr_ctx *ctx, const telr_seqset *qs, const telr_seqset *tg, const telr_map_opt *mo, int32_t n_chain,
+                                const int32_t *chains, const int32_t *prob_off, const int32_t *probs, int32_t *chain_out, int32_t *prob_out,
+                                uint32_t *cig_out, int64_t cig_cap, int32_t *n_retry_out, int64_t *acc_out)
+{
+    (void)hipGetLastError();
+    if (!ctx || !qs || !tg || !mo || n_chain < 0 || n_chain > (1 << 20) || !prob_off || !n_retry_out || !acc_out || cig_cap < 0 ||
+        (n_chain > 0 && (!chains || !probs || !chain_out || !prob_out || !cig_out))) return TELR_E_ARG;
+    TRY(check_map_opt(ctx, mo));
+    *n_retry_out = 0;
+    for (int z = 0; z <= TELR_N_DPCLS * 4; ++z) acc_out[z] = 0;
+    if (prob_off[0] != 0) { ctx->err = "telr_debug_align: prob_off[0] must be 0"; return TELR_E_ARG; }
+    if (n_chain == 0) return TELR_OK;
+    const int nk = n_chain;
+    for (int k = 0; k < nk; ++k)
+        if (prob_off[k + 1] <= prob_off[k] || prob_off[k + 1] > (1 << 20)) { ctx->err = "telr_debug_align: chain " + std::to_string(k) + ": prob_off must ascend (a chain has a fill) up to 2^20"; return TELR_E_ARG; }
+    const int np = prob_off[nk];
+    std::vector<DpProb> hp((size_t)np); std::vector<KeptLite> hl((size_t)nk);
+    memset(hl.data(), 0, (size_t)nk * sizeof(KeptLite));
+    for (int k = 0; k < nk; ++k) {
+        const int32_t *c = chains + (size_t)k * 7;
+        const int qid = c[0], tid = c[1], rev = c[2], cqs = c[3], cqe = c[4], crs = c[5], cre = c[6];
+        auto bad = [&](const std::string &why) { ctx->err = "telr_debug_align: chain " + std::to_string(k) + ": " + why; return TELR_E_ARG; };
+        if (qid < 0 || qid >= qs->n || tid < 0 || tid >= tg->n || (rev != 0 && rev != 1)) return bad("sequence id or strand");
+        const int qlen = qs->len[qid], tlen = tg->len[tid];
+        if (cqs < 0 || cqe < cqs || cqe > qlen || crs < 0 || cre < crs || cre > tlen) return bad("interval outside its sequence");
+        const bool has_left = cqs > 0 && crs > 0, has_right = cqe < qlen && cre < tlen;
+        const int p0 = prob_off[k], p1 = prob_off[k + 1];
+        for (int x = p0; x < p1; ++x) {
+            const int32_t *p = probs + (size_t)x * 12;
+            if (const char *why = debug_prob_row(qs, tg, mo, p, &hp[(size_t)x])) return bad("problem " + std::to_string(x) + ": " + why);
+            if (p[0] != qid || p[2] != tid || p[11] != rev) return bad("problem " + std::to_string(x) + ": not on the chain's sequences and strand");
+            const int kind = p[8];
+            if ((kind == 1) != (x == p0 && has_left)) return bad("a kind-1 row comes first, exactly when qs > 0 and rs > 0");
+            if ((kind == 2) != (x == p1 - 1 && has_right)) return bad("a kind-2 row comes last, exactly when qe < qlen and re < tlen");
+            hp[(size_t)x].chain = k;
+        }
+        if (p1 - p0 - (has_left ? 1 : 0) - (has_right ? 1 : 0) < 1) return bad("no fill");
+        KeptLite &L = hl[(size_t)k];
+        L.qid = qid; L.tid = tid; L.rev = rev; L.qs = cqs; L.qe = cqe; L.rs = crs; L.re = cre;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int NT = host_threads();
+    DpProb *d_probs; DpRes *d_res; uint32_t *d_rawcig = nullptr, *d_fin; const int32_t *d_retry = nullptr; int32_t n_retry = 0;
+    TRY(ctx_buf_t(ctx, "dbg_probs", (size_t)np, &d_probs));
+    HIPCHK(hipMemcpyAsync(d_probs, hp.data(), (size_t)np * sizeof(DpProb), hipMemcpyHostToDevice, st));
+    TRY(dp_passes(ctx, st, qs, tg, mo, d_probs, np, &d_res, &d_rawcig, &n_retry, &d_retry));
+    const std::vector<int32_t> h_poff(prob_off, prob_off + nk + 1);
+    StitchOut so;
+    TRY(stitch_count(ctx, st, NT, mo, hl.data(), nk, h_poff, d_probs, np, d_res, d_rawcig, &so));
+    const int64_t tot = so.h_foff[nk];
+    if (tot > cig_cap) { ctx->err = "telr_debug_align: cig_cap too small"; return TELR_E_RANGE; }
+    TRY(ctx_buf_t(ctx, "dbg_stitched", (size_t)tot + 1, &d_fin));
+    HIPCHK(hipMemsetAsync(d_fin, 0xff, ((size_t)tot + 1) * 4, st));          // an op nobody writes shows
+    hipLaunchKernelGGL(k_stitch_write, dim3((np + 31) / 32), dim3(256), 0, st, np, so.d_sp, d_probs, d_res, so.d_sv, d_rawcig, so.d_foff, d_fin);
+    HIPCHK(hipGetLastError());
+    std::vector<DpRes> hr((size_t)np); std::vector<int32_t> hretry((size_t)np);
+    HIPCHK(hipMemcpyAsync(hp.data(), d_probs, (size_t)np * sizeof(DpProb), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hr.data(), d_res, (size_t)np * sizeof(DpRes), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hretry.data(), d_retry, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+    if (tot) HIPCHK(hipMemcpyAsync(cig_out, d_fin, (size_t)tot * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    telr_aln *kal = kept_records(ctx, NT, qs, tg, hl.data(), nk);
+    chain_numbers(NT, hl.data(), nk, so.h_cs, kal);
+    for (int k = 0; k < nk; ++k) {
+        const telr_aln &r = kal[k];
+        const int32_t w[9] = { r.qs, r.qe, r.ts, r.te, r.mlen, r.blen, r.dp_score, (int32_t)(so.h_foff[k + 1] - so.h_foff[k]), (int32_t)so.h_foff[k] };
+        memcpy(chain_out + (size_t)k * 9, w, sizeof(w));
+    }
+    for (int x = 0; x < np; ++x) {
+        const DpRes &R = hr[(size_t)x];
+        const int32_t w[9] = { hp[(size_t)x].pad[0] & 0xff, hretry[(size_t)x], R.score, R.bi, R.bj, R.mlen, R.mcols, R.nops, R.cells };
+        memcpy(prob_out + (size_t)x * 9, w, sizeof(w));
+    }
+    *n_retry_out = n_retry;
+    for (int z = 0; z <= TELR_N_DPCLS * 4; ++z) acc_out[z] = (int64_t)so.h_acc[z];
     return TELR_OK;
 }
 
