@@ -260,6 +260,19 @@ int  telr_seqset_extract(telr_ctx *ctx, const telr_seqset *s, int64_t n, const i
  * null pointer where n > 0; TELR_E_RANGE from 2^31 - 16 pieces on. */
 int  telr_seqset_pieces(telr_ctx *ctx, const telr_seqset *parent, int32_t n, const int32_t *idx, const int32_t *start, const int32_t *len,
                         const uint8_t *rc /* NULL = all forward */, telr_seqset **out);
+/* Pieces CONCATENATED into a new set (tests/bridge_ref.py: join states the definition in plain Python): sequence o of
+ * *out is pieces piece_off[o] .. piece_off[o + 1] one after the other, in order; a piece is what telr_seqset_pieces defines (bases
+ * [start, start + len) of parent[idx], reverse-complemented when rc != 0, mask bits carried).  A sequence may have no pieces or pieces
+ * of length 0 (both give what they hold: nothing); pieces may repeat and overlap.  The set has the normal layout (64-base-aligned
+ * offsets, zero padding in both word arrays, an N has code 0) and carries no qualities.  n_out == 0 gives an empty set.  Made on the
+ * device from the packed words of `parent`, one lane per 2-bit output word; the bytes are the same on every run.  The set is the
+ * caller's (telr_seqset_free).  Checked on the host before any launch with the codes of telr_seqset_pieces (TELR_E_ARG: a negative
+ * n_out, an idx outside the set, a negative start or len, start + len beyond the sequence, a null pointer where one is read), and
+ * TELR_E_ARG for a piece_off that does not start at 0 or decreases; TELR_E_RANGE from 2^31 - 16 sequences or pieces on and for a
+ * joined length above INT32_MAX.  A refused call leaves no set behind. */
+int  telr_seqset_join(telr_ctx *ctx, const telr_seqset *parent, int32_t n_out, const int64_t *piece_off /* [n_out + 1] */,
+                      const int32_t *idx, const int32_t *start, const int32_t *len, const uint8_t *rc /* NULL = all forward */,
+                      telr_seqset **out);
 
 /* ---- FASTA / FASTQ text -> the arrays above (host code; plain files, not gzip).  Replaces handing the file names to
  *      ngmlr / minimap2 (src/telr/TELR_alignment.py:31-51, 69-82).  Names end at the first white space. */
@@ -632,6 +645,62 @@ int  telr_draft_contigs(telr_ctx *ctx, const telr_result *r, int32_t n_targets, 
 int64_t telr_drafts_count(const telr_drafts *d);                      /* = n_calls */
 const telr_draft *telr_drafts_data(const telr_drafts *d);
 void telr_draft_contigs_free(telr_drafts *d);
+
+/* ---- a bridge of two reads for a call that no single read spans (opt-in; tests/bridge_ref.py is the checker).  A sibling
+ *      of telr_draft_contigs for the calls it leaves without a draft: every supporting read runs from one flank into the element and
+ *      ends there, so the call has clip signatures (kind 2) only.  An OWN definition: NOT an assembler, and NOT wtdbg2 or flye.  Two reads
+ *      are joined at ONE shared k-mer; no consensus is formed (polishing follows, as it follows a draft).  Records only: the sequences are
+ *      made by telr_seqset_join from the two pieces of a record.
+ * Input, validation and the CIGAR source are those of telr_draft_contigs.  Strand coordinates qs', qe' as in telr_call_insertions; the
+ *      walk and lo(x) / hi(x) as in telr_draft_contigs.  STRAND BASES of a record: the read as the record aligns it (the reverse
+ *      complement of the forward read on TELR_F_REV).
+ * Left candidate of call (tid, pos): a kind-2 signature s with s.tid == tid, |s.pos - pos| <= reach, s.qid in the call's read list and
+ *      s.pos == a.te for a = s.rec (a tail clip).  cL = qlen - qe'_a; U = strand bases [qe'_a, qlen); xL = max(a.ts, s.pos - flank).
+ *      VALID iff a has CIGAR ops, s.pos - xL >= min_flank, lo_a(xL) exists and is >= 0, and cL >= k.
+ * Right candidate: a kind-2 signature with s.pos == b.ts for b = s.rec (a head clip).  cR = qs'_b; V = strand bases [0, qs'_b);
+ *      xR = min(b.te, s.pos + flank).  VALID iff b has CIGAR ops, xR - s.pos >= min_flank, hi_b(xR) exists and is <= qlen, and cR >= k.
+ * Ranking: each side by the key (-clip length, -flank length, qid, rec, index of s); the first `pairs` of each side are kept.  n_left
+ *      and n_right are the valid counts before that cut.  Every kept (l, r) pair with different qid is voted.
+ * Vote:   Wn = min(window, cL); the window is U[cL - Wn, cL).  A window k-mer is USABLE iff it lies wholly inside the window, none of
+ *      its bases is N, and its value occurs exactly once among the window's N-free k-mers.  Every j in [0, cR - k] whose N-free k-mer of
+ *      V equals a usable k-mer at U offset i is a MATCH (i, j) with diagonal d = i - j.  bin(d) = floor(d / 128) (towards minus
+ *      infinity); score(b) = count(b) + count(b + 1); b* = the bin of the highest score, the smallest such b on a tie; votes =
+ *      score(b*).  The BAND matches are those in bins b* and b* + 1; the JUNCTION (i*, j*) is the band match at the lower-median place
+ *      when they are ordered by j (each j has at most one match); diag = i* - j*.
+ * Pair choice: the pair with the most votes; on a tie the smaller left rank, then the smaller right rank.  It makes a bridge iff
+ *      votes >= min_votes and 1 <= len_l + len_r <= max_len; otherwise the call has none -- no second pair is tried.
+ * Bridge: left piece = strand bases [lo_a(xL), qe'_a + i*) of read a, right piece = strand bases [j*, hi_b(xR)) of read b; each is
+ *      reported on the forward read with start = lo (forward) or qlen - hi (TELR_F_REV) and rc as a draft reports it.  ins_off =
+ *      qe'_a - lo_a(xL); ins_len = i* + (cR - j*).  The contig is the left piece followed by the right piece: both read the same k
+ *      bases at the junction, so an error-free pair joins without a seam.  sig_l / sig_r = the two signatures' indices.
+ * A call with want[k] == 0 (want NULL = every call), or without a bridge: sig_l = sig_r = -1, n_left / n_right as found, zeros otherwise.
+ * STATED LIMITS.  Two clips that do not overlap but share a repeat (the two LTRs of one element) are joined at the repeat: the contig
+ *      then lacks what lies between them; the vote prefers the true overlap only when that overlap is longer than the repeat.  Chimeric
+ *      reads are not detected.  An overlap shorter than about min_votes surviving k-mers is not found.  Recall on real elements is not
+ *      measured.
+ * The output is the same on every run.  TELR_E_ARG: what telr_draft_contigs refuses, plus k outside 11 .. 15, window outside k .. 4096,
+ * pairs outside 1 .. 8, min_votes < 1.  TELR_E_RANGE from 2^31 - 16 (signature, call) pairs on.  opt NULL = the defaults. */
+typedef struct telr_bridge_opt {
+    int32_t flank;        /* 2000   */
+    int32_t min_flank;    /* 500    */
+    int32_t reach;        /* 50     */
+    int32_t max_len;      /* 100000 */
+    int32_t k;            /* 13     */
+    int32_t window;       /* 4096   */
+    int32_t min_votes;    /* 8      */
+    int32_t pairs;        /* 4      */
+} telr_bridge_opt;
+typedef struct telr_bridge { int32_t sig_l, sig_r, qid_l, start_l, len_l, rc_l, qid_r, start_r, len_r, rc_r,
+                             votes, diag, ins_off, ins_len, n_left, n_right; } telr_bridge;
+typedef struct telr_bridges telr_bridges;
+void telr_bridge_opt_default(telr_bridge_opt *o);
+int  telr_bridge_contigs(telr_ctx *ctx, const telr_result *r, int32_t n_targets, int64_t n_calls, const telr_ins_call *calls,
+                         const int64_t *read_off, const int32_t *reads, int64_t n_sig, const telr_ins_sig *sigs,
+                         const telr_seqset *read_set, const uint8_t *want /* [n_calls], NULL = every call */,
+                         const telr_bridge_opt *opt, telr_bridges **out);
+int64_t telr_bridges_count(const telr_bridges *b);                    /* = n_calls */
+const telr_bridge *telr_bridges_data(const telr_bridges *b);
+void telr_bridge_contigs_free(telr_bridges *b);
 
 /* ---- the reference's TE copies, annotated on the device for the liftover (opt-in).  Stands where the reference masks
  *      the reference genome with RepeatMasker and hands the BED to the liftover (src/telr/telr.py:132-159, TELR_te.py:391-469).  An OWN

@@ -93,6 +93,25 @@ class Draft(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sig", "qid", "start", "len", "rc", "ins_off", "ins_len", "set_index")]
 
 
+class BridgeOpt(C.Structure):
+    """telr_bridge_opt: the options of telr_bridge_contigs (defaults: BridgeOpt.default())"""
+    _fields_ = [(n, C.c_int32) for n in ("flank", "min_flank", "reach", "max_len", "k", "window", "min_votes", "pairs")]
+
+    @classmethod
+    def default(cls, **kw):
+        o = cls(2000, 500, 50, 100000, 13, 4096, 8, 4)
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("BridgeOpt has no field %r" % k)
+            setattr(o, k, int(v))
+        return o
+
+
+class Bridge(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sig_l", "sig_r", "qid_l", "start_l", "len_l", "rc_l", "qid_r", "start_r", "len_r", "rc_r",
+                                         "votes", "diag", "ins_off", "ins_len", "n_left", "n_right")]
+
+
 class RefTeOpt(C.Structure):
     """telr_refte_opt: the options of telr_annotate_hits (defaults: RefTeOpt.default())"""
     _fields_ = [(n, C.c_int32) for n in ("min_len", "min_mapq", "join_gap", "reserved")]
@@ -148,6 +167,8 @@ GENO_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsGt._fields_])
 assert GENO_DTYPE.itemsize == C.sizeof(InsGt) == 16 and C.sizeof(GenoOpt) == 32
 DRAFT_DTYPE = _np.dtype([(n, _np.int32) for n, _ in Draft._fields_])
 assert DRAFT_DTYPE.itemsize == C.sizeof(Draft) == 32 and C.sizeof(DraftOpt) == 32
+BRIDGE_DTYPE = _np.dtype([(n, _np.int32) for n, _ in Bridge._fields_])
+assert BRIDGE_DTYPE.itemsize == C.sizeof(Bridge) == 64 and C.sizeof(BridgeOpt) == 32
 TILE_DTYPE = _np.dtype([(n, _np.int32) for n, _ in Tile._fields_])
 TE_FEAT_DTYPE = _np.dtype([(n, _np.int32) for n, _ in TeFeat._fields_])
 assert TILE_DTYPE.itemsize == C.sizeof(Tile) == 12 and TE_FEAT_DTYPE.itemsize == C.sizeof(TeFeat) == 28 and C.sizeof(RefTeOpt) == 16

@@ -6,7 +6,7 @@ boundary (TELR_alignment.py:69-82 and the five other sites listed in include/tel
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._abi import IdxOpt, MapOpt, Counters, InsOpt, GenoOpt, DraftOpt, RefTeOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, DRAFT_DTYPE, TILE_DTYPE, \
+from ._abi import IdxOpt, MapOpt, Counters, InsOpt, GenoOpt, DraftOpt, BridgeOpt, RefTeOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, DRAFT_DTYPE, BRIDGE_DTYPE, TILE_DTYPE, \
     TE_FEAT_DTYPE, TELR_E_ARG, TELR_E_RANGE, MF_PER_TARGET, MF_KEEP_CIGARS, N_STAGES, N_DPCLS, STITCH_CHAIN_COLUMNS, ALIGN_CHAIN_COLUMNS, ALIGN_PROB_COLUMNS
 from .fasta import concat
 
@@ -462,6 +462,35 @@ class SeqSet:
             raise _lib.TelrError("telr_seqset_pieces: %s [%s]" % (eng.L.telr_strerror(code).decode(), eng.L.telr_last_error(eng.h).decode()), code)
         out = SeqSet.__new__(SeqSet)
         out.eng = eng; out.h = h; out.len = length.copy(); out.n = n
+        return out
+
+    def join(self, piece_off, idx, start, length, rc=None, eng=None):
+        """new set whose sequence o is pieces piece_off[o] .. piece_off[o + 1] one after the other, each piece as in `pieces` (bases
+        [start, start + length) of sequence idx, reverse-complemented where rc != 0; rc None: all forward), joined on the device from the
+        packed form (telr_seqset_join): N stays N, a sequence may have no pieces, no qualities are carried"""
+        piece_off = np.ascontiguousarray(piece_off, dtype=np.int64)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        n = len(idx)
+        if len(piece_off) < 1:
+            raise ValueError("join: piece_off holds one offset more than there are sequences")
+        if len(start) != n or len(length) != n or int(piece_off[-1]) != n:
+            raise ValueError("join: one start and one length per index, piece_off[-1] of them")
+        if rc is not None:
+            rc = np.ascontiguousarray(rc, dtype=np.uint8)
+            if len(rc) != n:
+                raise ValueError("join: one rc flag per index")
+        eng = self.eng if eng is None else eng
+        h = C.c_void_p()
+        code = eng.L.telr_seqset_join(eng.h, self.h, len(piece_off) - 1, piece_off.ctypes.data, idx.ctypes.data, start.ctypes.data, length.ctypes.data,
+                                      None if rc is None else rc.ctypes.data, C.byref(h))
+        if code != 0:
+            raise _lib.TelrError("telr_seqset_join: %s [%s]" % (eng.L.telr_strerror(code).decode(), eng.L.telr_last_error(eng.h).decode()), code)
+        out = SeqSet.__new__(SeqSet)
+        out.eng = eng; out.h = h; out.n = len(piece_off) - 1
+        ends = np.concatenate([[0], np.cumsum(length, dtype=np.int64)])
+        out.len = (ends[piece_off[1:]] - ends[piece_off[:-1]]).astype(np.int32)
         return out
 
     def packed(self):
@@ -963,6 +992,34 @@ class Index:
         out.len = np.ascontiguousarray(drafts["len"][drafts["sig"] >= 0], dtype=np.int32); out.n = len(out.len)
         return drafts, out
 
+    def bridge_contigs(self, r, ic, read_set, opt=None, want=None):
+        """a bridge of two reads per call of `ic` that no single read spans (telr_bridge_contigs; include/telr_hip.h has the definition --
+        not an assembler): a read entering the insertion from the left and one entering it from the right, joined at one shared k-mer of
+        their clips.  read_set the SeqSet r was mapped from, opt an _abi.BridgeOpt (None: the defaults), want one flag per call (None:
+        every call) -> one BRIDGE_DTYPE record per call (sig_l = sig_r = -1: no bridge).  Records only: SeqSet.join makes the sequences
+        of the two pieces (qid_l, start_l, len_l, rc_l) and (qid_r, start_r, len_r, rc_r)."""
+        o = BridgeOpt.default() if opt is None else opt
+        calls = np.ascontiguousarray(ic.calls, dtype=INS_CALL_DTYPE)
+        sigs = np.ascontiguousarray(ic.sigs, dtype=INS_SIG_DTYPE)
+        read_off = np.ascontiguousarray(ic.read_off, dtype=np.int64)
+        reads = np.ascontiguousarray(ic.reads, dtype=np.int32)
+        if len(read_off) != len(calls) + 1 or (len(calls) and int(read_off[-1]) > len(reads)):
+            raise _lib.TelrError("telr_bridge_contigs: read_off must hold len(calls) + 1 offsets into reads")
+        if want is not None:
+            want = np.ascontiguousarray(np.asarray(want) != 0, dtype=np.uint8)
+            if len(want) != len(calls):
+                raise _lib.TelrError("telr_bridge_contigs: one want flag per call")
+        h = C.c_void_p()
+        L = self.eng.L
+        rc = L.telr_bridge_contigs(self.eng.h, r, self.targets.n, len(calls), calls.ctypes.data, read_off.ctypes.data, reads.ctypes.data,
+                                   len(sigs), sigs.ctypes.data, read_set.h, None if want is None else want.ctypes.data, C.byref(o), C.byref(h))
+        if rc != 0:
+            raise _lib.TelrError("telr_bridge_contigs: %s [%s]" % (L.telr_strerror(rc).decode(), L.telr_last_error(self.eng.h).decode()), rc)
+        try:
+            return _np_from(L.telr_bridges_data(h), int(L.telr_bridges_count(h)), BRIDGE_DTYPE)
+        finally:
+            L.telr_bridge_contigs_free(h)
+
     # ---- debug taps for the stage-level parity tests ----------------------------------
     def debug_dump(self):
         L = self.eng.L
@@ -1011,7 +1068,7 @@ class PartIndex(Index):
     """An index over a target set of any total size: one Index per part (Engine.part_plan), the reads mapped against every part in turn
     and the per-part results merged on the device (telr_merge_parts; include/telr_hip.h has the definition).  `targets` is the full
     resident set and the merged result carries global target ids, so call_insertions, genotype_insertions, draft_contigs,
-    depth_medians, result_arrays, write_bam_device and the text writers work as on an Index.  Not for a multi-part index: qtarget /
+    bridge_contigs, depth_medians, result_arrays, write_bam_device and the text writers work as on an Index.  Not for a multi-part index: qtarget /
     MF_PER_TARGET, write_bam_slice, consensus, the debug taps.  All part indexes are resident together, and during a map the part
     results and the merged one live side by side."""
 

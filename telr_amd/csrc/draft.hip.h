@@ -19,9 +19,7 @@
 //                    ambiguity word; padding behind a draft is zero in both arrays.
 #pragma once
 
-struct DraftRec { int32_t ts, te, qs, qlen, rev, n_cigar; int64_t cigar_off; };      // qs on the record's own strand
 struct DraftCand { int64_t dlen; int32_t valid, fl, lo, n; };                         // a pair's share of the key and its piece of the read
-struct DraftPiece { int64_t src; int32_t len, rc; };                                  // src: first base of the piece in the parent set's base layout
 
 struct telr_drafts { std::vector<telr_draft> d; };
 
@@ -48,36 +46,6 @@ __global__ void __launch_bounds__(256) k_draft_pairs(const int64_t *__restrict__
     if (p >= np) return;
     const int32_t j = d_pair_owner(off, ns, p), k = first[j] + (int32_t)(p - off[j]), q = sigs[j].qid;
     psig[p] = j; pcall[p] = d_in_list(reads, read_off[k], read_off[k + 1], q) ? k : ~k;
-}
-
-// One wave walks the n CIGAR words at c from the state (ts, qs): lo = the smallest strand coordinate among the states at reference
-// coordinate xlo (the first op that holds xlo within [p, p + its reference length]), hi = the largest among those at xhi (the last
-// such op; an I at xhi is inside).  Every lane returns the same values.
-template <bool WANT_LO, bool WANT_HI>
-static __device__ __forceinline__ void draft_walk(const uint32_t *__restrict__ c, int32_t n, int64_t ts, int64_t qs, int64_t xlo, int64_t xhi, int lane,
-                                                  int64_t &lo, bool &flo, int64_t &hi, bool &fhi)
-{
-    const int64_t xend = WANT_HI ? xhi : xlo;
-    int64_t rbase = ts, qbase = qs;                       // the state before the step's first op (the same in every lane)
-    uint32_t next = lane < n ? c[lane] : 0u;
-    for (int32_t i0 = 0; i0 < n && rbase <= xend; i0 += 64) {
-        const int32_t i = i0 + lane;
-        const uint32_t word = next;
-        next = i < n - 64 ? c[i + 64] : 0u;               // the next step's words are on their way while this step's are summed
-        const int32_t op = (int32_t)(word & 15u);
-        const int64_t len = (int64_t)(word >> 4), r = (op == 0 || op == 2) ? len : 0, q = (op == 0 || op == 1) ? len : 0;
-        const int64_t ri = d_wave_incl<int64_t>(r, lane), qi = d_wave_incl<int64_t>(q, lane), p = rbase + ri - r, u = qbase + qi - q;
-        if (WANT_LO && !flo) {
-            const uint64_t m = __ballot(i < n && p <= xlo && xlo <= p + r);
-            if (m) { lo = __shfl(u + (op == 0 ? xlo - p : 0), __builtin_ctzll(m)); flo = true; }
-        }
-        if (WANT_HI) {
-            const uint64_t m = __ballot(i < n && p <= xhi && xhi <= p + r);
-            if (m) { hi = __shfl(u + (op == 0 ? xhi - p : op == 1 ? len : 0), 63 - __builtin_clzll(m)); fhi = true; }
-        }
-        if (WANT_LO && !WANT_HI && flo) break;
-        rbase += __shfl(ri, 63); qbase += __shfl(qi, 63);
-    }
 }
 
 __global__ void __launch_bounds__(256) k_draft_walk(const telr_ins_sig *__restrict__ sigs, const telr_ins_call *__restrict__ calls, const DraftRec *__restrict__ recs,
@@ -109,19 +77,6 @@ __global__ void __launch_bounds__(256) k_draft_walk(const telr_ins_sig *__restri
         }
     }
     if (lane == 0) cand[w] = out;
-}
-
-// first i in [0, n) with (tid, pos) of signature i >= v (UPPER: > v); the signatures ascend by (tid, pos)
-template <bool UPPER>
-static __device__ __forceinline__ int32_t draft_sig_bound(const telr_ins_sig *__restrict__ sigs, int32_t n, uint64_t v)
-{
-    int32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        const uint64_t x = ((uint64_t)(uint32_t)sigs[mid].tid << 32) | (uint32_t)sigs[mid].pos;
-        if (UPPER ? x <= v : x < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 struct DraftBest { int64_t dlen; int32_t has, fl, qid, rec, mate, j, lo, n; };
@@ -179,12 +134,6 @@ __global__ void __launch_bounds__(256) k_draft_select(const telr_ins_sig *__rest
     out[k] = d;
 }
 
-static __device__ __forceinline__ uint32_t draft_spread16(uint32_t v)     // bit i -> bit 2i
-{
-    v = (v | v << 8) & 0x00FF00FFu; v = (v | v << 4) & 0x0F0F0F0Fu; v = (v | v << 2) & 0x33333333u; v = (v | v << 1) & 0x55555555u;
-    return v;
-}
-
 // boff[nd + 1]: the drafts' base offsets in the output set (multiples of 64; boff[nd] = its padded bases = 16 * nw, nw even)
 __global__ void __launch_bounds__(256) k_draft_extract(const uint32_t *__restrict__ par2, const uint32_t *__restrict__ parn, const DraftPiece *__restrict__ piece,
                                                        const int64_t *__restrict__ boff, int32_t nd, int64_t nw, uint32_t *__restrict__ out2, uint32_t *__restrict__ outn)
@@ -205,7 +154,7 @@ __global__ void __launch_bounds__(256) k_draft_extract(const uint32_t *__restric
         if (P.rc) { code = ~d_rev16x2(code); m16 = __brev(m16) >> 16; }
         const uint32_t keep = kb == 16 ? 0xffffu : (1u << kb) - 1u;
         m16 &= keep;
-        code &= draft_spread16(keep & ~m16) * 3u;         // an N keeps its mask bit and code 0, as the packers write it
+        code &= d_spread16(keep & ~m16) * 3u;         // an N keeps its mask bit and code 0, as the packers write it
     }
     out2[w] = code;
     const uint32_t other = __shfl_xor(m16, 1);
@@ -295,20 +244,7 @@ extern "C" int telr_draft_contigs(telr_ctx *ctx, const telr_result *r, int32_t n
         e.ts = a.ts; e.te = a.te; e.qs = e.rev ? a.qlen - a.qe : a.qs; e.qlen = a.qlen; e.n_cigar = a.n_cigar; e.cigar_off = a.cigar_off;
     }
     // the signatures: as telr_call_insertions returned them -- ascending by (tid, pos), every index inside its array
-    uint64_t prev = 0;
-    for (int64_t j = 0; j < n_sig; ++j) {
-        const telr_ins_sig &s = sigs[j];
-        const std::string who = "signature " + std::to_string(j);
-        if (s.tid < 0 || s.tid >= n_targets) return bad(who + ": tid outside n_targets");
-        if (s.pos < 0) return bad(who + ": negative pos");
-        if (s.rec < 0 || (size_t)s.rec >= n) return bad(who + ": rec outside the records");
-        if (s.kind == 1 && (s.mate < 0 || (size_t)s.mate >= n)) return bad(who + ": mate outside the records");
-        if (s.qid < 0 || s.qid >= read_set->n) return bad(who + ": qid outside the read set");
-        if (r->alns[s.rec].qid != s.qid || (s.kind == 1 && r->alns[s.mate].qid != s.qid)) return bad(who + ": qid is not its records' read");
-        const uint64_t key = ((uint64_t)(uint32_t)s.tid << 32) | (uint32_t)s.pos;
-        if (j > 0 && key < prev) return bad(who + ": signatures not ascending by (tid, pos)");
-        prev = key;
-    }
+    if (!sig_list_check(n_sig, sigs, r->alns.data(), n, n_targets, read_set->n, &why)) return bad(why);
     telr_drafts *D = new telr_drafts();
     std::unique_ptr<telr_drafts> guard(D);
     telr_draft none; none.sig = -1; none.qid = 0; none.start = 0; none.len = 0; none.rc = 0; none.ins_off = 0; none.ins_len = 0; none.set_index = -1;

@@ -1,6 +1,6 @@
-// record_checks.h — what the call stages (telr_call_insertions, telr_genotype_insertions, telr_draft_contigs)
-// refuse in a result's records and in a call list, stated once.  These checks are all that stands between a caller's arrays and the
-// kernels that index with them.  Plain C++: no HIP call and no type of the engine's own, so they are pinned on a CPU and run under the
+// record_checks.h — what the call stages (telr_call_insertions, telr_genotype_insertions, telr_draft_contigs, telr_bridge_contigs;
+// DESIGN.md 5.10 - 5.12, 5.18) refuse in a result's records, in a call list and in a signature array, stated once.  These checks are
+// all that stands between a caller's arrays and the kernels that index with them.  Plain C++: no HIP call and no type of the engine's own, so they are pinned on a CPU and run under the
 // sanitizers from a stand-alone program (tools/record_checks_check.cpp).  The reason comes back in a std::string; the entry's name in
 // front of it ("telr_call_insertions: " ...) and the TELR_E_RANGE limits on the counts stay with the callers.
 //
@@ -49,6 +49,28 @@ static inline bool call_list_check(int64_t n_calls, const telr_ins_call *calls, 
             if (n_reads < 0 ? reads[j] < 0 : (reads[j] < 0 || reads[j] >= n_reads)) return bad(k, n_reads < 0 ? "negative read id" : "read id outside the read set");
             if (j > read_off[k] && reads[j] <= reads[j - 1]) return bad(k, "read list not ascending");
         }
+    }
+    return true;
+}
+
+// A signature array as telr_call_insertions returns it, against the n records it was made from (every one passed record_check) and a
+// read set of n_reads sequences: ascending by (tid, pos), every rec (and the mate of a kind 1) a record of the signature's own read.
+// True, or false with "signature j: <what>" in *why.  What telr_draft_contigs and telr_bridge_contigs refuse in their signatures.
+static inline bool sig_list_check(int64_t n_sig, const telr_ins_sig *sigs, const telr_aln *alns, size_t n, int32_t n_targets, int32_t n_reads, std::string *why)
+{
+    auto bad = [&](int64_t j, const char *what) { *why = "signature " + std::to_string(j) + ": " + what; return false; };
+    uint64_t prev = 0;
+    for (int64_t j = 0; j < n_sig; ++j) {
+        const telr_ins_sig &s = sigs[j];
+        if (s.tid < 0 || s.tid >= n_targets) return bad(j, "tid outside n_targets");
+        if (s.pos < 0) return bad(j, "negative pos");
+        if (s.rec < 0 || (size_t)s.rec >= n) return bad(j, "rec outside the records");
+        if (s.kind == 1 && (s.mate < 0 || (size_t)s.mate >= n)) return bad(j, "mate outside the records");
+        if (s.qid < 0 || s.qid >= n_reads) return bad(j, "qid outside the read set");
+        if (alns[s.rec].qid != s.qid || (s.kind == 1 && alns[s.mate].qid != s.qid)) return bad(j, "qid is not its records' read");
+        const uint64_t key = ((uint64_t)(uint32_t)s.tid << 32) | (uint32_t)s.pos;
+        if (j > 0 && key < prev) return bad(j, "signatures not ascending by (tid, pos)");
+        prev = key;
     }
     return true;
 }

@@ -1,8 +1,8 @@
 // What the stages on top of a mapped telr_result share: the CIGAR array on the device, the launch and bit-count
-// helpers, the wave and search inlines of the span / pair kernels, the funnel shifts of the piece cutters, and the stable permutation
-// sort over radix.hip.h.  Included by telr_engine.hip once telr_result is defined (telr_depth_medians is a caller), so before
-// every feature header (inscall, genotype, draft, refte, bam_in, seq_extract, part_merge, pileup, bam_dev): none of them takes a name
-// from a sibling.  The host-side record and call-list checks of the call stages are record_checks.h.
+// helpers, the wave and search inlines of the span / pair kernels, the funnel shifts of the piece cutters, the one-coordinate CIGAR walk
+// of the drafter and the bridge, and the stable permutation sort over radix.hip.h.  Included by telr_engine.hip once telr_result is
+// defined (telr_depth_medians is a caller), so before every feature header (inscall, genotype, draft, bridge, refte, bam_in, seq_extract,
+// part_merge, pileup, bam_dev): none of them takes a name from a sibling.  The host-side record and call-list checks of the call stages are record_checks.h.
 #pragma once
 #include "record_checks.h"
 
@@ -70,7 +70,7 @@ static __device__ __forceinline__ bool d_in_list(const int32_t *__restrict__ rea
     return lo < end && reads[lo] == q;
 }
 
-// ---- 2-bit packed bases: the funnel shifts of the piece cutters (k_draft_extract, k_seq_extract) -------------------------------------
+// ---- 2-bit packed bases: the funnel shifts of the piece cutters (k_draft_extract, k_seq_extract, k_seq_join, k_bridge_vote) ---------
 // 16 bases from base offset S of a packed array (S >= -15: what lies before the array reads as zero)
 static __device__ __forceinline__ uint32_t d_window2(const uint32_t *__restrict__ p, int64_t S)
 {
@@ -94,6 +94,71 @@ static __device__ __forceinline__ uint32_t d_rev16x2(uint32_t x)      // the six
     x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
     return __builtin_bswap32(x);
 }
+
+static __device__ __forceinline__ uint32_t d_spread16(uint32_t v)     // bit i -> bit 2i
+{
+    v = (v | v << 8) & 0x00FF00FFu; v = (v | v << 4) & 0x0F0F0F0Fu; v = (v | v << 2) & 0x33333333u; v = (v | v << 1) & 0x55555555u;
+    return v;
+}
+// 16 bases and their 16 mask bits from strand coordinate t (0 <= t < qlen) of the read of qlen bases at base offset src of a set: the read
+// itself, or with rc its reverse complement (read from the other end, base-reversed and complemented), so both strands cost the same.
+// What lies behind the read's last base is undefined: the caller masks it.
+static __device__ __forceinline__ void d_strand16(const uint32_t *__restrict__ p2, const uint32_t *__restrict__ pn, int64_t src, int32_t qlen, int rc, int64_t t,
+                                                  uint32_t &code, uint32_t &m16)
+{
+    const int64_t S = rc ? src + qlen - 16 - t : src + t;      // >= -15
+    code = d_window2(p2, S); m16 = d_window1(pn, S);
+    if (rc) { code = ~d_rev16x2(code); m16 = __brev(m16) >> 16; }
+}
+
+// ---- what the stages that cut reads at reference coordinates share (draft.hip.h, bridge.hip.h) ----------------------------------------
+struct DraftRec { int32_t ts, te, qs, qlen, rev, n_cigar; int64_t cigar_off; };      // qs on the record's own strand
+struct DraftPiece { int64_t src; int32_t len, rc; };                                  // src: first base of the piece in the parent set's base layout
+
+
+// One wave walks the n CIGAR words at c from the state (ts, qs): lo = the smallest strand coordinate among the states at reference
+// coordinate xlo (the first op that holds xlo within [p, p + its reference length]), hi = the largest among those at xhi (the last
+// such op; an I at xhi is inside).  Every lane returns the same values.
+template <bool WANT_LO, bool WANT_HI>
+static __device__ __forceinline__ void draft_walk(const uint32_t *__restrict__ c, int32_t n, int64_t ts, int64_t qs, int64_t xlo, int64_t xhi, int lane,
+                                                  int64_t &lo, bool &flo, int64_t &hi, bool &fhi)
+{
+    const int64_t xend = WANT_HI ? xhi : xlo;
+    int64_t rbase = ts, qbase = qs;                       // the state before the step's first op (the same in every lane)
+    uint32_t next = lane < n ? c[lane] : 0u;
+    for (int32_t i0 = 0; i0 < n && rbase <= xend; i0 += 64) {
+        const int32_t i = i0 + lane;
+        const uint32_t word = next;
+        next = i < n - 64 ? c[i + 64] : 0u;               // the next step's words are on their way while this step's are summed
+        const int32_t op = (int32_t)(word & 15u);
+        const int64_t len = (int64_t)(word >> 4), r = (op == 0 || op == 2) ? len : 0, q = (op == 0 || op == 1) ? len : 0;
+        const int64_t ri = d_wave_incl<int64_t>(r, lane), qi = d_wave_incl<int64_t>(q, lane), p = rbase + ri - r, u = qbase + qi - q;
+        if (WANT_LO && !flo) {
+            const uint64_t m = __ballot(i < n && p <= xlo && xlo <= p + r);
+            if (m) { lo = __shfl(u + (op == 0 ? xlo - p : 0), __builtin_ctzll(m)); flo = true; }
+        }
+        if (WANT_HI) {
+            const uint64_t m = __ballot(i < n && p <= xhi && xhi <= p + r);
+            if (m) { hi = __shfl(u + (op == 0 ? xhi - p : op == 1 ? len : 0), 63 - __builtin_clzll(m)); fhi = true; }
+        }
+        if (WANT_LO && !WANT_HI && flo) break;
+        rbase += __shfl(ri, 63); qbase += __shfl(qi, 63);
+    }
+}
+
+// first i in [0, n) with (tid, pos) of signature i >= v (UPPER: > v); the signatures ascend by (tid, pos)
+template <bool UPPER>
+static __device__ __forceinline__ int32_t draft_sig_bound(const telr_ins_sig *__restrict__ sigs, int32_t n, uint64_t v)
+{
+    int32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        const uint64_t x = ((uint64_t)(uint32_t)sigs[mid].tid << 32) | (uint32_t)sigs[mid].pos;
+        if (UPPER ? x <= v : x < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 
 // ---- stable permutation sort --------------------------------------------------------------------------------------------------------
 // LSD over a composite key, least significant group first: a permutation is carried from round to round, the keys of a round are

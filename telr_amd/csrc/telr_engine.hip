@@ -3337,6 +3337,7 @@ extern "C" int telr_seqset_attach_qual(telr_ctx *ctx, telr_seqset *s, const char
 #include "inscall.hip.h"
 #include "genotype.hip.h"
 #include "draft.hip.h"
+#include "bridge.hip.h"
 #include "refte.hip.h"
 #include "bam_in.hip.h"
 #include "bam_in_chunked.hip.h"

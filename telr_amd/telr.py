@@ -19,6 +19,10 @@ here; the flow is that of its `main` (src/telr/telr.py:22-189) with this project
                                one hop of the member headers decides and is handed on.  The outputs do not depend on the choice.
     calls                      telr_sv.call_insertions(..., reads=<the resident set>, genotype=True)      (not Sniffles)
     drafts                     telr_assembly.draft_loci(..., reads=<the resident set>)                     (not wtdbg2 / flye)
+    `--bridge`                 insertions that no single read spans: the caller runs with min_sized = 0, so a cluster of
+                               clips alone is a call; a call without a draft gets a bridge of two reads joined at one shared k-mer
+                               (Index.bridge_contigs + SeqSet.join; not an assembler); its row's sv_length and ins_seq become the
+                               bridge's ins_len and ALT.  Without the option nothing changes.
     asm10 index                Engine.index over the same resident reference
     a reference above 2^31     `--index_part_bases N`: the reference is cut into parts of at most N bases of padded extent, each
                                with an index of its own (Engine.index_parts); the reads are mapped against every part and the records merged
@@ -36,7 +40,8 @@ reference's bam2fasta leaves behind on the BAM route, is therefore not written; 
 Different from the reference on purpose: every value it prints a message for ends the run with status 1 (the reference goes on after
 four of its messages: -p below 1, a negative --af_flank_offset or --af_te_offset, --af_te_interval below 1); a reads file of any
 extension other than `.bam` is read as reads (a `.gz` on the device, see above; one it refuses, and every plain file, by the readers).  Not built: the ALT pre-screen, merge_rows on the
-caller's rows, the RepeatMasker route for families, the N-rank path, gzip on the BAM route.  On a multi-part reference: the occurrence
+caller's rows, the RepeatMasker route for families, the N-rank path, gzip on the BAM route, a bridge of more than two reads (an
+element longer than two reads' clips together stays without a contig).  On a multi-part reference: the occurrence
 cut-off of the seeding is per part, as with minimap2 -I (secondaries the unsplit index would not report), all parts are resident together,
 and `--ref_te engine` maps the tiles to the library, not to the reference, so it runs as it is.
 """
@@ -100,6 +105,8 @@ def get_args(argv=None):
                      "when it fits into half the free device memory next to its inflated stream, else chunks of the engine's own size (default = 0)")
     own.add_argument("--reads_chunk_mb", type=int, default=0, help="parse a gzip or BGZF reads file on the device in chunks of at most N MiB of text; "
                      "0: chunks of the engine's own size (default = 0)")
+    own.add_argument("--bridge", action="store_true", help="also call insertions that no single read spans (clusters of clipped reads alone) and draft them "
+                     "as a bridge of two reads joined at one shared k-mer (not an assembler)")
     own.add_argument("--sample", type=str, help="sample name (default: the reads file's name without its extension)")
     p._action_groups.append(opt)
     a = p.parse_args(argv)
@@ -248,15 +255,20 @@ def load_bam(eng, ix, args, tnames, tlens):
     return bi.qnames, bi.read_set, bi.result, lambda: (bi.free(), bi.read_set.free())
 
 
-def call_stage(ix, r, tnames, qnames, read_set, sample):
+def call_stage(ix, r, tnames, qnames, read_set, sample, bridge=False):
+    """bridge: the caller's min_sized = 0 -- a cluster of clips alone is a call (rep = -1, len = 0, ins_seq "N")"""
     from . import telr_sv
-    rows = telr_sv.call_insertions(ix, r, tnames, qnames, read_set, sample=sample, genotype=True)
-    return rows, ix.call_insertions(r)
+    from ._abi import InsOpt
+    opt = InsOpt.default(min_sized=0) if bridge else None
+    rows = telr_sv.call_insertions(ix, r, tnames, qnames, read_set, opt=opt, sample=sample, genotype=True)
+    return rows, ix.call_insertions(r, opt)
 
 
-def draft_stage(ix, r, ic, rows, read_set, chrom_ids):
+def draft_stage(ix, r, ic, rows, read_set, chrom_ids, bridge=False):
     from . import telr_assembly
-    return telr_assembly.draft_loci(ix, r, ic, rows, read_set, read_set, chrom_ids)
+    if not bridge:
+        return telr_assembly.draft_loci(ix, r, ic, rows, read_set, read_set, chrom_ids)
+    return telr_assembly.draft_loci(ix, r, ic, rows, read_set, read_set, chrom_ids, bridge=True)
 
 
 def ref_te_stage(eng, ix, tnames, lib_names, lib_seqs, args, bed_path):
@@ -284,7 +296,8 @@ EMPTY_RESULT = {"annotation": [], "liftover": [], "summary": {}, "af": {}}
 
 def run(args, engine=None):
     """One run of the pipeline with the Namespace of `get_args` -> dict(final = the rows of `<sample>.telr.json`, files = {name: path},
-    counts = {reads, records, calls, calls_without_draft, loci_annotated, loci_lifted, loci_written}, seconds = {stage: wall time}).
+    counts = {reads, records, calls, calls_without_draft, loci_annotated, loci_lifted, loci_written; with --bridge also calls_bridged},
+    seconds = {stage: wall time}).
     engine: an aligner.Engine to run on (default: a new one on args.device, closed at the end).  Engine errors are raised as TelrError;
     nothing falls back to another path."""
     from . import fasta, locus_pipeline, telr_sv
@@ -338,7 +351,8 @@ def run(args, engine=None):
         counts["records"] = int(eng.L.telr_result_count(r))
         done("reads", "%d reads, %d records (%s)" % (counts["reads"], counts["records"], route))
         # 4. the calls, genotyped
-        rows, ic = call_stage(ix, r, tnames, qnames, read_set, sample)
+        bridge = bool(getattr(args, "bridge", False))
+        rows, ic = call_stage(ix, r, tnames, qnames, read_set, sample, bridge) if bridge else call_stage(ix, r, tnames, qnames, read_set, sample)
         counts["calls"] = len(rows)
         done("calls", "%d insertion calls" % len(rows))
         if not rows:
@@ -348,9 +362,21 @@ def run(args, engine=None):
             done("outputs", "TELR found no non-reference TE insertions")
             return dict(final=final, files=files, counts=counts, seconds=seconds)
         # 5. a draft per call
-        loci, cset, skipped = draft_stage(ix, r, ic, rows, read_set, chrom_ids)
-        counts["calls_without_draft"] = len(skipped)
-        done("drafts", "%d drafts, %d calls without one" % (len(loci), len(skipped)))
+        if bridge:
+            loci, cset, skipped = draft_stage(ix, r, ic, rows, read_set, chrom_ids, True)
+            # a bridged call's row: the length and the ALT are the bridge's (the caller had no sized signature to take them from)
+            by_locus = {l["name"]: l for l in loci if l.get("bridged")}
+            for row in rows:
+                l = by_locus.get(telr_sv.locus_name(row))
+                if l is not None:
+                    row[3], row[7] = str(l["ins_len"]), l["alt"] or "N"
+            counts["calls_bridged"] = len(by_locus)
+            counts["calls_without_draft"] = len(skipped)
+            done("drafts", "%d drafts, %d of them bridges of two reads, %d calls without one" % (len(loci), len(by_locus), len(skipped)))
+        else:
+            loci, cset, skipped = draft_stage(ix, r, ic, rows, read_set, chrom_ids)
+            counts["calls_without_draft"] = len(skipped)
+            done("drafts", "%d drafts, %d calls without one" % (len(loci), len(skipped)))
         if hasattr(eng, "release_scratch"):
             eng.release_scratch()                   # stage 1 will not run again: its mapping scratch goes back to the device
         # 6. the asm10 index over the same resident reference

@@ -68,7 +68,7 @@ def annotate_vcf_with_counts(loci, reads_per_locus):
     return [list(r) + [str(len(x))] for r, x in zip(loci, reads_per_locus)]
 
 
-def draft_loci(index, result, ic, rows, read_set, reads, chrom_ids, window=1000, opt=None):
+def draft_loci(index, result, ic, rows, read_set, reads, chrom_ids, window=1000, opt=None, bridge=None):
     """The loci `locus_pipeline.run_loci(..., read_set=read_set)` takes, one per call that has a draft: index / result as in
     `telr_sv.call_insertions`, ic = `index.call_insertions(result)`, rows = the candidate-locus rows of those calls (one per call, in
     call order), read_set = the SeqSet the result was mapped from, reads = the same reads on the host (a list of str / bytes, or the
@@ -78,6 +78,11 @@ def draft_loci(index, result, ic, rows, read_set, reads, chrom_ids, window=1000,
     reads may also be a resident `aligner.SeqSet` (read_set itself): the contig pieces (the drafts' qid, start, len, rc) are then cut on
     the device in ONE `SeqSet.extract` call, and no host copy of the reads is needed.  The loci are equal between the two forms: both give
     the letters as the set holds them.
+    bridge: None -- what is said above; an `_abi.BridgeOpt` or True (the defaults) -- the calls without a draft go to
+    `index.bridge_contigs` (not an assembler either: a read entering the insertion from the left and one entering it from
+    the right, joined at one shared k-mer).  The contig set is then ONE `read_set.join` in locus order (one piece for a drafted call, two
+    for a bridged one) and the contig text comes from one `extract` call on it; a bridged locus carries alt = contig[ins_off : ins_off +
+    ins_len], bridged=True and ins_len, and only the calls with neither a draft nor a bridge are skipped.
     -> (list of dict(name, contig, alt, read_idx), the contigs' SeqSet in the same order -- `run_loci(..., contig_set=...)` --, the names
     of the calls without a draft)"""
     from . import telr_sv
@@ -85,6 +90,9 @@ def draft_loci(index, result, ic, rows, read_set, reads, chrom_ids, window=1000,
     if len(rows) != len(ic.calls):
         raise ValueError("draft_loci: one row per call")
     drafts, cset = index.draft_contigs(result, ic, read_set, opt)
+    if bridge is not None and bridge is not False:
+        cset.free()
+        return _bridged_loci(index, result, ic, rows, read_set, chrom_ids, window, drafts, None if bridge is True else bridge)
     wr = window_reads(index.result_arrays(result).alns, chrom_ids, rows, window) if len(rows) else []
 
     cut = None
@@ -104,6 +112,36 @@ def draft_loci(index, result, ic, rows, read_set, reads, chrom_ids, window=1000,
             if d["rc"]:
                 seq = revcomp(seq)
         loci.append(dict(name=telr_sv.locus_name(row), contig=seq.decode(), alt=row[7], read_idx=np.asarray(wr[k], np.int32)))
+    return loci, cset, skipped
+
+
+def _bridged_loci(index, result, ic, rows, read_set, chrom_ids, window, drafts, bopt):
+    """draft_loci with bridge: the drafted calls as they are, the others through index.bridge_contigs; one joined contig set"""
+    from . import telr_sv
+    br = index.bridge_contigs(result, ic, read_set, bopt, want=drafts["sig"] < 0)
+    wr = window_reads(index.result_arrays(result).alns, chrom_ids, rows, window) if len(rows) else []
+    piece_off, idx, start, length, rc = [0], [], [], [], []
+    kept, skipped = [], []
+    for k, row in enumerate(rows):
+        d, b = drafts[k], br[k]
+        if d["sig"] >= 0:
+            idx.append(d["qid"]); start.append(d["start"]); length.append(d["len"]); rc.append(d["rc"] != 0)
+        elif b["sig_l"] >= 0:
+            idx += [b["qid_l"], b["qid_r"]]; start += [b["start_l"], b["start_r"]]; length += [b["len_l"], b["len_r"]]; rc += [b["rc_l"] != 0, b["rc_r"] != 0]
+        else:
+            skipped.append(telr_sv.locus_name(row))
+            continue
+        piece_off.append(len(idx)); kept.append(k)
+    cset = read_set.join(piece_off, idx, start, length, rc, eng=index.eng)
+    text = cset.extract(np.arange(cset.n), np.zeros(cset.n, np.int32), cset.len)
+    loci = []
+    for k, seq in zip(kept, text):
+        row, contig = rows[k], seq.decode()
+        locus = dict(name=telr_sv.locus_name(row), contig=contig, alt=row[7], read_idx=np.asarray(wr[k], np.int32))
+        if drafts[k]["sig"] < 0:
+            b = br[k]
+            locus.update(alt=contig[int(b["ins_off"]):int(b["ins_off"]) + int(b["ins_len"])], bridged=True, ins_len=int(b["ins_len"]))
+        loci.append(locus)
     return loci, cset, skipped
 
 

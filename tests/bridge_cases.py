@@ -1,0 +1,333 @@
+"""Hand-built records and reads for telr_seqset_join and telr_bridge_contigs.  Every bridge case names the edge it
+claims and carries a check of that claim on the checker's own answer (tests/test_bridge_ref.py runs them on tests/bridge_ref.py;
+tests/test_gpu_bridge.py holds the engine to bridge_ref on the same inputs, field for field)."""
+import types
+
+import numpy as np
+
+import bridge_ref as bref
+import draft_ref as dref
+import inscall_ref as iref
+from draft_cases import call
+from inscall_cases import rec, pack
+from telr_amd._abi import INS_CALL_DTYPE, INS_SIG_DTYPE
+
+SIG_OPT = dict(min_clip=1, min_mapq=0, min_len=1 << 30)          # every clip is a signature, nothing else is
+SMALL = dict(flank=20, min_flank=5, min_votes=1)
+K = 13
+
+
+def as_ic(calls, sigs):
+    """checker-style calls and signatures -> what Index.draft_contigs / bridge_contigs take"""
+    a = np.zeros(len(calls), INS_CALL_DTYPE)
+    for k, c in enumerate(calls):
+        for f in ("tid", "pos", "len", "support", "n_sized", "rep"):
+            a[k][f] = c[f]
+    s = np.zeros(len(sigs), INS_SIG_DTYPE)
+    for k, x in enumerate(sigs):
+        for f in iref.SIG_FIELDS:
+            s[k][f] = x[f]
+    off = np.zeros(len(calls) + 1, np.int64)
+    off[1:] = np.cumsum([len(c["reads"]) for c in calls])
+    return types.SimpleNamespace(calls=a, sigs=s, read_off=off, reads=np.array([q for c in calls for q in c["reads"]], np.int32))
+
+
+def rand_seq(rng, n):
+    return "".join(rng.choice(list("ACGT"), n)) if n else ""
+
+
+# ---- join ---------------------------------------------------------------------------------------------------------------------------
+JOIN_LENS = (0, 1, 15, 16, 17, 31, 32, 33, 63, 64, 65)
+
+
+def join_parent(seed=5):
+    """four parent sequences with some N; sequence 3 has an N on both ends"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for n in (200, 131, 64, 97):
+        s = rng.choice(list("ACGTN"), n, p=[0.24, 0.24, 0.24, 0.24, 0.04])
+        out.append("".join(s))
+    out[3] = "N" + out[3][1:-1] + "N"
+    return out
+
+
+def join_cases(parent):
+    """-> (piece_off, idx, start, length, rc, names): one output sequence per case.  Every pair of JOIN_LENS as two pieces (so the second
+    piece starts at residues 0, 1, 15, 16, 17, 31 of a 32-base mask word and of the 16-base code word), a second piece at EVERY residue
+    mod 32, one and three pieces, three pieces inside one output word, rc on either or both pieces, an N on both sides of a seam,
+    repeated and overlapping pieces, a sequence without pieces and one of empty pieces only"""
+    off, idx, start, ln, rc, names = [0], [], [], [], [], []
+
+    def seq(name, pieces):
+        for p in pieces:
+            i, s, n, r = p
+            assert 0 <= s and s + n <= len(parent[i])
+            idx.append(i); start.append(s); ln.append(n); rc.append(r)
+        off.append(len(idx)); names.append(name)
+
+    for a in JOIN_LENS:
+        seq("one_%d" % a, [(0, 3, a, a % 2)])
+        for b in JOIN_LENS:
+            seq("two_%d_%d" % (a, b), [(0, 5, a, 0), (1, 7, b, 0)])
+    for r in range(32):                                   # the second piece starts at residue r of the output
+        seq("residue_%d" % r, [(0, 1, 64 + r, r % 2), (1, 2, 40, 1 - r % 2)])
+    for a, b, c in ((1, 1, 1), (3, 5, 4), (5, 0, 6), (16, 16, 16), (17, 30, 18), (64, 1, 64), (0, 0, 0)):
+        seq("three_%d_%d_%d" % (a, b, c), [(0, 9, a, 0), (1, 11, b, 1), (2, 0, c, 0)])
+    for ra in (0, 1):
+        for rb in (0, 1):
+            seq("rc_%d%d" % (ra, rb), [(0, 20, 37, ra), (1, 30, 41, rb)])
+    # sequence 3 is N at both ends: a seam with an N on both sides (forward end + forward start, and through rc)
+    n3 = len(parent[3])
+    seq("N_seam_ff", [(3, n3 - 10, 10, 0), (3, 0, 10, 0)])
+    seq("N_seam_rr", [(3, 0, 10, 1), (3, n3 - 10, 10, 1)])
+    seq("repeat", [(0, 10, 50, 0), (0, 10, 50, 0), (0, 10, 50, 1)])
+    seq("overlap", [(0, 10, 50, 0), (0, 30, 50, 0), (0, 0, 200, 0)])
+    seq("no_pieces", [])
+    seq("empty_pieces", [(0, 200, 0, 0), (1, 0, 0, 1)])
+    seq("whole_last", [(3, 0, n3, 0), (3, 0, n3, 1)])
+    return off, idx, start, ln, rc, names
+
+
+# ---- bridge: builders -----------------------------------------------------------------------------------------------------------------
+class Build:
+    """records, reads and calls of bridge cases: loci 100,000 apart; a left read = <fl> aligned bases ending at the locus + the clip U,
+    a right read = the clip V + <fl> aligned bases starting at the locus (both on the record's strand; rev = the read is stored
+    reverse-complemented and the record carries TELR_F_REV)"""
+
+    def __init__(self, seed=1):
+        self.rng = np.random.default_rng(seed)
+        self.recs, self.reads, self.calls = [], [], []
+
+    def read(self, strand_seq, rev):
+        self.reads.append(dref.revcomp(strand_seq) if rev else strand_seq)
+        return len(self.reads) - 1
+
+    def left(self, pos, U, fl=30, rev=0, qid=None, tid=0):
+        q = self.read(rand_seq(self.rng, fl) + U, rev) if qid is None else qid
+        n = fl + len(U)
+        qs, qe = (n - fl, n) if rev else (0, fl)
+        self.recs.append(rec(q, n, qs, qe, pos - fl, pos, [(fl, "M")] if fl else [], tid=tid, flags=8 if rev else 0))
+        return q
+
+    def right(self, pos, V, fl=30, rev=0, qid=None, tid=0):
+        q = self.read(V + rand_seq(self.rng, fl), rev) if qid is None else qid
+        n = fl + len(V)
+        qs, qe = (0, fl) if rev else (n - fl, n)
+        self.recs.append(rec(q, n, qs, qe, pos, pos + fl, [(fl, "M")] if fl else [], tid=tid, flags=8 if rev else 0))
+        return q
+
+    def locus(self):
+        return 100000 * (len(self.calls) + 1)
+
+    def call(self, pos, reads, tid=0):
+        self.calls.append(call(tid, pos, 0, reads))
+
+    def done(self):
+        alns, cig = pack(self.recs)
+        return alns, cig, iref.signatures(alns, cig, SIG_OPT), self.calls, self.reads
+
+
+def planted(rng, cL, cR, groups, k=K, n_at=()):
+    """U (cL bases) and V (cR bases), random but for the groups (d, n, i): a block of n + k - 1 bases (n matches) at U offset i and V
+    offset i - d.  n_at: (which, offset) places overwritten with N afterwards"""
+    U, V = list(rand_seq(rng, cL)), list(rand_seq(rng, cR))
+    for d, n, i in groups:
+        L = n + k - 1
+        assert 0 <= i and i + L <= cL and 0 <= i - d and i - d + L <= cR
+        j = i - d
+        V[j:j + L] = U[i:i + L]
+        for di, dj in ((i - 1, j - 1), (i + L, j + L)):      # the bases next to the block differ: no match more than n
+            if 0 <= di < cL and 0 <= dj < cR and V[dj] == U[di]:
+                V[dj] = "ACGT"[("ACGT".index(U[di]) + 1) % 4]
+    for which, at in n_at:
+        (U if which == "U" else V)[at] = "N"
+    return "".join(U), "".join(V)
+
+
+def single(name, U, V, opt=None, expect=None, rev=(0, 0), seed=1, want=None):
+    """one call, one left and one right read"""
+    b = Build(seed)
+    p = b.locus()
+    b.call(p, [b.left(p, U, rev=rev[0]), b.right(p, V, rev=rev[1])])
+    return dict(name=name, data=b.done(), opt=dict(SMALL, **(opt or {})), want=want, expect=expect)
+
+
+def bridge_cases():
+    """-> list of dict(name, data = (alns, cig, sigs, calls, reads), opt, want, expect): expect(out, seqs) asserts the case's claim on the
+    checker's answer"""
+    C = []
+    rng = np.random.default_rng(17)
+
+    def exp(**kw):
+        def f(out, seqs):
+            for key, v in kw.items():
+                assert [d[key] for d in out] == (v if isinstance(v, list) else [v]), (key, [d[key] for d in out], v)
+        return f
+
+    # cL == k: the one window k-mer; cL == k - 1: the left candidate is not valid
+    V = rand_seq(rng, 300)
+    C.append(single("cL_eq_k", V[100:100 + K], V, expect=exp(votes=1, diag=-100, n_left=1, n_right=1, len_l=20 + 0, ins_len=200)))
+    C.append(single("cL_eq_k_minus_1", V[100:100 + K - 1], V, expect=exp(sig_l=-1, n_left=0, n_right=1)))
+    C.append(single("cR_eq_k", rand_seq(rng, 50) + V[:K] + rand_seq(rng, 40), V[:K], expect=exp(votes=1, diag=50, ins_len=50 + K)))
+    C.append(single("cR_eq_k_minus_1", rand_seq(rng, 50) + V[:K] + rand_seq(rng, 40), V[:K - 1], expect=exp(sig_l=-1, n_left=1, n_right=0)))
+    # cL == window: the k-mer at U offset 0 is the window's first; cL == window + 1: it straddles the window's first base and must not count
+    for w in (64, 4096):
+        U = rand_seq(rng, w)
+        Vs = rand_seq(rng, 200) + U[:K] + rand_seq(rng, 100)
+        C.append(single("cL_eq_window_%d" % w, U, Vs, dict(window=w), exp(votes=1, diag=-200)))
+        C.append(single("cL_eq_window_plus_1_%d" % w, U[:1] + U, Vs[:201] + U[:K - 1] + Vs[201 + K - 1:], dict(window=w), exp(sig_l=-1, votes=0, n_left=1)))
+    # a window k-mer that occurs twice: V holds it three times.  Used, its bin would hold 3 matches and beat the true overlap's 2.
+    U, V = planted(rng, 600, 2000, [(-1000, 2, 300)])
+    X = U[100:100 + K]
+    U = U[:500] + X + U[500 + K:]
+    V = V[:200] + X + V[200 + K:240] + X + V[240 + K:280] + X + V[280 + K:]
+    C.append(single("window_duplicate", U, V, expect=exp(votes=2, diag=-1000)))
+    # an N inside a k-mer: a block of 20 matches loses the K k-mers that hold the N, on either side
+    for which in ("U", "V"):
+        U, V = planted(rng, 500, 500, [(30, 20, 200)], n_at=[(which, 200 + 16 if which == "U" else 170 + 16)])
+        C.append(single("N_in_%s" % which, U, V, expect=exp(votes=20 - K, diag=30)))
+    # the bins' edges.  floor(-129 / 128) = -2, floor(-128 / 128) = -1, floor(-1 / 128) = -1, floor(127 / 128) = 0, floor(128 / 128) = 1.
+    # groups (d, matches): two neighbours of an edge and a third one bin further; the score pairs bins b and b + 1 only
+    for name, groups, votes, diag in (
+            ("bin_edge_m129_m128", [(-129, 2, 400), (-128, 2, 900), (0, 3, 1400)], 5, 0),          # bins -2, -1, 0: score(-2) = 4, score(-1) = 5; the median is of d = 0
+            ("bin_edge_m129_m128_low", [(-300, 3, 400), (-129, 2, 900), (-128, 2, 1400)], 5, -300),  # bins -3, -2, -1: score(-3) = 5 before score(-2) = 4
+            ("bin_edge_m1_0", [(-1, 2, 400), (0, 2, 900), (200, 1, 1400)], 4, -1),                  # bins -1, 0, 1: score(-1) = 4, score(0) = 3
+            ("bin_edge_127_128", [(127, 2, 400), (128, 2, 900), (300, 5, 1400)], 7, 300),           # bins 0, 1, 2: score(0) = 4, score(1) = 7
+            ("bin_not_adjacent", [(0, 3, 400), (256, 3, 900), (257, 1, 1400)], 4, 256)):             # bins 0 and 2 are not paired: score(0) = 3, score(1) = 4, score(2) = 4
+        U, V = planted(rng, 2000, 2400, groups)
+        C.append(single(name, U, V, expect=exp(votes=votes, diag=diag)))
+    # two bins tied: the smaller one wins
+    U, V = planted(rng, 2000, 2400, [(-1000, 3, 400), (500, 3, 900)])
+    C.append(single("bins_tied", U, V, expect=exp(votes=3, diag=-1000)))
+    # an even number of band matches: the lower median is the second of four (by j)
+    U, V = planted(rng, 2000, 2400, [(10, 1, 400), (20, 1, 600), (30, 1, 800), (40, 1, 1000)])
+    C.append(single("even_band", U, V, expect=exp(votes=4, diag=20)))
+    # votes == min_votes and one less (the default min_votes of 8)
+    U, V = planted(rng, 1000, 1000, [(50, 8, 400)])
+    C.append(single("votes_eq_min_votes", U, V, dict(min_votes=8), exp(votes=8, diag=50)))
+    C.append(single("votes_below_min_votes", U, V, dict(min_votes=9), exp(sig_l=-1, votes=0)))
+    # max_len: the junction is the fourth of the 8 matches, (403, 353).  The flank of 20 starts 10 bases into the 30 aligned ones:
+    # len_l = 20 + 403, len_r = (1000 - 353) + 20
+    C.append(single("max_len_exact", U, V, dict(max_len=423 + 667), exp(len_l=423, len_r=667, ins_off=20, ins_len=403 + 647)))
+    C.append(single("max_len_one_over", U, V, dict(max_len=423 + 666), exp(sig_l=-1, votes=0)))
+    # the four strand combinations
+    for rl in (0, 1):
+        for rr in (0, 1):
+            C.append(single("strands_%d%d" % (rl, rr), U, V, rev=(rl, rr), expect=exp(votes=8, rc_l=rl, rc_r=rr, start_l=597 if rl else 10, start_r=10 if rr else 353)))
+    # a V of several streaming chunks, the overlap behind the second chunk seam; and one whose diagonal range needs a second pass of bins
+    U, V = planted(rng, 3000, 10000, [(-8000, 40, 1000)])
+    C.append(single("V_several_chunks", U, V, expect=exp(votes=40, diag=-8000)))
+    U, V = planted(rng, 500, 300000, [(-290000, 30, 100), (-5000, 10, 300)])
+    C.append(single("V_second_bin_pass", U, V, expect=exp(votes=30, diag=-290000)))
+    # the table at its fullest: 4,096 - K + 1 window k-mers, all distinct
+    U, V = planted(rng, 4096, 4096, [(3000, 60, 3500)])
+    assert len(set(U[i:i + K] for i in range(4096 - K + 1))) == 4096 - K + 1
+    C.append(single("table_full", U, V, expect=exp(votes=60, diag=3000)))
+
+    # several candidates per side.  Lefts with clips of 900 .. 400 (rank = order); the one right read overlaps the SHORTEST left only
+    def many(name, pairs, n_left, expect):
+        b = Build(3)
+        p = b.locus()
+        r2 = np.random.default_rng(5)
+        Ul, V = planted(r2, 900 - 100 * (n_left - 1), 800, [(-200, 28, 100)])
+        qs = []
+        for i in range(n_left):
+            qs.append(b.left(p + i, Ul if i == n_left - 1 else rand_seq(r2, 900 - 100 * i)))
+        qs.append(b.right(p, V))
+        b.call(p, qs)
+        C.append(dict(name=name, data=b.done(), opt=dict(SMALL, pairs=pairs), want=None, expect=expect))
+
+    many("fewer_than_pairs", 4, 3, exp(n_left=3, n_right=1, votes=28, qid_l=2))
+    many("cut_matters", 4, 6, exp(sig_l=-1, n_left=6, n_right=1))
+    many("cut_wide_enough", 8, 6, exp(n_left=6, votes=28, qid_l=5))
+    # only same-read pairs: one read with a tail clip and a head clip at the locus
+    b = Build(4)
+    p = b.locus()
+    mid = rand_seq(rng, 300)
+    q = b.read(rand_seq(rng, 30) + mid + rand_seq(rng, 30), 0)
+    b.recs.append(rec(q, 360, 0, 30, p - 30, p, [(30, "M")]))
+    b.recs.append(rec(q, 360, 330, 360, p, p + 30, [(30, "M")], flags=4))
+    b.call(p, [q])
+    C.append(dict(name="same_read_only", data=b.done(), opt=SMALL, want=None, expect=exp(sig_l=-1, n_left=1, n_right=1, n_voted=0)))
+    # two pairs tied on votes: two left reads with the same clip (the smaller qid ranks first), and two right reads likewise
+    b = Build(6)
+    p = b.locus()
+    U, V = planted(rng, 700, 700, [(100, 12, 300)])
+    b.call(p, [b.left(p, U), b.left(p, U), b.right(p, V), b.right(p, V)])
+    C.append(dict(name="pairs_tied", data=b.done(), opt=SMALL, want=None, expect=exp(votes=12, qid_l=0, qid_r=2, n_voted=4)))
+    # key order: a longer clip ranks first although its flank is shorter; then the longer flank; a rank-0 pair without votes loses to rank 1
+    b = Build(7)
+    p = b.locus()
+    b.call(p, [b.left(p, rand_seq(rng, 800), fl=10), b.left(p, U, fl=30), b.left(p, U, fl=12), b.right(p, V)])
+    C.append(dict(name="rank_order", data=b.done(), opt=SMALL, want=None, expect=exp(votes=12, qid_l=1, n_left=3, n_voted=3)))
+    # a call with left candidates only | a read that is no supporter | another target | reach 50 and 51 | no CIGAR ops | min_flank
+    b = Build(8)
+    p = b.locus(); b.call(p, [b.left(p, U), b.left(p, U)])
+    p = b.locus(); ql = b.left(p, U); qr = b.right(p, V); b.call(p, [ql])
+    p = b.locus(); ql = b.left(p, U); qr = b.right(p, V, tid=1); b.call(p, [ql, qr])
+    p = b.locus(); b.call(p, [b.left(p - 50, U), b.right(p + 50, V)])
+    p = b.locus(); b.call(p, [b.left(p - 51, U), b.right(p + 50, V)])
+    p = b.locus(); b.call(p, [b.left(p, U, fl=0), b.right(p, V)])
+    p = b.locus(); b.call(p, [b.left(p, U, fl=5), b.right(p, V, fl=4)])
+    C.append(dict(name="no_bridge_reasons", data=b.done(), opt=SMALL, want=None,
+                  expect=exp(sig_l=[-1, -1, -1, 5, -1, -1, -1], n_left=[2, 1, 1, 1, 0, 0, 1], n_right=[0, 0, 0, 1, 1, 1, 0])))
+    # want masks: three bridgeable calls, the middle one not wanted keeps its counts
+    b = Build(9)
+    for _ in range(3):
+        p = b.locus(); b.call(p, [b.left(p, U), b.right(p, V)])
+    data = b.done()
+    C.append(dict(name="want_all", data=data, opt=SMALL, want=None, expect=exp(votes=[12, 12, 12])))
+    C.append(dict(name="want_mask", data=data, opt=SMALL, want=[1, 0, 1], expect=exp(votes=[12, 0, 12], sig_l=[0, -1, 4], n_left=[1, 1, 1], n_right=[1, 1, 1])))
+    C.append(dict(name="want_none", data=data, opt=SMALL, want=[0, 0, 0], expect=exp(sig_l=[-1, -1, -1], n_left=[1, 1, 1])))
+    return C
+
+
+def mutate(rng, s, rate):
+    """the project's 40 / 20 / 40 substitution / deletion / insertion split"""
+    out = []
+    for ch in s:
+        x = rng.random()
+        if x < rate * 0.4:
+            out.append("ACGT"[("ACGT".index(ch) + 1 + int(rng.integers(3))) % 4])
+        elif x < rate * 0.6:
+            continue
+        elif x < rate:
+            out.append(ch); out.append("ACGT"[int(rng.integers(4))])
+        else:
+            out.append(ch)
+    return "".join(out)
+
+
+def noisy_pairs(n=200, rate=0.10, seed=23):
+    """n loci, each one left and one right read of a random element of 3,000 bases with `rate` errors, overlapping by 600 to 1,400
+    bases, on seeded strands -> (data, opt)"""
+    b = Build(seed)
+    rng = np.random.default_rng(seed + 1)
+    for t in range(n):
+        E = rand_seq(rng, 3000)
+        ov = 600 + int(rng.integers(801))
+        a = 1000 + int(rng.integers(500))                 # the left read holds E[:a + ov], the right one E[a:]
+        p = b.locus()
+        b.call(p, [b.left(p, mutate(rng, E[:a + ov], rate), fl=600, rev=int(rng.integers(2))),
+                   b.right(p, mutate(rng, E[a:], rate), fl=600, rev=int(rng.integers(2)))])
+    return b.done(), {}
+
+
+# ---- a planted insertion that no read spans ----------------------------------------------------------------------------------------------
+def spanless_fixture(seed=41):
+    """One random chromosome of 40,000 bases, one family `famL` of 9,000 bases planted once at 20,000, and fourteen error-free reads of
+    8,000 bases: seven enter the element from each side, their flanks staggered by 300 bases from 2,500 on, on alternating strands.  No
+    read spans: the longest clip of either side holds 5,500 bases of the element, so those two overlap by 2,000.
+    -> dict(chrom, fam, pos, hap, reads, names)"""
+    rng = np.random.default_rng(seed)
+    chrom, fam = rand_seq(rng, 40000), rand_seq(rng, 9000)
+    pos = 20000
+    hap = chrom[:pos] + fam + chrom[pos:]
+    reads, names = [], []
+    for i in range(7):
+        fl = 2500 + 300 * i
+        for side, s in (("L", hap[pos - fl:pos - fl + 8000]), ("R", hap[pos + 9000 + fl - 8000:pos + 9000 + fl])):
+            reads.append(dref.revcomp(s) if (i + (side == "R")) % 2 else s)
+            names.append("%s%d" % (side, i))
+    assert all(len(r) == 8000 for r in reads) and 2 * 5500 - 9000 >= 1000
+    return dict(chrom=chrom, fam=fam, pos=pos, hap=hap, reads=reads, names=names)

@@ -1,6 +1,6 @@
-// telr_amd/csrc/record_checks.h alone -- the record and call-list refusals of telr_call_insertions, telr_genotype_insertions and
-// telr_draft_contigs -- as a program of its own for a sanitizer build (the Python tests load the engine library, which a sanitizer
-// does not see into):
+// telr_amd/csrc/record_checks.h alone -- the record, call-list and signature refusals of telr_call_insertions, telr_genotype_insertions,
+// telr_draft_contigs and telr_bridge_contigs -- as a program of its own for a sanitizer build (the Python tests load the engine library,
+// which a sanitizer does not see into):
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o tools/record_checks_check tools/record_checks_check.cpp && tools/record_checks_check
 // Every refusal with its full text, the edges of the CIGAR range (the C ABI cannot produce that one on a device: telr_result_from_arrays
 // refuses it first), the order of a record's faults, and the keys and supports a passing call list leaves.  Exit status 0 and
@@ -182,6 +182,44 @@ int main()
         expect("the calls before the offsets", list_why(L, -1), "call 2: tid outside n_targets");
         L = three(); L.reads = {3, 9, 0, -1, -2};
         expect("the id before the order", list_why(L, -1), "call 2: negative read id");
+    }
+    // ---- the signature array (telr_draft_contigs, telr_bridge_contigs): two records of read 4, one of read 5; 3 targets, 6 reads
+    {
+        std::vector<telr_aln> recs(3, good());
+        recs[2].qid = 5;
+        auto sig = [](int tid, int pos, int qid, int kind, int rec, int mate) {
+            telr_ins_sig s; memset(&s, 0, sizeof(s)); s.tid = tid; s.pos = pos; s.qid = qid; s.kind = kind; s.rec = rec; s.mate = mate; return s; };
+        auto sig_why = [&](const std::vector<telr_ins_sig> &S, int32_t n_reads = 6) {
+            std::string why = "untouched";
+            return sig_list_check((int64_t)S.size(), S.empty() ? nullptr : S.data(), recs.data(), recs.size(), 3, n_reads, &why) ? std::string("") : why; };
+        const std::vector<telr_ins_sig> ok = {sig(0, 10, 4, 0, 0, -1), sig(0, 10, 4, 1, 0, 1), sig(2, 5, 5, 2, 2, -1)};
+        expect("a passing signature array", sig_why(ok), "");
+        expect("no signatures", sig_why({}), "");
+        std::vector<telr_ins_sig> S = ok; S[1].tid = 3;
+        expect("sig tid = n_targets", sig_why(S), "signature 1: tid outside n_targets");
+        S = ok; S[0].tid = -1;
+        expect("sig tid -1", sig_why(S), "signature 0: tid outside n_targets");
+        S = ok; S[2].pos = -1;
+        expect("sig negative pos", sig_why(S), "signature 2: negative pos");
+        S = ok; S[0].rec = 3;
+        expect("sig rec = n", sig_why(S), "signature 0: rec outside the records");
+        S = ok; S[0].rec = -1;
+        expect("sig rec -1", sig_why(S), "signature 0: rec outside the records");
+        S = ok; S[1].mate = 3;
+        expect("sig mate = n", sig_why(S), "signature 1: mate outside the records");
+        S = ok; S[1].mate = -1;
+        expect("sig mate -1 on a split", sig_why(S), "signature 1: mate outside the records");
+        S = ok; S[0].mate = 99;
+        expect("the mate of a kind 0 is not read", sig_why(S), "");
+        expect("sig qid = n_reads", sig_why(ok, 5), "signature 2: qid outside the read set");
+        S = ok; S[0].qid = 5;
+        expect("sig qid of another read", sig_why(S), "signature 0: qid is not its records' read");
+        S = ok; S[1].mate = 2;
+        expect("sig mate of another read", sig_why(S), "signature 1: qid is not its records' read");
+        S = {ok[2], ok[0]};
+        expect("sigs descend", sig_why(S), "signature 1: signatures not ascending by (tid, pos)");
+        S = {ok[1], ok[0]};
+        expect("equal keys pass", sig_why(S), "");
     }
     if (n_bad) { fprintf(stderr, "record_checks: %d of %d checks FAILED\n", n_bad, n_checks); return 1; }
     printf("record_checks: %d checks ok\n", n_checks);
