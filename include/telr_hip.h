@@ -788,8 +788,10 @@ void telr_te_feats_free(telr_te_feats *f);
  *      chunk k + 1 inflating while chunk k is parsed.  The bytes of a chunk behind its last complete record (or all of it while the
  *      header is incomplete) are carried in front of the next chunk; a record or header longer than a chunk makes that carry grow
  *      and is no error.  Two passes: the first collects every record's fields and names, the host decides, the second inflates
- *      again and writes CIGAR words, bases and qualities where they stay.  Beyond the result and the set, the device holds two chunk
- *      slots (the chunk's file bytes and its buffer: carry + inflated members), the per-record tables of one chunk and fixed tables.
+ *      again and writes CIGAR words, bases and qualities where they stay.  A load of one chunk does not inflate again: its second
+ *      pass reads the chunk where the first left it (passes is still 2: it counts the walks over the records).  Beyond the result
+ *      and the set, the device holds two chunk slots (one when there is one chunk; the chunk's file bytes and its buffer: carry +
+ *      inflated members), the per-record tables of one chunk and fixed tables.
  *      chunk_bytes: n > 0 that size; 0 the engine's own: free device memory (telr_device_mem) / 16, at least 1 MiB, at most 1 GiB;
  *      TELR_BAM_CHUNK_FIT: telr_bam_load's whole-file path when file size + sum of ISIZE is below half the free device memory, else
  *      as 0 (one hop of the member headers serves the decision and the load).
@@ -824,10 +826,11 @@ telr_result *telr_bam_in_detach_result(telr_bam_in *in);
 int  telr_bam_in_counters(const telr_bam_in *in, int64_t *out /* [9] */);
 /* the `bam2fasta` text, decoded on demand on the device: buf[off[q] .. off[q] + len[q]) = read q, off[q] = the bases before it */
 int  telr_bam_in_ascii(const telr_bam_in *in, char *buf, int64_t *off);
-/* wall-clock milliseconds of the load's phases: host hop, upload, inflate, chain, parse, names on the host, sequences, total.
- * After telr_bam_load_chunked they are sums over the chunks (upload, inflate: both passes, device time between events on the second
- * stream; chain: device time; parse: host time of pass 1 behind the chain; sequences: the whole second pass); upload and inflate
- * overlap with the others, so total (wall clock) is no longer the sum of the rest */
+/* milliseconds of the load's phases: host hop, upload, inflate, chain, parse, names on the host, sequences, total.  After either load
+ * they are sums over the chunks (upload, inflate: both passes, device time between events on the second stream; chain: device time;
+ * parse: host time of pass 1 behind the chain; sequences: the whole second pass, wall clock); total is wall clock.  With more than one
+ * chunk upload and inflate overlap with the others, so total is not the sum of the rest.  telr_bam_load is the load of one chunk: its
+ * upload, inflate and chain used to be host wall clock, each ending in a synchronisation, and are device times between events now */
 int  telr_bam_in_phase_ms(const telr_bam_in *in, float *out /* [8] */);
 
 /* ---- a FASTA / FASTQ file -- plain, gzip or BGZF -- as a read set, parsed and packed on the device (opt-in).  The

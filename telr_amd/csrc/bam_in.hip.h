@@ -1,19 +1,19 @@
-// bam_in.hip.h -- telr_bam_load: a BAM file becomes what the stage-1 consumers take, on the device (the definition is in
-// include/telr_hip.h and, as plain Python, in tests/bam_in_ref.py).
+// bam_in.hip.h -- a BAM file becomes what the stage-1 consumers take, on the device (the definition is in
+// include/telr_hip.h and, as plain Python, in tests/bam_in_ref.py).  Here: the kernels, the hop over the file, the header, what the host
+// decides, and the handle.  The load itself -- one load for telr_bam_load and telr_bam_load_chunked: the whole file is the plan of one
+// chunk -- is bam_load in bam_in_chunked.hip.h.  Per chunk:
 //
-//   host      map the file, hop the BGZF member headers -> table of (deflate bytes, their length, ISIZE, CRC); upload file + table
-//   device    scan of ISIZE -> every member's place in the inflated stream
-//             k_bgzf_inflate   one workgroup (one wave) per member: RFC 1951 into a 64-KiB window in LDS, CRC-32, window -> stream
+//   host      (once) map the file, hop the BGZF member headers -> table of (deflate bytes, their length, ISIZE, CRC)
+//   device    k_bgzf_inflate   one workgroup (one wave) per member: RFC 1951 into a 64-KiB window in LDS, CRC-32, window -> buffer
 //   host      the BAM header (copied back: it is small)
 //   device    k_bam_chain      the record offsets: record i + 1 starts block_size(i) behind record i -- one lane walks
 //             k_bam_rec        one wave per record: fixed fields, tags, CIGAR rules (count pass), name length
 //             k_bam_names      the names into one compact buffer
-//   host      names -> read numbers (hash map), which records are kept, their order and CIGAR offsets
+//   host      (once, all chunks' records) names -> read numbers (hash map), which records are kept, their order and CIGAR offsets
 //   device    k_bam_cig        the normalised CIGAR words of the kept records (emit pass) into the result's device array
 //             k_bam_seq / k_bam_qual   the reads' 2-bit words, mask words and Phred bytes in the set's layout
 //             k_bam_ascii      the set as text, on demand
 // Every store position is a scan's or the lane's own index; there is no atomic; the bytes are the same on every run.
-// telr_bam_load_chunked (bam_in_chunked.hip.h) runs the same kernels and the same host decision chunk by chunk, for a file of any size.
 //
 // The window is in LDS, not in the member's global output: a match copy reads what the symbol before it wrote, and the turn-around
 // of an LDS store -> load inside one wave is some hundred cycles where a global one is a microsecond or more.  64 KiB of window +
@@ -119,11 +119,10 @@ static __device__ __forceinline__ uint32_t bi_ld32(const uint8_t *__restrict__ s
 }
 static __device__ __forceinline__ uint32_t bi_ld16(const uint8_t *__restrict__ s, int64_t p) { return (uint32_t)s[p] | (uint32_t)s[p + 1] << 8; }
 
-// res[0] = records, res[1] = 0 | 1 (record res[0] runs past the stream) | 2 (its block_size is below 32) | 3 (more records than `cap`);
-// PART (a chunk's buffer, bam_in_chunked.hip.h): res[2] = where the walk ended -- behind the last complete record
-template <bool PART>
-static __device__ __forceinline__ void bam_chain_walk(const uint8_t *__restrict__ stream, int64_t total, int64_t start, int64_t *__restrict__ offs, int64_t cap,
-                                                      int64_t *__restrict__ res)
+// res[0] = records, res[1] = 0 | 1 (record res[0] runs past the buffer) | 2 (its block_size is below 32) | 3 (more records than `cap`),
+// res[2] = where the walk ended -- behind the last complete record: the next chunk's carry starts there
+__global__ void __launch_bounds__(64) k_bam_chain(const uint8_t *__restrict__ stream, int64_t total, int64_t start, int64_t *__restrict__ offs, int64_t cap,
+                                                  int64_t *__restrict__ res)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int64_t p = start, n = 0, st = 0;
@@ -136,18 +135,7 @@ static __device__ __forceinline__ void bam_chain_walk(const uint8_t *__restrict_
         offs[n++] = p;
         p += 4 + (int64_t)bs;
     }
-    res[0] = n; res[1] = st;
-    if (PART) res[2] = p;
-}
-__global__ void __launch_bounds__(64) k_bam_chain(const uint8_t *__restrict__ stream, int64_t total, int64_t start, int64_t *__restrict__ offs, int64_t cap,
-                                                  int64_t *__restrict__ res)
-{
-    bam_chain_walk<false>(stream, total, start, offs, cap, res);
-}
-__global__ void __launch_bounds__(64) k_bam_chain_part(const uint8_t *__restrict__ stream, int64_t total, int64_t start, int64_t *__restrict__ offs, int64_t cap,
-                                                       int64_t *__restrict__ res)
-{
-    bam_chain_walk<true>(stream, total, start, offs, cap, res);
+    res[0] = n; res[1] = st; res[2] = p;
 }
 
 enum { BREC_OK = 0, BREC_FIELDS = 1, BREC_TAGS = 2, BREC_REF = 3, BREC_CLIP = 4, BREC_OP = 5, BREC_RANGE = 6 };
@@ -390,16 +378,9 @@ static __device__ __forceinline__ void bam_seq_word(const uint8_t *__restrict__ 
     const uint32_t other = __shfl_xor(m16, 1);
     if (!(w & 1)) outn[w >> 1] = m16 | (other << 16);
 }
+// words [w0, w1) of the set's layout, both multiples of 4: the reads first met in one chunk; reads / boff start at the chunk's first read
 __global__ void __launch_bounds__(256) k_bam_seq(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
-                                                 int64_t nw, uint32_t *__restrict__ out2, uint32_t *__restrict__ outn)
-{
-    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (w >= nw) return;
-    bam_seq_word(stream, reads, boff, n, w, out2, outn);
-}
-// a chunk's reads (bam_in_chunked.hip.h): words [w0, w1) of the set's layout, both multiples of 4; reads / boff start at the chunk's first read
-__global__ void __launch_bounds__(256) k_bam_seq_part(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
-                                                      int64_t w0, int64_t w1, uint32_t *__restrict__ out2, uint32_t *__restrict__ outn)
+                                                 int64_t w0, int64_t w1, uint32_t *__restrict__ out2, uint32_t *__restrict__ outn)
 {
     const int64_t w = w0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (w >= w1) return;
@@ -425,14 +406,7 @@ static __device__ __forceinline__ void bam_qual_word(const uint8_t *__restrict__
     if (big) over[q] = 1;
 }
 __global__ void __launch_bounds__(256) k_bam_qual(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
-                                                  int64_t nw, uint32_t *__restrict__ out4, int32_t *__restrict__ over)
-{
-    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (w >= nw) return;
-    bam_qual_word(stream, reads, boff, n, w, out4, over);
-}
-__global__ void __launch_bounds__(256) k_bam_qual_part(const uint8_t *__restrict__ stream, const BamRead *__restrict__ reads, const int64_t *__restrict__ boff, int32_t n,
-                                                       int64_t w0, int64_t w1, uint32_t *__restrict__ out4, int32_t *__restrict__ over)
+                                                  int64_t w0, int64_t w1, uint32_t *__restrict__ out4, int32_t *__restrict__ over)
 {
     const int64_t w = w0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (w >= w1) return;
@@ -454,7 +428,6 @@ __global__ void __launch_bounds__(256) k_bam_ascii(const uint32_t *__restrict__ 
     for (int b = 0; b < 4 && j0 + b < L; ++b) d[b] = (m4 >> b & 1u) ? 'N' : "ACGT"[(c8 >> (2 * b)) & 3u];
 }
 
-#ifndef BAM_IN_KERNELS_ONLY
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -471,7 +444,7 @@ struct telr_bam_in {
     bool set_owned = true, res_owned = true;
     int64_t counters[9] = {0};
     float phase_ms[BIN_NPHASE] = {0};
-    int64_t chunk_info[4] = {0};       // telr_bam_load_chunked: chunks, passes, largest chunk buffer, largest carry
+    int64_t chunk_info[4] = {0};       // telr_bam_load_chunked: chunks, passes, largest chunk buffer, largest carry (telr_bam_load leaves them 0)
 };
 struct BamInClock {
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
@@ -490,7 +463,7 @@ static const char *infl_text(int st)
     return st >= 0 && st <= 9 ? T[st] : "?";
 }
 
-// the mapped file and its member table (host only): what the whole-file load and the chunked load both start from
+// the mapped file and its member table (host only): what a load starts from
 struct BamInHop {
     BamInFile F;
     std::vector<BgzfMember> mem; std::vector<int32_t> isz;      // mem[k].off: file offset of member k's deflate bytes
@@ -543,65 +516,6 @@ static int bam_in_hop(telr_ctx *ctx, const char *what, const char *path, BamInHo
     return TELR_OK;
 }
 
-// the file -> its inflated stream in the context's scratch ("bamin_stream"; valid until the next load on the context)
-static int bam_in_inflate(telr_ctx *ctx, const char *what, const BamInHop &H, uint8_t **d_stream_out, int64_t *total_out, int64_t *n_members, int64_t *no_eof, float *phase)
-{
-    BamInClock clk;
-    const uint8_t *d = H.F.p; const size_t size = H.F.n;
-    const std::vector<BgzfMember> &mem = H.mem; const std::vector<int32_t> &isz = H.isz;
-    const size_t nm = mem.size();
-    const int64_t total = H.total;
-    *n_members = (int64_t)nm; *no_eof = H.no_eof;
-    phase[BIN_HOP] = H.ms;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    uint8_t *d_file, *d_stream; BgzfMember *d_mem; int32_t *d_isz, *d_status; int64_t *d_ooff; CrcTabs *d_tabs;
-    const size_t fpad = ((size + 3) & ~(size_t)3) + BGZF_INCH + 16;
-    // (a file that does not fit next to its inflated stream: hipErrorOutOfMemory -> TELR_E_NOMEM)
-    TRY(ctx_buf_t(ctx, "bamin_file", fpad, &d_file));
-    TRY(ctx_buf_t(ctx, "bamin_stream", (size_t)total + 64, &d_stream));
-    TRY(ctx_buf_t(ctx, "bamin_mem", nm + 1, &d_mem));
-    TRY(ctx_buf_t(ctx, "bamin_isize", nm + 1, &d_isz));
-    TRY(ctx_buf_t(ctx, "bamin_status", nm + 1, &d_status));
-    TRY(ctx_buf_t(ctx, "bamin_ooff", nm + 2, &d_ooff));
-    TRY(ctx_buf_t(ctx, "bamin_crctabs", 1, &d_tabs));
-    if (size) HIPCHK(hipMemcpyAsync(d_file, d, size, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_file + size, 0, fpad - size, st));
-    HIPCHK(hipMemsetAsync(d_stream + total, 0, 64, st));
-    if (nm) {
-        HIPCHK(hipMemcpyAsync(d_mem, mem.data(), nm * sizeof(BgzfMember), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_isz, isz.data(), nm * 4, hipMemcpyHostToDevice, st));
-    }
-    { static CrcTabs T; static bool made = false; if (!made) { crc_tabs_make(T); made = true; } HIPCHK(hipMemcpyAsync(d_tabs, &T, sizeof(T), hipMemcpyHostToDevice, st)); }
-    HIPCHK(hipStreamSynchronize(st));
-    phase[BIN_UPLOAD] = clk.lap();
-    if (nm) {
-        TRY((dev_qscan<int32_t, int64_t>(ctx, d_isz, (int32_t)nm, d_ooff, nullptr, 0, nullptr, nullptr)));
-        hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)nm), dim3(64), 0, st, d_file, d_mem, d_ooff, d_tabs, d_stream, d_status);
-        HIPCHK(hipGetLastError());
-        std::vector<int32_t> status(nm);
-        HIPCHK(hipMemcpyAsync(status.data(), d_status, nm * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (size_t k = 0; k < nm; ++k) if (status[k] != INFL_OK) { ctx->err = std::string(what) + ": block " + std::to_string(k) + ": " + infl_text(status[k]); return TELR_E_ARG; }
-    }
-    phase[BIN_INFLATE] = clk.lap();
-    *d_stream_out = d_stream; *total_out = total;
-    return TELR_OK;
-}
-
-// test tap: the inflated stream of a BGZF file (any payload) -> out[0 .. cap); *n = its length (nothing is copied when it exceeds cap)
-extern "C" int telr_debug_bgzf_inflate(telr_ctx *ctx, const char *path, uint8_t *out, int64_t cap, int64_t *n)
-{
-    (void)hipGetLastError();
-    if (!ctx || !path || !n) return TELR_E_ARG;
-    uint8_t *d_stream; int64_t total, nm, ne; float ph[BIN_NPHASE];
-    BamInHop H;
-    TRY(bam_in_hop(ctx, "telr_debug_bgzf_inflate", path, H));
-    TRY(bam_in_inflate(ctx, "telr_debug_bgzf_inflate", H, &d_stream, &total, &nm, &ne, ph));
-    *n = total;
-    if (total && total <= cap && out) HIPCHK(hipMemcpy(out, d_stream, (size_t)total, hipMemcpyDeviceToHost));
-    return TELR_OK;
-}
 // test tap: the Phred bytes of a set in its base layout (padded_bases of them) -> out; returns their number, -1 without qualities
 extern "C" int64_t telr_debug_seqset_qual(const telr_seqset *s, uint8_t *out, int64_t cap)
 {
@@ -647,7 +561,7 @@ extern "C" void telr_bam_in_free(telr_bam_in *in)
     delete in;
 }
 
-// ---- what the host decides from the records' fields and names (both loads: the whole file's records, in file order) ----
+// ---- what the host decides from the records' fields and names (the whole file's records, in file order) ----
 // the first of recs[0 .. n) that breaks a rule; its number in the text is base + its index
 static int bam_in_rec_fault(telr_ctx *ctx, const BamRec *recs, int64_t n, int64_t base)
 {
@@ -756,141 +670,6 @@ static void bam_in_finish(telr_bam_in *B, telr_seqset *S, telr_result *R)
     B->set = S; B->res = R;
 }
 
-static int bam_load_whole(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual, telr_bam_in **out)
-{
-    BamInClock wall, clk;
-    std::unique_ptr<telr_bam_in, void (*)(telr_bam_in*)> B(new telr_bam_in(), telr_bam_in_free);
-    B->ctx = ctx;
-    uint8_t *d_stream; int64_t total = 0;
-    TRY(bam_in_inflate(ctx, "telr_bam_load", H, &d_stream, &total, &B->counters[0], &B->counters[8], B->phase_ms));
-    hipStream_t st = ctx->stream;
-    clk.lap();
-    // the header: small, parsed on the host
-    int64_t start = 0;
-    {
-        std::vector<uint8_t> h;
-        int64_t have = std::min<int64_t>(total, 1 << 16), need = 0;
-        for (;;) {
-            h.resize((size_t)have + 1);
-            if (have) HIPCHK(hipMemcpy(h.data(), d_stream, (size_t)have, hipMemcpyDeviceToHost));
-            const int rc = bam_in_header(ctx, h.data(), have, total, B.get(), &start, &need);
-            if (rc == TELR_OK) break;
-            if (rc != 1) return rc;
-            have = std::min<int64_t>(total, std::max<int64_t>(need, have * 4));
-        }
-    }
-    const int32_t n_ref = (int32_t)B->tnames.size();
-    // the record chain
-    const int64_t cap = (total - start) / 36 + 1;
-    int64_t *d_offs, *d_res; int64_t res[2] = {0, 0};
-    TRY(ctx_buf_t(ctx, "bamin_offs", (size_t)cap + 1, &d_offs));
-    TRY(ctx_buf_t(ctx, "bamin_res", 2, &d_res));
-    hipLaunchKernelGGL(k_bam_chain, dim3(1), dim3(64), 0, st, d_stream, total, start, d_offs, cap, d_res);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    B->phase_ms[BIN_CHAIN] = clk.lap();
-    if (res[1] == 1) { ctx->err = "telr_bam_load: record " + std::to_string(res[0]) + ": runs past the stream"; return TELR_E_ARG; }
-    if (res[1] == 2) { ctx->err = "telr_bam_load: record " + std::to_string(res[0]) + ": block_size below 32"; return TELR_E_ARG; }
-    if (res[1] != 0 || res[0] >= 0x7ffffff0LL) { ctx->err = "telr_bam_load: too many records"; return TELR_E_RANGE; }
-    const int64_t nrec = res[0];
-    // the records' fields and names
-    std::vector<BamRec> recs((size_t)nrec);
-    std::vector<int64_t> noff((size_t)nrec + 1, 0);
-    std::vector<char> names;
-    BamRec *d_recs = nullptr;
-    if (nrec) {
-        int32_t *d_nlen; int64_t *d_noff, *d_ntot; uint8_t *d_names; int64_t ntot = 0;
-        TRY(ctx_buf_t(ctx, "bamin_recs", (size_t)nrec, &d_recs));
-        TRY(ctx_buf_t(ctx, "bamin_nlen", (size_t)nrec + 1, &d_nlen));
-        TRY(ctx_buf_t(ctx, "bamin_noff", (size_t)nrec + 2, &d_noff));
-        TRY(ctx_buf_t(ctx, "bamin_ntot", 2, &d_ntot));
-        const dim3 grid((unsigned)((nrec + 3) / 4));
-        hipLaunchKernelGGL(k_bam_rec, grid, dim3(256), 0, st, d_stream, d_offs, nrec, n_ref, d_recs, d_nlen);
-        HIPCHK(hipGetLastError());
-        TRY((dev_qscan<int32_t, int64_t>(ctx, d_nlen, (int32_t)nrec, d_noff, d_ntot, 0, nullptr, nullptr)));
-        HIPCHK(hipMemcpyAsync(&ntot, d_ntot, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        TRY(ctx_buf_t(ctx, "bamin_names", (size_t)ntot + 1, &d_names));
-        hipLaunchKernelGGL(k_bam_names, grid, dim3(256), 0, st, d_stream, d_offs, nrec, d_nlen, d_noff, d_names);
-        HIPCHK(hipGetLastError());
-        names.resize((size_t)ntot + 1);
-        HIPCHK(hipMemcpyAsync(recs.data(), d_recs, (size_t)nrec * sizeof(BamRec), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(noff.data(), d_noff, ((size_t)nrec + 1) * 8, hipMemcpyDeviceToHost, st));
-        if (ntot) HIPCHK(hipMemcpyAsync(names.data(), d_names, (size_t)ntot, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    B->phase_ms[BIN_PARSE] = clk.lap();
-    // ---- host: the first record in file order that breaks a rule; names -> read numbers; which records are kept, and where
-    TRY(bam_in_rec_fault(ctx, recs.data(), nrec, 0));
-    BamInDecided D;
-    TRY(bam_in_decide(ctx, B.get(), recs, names, noff, D));
-    std::vector<BamRead> &reads = D.reads; std::vector<int32_t> &first_rec = D.first_rec;
-    const bool any_ff = D.any_ff;
-    const int32_t nq = (int32_t)reads.size();
-    const size_t nk = D.kept_rec.size();
-    const int64_t ncig = D.ncig;
-    std::unique_ptr<telr_result> R(std::move(D.R));
-    B->phase_ms[BIN_NAMES_HOST] = clk.lap();
-    // ---- the result: CIGAR words written on the device where the result keeps them, mirrored to the host once
-    TRY(bam_in_result_arrays(ctx, R.get(), ncig));
-    if (nk) {
-        int32_t *d_krec; int64_t *d_koff;
-        TRY(ctx_buf_t(ctx, "bamin_krec", nk, &d_krec));
-        TRY(ctx_buf_t(ctx, "bamin_koff", nk, &d_koff));
-        HIPCHK(hipMemcpyAsync(d_krec, D.kept_rec.data(), nk * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_koff, D.kept_off.data(), nk * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_bam_cig, dim3((unsigned)((nk + 3) / 4)), dim3(256), 0, st, d_stream, d_recs, d_krec, d_koff, (int64_t)nk, R->d_cig);
-        HIPCHK(hipGetLastError());
-        if (ncig) HIPCHK(hipMemcpyAsync(R->cig, R->d_cig, (size_t)ncig * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    R->twin_n = R->ncig; R->twin_off = false;
-    // ---- the reads
-    telr_seqset *S = new telr_seqset();
-    S->ctx = ctx; S->n = nq; S->len = D.rlen;
-    TRY(seqset_alloc(ctx, S, "telr_bam_load", true, st));          // (frees S on failure)
-    std::unique_ptr<telr_seqset, void (*)(telr_seqset*)> Sg(S, telr_seqset_free);
-    if (nq) {
-        BamRead *d_reads;
-        TRY(ctx_buf_t(ctx, "bamin_reads", (size_t)nq, &d_reads));
-        HIPCHK(hipMemcpyAsync(d_reads, reads.data(), (size_t)nq * sizeof(BamRead), hipMemcpyHostToDevice, st));
-        const int64_t nw = S->padded_bases / 16;
-        hipLaunchKernelGGL(k_bam_seq, grid256(nw), dim3(256), 0, st, d_stream, d_reads, S->d_boff, nq, nw, S->d_seq2, S->d_nmask);
-        HIPCHK(hipGetLastError());
-        if (keep_qual && !any_ff) {
-            int32_t *d_over;
-            TRY(ctx_buf_t(ctx, "bamin_over", (size_t)nq, &d_over));
-            HIPCHK(hipMemsetAsync(d_over, 0, (size_t)nq * 4, st));
-            HIPCHK(hipMalloc(&S->d_qual, (size_t)S->padded_bases + 64));
-            HIPCHK(hipMemsetAsync(S->d_qual + S->padded_bases, 0, 64, st));
-            hipLaunchKernelGGL(k_bam_qual, grid256(S->padded_bases / 4), dim3(256), 0, st, d_stream, d_reads, S->d_boff, nq, S->padded_bases / 4, (uint32_t*)S->d_qual, d_over);
-            HIPCHK(hipGetLastError());
-            std::vector<int32_t> over((size_t)nq);
-            HIPCHK(hipMemcpyAsync(over.data(), d_over, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            int32_t worst = -1;
-            for (int32_t q = 0; q < nq; ++q) if (over[(size_t)q] && (worst < 0 || first_rec[(size_t)q] < worst)) worst = first_rec[(size_t)q];
-            if (worst >= 0) { ctx->err = "telr_bam_load: record " + std::to_string(worst) + ": a base quality above 93"; return TELR_E_ARG; }
-        }
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    B->phase_ms[BIN_SEQ] = clk.lap();
-    B->phase_ms[BIN_TOTAL] = wall.lap() + H.ms;
-    bam_in_finish(B.get(), Sg.release(), R.release());
-    *out = B.release();
-    return TELR_OK;
-}
-extern "C" int telr_bam_load(telr_ctx *ctx, const char *path, int32_t keep_qual, telr_bam_in **out)
-{
-    (void)hipGetLastError();
-    if (!ctx) return TELR_E_ARG;
-    if (!path || !out) { ctx->err = "telr_bam_load: null path or output"; return TELR_E_ARG; }
-    BamInHop H;
-    TRY(bam_in_hop(ctx, "telr_bam_load", path, H));
-    return bam_load_whole(ctx, H, keep_qual, out);
-}
-
 extern "C" int32_t telr_bam_in_target_count(const telr_bam_in *in) { return in ? (int32_t)in->tnames.size() : 0; }
 extern "C" const char *const *telr_bam_in_target_names(const telr_bam_in *in) { return in ? in->tname_ptr.data() : nullptr; }
 extern "C" const int32_t *telr_bam_in_target_lens(const telr_bam_in *in) { return in ? in->tlens.data() : nullptr; }
@@ -927,4 +706,3 @@ extern "C" int telr_bam_in_ascii(const telr_bam_in *in, char *buf, int64_t *off)
     HIPCHK(hipStreamSynchronize(st));
     return TELR_OK;
 }
-#endif

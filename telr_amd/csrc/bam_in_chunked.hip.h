@@ -1,16 +1,17 @@
-// bam_in_chunked.hip.h -- telr_bam_load_chunked: the load of bam_in.hip.h for a file of any size.  The file is cut into
-// chunks of whole BGZF members (bam_chunk_plan.h); every chunk is uploaded, inflated and parsed in turn, so that the transient device
-// memory depends on the chunk and not on the file.  The kernels are those of bam_in.hip.h; the result is the whole-file load's.
+// bam_in_chunked.hip.h -- bam_load: the one load behind telr_bam_load and telr_bam_load_chunked, its chunk slots, and
+// the entry points.  The file is cut into chunks of whole BGZF members (bam_chunk_plan.h); every chunk is uploaded, inflated and parsed
+// in turn, so that the transient device memory depends on the chunk and not on the file.  telr_bam_load is the plan of one chunk: one
+// slot, the file next to its inflated stream.  The kernels are those of bam_in.hip.h.
 //
 // Two passes.  Which records are kept and where their words and bases go depends on the whole file (a supplementary record may come
 // any number of chunks before its primary, the first name wins across chunks, orphans and len_mismatch need the primary's length):
-//   pass 1    per chunk: upload, k_bgzf_inflate, k_bam_chain_part, k_bam_rec, k_bam_names; fields and names go to the host, as in the
-//             whole-file load
-//   host      bam_in_decide: the same code as the whole-file load, on the same arrays
-//   pass 2    per chunk: upload and inflate again, then k_bam_cig, k_bam_seq_part, k_bam_qual_part straight into the final arrays at their
+//   pass 1    per chunk: upload, k_bgzf_inflate, k_bam_chain, k_bam_rec, k_bam_names; fields and names go to the host
+//   host      bam_in_decide, on the whole file's records
+//   pass 2    per chunk: upload and inflate again, then k_bam_cig, k_bam_seq, k_bam_qual straight into the final arrays at their
 //             final offsets.  The reads first met in one chunk have consecutive numbers: one contiguous stretch of the set's layout.
+//             One chunk: it is still in its slot, inflated, and so are its records' fields; nothing is uploaded or inflated again.
 // So every store position stays a scan's result or the lane's own index, there is no atomic and no provisional array to gather from;
-// the price is a second inflate.
+// the price, with more than one chunk, is a second inflate.
 //
 // A chunk's buffer.  slot = [ room | the chunk's inflated members | 64 ].  The members are inflated to a fixed place behind `room`, so the
 // inflate of chunk k + 1 can run before chunk k's record chain has said how long the carry is; the carry -- the bytes of chunk k behind
@@ -19,8 +20,8 @@
 // longer than a chunk grows it over several chunks) makes the slot grow; that is no error.  Offsets into `buf` are the same in both
 // passes: same carry, same members.
 //
-// Overlap.  Two slots.  Chunk k + 1 is uploaded and inflated on a second stream while chunk k is chained and parsed on the context's
-// stream; the host waits for chunk k's results at the end of every chunk (it needs them), which also orders the slots' reuse.
+// Overlap.  Two slots (one chunk: one).  Chunk k + 1 is uploaded and inflated on a second stream while chunk k is chained and parsed on
+// the context's stream; the host waits for chunk k's results at the end of every chunk (it needs them), which also orders the slots' reuse.
 #include "bam_chunk_plan.h"
 
 #define BAMC_AUTO_DIV  16               /* chunk_bytes 0: free device memory / 16 ... */
@@ -28,6 +29,7 @@
 #define BAMC_AUTO_MIN  (1LL << 20)      /* ... at least 1 MiB */
 #define BAMC_ROOM      (65536 - 64)     /* a slot's carry room is a multiple of this: with the 64 bytes behind the members a slot is never
                                            more than 64 KiB above carry + members */
+#define BAMC_WHOLE     INT64_MAX        /* a chunk_bytes that no sum of ISIZE reaches (below 2^31 members of at most 64 KiB): one chunk */
 
 struct BamChunkSlot {
     char nm_file[32], nm_buf[32], nm_mem[32], nm_ooff[32], nm_status[32];
@@ -44,6 +46,8 @@ struct BamChunked {
     int64_t nch = 0;
     size_t max_payload = 0, max_cbytes = 0, max_members = 0, max_alloc = 0;      // max_alloc: the largest slot buffer of the load
     BamChunkSlot slot[2];
+    int nslot = 2;                       // 1 or 2 of them are set up; chunk k runs in at(k)
+    BamChunkSlot &at(int64_t k) { return slot[k & (nslot - 1)]; }
     CrcTabs *d_tabs = nullptr;
     hipEvent_t ec0 = nullptr, ec1 = nullptr;      // around a chunk's record chain
     float ms_upload = 0, ms_inflate = 0, ms_chain = 0;
@@ -68,9 +72,12 @@ static int bamc_room(BamChunked &C, BamChunkSlot &s, size_t need, size_t keep)
     C.max_alloc = std::max(C.max_alloc, bytes);
     HIPCHK(hipStreamSynchronize(C.s_io)); HIPCHK(hipStreamSynchronize(C.s_main));
     DBuf &b = ctx->bufs[s.nm_buf];
+    const bool move = keep && s.d_buf;
+    // nothing moves: the old buffer (an earlier load's, too) goes first, so that a load never holds a slot twice
+    if (!move && b.p) { s.d_buf = nullptr; HIPCHK(hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
     void *p = nullptr;
     HIPCHK(hipMalloc(&p, bytes));
-    if (keep && s.d_buf) {
+    if (move) {
         const hipError_t e = hipMemcpy((uint8_t*)p + room, s.d_buf + s.room, keep, hipMemcpyDeviceToDevice);
         if (e != hipSuccess) { (void)hipFree(p); HIPCHK(e); }
     }
@@ -80,7 +87,33 @@ static int bamc_room(BamChunked &C, BamChunkSlot &s, size_t need, size_t keep)
     return TELR_OK;
 }
 
-static int bamc_setup(BamChunked &C, int64_t chunk_bytes)
+// the load's `nslot` slots: names, carry room (C.max_payload says how much follows it) and events; `members`: and what a chunk of BGZF
+// members needs on its way -- its slice of the file, its member table, output offsets and statuses (C.max_cbytes, C.max_members)
+static int bamc_slots(BamChunked &C, int nslot, bool members)
+{
+    telr_ctx *ctx = C.ctx;
+    C.nslot = nslot;
+    for (int i = 0; i < nslot; ++i) {
+        BamChunkSlot &s = C.slot[i];
+        snprintf(s.nm_file, sizeof(s.nm_file), "bamin_c%d_file", i); snprintf(s.nm_buf, sizeof(s.nm_buf), "bamin_c%d_buf", i);
+        snprintf(s.nm_mem, sizeof(s.nm_mem), "bamin_c%d_mem", i); snprintf(s.nm_ooff, sizeof(s.nm_ooff), "bamin_c%d_ooff", i);
+        snprintf(s.nm_status, sizeof(s.nm_status), "bamin_c%d_status", i);
+        if (members) {
+            TRY(ctx_buf_t(ctx, s.nm_file, ((C.max_cbytes + 3) & ~(size_t)3) + BGZF_INCH + 16, &s.d_file));
+            TRY(ctx_buf_t(ctx, s.nm_mem, C.max_members + 1, &s.d_mem));
+            TRY(ctx_buf_t(ctx, s.nm_ooff, C.max_members + 1, &s.d_ooff));
+            TRY(ctx_buf_t(ctx, s.nm_status, C.max_members + 1, &s.d_status));
+        }
+        // (the buffer of an earlier load is not taken over: its room and its members' place are this load's)
+        s.d_buf = nullptr; s.room = 0;
+        TRY(bamc_room(C, s, 0, 0));
+        HIPCHK(hipEventCreate(&s.e0)); HIPCHK(hipEventCreate(&s.e1)); HIPCHK(hipEventCreate(&s.e2));
+    }
+    return TELR_OK;
+}
+
+// the chunk plan and its slots: two, or one where the plan has at most one chunk and the caller asks for no more (min_slots 1)
+static int bamc_setup(BamChunked &C, int64_t chunk_bytes, int min_slots)
 {
     telr_ctx *ctx = C.ctx;
     const std::vector<BgzfMember> &mem = C.H.mem;
@@ -97,20 +130,7 @@ static int bamc_setup(BamChunked &C, int64_t chunk_bytes)
         C.max_cbytes = std::max(C.max_cbytes, (size_t)(mem[(size_t)m1 - 1].off + mem[(size_t)m1 - 1].clen - mem[(size_t)m0].off));
         C.max_members = std::max(C.max_members, (size_t)(m1 - m0));
     }
-    for (int i = 0; i < 2; ++i) {
-        BamChunkSlot &s = C.slot[i];
-        snprintf(s.nm_file, sizeof(s.nm_file), "bamin_c%d_file", i); snprintf(s.nm_buf, sizeof(s.nm_buf), "bamin_c%d_buf", i);
-        snprintf(s.nm_mem, sizeof(s.nm_mem), "bamin_c%d_mem", i); snprintf(s.nm_ooff, sizeof(s.nm_ooff), "bamin_c%d_ooff", i);
-        snprintf(s.nm_status, sizeof(s.nm_status), "bamin_c%d_status", i);
-        TRY(ctx_buf_t(ctx, s.nm_file, ((C.max_cbytes + 3) & ~(size_t)3) + BGZF_INCH + 16, &s.d_file));
-        TRY(ctx_buf_t(ctx, s.nm_mem, C.max_members + 1, &s.d_mem));
-        TRY(ctx_buf_t(ctx, s.nm_ooff, C.max_members + 1, &s.d_ooff));
-        TRY(ctx_buf_t(ctx, s.nm_status, C.max_members + 1, &s.d_status));
-        // (the buffer of an earlier load is not taken over: its room and its members' place are this load's)
-        s.d_buf = nullptr; s.room = 0;
-        TRY(bamc_room(C, s, 0, 0));
-        HIPCHK(hipEventCreate(&s.e0)); HIPCHK(hipEventCreate(&s.e1)); HIPCHK(hipEventCreate(&s.e2));
-    }
+    TRY(bamc_slots(C, (int)std::max<int64_t>(std::min<int64_t>(nch, 2), min_slots), true));
     HIPCHK(hipEventCreate(&C.ec0)); HIPCHK(hipEventCreate(&C.ec1));
     TRY(ctx_buf_t(ctx, "bamin_crctabs", 1, &C.d_tabs));
     { static CrcTabs T; static bool made = false; if (!made) { crc_tabs_make(T); made = true; } HIPCHK(hipMemcpyAsync(C.d_tabs, &T, sizeof(T), hipMemcpyHostToDevice, C.s_main)); }
@@ -122,7 +142,7 @@ static int bamc_setup(BamChunked &C, int64_t chunk_bytes)
 static int bamc_issue(BamChunked &C, int64_t k)
 {
     telr_ctx *ctx = C.ctx;
-    BamChunkSlot &s = C.slot[k & 1];
+    BamChunkSlot &s = C.at(k);
     const std::vector<BgzfMember> &mem = C.H.mem;
     const int64_t m0 = C.first[(size_t)k], m1 = C.first[(size_t)k + 1], n = m1 - m0;
     const int64_t f0 = mem[(size_t)m0].off, f1 = mem[(size_t)m1 - 1].off + mem[(size_t)m1 - 1].clen;
@@ -147,7 +167,7 @@ static int bamc_issue(BamChunked &C, int64_t k)
 static int bamc_wait(BamChunked &C, int64_t k)
 {
     telr_ctx *ctx = C.ctx;
-    BamChunkSlot &s = C.slot[k & 1];
+    BamChunkSlot &s = C.at(k);
     HIPCHK(hipEventSynchronize(s.e2));
     float a = 0, b = 0;
     HIPCHK(hipEventElapsedTime(&a, s.e0, s.e1)); HIPCHK(hipEventElapsedTime(&b, s.e1, s.e2));
@@ -156,18 +176,20 @@ static int bamc_wait(BamChunked &C, int64_t k)
         if (s.h_status[j] != INFL_OK) { ctx->err = std::string(C.what) + ": block " + std::to_string(C.first[(size_t)k] + (int64_t)j) + ": " + infl_text(s.h_status[j]); return TELR_E_ARG; }
     return TELR_OK;
 }
-// the `len` bytes at src (chunk k's buffer) become chunk k + 1's carry: the end of its slot's room
-static int bamc_carry(BamChunked &C, int64_t k, const uint8_t *src, int64_t len)
+// the `len` bytes at src (chunk k's buffer) become chunk k + 1's carry: the end of its slot's room.  keep: the bytes of chunk k + 1 that
+// are behind that room already, or on their way there; they move with a room that grows
+static int bamc_carry(BamChunked &C, int64_t k, const uint8_t *src, int64_t len, size_t keep)
 {
     telr_ctx *ctx = C.ctx;
-    BamChunkSlot &d = C.slot[(k + 1) & 1];
-    TRY(bamc_room(C, d, (size_t)len, (size_t)C.payload(k + 1)));
+    BamChunkSlot &d = C.at(k + 1);
+    TRY(bamc_room(C, d, (size_t)len, keep));
     if (len) HIPCHK(hipMemcpyAsync(d.d_buf + d.room - len, src, (size_t)len, hipMemcpyDeviceToDevice, C.s_main));
     HIPCHK(hipStreamSynchronize(C.s_main));
     return TELR_OK;
 }
 
-static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual, int64_t chunk_bytes, telr_bam_in **out)
+// the load.  chunk_bytes BAMC_WHOLE: the whole file as one chunk in one slot.  report: the handle's chunk_info is filled
+static int bam_load(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual, int64_t chunk_bytes, bool report, telr_bam_in **out)
 {
     BamInClock wall, clk;
     std::unique_ptr<telr_bam_in, void (*)(telr_bam_in*)> B(new telr_bam_in(), telr_bam_in_free);
@@ -176,7 +198,7 @@ static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual,
     B->phase_ms[BIN_HOP] = H.ms;
     HIPCHK(hipSetDevice(ctx->device));
     BamChunked C(ctx, H);
-    TRY(bamc_setup(C, chunk_bytes));
+    TRY(bamc_setup(C, chunk_bytes, 1));
     hipStream_t st = C.s_main;
     const int64_t nch = C.nch, nrun = std::max<int64_t>(nch, 1);      // (a file without members: one empty chunk, for the header's error)
     // ---- pass 1: every chunk's records and names
@@ -190,7 +212,7 @@ static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual,
     for (int64_t k = 0; k < nrun; ++k) {
         const bool last = k + 1 >= nrun;
         if (nch) TRY(bamc_wait(C, k));
-        BamChunkSlot &s = C.slot[k & 1];
+        BamChunkSlot &s = C.at(k);
         const int64_t buflen = carry + (nch ? C.payload(k) : 0);
         uint8_t *buf = s.d_buf + s.room - carry;
         carry_in[(size_t)k] = carry; max_carry = std::max(max_carry, carry);
@@ -216,7 +238,7 @@ static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual,
             TRY(ctx_buf_t(ctx, "bamin_offs", (size_t)cap + 1, &d_offs));
             TRY(ctx_buf_t(ctx, "bamin_res", 3, &d_res));
             HIPCHK(hipEventRecord(C.ec0, st));
-            hipLaunchKernelGGL(k_bam_chain_part, dim3(1), dim3(64), 0, st, buf, buflen, from, d_offs, cap, d_res);
+            hipLaunchKernelGGL(k_bam_chain, dim3(1), dim3(64), 0, st, buf, buflen, from, d_offs, cap, d_res);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(C.ec1, st));
         }
@@ -261,10 +283,10 @@ static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual,
         rec0[(size_t)k + 1] = rec0[(size_t)k] + nrec_k;
         cut[(size_t)k] = p_end;
         carry = buflen - p_end;
-        if (!last) TRY(bamc_carry(C, k, buf + p_end, carry));
+        if (!last) TRY(bamc_carry(C, k, buf + p_end, carry, (size_t)C.payload(k + 1)));
     }
     B->phase_ms[BIN_CHAIN] = C.ms_chain; B->phase_ms[BIN_PARSE] = ms_parse;
-    // ---- host: names -> read numbers; which records are kept, and where (the whole-file load's code)
+    // ---- host: names -> read numbers; which records are kept, and where
     clk.lap();
     names.push_back(0);
     BamInDecided D;
@@ -272,9 +294,8 @@ static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual,
     const int32_t nq = (int32_t)D.reads.size();
     const size_t nk = D.kept_rec.size();
     std::unique_ptr<telr_result> R(std::move(D.R));
-    std::vector<size_t> order(nk);                             // the kept records in file order: chunk by chunk
-    for (size_t i = 0; i < nk; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return D.kept_rec[a] < D.kept_rec[b]; });
+    std::vector<int32_t> kept_at(recs.size(), -1);             // record -> its place among the kept ones: pass 2 meets them in file order
+    for (size_t i = 0; i < nk; ++i) kept_at[(size_t)D.kept_rec[i]] = (int32_t)i;
     B->phase_ms[BIN_NAMES_HOST] = clk.lap();
     // ---- the result's arrays and the set, final from the start
     TRY(bam_in_result_arrays(ctx, R.get(), D.ncig));
@@ -287,30 +308,31 @@ static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual,
         HIPCHK(hipMalloc(&S->d_qual, (size_t)S->padded_bases + 64));
         HIPCHK(hipMemsetAsync(S->d_qual + S->padded_bases, 0, 64, st));
     }
-    // ---- pass 2: inflate again; the kept records' words and the reads' bases go where they stay
+    // ---- pass 2: the kept records' words and the reads' bases go where they stay.  More than one chunk: each is uploaded and inflated
+    // again.  One chunk: slot 0 holds it where pass 1 left it (carry_in[0] == 0) and "bamin_recs" holds its records' fields
     int64_t passes = 1;
     if (nq || nk) {
         passes = 2;
-        for (BamChunkSlot &s : C.slot) TRY(bamc_room(C, s, (size_t)max_carry, 0));
-        std::vector<BamRec> h_recs; std::vector<int32_t> h_idx, h_over; std::vector<int64_t> h_off; std::vector<BamRead> h_reads;
-        size_t ki = 0; int32_t q = 0;
-        TRY(bamc_issue(C, 0));
+        const bool again = nch > 1;
+        // (keep 0: a room that grew would drop the members behind it.  One chunk has no carry, max_carry is 0 and its room stays)
+        for (int i = 0; i < C.nslot; ++i) TRY(bamc_room(C, C.slot[i], (size_t)max_carry, 0));
+        std::vector<int32_t> h_idx, h_over; std::vector<int64_t> h_off;
+        int32_t q = 0;
+        if (again) TRY(bamc_issue(C, 0));
         for (int64_t k = 0; k < nch; ++k) {
-            TRY(bamc_wait(C, k));
-            BamChunkSlot &s = C.slot[k & 1];
+            if (again) TRY(bamc_wait(C, k));
+            BamChunkSlot &s = C.at(k);
             const uint8_t *buf = s.d_buf + s.room - carry_in[(size_t)k];
             const int64_t r0 = rec0[(size_t)k], r1 = rec0[(size_t)k + 1];
-            h_recs.clear(); h_idx.clear(); h_off.clear();
-            for (; ki < nk && D.kept_rec[order[ki]] < r1; ++ki) {
-                h_idx.push_back((int32_t)h_recs.size()); h_recs.push_back(recs[(size_t)D.kept_rec[order[ki]]]); h_off.push_back(D.kept_off[order[ki]]);
-            }
-            if (!h_recs.empty()) {
-                const size_t n = h_recs.size();
+            h_idx.clear(); h_off.clear();
+            for (int64_t r = r0; r < r1; ++r) if (kept_at[(size_t)r] >= 0) { h_idx.push_back((int32_t)(r - r0)); h_off.push_back(D.kept_off[(size_t)kept_at[(size_t)r]]); }
+            if (!h_idx.empty()) {
+                const size_t n = h_idx.size();
                 BamRec *d_recs; int32_t *d_krec; int64_t *d_koff;
-                TRY(ctx_buf_t(ctx, "bamin_recs", n, &d_recs));
+                TRY(ctx_buf_t(ctx, "bamin_recs", (size_t)(r1 - r0), &d_recs));
                 TRY(ctx_buf_t(ctx, "bamin_krec", n, &d_krec));
                 TRY(ctx_buf_t(ctx, "bamin_koff", n, &d_koff));
-                HIPCHK(hipMemcpyAsync(d_recs, h_recs.data(), n * sizeof(BamRec), hipMemcpyHostToDevice, st));
+                if (again) HIPCHK(hipMemcpyAsync(d_recs, recs.data() + r0, (size_t)(r1 - r0) * sizeof(BamRec), hipMemcpyHostToDevice, st));
                 HIPCHK(hipMemcpyAsync(d_krec, h_idx.data(), n * 4, hipMemcpyHostToDevice, st));
                 HIPCHK(hipMemcpyAsync(d_koff, h_off.data(), n * 8, hipMemcpyHostToDevice, st));
                 hipLaunchKernelGGL(k_bam_cig, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, buf, d_recs, d_krec, d_koff, (int64_t)n, R->d_cig);
@@ -325,12 +347,12 @@ static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual,
                 TRY(ctx_buf_t(ctx, "bamin_reads", (size_t)nqk, &d_reads));
                 HIPCHK(hipMemcpyAsync(d_reads, D.reads.data() + q0, (size_t)nqk * sizeof(BamRead), hipMemcpyHostToDevice, st));
                 const int64_t b0 = S->boff[(size_t)q0], b1 = S->boff[(size_t)q];
-                hipLaunchKernelGGL(k_bam_seq_part, grid256((b1 - b0) / 16), dim3(256), 0, st, buf, d_reads, S->d_boff + q0, nqk, b0 / 16, b1 / 16, S->d_seq2, S->d_nmask);
+                hipLaunchKernelGGL(k_bam_seq, grid256((b1 - b0) / 16), dim3(256), 0, st, buf, d_reads, S->d_boff + q0, nqk, b0 / 16, b1 / 16, S->d_seq2, S->d_nmask);
                 HIPCHK(hipGetLastError());
                 if (with_qual) {
                     TRY(ctx_buf_t(ctx, "bamin_over", (size_t)nqk, &d_over));
                     HIPCHK(hipMemsetAsync(d_over, 0, (size_t)nqk * 4, st));
-                    hipLaunchKernelGGL(k_bam_qual_part, grid256((b1 - b0) / 4), dim3(256), 0, st, buf, d_reads, S->d_boff + q0, nqk, b0 / 4, b1 / 4, (uint32_t*)S->d_qual, d_over);
+                    hipLaunchKernelGGL(k_bam_qual, grid256((b1 - b0) / 4), dim3(256), 0, st, buf, d_reads, S->d_boff + q0, nqk, b0 / 4, b1 / 4, (uint32_t*)S->d_qual, d_over);
                     HIPCHK(hipGetLastError());
                     h_over.resize((size_t)nqk);
                     HIPCHK(hipMemcpyAsync(h_over.data(), d_over, (size_t)nqk * 4, hipMemcpyDeviceToHost, st));
@@ -342,7 +364,7 @@ static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual,
                 for (int32_t j = 0; j < nqk; ++j) if (h_over[(size_t)j]) {
                     ctx->err = "telr_bam_load: record " + std::to_string(D.first_rec[(size_t)(q0 + j)]) + ": a base quality above 93"; return TELR_E_ARG;
                 }
-            if (k + 1 < nch) TRY(bamc_carry(C, k, buf + cut[(size_t)k], carry_in[(size_t)k + 1]));
+            if (k + 1 < nch) TRY(bamc_carry(C, k, buf + cut[(size_t)k], carry_in[(size_t)k + 1], (size_t)C.payload(k + 1)));
         }
         if (D.ncig) HIPCHK(hipMemcpyAsync(R->cig, R->d_cig, (size_t)D.ncig * 4, hipMemcpyDeviceToHost, st));
     }
@@ -351,7 +373,7 @@ static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual,
     B->phase_ms[BIN_SEQ] = clk.lap();
     B->phase_ms[BIN_UPLOAD] = C.ms_upload; B->phase_ms[BIN_INFLATE] = C.ms_inflate;
     B->phase_ms[BIN_TOTAL] = wall.lap() + H.ms;
-    B->chunk_info[0] = nch; B->chunk_info[1] = passes; B->chunk_info[2] = (int64_t)C.max_alloc; B->chunk_info[3] = max_carry;
+    if (report) { B->chunk_info[0] = nch; B->chunk_info[1] = passes; B->chunk_info[2] = (int64_t)C.max_alloc; B->chunk_info[3] = max_carry; }
     bam_in_finish(B.get(), Sg.release(), R.release());
     *out = B.release();
     return TELR_OK;
@@ -360,6 +382,16 @@ static int bam_load_chunked(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual,
 extern "C" int telr_bam_chunk_plan(int64_t n_members, const int32_t *isize, int64_t chunk_bytes, int64_t *first_member_of_chunk, int64_t cap, int64_t *n_chunks)
 {
     return bam_chunk_plan(n_members, isize, chunk_bytes, first_member_of_chunk, cap, n_chunks);
+}
+
+extern "C" int telr_bam_load(telr_ctx *ctx, const char *path, int32_t keep_qual, telr_bam_in **out)
+{
+    (void)hipGetLastError();
+    if (!ctx) return TELR_E_ARG;
+    if (!path || !out) { ctx->err = "telr_bam_load: null path or output"; return TELR_E_ARG; }
+    BamInHop H;
+    TRY(bam_in_hop(ctx, "telr_bam_load", path, H));
+    return bam_load(ctx, H, keep_qual, BAMC_WHOLE, false, out);
 }
 
 extern "C" int telr_bam_load_chunked(telr_ctx *ctx, const char *path, int32_t keep_qual, int64_t chunk_bytes, telr_bam_in **out)
@@ -373,8 +405,25 @@ extern "C" int telr_bam_load_chunked(telr_ctx *ctx, const char *path, int32_t ke
     if (chunk_bytes <= 0) {
         int64_t fr = 0;
         TRY(telr_device_mem(ctx, &fr, nullptr));
-        if (chunk_bytes == TELR_BAM_CHUNK_FIT && (int64_t)H.F.n + H.total < fr / 2) return bam_load_whole(ctx, H, keep_qual, out);
+        if (chunk_bytes == TELR_BAM_CHUNK_FIT && (int64_t)H.F.n + H.total < fr / 2) return bam_load(ctx, H, keep_qual, BAMC_WHOLE, false, out);
         chunk_bytes = std::min<int64_t>(std::max<int64_t>(fr / BAMC_AUTO_DIV, BAMC_AUTO_MIN), BAMC_AUTO_MAX);
     }
-    return bam_load_chunked(ctx, H, keep_qual, chunk_bytes, out);
+    return bam_load(ctx, H, keep_qual, chunk_bytes, true, out);
+}
+
+// test tap: the inflated stream of a BGZF file (any payload) -> out[0 .. cap); *n = its length (nothing is copied when it exceeds cap)
+extern "C" int telr_debug_bgzf_inflate(telr_ctx *ctx, const char *path, uint8_t *out, int64_t cap, int64_t *n)
+{
+    (void)hipGetLastError();
+    if (!ctx || !path || !n) return TELR_E_ARG;
+    BamInHop H;
+    TRY(bam_in_hop(ctx, "telr_debug_bgzf_inflate", path, H));
+    HIPCHK(hipSetDevice(ctx->device));
+    BamChunked C(ctx, H);
+    C.what = "telr_debug_bgzf_inflate";
+    TRY(bamc_setup(C, BAMC_WHOLE, 1));
+    if (C.nch) { TRY(bamc_issue(C, 0)); TRY(bamc_wait(C, 0)); }
+    *n = H.total;
+    if (H.total && H.total <= cap && out) HIPCHK(hipMemcpy(out, C.slot[0].d_buf + C.slot[0].room, (size_t)H.total, hipMemcpyDeviceToHost));
+    return TELR_OK;
 }

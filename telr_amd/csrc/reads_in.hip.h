@@ -456,41 +456,18 @@ static int rt_parse(RtLoad &L, const uint8_t *buf, int64_t buflen, bool last, in
     return TELR_OK;
 }
 
-// slots for text that comes from the host (gzip, plain): the layout of bam_in_chunked.hip.h, the payload `cap` bytes at the most
-static int rt_setup_host(BamChunked &C, size_t cap)
-{
-    telr_ctx *ctx = C.ctx;
-    C.nch = 0; C.max_payload = cap;
-    for (int i = 0; i < 2; ++i) {
-        BamChunkSlot &s = C.slot[i];
-        snprintf(s.nm_buf, sizeof(s.nm_buf), "bamin_c%d_buf", i);
-        s.d_buf = nullptr; s.room = 0;
-        TRY(bamc_room(C, s, 0, 0));
-        HIPCHK(hipEventCreate(&s.e0)); HIPCHK(hipEventCreate(&s.e1)); HIPCHK(hipEventCreate(&s.e2));
-    }
-    return TELR_OK;
-}
+// text that comes from the host (gzip, plain) goes straight behind a slot's room (bamc_slots without the members' buffers: the layout
+// of bam_in_chunked.hip.h, the payload C.max_payload bytes at the most)
 static int rt_issue_host(BamChunked &C, int64_t k, const uint8_t *p, size_t n)
 {
     telr_ctx *ctx = C.ctx;
-    BamChunkSlot &s = C.slot[k & 1];
+    BamChunkSlot &s = C.at(k);
     HIPCHK(hipEventRecord(s.e0, C.s_io));
     if (n) HIPCHK(hipMemcpyAsync(s.d_buf + s.room, p, n, hipMemcpyHostToDevice, C.s_io));
     HIPCHK(hipMemsetAsync(s.d_buf + s.room + n, 0, 64, C.s_io));
     HIPCHK(hipEventRecord(s.e1, C.s_io));
     return TELR_OK;
 }
-// the `len` bytes at src become the next slot's carry; its `keep` bytes of text, already there, move with a room that grows
-static int rt_carry(BamChunked &C, int64_t k, const uint8_t *src, int64_t len, size_t keep)
-{
-    telr_ctx *ctx = C.ctx;
-    BamChunkSlot &d = C.slot[(k + 1) & 1];
-    TRY(bamc_room(C, d, (size_t)len, keep));
-    if (len) HIPCHK(hipMemcpyAsync(d.d_buf + d.room - len, src, (size_t)len, hipMemcpyDeviceToDevice, C.s_main));
-    HIPCHK(hipStreamSynchronize(C.s_main));
-    return TELR_OK;
-}
-
 static int reads_load(telr_ctx *ctx, const BamInHop &H, int container, int32_t keep_qual, int64_t chunk_bytes, telr_reads_in **out)
 {
     BamInClock wall, clk;
@@ -508,11 +485,12 @@ static int reads_load(telr_ctx *ctx, const BamInHop &H, int container, int32_t k
     size_t ppos = 0;                                   // plain: the next byte of the file
     size_t pay[2] = { 0, 0 }; bool lastf[2] = { false, false };
     const size_t chunk = (size_t)chunk_bytes;
-    if (container == RIN_BGZF) TRY(bamc_setup(C, chunk_bytes));
+    if (container == RIN_BGZF) TRY(bamc_setup(C, chunk_bytes, 2));
     else if (container == RIN_GZIP) {
         // (deflate does not expand beyond 1,032 times: a small file needs no buffer of a whole chunk)
         const size_t cap = (size_t)std::min<double>((double)chunk + RT_GATHER, (double)fn * 1032.0 + RT_GATHER);
-        TRY(rt_setup_host(C, cap));
+        C.max_payload = cap;
+        TRY(bamc_slots(C, 2, false));
         void *p;
         TRY(ctx_hbuf(ctx, "rin_pin0", cap + 64, &p)); Z.pin[0] = (uint8_t*)p;
         TRY(ctx_hbuf(ctx, "rin_pin1", cap + 64, &p)); Z.pin[1] = (uint8_t*)p;
@@ -521,7 +499,10 @@ static int reads_load(telr_ctx *ctx, const BamInHop &H, int container, int32_t k
         if (inflateInit2(&Z.z, 47) != Z_OK) { ctx->err = "telr_reads_load: gzip: zlib does not start"; return TELR_E_NOMEM; }
         Z.z_on = true;
         Z.th = std::thread([&Z] { Z.run(); });
-    } else TRY(rt_setup_host(C, std::min<size_t>(chunk + RT_GATHER, std::max<size_t>(fn, 1))));
+    } else {
+        C.max_payload = std::min<size_t>(chunk + RT_GATHER, std::max<size_t>(fn, 1));
+        TRY(bamc_slots(C, 2, false));
+    }
     // chunk k on its way to its slot; BGZF: inflated there
     auto issue = [&](int64_t k) -> int {
         const int i = (int)(k & 1);
@@ -546,7 +527,7 @@ static int reads_load(telr_ctx *ctx, const BamInHop &H, int container, int32_t k
     };
     auto wait = [&](int64_t k) -> int {
         if (container == RIN_BGZF) return bamc_wait(C, k);
-        BamChunkSlot &s = C.slot[k & 1];
+        BamChunkSlot &s = C.at(k);
         HIPCHK(hipEventSynchronize(s.e1));
         float a = 0;
         HIPCHK(hipEventElapsedTime(&a, s.e0, s.e1)); C.ms_upload += a;
@@ -563,7 +544,7 @@ static int reads_load(telr_ctx *ctx, const BamInHop &H, int container, int32_t k
             const int64_t payload = (int64_t)pay[i];
             bool ahead = false;
             if (!last && container != RIN_GZIP) { TRY(issue(k + 1)); ahead = true; }          // (gzip: its thread is ahead already; the upload follows the parse)
-            BamChunkSlot &s = C.slot[i];
+            BamChunkSlot &s = C.at(k);
             const int64_t buflen = carry + payload;
             const uint8_t *buf = s.d_buf + s.room - carry;
             max_carry = std::max(max_carry, carry); text += payload; ++nchunks;
@@ -577,7 +558,7 @@ static int reads_load(telr_ctx *ctx, const BamInHop &H, int container, int32_t k
             TRY(rt_parse(L, buf, buflen, last, &cut));
             if (last) break;
             carry = buflen - cut;
-            TRY(rt_carry(C, k, buf + cut, carry, ahead ? pay[(k + 1) & 1] : 0));
+            TRY(bamc_carry(C, k, buf + cut, carry, ahead ? pay[(k + 1) & 1] : 0));
             if (!ahead) TRY(issue(k + 1));
         }
     }

@@ -194,6 +194,44 @@ def test_empty_file_in_chunks(engine, tmp_path):
     assert str(e.value) == str(w.value) and "header" in str(e.value)
 
 
+@pytest.mark.parametrize("data", [b"", R.EOF_MARKER], ids=["zero_bytes", "eof_marker_alone"])
+def test_no_member_with_a_byte(engine, tmp_path, data):
+    """no chunk to inflate, or one of no bytes: the definition's header error, the same words on both entry points"""
+    with pytest.raises(R.BamInError) as d:
+        R.load(data)
+    assert d.value.code == R.E_ARG and d.value.text == "header: magic runs past the stream"
+    p = tmp_path / "none.bam"
+    p.write_bytes(data)
+    seen = []
+    for c in (None, 1):
+        with pytest.raises(TelrError) as e:
+            engine.load_bam(str(p), chunk_bytes=c)
+        assert e.value.code == d.value.code and d.value.text in str(e.value), str(e.value)
+        seen.append(str(e.value))
+    assert seen[0] == seen[1]
+
+
+def test_one_chunk_second_pass_reuses_its_slot(engine, whole):
+    """one chunk, something kept, qualities on: the second pass reads the chunk where the first left it, on every way to one chunk; a
+    load in two slots right behind it on the same engine sees nothing of that slot's state"""
+    case = RECORD[0]
+    ref = definition(case)
+    assert case["keep_qual"] and ref.quals is not None and len(ref.alns)
+    path, snap = whole(case)
+    for c in (None, sum(isizes(case["data"])) + 1, 0, 1):
+        bi = engine.load_bam(path, keep_qual=True, chunk_bytes=c)
+        loaded_equals(engine, bi, ref)
+        assert snapshot(engine, bi) == snap
+        info = bi.chunk_info
+        bi.free()
+        if c is None:
+            assert info == dict(chunks=0, passes=0, largest_buffer=0, largest_carry=0)
+        elif c != 1:
+            assert info["chunks"] == 1 and info["passes"] == 2 and info["largest_carry"] == 0
+        else:
+            assert info["chunks"] > 2 and info["passes"] == 2
+
+
 # ---- 4. memory bound ----------------------------------------------------------------------------------------------------------------
 def test_chunk_buffer_does_not_grow_with_the_file(engine, tmp_path):
     c = 65536

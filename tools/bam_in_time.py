@@ -97,8 +97,9 @@ def main():
         "telr_map_ms": map_ms, "write_bam_device_ms": write_ms,
         "legs": legs,
         "chain_share_of_load": med["chain"] / max(med["total"], 1e-9),
-        "timing": "per leg %d repeats after one untimed call, the context's scratch released before every call.  whole: wall clock inside telr_bam_load per "
-                  "phase (each phase ends with a stream synchronisation).  chunked_*: sums over the chunks -- upload and inflate are device times of both "
+        "timing": "per leg %d repeats after one untimed call, the context's scratch released before every call.  whole: the load of one chunk -- upload, "
+                  "inflate and chain are device times between events, parse, names and sequences host wall clock, nothing is inflated twice.  chunked_*: sums over "
+                  "the chunks -- upload and inflate are device times of both "
                   "passes on the second stream and overlap with the rest, chain is device time, parse the host time of pass 1 behind the chain, sequences "
                   "the whole second pass; total is wall clock and not the sum of the others.  peak_device_bytes: free device memory (telr_device_mem) before "
                   "the call minus its minimum during the call, sampled every 2 ms by a host thread; the result and the set are part of it.  telr_map and "
