@@ -20,6 +20,18 @@ def _np_from(ptr, n, dtype):
     return np.frombuffer(buf, dtype=dt, count=n).copy()
 
 
+def _ic_arrays(entry, ic, with_sigs=False):
+    """an InsCalls (or anything with calls / read_off / reads / sigs of that form) as the C ABI takes it ->
+    contiguous (calls, read_off, reads, sigs or None); `entry` opens the error text"""
+    calls = np.ascontiguousarray(ic.calls, dtype=INS_CALL_DTYPE)
+    sigs = np.ascontiguousarray(ic.sigs, dtype=INS_SIG_DTYPE) if with_sigs else None
+    read_off = np.ascontiguousarray(ic.read_off, dtype=np.int64)
+    reads = np.ascontiguousarray(ic.reads, dtype=np.int32)
+    if len(read_off) != len(calls) + 1 or (len(calls) and int(read_off[-1]) > len(reads)):
+        raise _lib.TelrError("%s: read_off must hold len(calls) + 1 offsets into reads" % entry)
+    return calls, read_off, reads, sigs
+
+
 def _qual_arrays(qual):
     """base qualities as the C ABI takes them: a list of quality strings (str / bytes, Phred + 33, one per sequence) or the
     (buffer, offsets) pair of fasta.FastaFile.qual -> (uint8 buffer, int64 offsets)"""
@@ -945,11 +957,7 @@ class Index:
         read_off / reads of that form) on raw result r (telr_genotype_insertions; include/telr_hip.h has the definition, which is
         not Sniffles'): opt an _abi.GenoOpt (None: the defaults) -> InsGenotypes"""
         o = GenoOpt.default() if opt is None else opt
-        calls = np.ascontiguousarray(ic.calls, dtype=INS_CALL_DTYPE)
-        read_off = np.ascontiguousarray(ic.read_off, dtype=np.int64)
-        reads = np.ascontiguousarray(ic.reads, dtype=np.int32)
-        if len(read_off) != len(calls) + 1 or (len(calls) and int(read_off[-1]) > len(reads)):
-            raise _lib.TelrError("telr_genotype_insertions: read_off must hold len(calls) + 1 offsets into reads")
+        calls, read_off, reads, _ = _ic_arrays("telr_genotype_insertions", ic)
         h = C.c_void_p()
         rc = self.eng.L.telr_genotype_insertions(self.eng.h, r, self.targets.n, len(calls), calls.ctypes.data, read_off.ctypes.data, reads.ctypes.data,
                                                  C.byref(o), C.byref(h))
@@ -971,12 +979,7 @@ class Index:
         read_set the SeqSet r was mapped from, opt an _abi.DraftOpt (None: the defaults) -> (drafts, set): one DRAFT_DTYPE record per
         call (sig = set_index = -1: no draft) and the SeqSet of the drafts, in call order, on the reference strand"""
         o = DraftOpt.default() if opt is None else opt
-        calls = np.ascontiguousarray(ic.calls, dtype=INS_CALL_DTYPE)
-        sigs = np.ascontiguousarray(ic.sigs, dtype=INS_SIG_DTYPE)
-        read_off = np.ascontiguousarray(ic.read_off, dtype=np.int64)
-        reads = np.ascontiguousarray(ic.reads, dtype=np.int32)
-        if len(read_off) != len(calls) + 1 or (len(calls) and int(read_off[-1]) > len(reads)):
-            raise _lib.TelrError("telr_draft_contigs: read_off must hold len(calls) + 1 offsets into reads")
+        calls, read_off, reads, sigs = _ic_arrays("telr_draft_contigs", ic, True)
         h, hs = C.c_void_p(), C.c_void_p()
         L = self.eng.L
         rc = L.telr_draft_contigs(self.eng.h, r, self.targets.n, len(calls), calls.ctypes.data, read_off.ctypes.data, reads.ctypes.data,
@@ -999,12 +1002,7 @@ class Index:
         every call) -> one BRIDGE_DTYPE record per call (sig_l = sig_r = -1: no bridge).  Records only: SeqSet.join makes the sequences
         of the two pieces (qid_l, start_l, len_l, rc_l) and (qid_r, start_r, len_r, rc_r)."""
         o = BridgeOpt.default() if opt is None else opt
-        calls = np.ascontiguousarray(ic.calls, dtype=INS_CALL_DTYPE)
-        sigs = np.ascontiguousarray(ic.sigs, dtype=INS_SIG_DTYPE)
-        read_off = np.ascontiguousarray(ic.read_off, dtype=np.int64)
-        reads = np.ascontiguousarray(ic.reads, dtype=np.int32)
-        if len(read_off) != len(calls) + 1 or (len(calls) and int(read_off[-1]) > len(reads)):
-            raise _lib.TelrError("telr_bridge_contigs: read_off must hold len(calls) + 1 offsets into reads")
+        calls, read_off, reads, sigs = _ic_arrays("telr_bridge_contigs", ic, True)
         if want is not None:
             want = np.ascontiguousarray(np.asarray(want) != 0, dtype=np.uint8)
             if len(want) != len(calls):

@@ -4,9 +4,9 @@
 // enters from the right are joined at ONE shared k-mer of their clips.  An own, fully specified definition that is NOT an assembler and
 // NOT wtdbg2 or flye: no consensus is formed, polishing follows as it follows a draft.  Records only: telr_seqset_join makes the sequences.
 //
-//   k_bridge_span    one lane per signature: a clip (kind 2) takes a lower and an upper bound in the calls' (tid, pos) keys; counted, then
-//                    scanned in 64 bits -- the (signature, call) pairs, and which clips lie within `reach` of a call at all;
-//   k_bridge_cand    one wave per such clip: the one-coordinate walk of draft_walk (stage2_common.hip.h) -- lo_a(xL) of a tail clip,
+//   CutInput         (stage2_common.hip.h) the input, its refusals and its uploads are those of telr_draft_contigs; its k_cut_span here
+//                    counts the clips (kind 2): the (signature, call) pairs, and which clips lie within `reach` of a call at all;
+//   k_bridge_cand   one wave per such clip: the one-coordinate walk of draft_walk (stage2_common.hip.h) -- lo_a(xL) of a tail clip,
 //                    hi_b(xR) of a head clip; a candidate's validity, clip length and flank do not depend on the call;
 //   k_bridge_top     one wave per call: the clips within `reach` of it are a contiguous run of the sorted signature array; the valid
 //                    ones of its own reads counted, then the first `pairs` of each side by repeated butterfly minima over the total
@@ -31,29 +31,13 @@
 #define BR_CHUNK 4096            /* start positions of V per step: 16 per lane */
 #define BR_MAX_PAIRS 8
 
-struct BridgeRec { int32_t ts, te, qs, qe, qlen, rev, n_cigar, pad; int64_t cigar_off; };      // qs, qe on the record's own strand
 struct BridgeCand { int32_t valid, clip, fl, x; };                                             // x = lo_a(xL) of a left, hi_b(xR) of a right candidate
 struct BridgeTop { int32_t sl[BR_MAX_PAIRS], sr[BR_MAX_PAIRS], nl, nr; };                       // the kept signatures by rank (-1: none), the valid counts
 struct BridgeVote { int32_t votes, i, j; };                                                    // votes -1: the pair is not voted
 
 struct telr_bridges { std::vector<telr_bridge> d; };
 
-__global__ void __launch_bounds__(256) k_bridge_span(const telr_ins_sig *__restrict__ sigs, int32_t ns, const uint64_t *__restrict__ ckeys, int32_t ncall, int32_t reach,
-                                                     int32_t *__restrict__ cnt)
-{
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= ns) return;
-    const telr_ins_sig s = sigs[j];
-    int32_t f = 0, c = 0;
-    if (s.kind == 2) {
-        const int64_t lo = s.pos > reach ? (int64_t)s.pos - reach : 0, hi = (int64_t)s.pos + reach < 0x7fffffffLL ? (int64_t)s.pos + reach : 0x7fffffffLL;
-        d_span(ckeys, ncall, s.tid, lo, hi, &f, &c);
-    }
-    (void)f;
-    cnt[j] = c;
-}
-
-__global__ void __launch_bounds__(256) k_bridge_cand(const telr_ins_sig *__restrict__ sigs, int32_t ns, const int32_t *__restrict__ cnt, const BridgeRec *__restrict__ recs,
+__global__ void __launch_bounds__(256) k_bridge_cand(const telr_ins_sig *__restrict__ sigs, int32_t ns, const int32_t *__restrict__ cnt, const CutRec *__restrict__ recs,
                                                      const uint32_t *__restrict__ cig, int32_t flank, int32_t min_flank, int32_t k,
                                                      BridgeCand *__restrict__ candl, BridgeCand *__restrict__ candr)
 {
@@ -64,7 +48,7 @@ __global__ void __launch_bounds__(256) k_bridge_cand(const telr_ins_sig *__restr
     L.valid = 0; L.clip = 0; L.fl = 0; L.x = 0; R = L;
     const telr_ins_sig s = sigs[w];
     if (s.kind == 2 && cnt[w] > 0) {                      // (the same in every lane of the wave)
-        const BridgeRec A = recs[s.rec];
+        const CutRec A = recs[s.rec];
         int64_t lo = 0, hi = 0; bool flo = false, fhi = false;
         if (s.pos == A.te) {                              // a tail clip: the read goes on to the right of the reference position
             const int64_t xL = (int64_t)s.pos - flank > A.ts ? (int64_t)s.pos - flank : (int64_t)A.ts;
@@ -142,9 +126,8 @@ __global__ void __launch_bounds__(256) k_bridge_top(const telr_ins_sig *__restri
     const int64_t k = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
     if (k >= ncall) return;
     const telr_ins_call c = calls[k];
-    const int64_t plo = c.pos > reach ? (int64_t)c.pos - reach : 0, phi = (int64_t)c.pos + reach < 0x7fffffffLL ? (int64_t)c.pos + reach : 0x7fffffffLL;
-    const uint64_t t = (uint64_t)(uint32_t)c.tid << 32;
-    const int32_t s0 = draft_sig_bound<false>(sigs, ns, t | (uint64_t)plo), s1 = draft_sig_bound<true>(sigs, ns, t | (uint64_t)phi);
+    int32_t s0, s1;
+    d_sig_window(sigs, ns, c, reach, &s0, &s1);
     BridgeTop *T = top + k;
     if (lane == 0) for (int q = 0; q < BR_MAX_PAIRS; ++q) { T->sl[q] = -1; T->sr[q] = -1; }
     const int32_t nl = bridge_top_side(sigs, s0, s1, candl, reads, read_off[k], read_off[k + 1], pairs, lane, T->sl);
@@ -196,7 +179,7 @@ static __device__ __forceinline__ void bridge_group(const uint32_t *__restrict__
 }
 
 __global__ void __launch_bounds__(256) k_bridge_vote(const uint32_t *__restrict__ par2, const uint32_t *__restrict__ parn, const int64_t *__restrict__ sboff,
-                                                     const telr_ins_sig *__restrict__ sigs, const BridgeRec *__restrict__ recs, const BridgeTop *__restrict__ top,
+                                                     const telr_ins_sig *__restrict__ sigs, const CutRec *__restrict__ recs, const BridgeTop *__restrict__ top,
                                                      const uint8_t *__restrict__ want, int32_t pairs, int32_t k, int32_t window, BridgeVote *__restrict__ out)
 {
     __shared__ uint32_t wc[BR_WWORDS], wm[BR_WWORDS];
@@ -212,7 +195,7 @@ __global__ void __launch_bounds__(256) k_bridge_vote(const uint32_t *__restrict_
     if (go) go = sigs[jl].qid != sigs[jr].qid;
     if (!go) { if (tid == 0) out[blockIdx.x] = res; return; }
     const telr_ins_sig SL = sigs[jl], SR = sigs[jr];
-    const BridgeRec A = recs[SL.rec], B = recs[SR.rec];
+    const CutRec A = recs[SL.rec], B = recs[SR.rec];
     const int32_t cL = A.qlen - A.qe, cR = B.qs;                                  // both >= k: the candidates are valid
     const int32_t Wn = window < cL ? window : cL, ilo = cL - Wn;
     const int64_t srcA = sboff[SL.qid], srcB = sboff[SR.qid], t0 = (int64_t)A.qlen - Wn;      // the window = the read's last Wn strand bases
@@ -306,7 +289,7 @@ __global__ void __launch_bounds__(256) k_bridge_vote(const uint32_t *__restrict_
     if (tid == 0) out[blockIdx.x] = res;
 }
 
-__global__ void __launch_bounds__(256) k_bridge_pick(const telr_ins_sig *__restrict__ sigs, const BridgeRec *__restrict__ recs, const BridgeCand *__restrict__ candl,
+__global__ void __launch_bounds__(256) k_bridge_pick(const telr_ins_sig *__restrict__ sigs, const CutRec *__restrict__ recs, const BridgeCand *__restrict__ candl,
                                                      const BridgeCand *__restrict__ candr, const BridgeTop *__restrict__ top, const BridgeVote *__restrict__ votes,
                                                      const uint8_t *__restrict__ want, int32_t ncall, int32_t pairs, int32_t min_votes, int32_t max_len,
                                                      telr_bridge *__restrict__ out)
@@ -326,7 +309,7 @@ __global__ void __launch_bounds__(256) k_bridge_pick(const telr_ins_sig *__restr
         if (best >= 0 && bv.votes >= min_votes) {         // otherwise the call has none: no second pair is tried
             const int32_t jl = top[kc].sl[best / pairs], jr = top[kc].sr[best % pairs];
             const telr_ins_sig SL = sigs[jl], SR = sigs[jr];
-            const BridgeRec A = recs[SL.rec], B = recs[SR.rec];
+            const CutRec A = recs[SL.rec], B = recs[SR.rec];
             const int64_t lo_l = candl[jl].x, hi_l = (int64_t)A.qe + bv.i, lo_r = bv.j, hi_r = candr[jr].x;
             const int64_t len_l = hi_l - lo_l, len_r = hi_r - lo_r;
             if (len_l + len_r >= 1 && len_l + len_r <= max_len) {
@@ -356,38 +339,16 @@ extern "C" int telr_bridge_contigs(telr_ctx *ctx, const telr_result *r, int32_t 
 {
     (void)hipGetLastError();
     if (!ctx) return TELR_E_ARG;
-    auto bad = [&](const std::string &why) { ctx->err = "telr_bridge_contigs: " + why; return TELR_E_ARG; };
-    if (!r || !out || !read_set) return bad("null result, read set or output");
-    if (n_targets <= 0) return bad("n_targets must be positive");
-    if (n_calls < 0 || (n_calls > 0 && (!calls || !read_off))) return bad("null calls or read offsets");
-    if (n_sig < 0 || (n_sig > 0 && !sigs)) return bad("null signatures");
     telr_bridge_opt O;
     if (opt) O = *opt; else telr_bridge_opt_default(&O);
-    if (O.flank < 0 || O.min_flank < 0 || O.reach < 0 || O.max_len < 0) return bad("negative option");
-    if (O.min_flank > O.flank) return bad("min_flank > flank");
-    if (O.k < 11 || O.k > 15) return bad("k outside 11 .. 15");
-    if (O.window < O.k || O.window > 4096) return bad("window outside k .. 4096");
-    if (O.pairs < 1 || O.pairs > BR_MAX_PAIRS) return bad("pairs outside 1 .. 8");
-    if (O.min_votes < 1) return bad("min_votes below 1");
-    const size_t n = r->alns.size();
-    if (n >= 0x7ffffff0u) { ctx->err = "telr_bridge_contigs: too many records"; return TELR_E_RANGE; }
-    if (n_calls >= 0x7ffffff0LL) { ctx->err = "telr_bridge_contigs: too many calls"; return TELR_E_RANGE; }
-    if (n_sig >= 0x7ffffff0LL) { ctx->err = "telr_bridge_contigs: too many signatures"; return TELR_E_RANGE; }
-    std::vector<uint64_t> ckeys((size_t)n_calls);
-    std::string why;
-    if (!call_list_check(n_calls, calls, read_off, reads, n_targets, read_set->n, ckeys.data(), nullptr, &why)) return bad(why);
-    std::vector<BridgeRec> recs(n);
-    for (size_t i = 0; i < n; ++i) {
-        const telr_aln &a = r->alns[i];
-        if (!record_check(a, i, n_targets, r->ncig, &why)) return bad(why);
-        if (a.qid >= read_set->n) return bad("record " + std::to_string(i) + ": qid outside the read set");
-        if (a.qlen != read_set->len[a.qid]) return bad("record " + std::to_string(i) + ": qlen is not the length of its read in the read set");
-        BridgeRec &e = recs[i];
-        e.rev = (a.flags & TELR_F_REV) ? 1 : 0;
-        e.ts = a.ts; e.te = a.te; e.qs = e.rev ? a.qlen - a.qe : a.qs; e.qe = e.rev ? a.qlen - a.qs : a.qe; e.qlen = a.qlen; e.n_cigar = a.n_cigar; e.pad = 0;
-        e.cigar_off = a.cigar_off;
-    }
-    if (!sig_list_check(n_sig, sigs, r->alns.data(), n, n_targets, read_set->n, &why)) return bad(why);
+    const char *fault = (O.flank < 0 || O.min_flank < 0 || O.reach < 0 || O.max_len < 0) ? "negative option"
+                        : O.min_flank > O.flank ? "min_flank > flank"
+                        : (O.k < 11 || O.k > 15) ? "k outside 11 .. 15"
+                        : (O.window < O.k || O.window > 4096) ? "window outside k .. 4096"
+                        : (O.pairs < 1 || O.pairs > BR_MAX_PAIRS) ? "pairs outside 1 .. 8"
+                        : O.min_votes < 1 ? "min_votes below 1" : nullptr;
+    CutInput in;
+    TRY(in.check(ctx, "telr_bridge_contigs", r, out != nullptr, n_targets, n_calls, calls, read_off, reads, n_sig, sigs, read_set, fault));
     const int64_t pp = (int64_t)O.pairs * O.pairs;
     if (n_calls * pp >= 0x7ffffff0LL) { ctx->err = "telr_bridge_contigs: too many (call, pair) workgroups"; return TELR_E_RANGE; }
     telr_bridges *D = new telr_bridges();
@@ -397,55 +358,28 @@ extern "C" int telr_bridge_contigs(telr_ctx *ctx, const telr_result *r, int32_t 
     D->d.assign((size_t)n_calls, none);
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const int32_t nc = (int32_t)n_calls, ns = (int32_t)n_sig;
-    if (nc > 0 && ns > 0) {
-        result_wait(r);
-        int64_t P = 0;
-        telr_ins_sig *d_sig; telr_ins_call *d_calls; uint64_t *d_ckeys; int32_t *d_cnt; int64_t *d_off, *d_tot;
-        TRY(ctx_buf_t(ctx, "bridge_sig", (size_t)ns, &d_sig));
-        TRY(ctx_buf_t(ctx, "bridge_calls", (size_t)nc, &d_calls));
-        TRY(ctx_buf_t(ctx, "bridge_ckeys", (size_t)nc, &d_ckeys));
-        TRY(ctx_buf_t(ctx, "bridge_cnt", (size_t)ns + 1, &d_cnt));
-        TRY(ctx_buf_t(ctx, "bridge_off", (size_t)ns + 1, &d_off));
-        TRY(ctx_buf_t(ctx, "bridge_tot", 4, &d_tot));
-        HIPCHK(hipMemcpyAsync(d_sig, sigs, (size_t)ns * sizeof(telr_ins_sig), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_calls, calls, (size_t)nc * sizeof(telr_ins_call), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_ckeys, ckeys.data(), (size_t)nc * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_bridge_span, grid256((int64_t)ns), dim3(256), 0, st, d_sig, ns, d_ckeys, nc, O.reach, d_cnt);
-        HIPCHK(hipGetLastError());
-        TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt, ns, d_off, d_tot, 0, nullptr, nullptr)));
-        HIPCHK(hipMemcpyAsync(&P, d_tot, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (P >= 0x7ffffff0LL) { ctx->err = "telr_bridge_contigs: too many (signature, call) pairs"; return TELR_E_RANGE; }
-        if (P > 0) {
-            uint32_t *d_cig;
-            TRY(result_dev_cigars(ctx, r, "bridge_cig", true, &d_cig, nullptr));
-            const int64_t nreads = read_off[n_calls];
-            BridgeRec *d_rec; int64_t *d_roff; int32_t *d_reads; BridgeCand *d_cl, *d_cr; BridgeTop *d_top; BridgeVote *d_votes; uint8_t *d_want = nullptr; telr_bridge *d_out;
-            TRY(ctx_buf_t(ctx, "bridge_rec", n, &d_rec));
-            TRY(ctx_buf_t(ctx, "bridge_roff", (size_t)nc + 1, &d_roff));
-            TRY(ctx_buf_t(ctx, "bridge_reads", (size_t)nreads, &d_reads));
-            TRY(ctx_buf_t(ctx, "bridge_candl", (size_t)ns, &d_cl));
-            TRY(ctx_buf_t(ctx, "bridge_candr", (size_t)ns, &d_cr));
-            TRY(ctx_buf_t(ctx, "bridge_top", (size_t)nc, &d_top));
-            TRY(ctx_buf_t(ctx, "bridge_votes", (size_t)(nc * pp), &d_votes));
-            TRY(ctx_buf_t(ctx, "bridge_out", (size_t)nc, &d_out));
-            if (want) {
-                TRY(ctx_buf_t(ctx, "bridge_want", (size_t)nc, &d_want));
-                HIPCHK(hipMemcpyAsync(d_want, want, (size_t)nc, hipMemcpyHostToDevice, st));
-            }
-            HIPCHK(hipMemcpyAsync(d_rec, recs.data(), n * sizeof(BridgeRec), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(d_roff, read_off, ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
-            if (nreads) HIPCHK(hipMemcpyAsync(d_reads, reads, (size_t)nreads * 4, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_bridge_cand, dim3((unsigned)(((int64_t)ns + 3) / 4)), dim3(256), 0, st, d_sig, ns, d_cnt, d_rec, d_cig, O.flank, O.min_flank, O.k, d_cl, d_cr);
-            hipLaunchKernelGGL(k_bridge_top, dim3((unsigned)(((int64_t)nc + 3) / 4)), dim3(256), 0, st, d_sig, ns, d_calls, nc, d_cl, d_cr, d_roff, d_reads, O.reach, O.pairs, d_top);
-            hipLaunchKernelGGL(k_bridge_vote, dim3((unsigned)(nc * pp)), dim3(256), 0, st, read_set->d_seq2, read_set->d_nmask, read_set->d_boff, d_sig, d_rec, d_top,
-                               d_want, O.pairs, O.k, O.window, d_votes);
-            hipLaunchKernelGGL(k_bridge_pick, grid256((int64_t)nc), dim3(256), 0, st, d_sig, d_rec, d_cl, d_cr, d_top, d_votes, d_want, nc, O.pairs, O.min_votes, O.max_len, d_out);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(D->d.data(), d_out, (size_t)nc * sizeof(telr_bridge), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
+    const int32_t nc = in.nc, ns = in.ns;
+    TRY(in.span(O.reach, 1u << 2, false));                                        // the clips: kind 2
+    if (in.P > 0) {
+        TRY(in.prepare_pairs());
+        BridgeCand *d_cl, *d_cr; BridgeTop *d_top; BridgeVote *d_votes; uint8_t *d_want = nullptr; telr_bridge *d_out;
+        TRY(ctx_buf_t(ctx, "bridge_candl", (size_t)ns, &d_cl));
+        TRY(ctx_buf_t(ctx, "bridge_candr", (size_t)ns, &d_cr));
+        TRY(ctx_buf_t(ctx, "bridge_top", (size_t)nc, &d_top));
+        TRY(ctx_buf_t(ctx, "bridge_votes", (size_t)(nc * pp), &d_votes));
+        TRY(ctx_buf_t(ctx, "bridge_out", (size_t)nc, &d_out));
+        if (want) {
+            TRY(ctx_buf_t(ctx, "bridge_want", (size_t)nc, &d_want));
+            HIPCHK(hipMemcpyAsync(d_want, want, (size_t)nc, hipMemcpyHostToDevice, st));
         }
+        hipLaunchKernelGGL(k_bridge_cand, dim3((unsigned)(((int64_t)ns + 3) / 4)), dim3(256), 0, st, in.d_sig, ns, in.d_cnt, in.d_rec, in.d_cig, O.flank, O.min_flank, O.k, d_cl, d_cr);
+        hipLaunchKernelGGL(k_bridge_top, dim3((unsigned)(((int64_t)nc + 3) / 4)), dim3(256), 0, st, in.d_sig, ns, in.d_calls, nc, d_cl, d_cr, in.d_roff, in.d_reads, O.reach, O.pairs, d_top);
+        hipLaunchKernelGGL(k_bridge_vote, dim3((unsigned)(nc * pp)), dim3(256), 0, st, read_set->d_seq2, read_set->d_nmask, read_set->d_boff, in.d_sig, in.d_rec, d_top,
+                           d_want, O.pairs, O.k, O.window, d_votes);
+        hipLaunchKernelGGL(k_bridge_pick, grid256((int64_t)nc), dim3(256), 0, st, in.d_sig, in.d_rec, d_cl, d_cr, d_top, d_votes, d_want, nc, O.pairs, O.min_votes, O.max_len, d_out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(D->d.data(), d_out, (size_t)nc * sizeof(telr_bridge), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
     *out = guard.release();
     return TELR_OK;

@@ -4,8 +4,8 @@
 // every call one supporting read is the backbone, and the piece of it that carries the insertion between reference-aligned flanks is
 // the draft, on the reference strand.
 //
-//   k_draft_span     one lane per signature: a sized one (kind 0 / 1) takes a lower and an upper bound in the calls' (tid, pos) keys --
-//                    the calls within `reach` are a contiguous run of the ascending keys; counted, then scanned in 64 bits;
+//   CutInput         (stage2_common.hip.h, the input that telr_bridge_contigs takes too) the refusals, the uploads, k_cut_span over the
+//                    sized signatures (kinds 0 and 1) and the 64-bit scan of its counts: the (signature, call) pairs;
 //   k_draft_pairs    one lane per (signature, call) pair: its signature from a binary search in the scanned counts, its call from its
 //                    rank in the run, membership of the signature's read in the call's supporter list from a binary search;
 //   k_draft_walk     one wave per pair, 64 CIGAR words per step (coalesced dwords), wave prefix sums of the reference and query lengths
@@ -23,20 +23,6 @@ struct DraftCand { int64_t dlen; int32_t valid, fl, lo, n; };                   
 
 struct telr_drafts { std::vector<telr_draft> d; };
 
-__global__ void __launch_bounds__(256) k_draft_span(const telr_ins_sig *__restrict__ sigs, int32_t ns, const uint64_t *__restrict__ ckeys, int32_t ncall, int32_t reach,
-                                                    int32_t *__restrict__ first, int32_t *__restrict__ cnt)
-{
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= ns) return;
-    const telr_ins_sig s = sigs[j];
-    int32_t f = 0, c = 0;
-    if (s.kind == 0 || s.kind == 1) {
-        const int64_t lo = s.pos > reach ? (int64_t)s.pos - reach : 0, hi = (int64_t)s.pos + reach < 0x7fffffffLL ? (int64_t)s.pos + reach : 0x7fffffffLL;
-        d_span(ckeys, ncall, s.tid, lo, hi, &f, &c);
-    }
-    first[j] = f; cnt[j] = c;
-}
-
 // off = exclusive scan of cnt (off[ns] = np).  pcall[p] = the pair's call, or ~call when the signature's read is no supporter of it
 __global__ void __launch_bounds__(256) k_draft_pairs(const int64_t *__restrict__ off, int32_t ns, const int32_t *__restrict__ first, int64_t np,
                                                      const telr_ins_sig *__restrict__ sigs, const int64_t *__restrict__ read_off, const int32_t *__restrict__ reads,
@@ -48,7 +34,7 @@ __global__ void __launch_bounds__(256) k_draft_pairs(const int64_t *__restrict__
     psig[p] = j; pcall[p] = d_in_list(reads, read_off[k], read_off[k + 1], q) ? k : ~k;
 }
 
-__global__ void __launch_bounds__(256) k_draft_walk(const telr_ins_sig *__restrict__ sigs, const telr_ins_call *__restrict__ calls, const DraftRec *__restrict__ recs,
+__global__ void __launch_bounds__(256) k_draft_walk(const telr_ins_sig *__restrict__ sigs, const telr_ins_call *__restrict__ calls, const CutRec *__restrict__ recs,
                                                     const uint32_t *__restrict__ cig, const int32_t *__restrict__ psig, const int32_t *__restrict__ pcall, int64_t np,
                                                     int32_t flank, int32_t min_flank, int32_t max_len, DraftCand *__restrict__ cand)
 {
@@ -59,7 +45,7 @@ __global__ void __launch_bounds__(256) k_draft_walk(const telr_ins_sig *__restri
     DraftCand out; out.dlen = 0; out.valid = 0; out.fl = 0; out.lo = 0; out.n = 0;
     if (k >= 0) {                                         // (the same in every lane of the wave)
         const telr_ins_sig s = sigs[psig[w]];
-        const DraftRec A = recs[s.rec], B = s.kind == 0 ? A : recs[s.mate];
+        const CutRec A = recs[s.rec], B = s.kind == 0 ? A : recs[s.mate];
         const int64_t lpos = s.pos, rpos = s.kind == 0 ? (int64_t)s.pos : (int64_t)B.ts;
         const int64_t xL = lpos - flank > A.ts ? lpos - flank : (int64_t)A.ts, xR = rpos + flank < B.te ? rpos + flank : (int64_t)B.te;
         const int64_t fl = lpos - xL < xR - rpos ? lpos - xL : xR - rpos;
@@ -92,16 +78,15 @@ static __device__ __forceinline__ bool draft_better(const DraftBest &x, const Dr
 }
 
 __global__ void __launch_bounds__(256) k_draft_select(const telr_ins_sig *__restrict__ sigs, int32_t ns, const telr_ins_call *__restrict__ calls, int32_t ncall,
-                                                      const DraftRec *__restrict__ recs, const int32_t *__restrict__ first, const int32_t *__restrict__ cnt,
+                                                      const CutRec *__restrict__ recs, const int32_t *__restrict__ first, const int32_t *__restrict__ cnt,
                                                       const int64_t *__restrict__ off, const DraftCand *__restrict__ cand, int32_t reach, telr_draft *__restrict__ out)
 {
     const int lane = threadIdx.x & 63;
     const int64_t k = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
     if (k >= ncall) return;
     const telr_ins_call c = calls[k];
-    const int64_t plo = c.pos > reach ? (int64_t)c.pos - reach : 0, phi = (int64_t)c.pos + reach < 0x7fffffffLL ? (int64_t)c.pos + reach : 0x7fffffffLL;
-    const uint64_t t = (uint64_t)(uint32_t)c.tid << 32;
-    const int32_t s0 = draft_sig_bound<false>(sigs, ns, t | (uint64_t)plo), s1 = draft_sig_bound<true>(sigs, ns, t | (uint64_t)phi);
+    int32_t s0, s1;
+    d_sig_window(sigs, ns, c, reach, &s0, &s1);
     DraftBest best; best.has = 0; best.dlen = 0; best.fl = 0; best.qid = 0; best.rec = 0; best.mate = 0; best.j = 0; best.lo = 0; best.n = 0;
     for (int32_t j = s0 + lane; j < s1; j += 64) {
         const int32_t f = first[j], r = (int32_t)k - f;
@@ -124,7 +109,7 @@ __global__ void __launch_bounds__(256) k_draft_select(const telr_ins_sig *__rest
     d.sig = -1; d.qid = 0; d.start = 0; d.len = 0; d.rc = 0; d.ins_off = 0; d.ins_len = 0; d.set_index = -1;
     if (best.has) {
         const telr_ins_sig s = sigs[best.j];
-        const DraftRec A = recs[s.rec];
+        const CutRec A = recs[s.rec];
         d.sig = best.j; d.qid = s.qid; d.len = best.n; d.rc = A.rev;
         d.start = A.rev ? A.qlen - (best.lo + best.n) : best.lo;
         d.ins_len = s.seg_len;
@@ -214,84 +199,31 @@ extern "C" int telr_draft_contigs(telr_ctx *ctx, const telr_result *r, int32_t n
 {
     (void)hipGetLastError();
     if (!ctx) return TELR_E_ARG;
-    auto bad = [&](const std::string &why) { ctx->err = "telr_draft_contigs: " + why; return TELR_E_ARG; };
-    if (!r || !out || !out_set || !read_set) return bad("null result, read set or output");
-    if (n_targets <= 0) return bad("n_targets must be positive");
-    if (n_calls < 0 || (n_calls > 0 && (!calls || !read_off))) return bad("null calls or read offsets");
-    if (n_sig < 0 || (n_sig > 0 && !sigs)) return bad("null signatures");
     telr_draft_opt O;
     if (opt) O = *opt; else telr_draft_opt_default(&O);
-    if (O.flank < 0 || O.min_flank < 0 || O.reach < 0 || O.max_len < 0 || O.reserved[0] < 0 || O.reserved[1] < 0 || O.reserved[2] < 0 || O.reserved[3] < 0)
-        return bad("negative option");
-    if (O.min_flank > O.flank) return bad("min_flank > flank");
-    const size_t n = r->alns.size();
-    if (n >= 0x7ffffff0u) { ctx->err = "telr_draft_contigs: too many records"; return TELR_E_RANGE; }
-    if (n_calls >= 0x7ffffff0LL) { ctx->err = "telr_draft_contigs: too many calls"; return TELR_E_RANGE; }
-    if (n_sig >= 0x7ffffff0LL) { ctx->err = "telr_draft_contigs: too many signatures"; return TELR_E_RANGE; }
-    // the calls: 64-bit (tid, pos) keys, strictly ascending; the supporter lists ascending and distinct
-    std::vector<uint64_t> ckeys((size_t)n_calls);
-    std::string why;
-    if (!call_list_check(n_calls, calls, read_off, reads, n_targets, read_set->n, ckeys.data(), nullptr, &why)) return bad(why);
-    // the records: the shared refusals (record_checks.h), and every record's read is a sequence of the set with its length
-    std::vector<DraftRec> recs(n);
-    for (size_t i = 0; i < n; ++i) {
-        const telr_aln &a = r->alns[i];
-        if (!record_check(a, i, n_targets, r->ncig, &why)) return bad(why);
-        if (a.qid >= read_set->n) return bad("record " + std::to_string(i) + ": qid outside the read set");
-        if (a.qlen != read_set->len[a.qid]) return bad("record " + std::to_string(i) + ": qlen is not the length of its read in the read set");
-        DraftRec &e = recs[i];
-        e.rev = (a.flags & TELR_F_REV) ? 1 : 0;
-        e.ts = a.ts; e.te = a.te; e.qs = e.rev ? a.qlen - a.qe : a.qs; e.qlen = a.qlen; e.n_cigar = a.n_cigar; e.cigar_off = a.cigar_off;
-    }
-    // the signatures: as telr_call_insertions returned them -- ascending by (tid, pos), every index inside its array
-    if (!sig_list_check(n_sig, sigs, r->alns.data(), n, n_targets, read_set->n, &why)) return bad(why);
+    const char *fault = (O.flank < 0 || O.min_flank < 0 || O.reach < 0 || O.max_len < 0 || O.reserved[0] < 0 || O.reserved[1] < 0 || O.reserved[2] < 0 || O.reserved[3] < 0)
+                            ? "negative option" : O.min_flank > O.flank ? "min_flank > flank" : nullptr;
+    CutInput in;
+    TRY(in.check(ctx, "telr_draft_contigs", r, out && out_set, n_targets, n_calls, calls, read_off, reads, n_sig, sigs, read_set, fault));
     telr_drafts *D = new telr_drafts();
     std::unique_ptr<telr_drafts> guard(D);
     telr_draft none; none.sig = -1; none.qid = 0; none.start = 0; none.len = 0; none.rc = 0; none.ins_off = 0; none.ins_len = 0; none.set_index = -1;
     D->d.assign((size_t)n_calls, none);
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const int32_t nc = (int32_t)n_calls, ns = (int32_t)n_sig;
-    int64_t P = 0;
-    telr_ins_sig *d_sig = nullptr; telr_ins_call *d_calls = nullptr; int32_t *d_first = nullptr, *d_cnt = nullptr; int64_t *d_off = nullptr, *d_tot = nullptr;
-    if (nc > 0 && ns > 0) {
-        result_wait(r);
-        uint64_t *d_ckeys;
-        TRY(ctx_buf_t(ctx, "draft_sig", (size_t)ns, &d_sig));
-        TRY(ctx_buf_t(ctx, "draft_calls", (size_t)nc, &d_calls));
-        TRY(ctx_buf_t(ctx, "draft_ckeys", (size_t)nc, &d_ckeys));
-        TRY(ctx_buf_t(ctx, "draft_first", (size_t)ns, &d_first));
-        TRY(ctx_buf_t(ctx, "draft_cnt", (size_t)ns + 1, &d_cnt));
-        TRY(ctx_buf_t(ctx, "draft_off", (size_t)ns + 1, &d_off));
-        TRY(ctx_buf_t(ctx, "draft_tot", 4, &d_tot));
-        HIPCHK(hipMemcpyAsync(d_sig, sigs, (size_t)ns * sizeof(telr_ins_sig), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_calls, calls, (size_t)nc * sizeof(telr_ins_call), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_ckeys, ckeys.data(), (size_t)nc * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_draft_span, grid256((int64_t)ns), dim3(256), 0, st, d_sig, ns, d_ckeys, nc, O.reach, d_first, d_cnt);
-        HIPCHK(hipGetLastError());
-        TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt, ns, d_off, d_tot, 0, nullptr, nullptr)));
-        HIPCHK(hipMemcpyAsync(&P, d_tot, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (P >= 0x7ffffff0LL) { ctx->err = "telr_draft_contigs: too many (signature, call) pairs"; return TELR_E_RANGE; }
-    }
+    const int32_t nc = in.nc, ns = in.ns;
+    TRY(in.span(O.reach, 1u << 0 | 1u << 1, true));                               // the sized signatures: kinds 0 and 1
+    const int64_t P = in.P;
     if (P > 0) {
-        uint32_t *d_cig;
-        TRY(result_dev_cigars(ctx, r, "draft_cig", true, &d_cig, nullptr));
-        const int64_t nreads = read_off[n_calls];
-        DraftRec *d_rec; int64_t *d_roff; int32_t *d_reads, *d_psig, *d_pcall; DraftCand *d_cand; telr_draft *d_out;
-        TRY(ctx_buf_t(ctx, "draft_rec", n, &d_rec));
-        TRY(ctx_buf_t(ctx, "draft_roff", (size_t)nc + 1, &d_roff));
-        TRY(ctx_buf_t(ctx, "draft_reads", (size_t)nreads, &d_reads));
+        TRY(in.prepare_pairs());
+        int32_t *d_psig, *d_pcall; DraftCand *d_cand; telr_draft *d_out;
         TRY(ctx_buf_t(ctx, "draft_psig", (size_t)P, &d_psig));
         TRY(ctx_buf_t(ctx, "draft_pcall", (size_t)P, &d_pcall));
         TRY(ctx_buf_t(ctx, "draft_cand", (size_t)P, &d_cand));
         TRY(ctx_buf_t(ctx, "draft_out", (size_t)nc, &d_out));
-        HIPCHK(hipMemcpyAsync(d_rec, recs.data(), n * sizeof(DraftRec), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_roff, read_off, ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
-        if (nreads) HIPCHK(hipMemcpyAsync(d_reads, reads, (size_t)nreads * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_draft_pairs, grid256(P), dim3(256), 0, st, d_off, ns, d_first, P, d_sig, d_roff, d_reads, d_psig, d_pcall);
-        hipLaunchKernelGGL(k_draft_walk, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, st, d_sig, d_calls, d_rec, d_cig, d_psig, d_pcall, P, O.flank, O.min_flank, O.max_len, d_cand);
-        hipLaunchKernelGGL(k_draft_select, dim3((unsigned)(((int64_t)nc + 3) / 4)), dim3(256), 0, st, d_sig, ns, d_calls, nc, d_rec, d_first, d_cnt, d_off, d_cand, O.reach, d_out);
+        hipLaunchKernelGGL(k_draft_pairs, grid256(P), dim3(256), 0, st, in.d_off, ns, in.d_first, P, in.d_sig, in.d_roff, in.d_reads, d_psig, d_pcall);
+        hipLaunchKernelGGL(k_draft_walk, dim3((unsigned)((P + 3) / 4)), dim3(256), 0, st, in.d_sig, in.d_calls, in.d_rec, in.d_cig, d_psig, d_pcall, P, O.flank, O.min_flank, O.max_len, d_cand);
+        hipLaunchKernelGGL(k_draft_select, dim3((unsigned)(((int64_t)nc + 3) / 4)), dim3(256), 0, st, in.d_sig, ns, in.d_calls, nc, in.d_rec, in.d_first, in.d_cnt, in.d_off, d_cand, O.reach, d_out);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(D->d.data(), d_out, (size_t)nc * sizeof(telr_draft), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));

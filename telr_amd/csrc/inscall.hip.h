@@ -218,8 +218,8 @@ extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t
         if (!record_check(a, i, n_targets, r->ncig, &why)) return bad(why);
         if ((a.flags & TELR_F_SECONDARY) || a.mapq < O.min_mapq) continue;
         InsRec e;
-        e.qid = a.qid; e.tid = a.tid; e.ts = a.ts; e.te = a.te; e.qlen = a.qlen; e.rev = (a.flags & TELR_F_REV) ? 1 : 0;
-        e.qs = e.rev ? a.qlen - a.qe : a.qs; e.qe = e.rev ? a.qlen - a.qs : a.qe;
+        const StrandCoords s = strand_coords(a);
+        e.qid = a.qid; e.tid = a.tid; e.ts = a.ts; e.te = a.te; e.qlen = a.qlen; e.rev = s.rev; e.qs = s.qs; e.qe = s.qe;
         e.n_cigar = a.n_cigar; e.rec = (int32_t)i; e.g0 = e.g1 = 0; e.cigar_off = a.cigar_off;
         if (!er.empty() && er.back().qid > e.qid) in_order = false;
         max_qid = std::max(max_qid, a.qid);

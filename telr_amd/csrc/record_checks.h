@@ -1,5 +1,6 @@
 // record_checks.h — what the call stages (telr_call_insertions, telr_genotype_insertions, telr_draft_contigs, telr_bridge_contigs;
-// DESIGN.md 5.10 - 5.12, 5.18) refuse in a result's records, in a call list and in a signature array, stated once.  These checks are
+// DESIGN.md 5.10 - 5.12, 5.18) refuse in a result's records, in a call list and in a signature array, stated once, with a record's strand
+// coordinates (strand_coords) and the record that the two stages which cut reads at reference coordinates upload (CutRec).  These checks are
 // all that stands between a caller's arrays and the kernels that index with them.  Plain C++: no HIP call and no type of the engine's own, so they are pinned on a CPU and run under the
 // sanitizers from a stand-alone program (tools/record_checks_check.cpp).  The reason comes back in a std::string; the entry's name in
 // front of it ("telr_call_insertions: " ...) and the TELR_E_RANGE limits on the counts stay with the callers.
@@ -23,6 +24,30 @@ static inline bool record_check(const telr_aln &a, size_t i, int32_t n_targets, 
     else if (a.n_cigar < 0 || a.cigar_off < 0 || (uint64_t)a.cigar_off + (uint64_t)a.n_cigar > ncig) what = "CIGAR range outside the result's array";
     if (what) *why = "record " + std::to_string(i) + ": " + what;
     return !what;
+}
+
+// A record on its own strand: the query interval as stored on a forward record, mirrored in the read on TELR_F_REV.
+struct StrandCoords { int32_t rev, qs, qe; };
+static inline StrandCoords strand_coords(const telr_aln &a)
+{
+    const int32_t rev = (a.flags & TELR_F_REV) ? 1 : 0;
+    return {rev, rev ? a.qlen - a.qe : a.qs, rev ? a.qlen - a.qs : a.qe};
+}
+
+// A record as the stages that cut reads at reference coordinates (telr_draft_contigs, telr_bridge_contigs) hold it on the device, one
+// per record of the result: 40 bytes, qs / qe on the record's own strand.
+struct CutRec { int32_t ts, te, qs, qe, qlen, rev, n_cigar, pad; int64_t cigar_off; };
+
+// Record i against a read set of n_reads sequences of lengths read_len: record_check, then the record's read is a sequence of the set,
+// then with its length; the first fault is the one reported.  True with *e filled, or false with "record i: <what>" in *why.
+static inline bool cut_rec_check(const telr_aln &a, size_t i, int32_t n_targets, uint64_t ncig, int32_t n_reads, const int32_t *read_len, CutRec *e, std::string *why)
+{
+    if (!record_check(a, i, n_targets, ncig, why)) return false;
+    const char *what = a.qid >= n_reads ? "qid outside the read set" : a.qlen != read_len[a.qid] ? "qlen is not the length of its read in the read set" : nullptr;
+    if (what) { *why = "record " + std::to_string(i) + ": " + what; return false; }
+    const StrandCoords s = strand_coords(a);
+    *e = {a.ts, a.te, s.qs, s.qe, a.qlen, s.rev, a.n_cigar, 0, a.cigar_off};
+    return true;
 }
 
 // A call list as telr_call_insertions returns it: (tid, pos) strictly ascending, read_off from 0 and ascending, every supporter list

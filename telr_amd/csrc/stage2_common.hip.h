@@ -1,6 +1,6 @@
 // What the stages on top of a mapped telr_result share: the CIGAR array on the device, the launch and bit-count
-// helpers, the wave and search inlines of the span / pair kernels, the funnel shifts of the piece cutters, the one-coordinate CIGAR walk
-// of the drafter and the bridge, and the stable permutation sort over radix.hip.h.  Included by telr_engine.hip once telr_result is
+// helpers, the wave and search inlines of the span / pair kernels, the funnel shifts of the piece cutters, what the drafter and the bridge
+// share (the one-coordinate CIGAR walk, the reach clamp, the signature window, the span kernel, their input: CutInput), and the stable permutation sort over radix.hip.h.  Included by telr_engine.hip once telr_result is
 // defined (telr_depth_medians is a caller), so before every feature header (inscall, genotype, draft, bridge, refte, bam_in, seq_extract,
 // part_merge, pileup, bam_dev): none of them takes a name from a sibling.  The host-side record and call-list checks of the call stages are record_checks.h.
 #pragma once
@@ -112,9 +112,14 @@ static __device__ __forceinline__ void d_strand16(const uint32_t *__restrict__ p
 }
 
 // ---- what the stages that cut reads at reference coordinates share (draft.hip.h, bridge.hip.h) ----------------------------------------
-struct DraftRec { int32_t ts, te, qs, qlen, rev, n_cigar; int64_t cigar_off; };      // qs on the record's own strand
 struct DraftPiece { int64_t src; int32_t len, rc; };                                  // src: first base of the piece in the parent set's base layout
 
+// the positions within `reach` of pos: [max(pos - reach, 0), min(pos + reach, 2^31 - 1)]
+static __device__ __forceinline__ void d_reach(int32_t pos, int32_t reach, int64_t *lo, int64_t *hi)
+{
+    *lo = pos > reach ? (int64_t)pos - reach : 0;
+    *hi = (int64_t)pos + reach < 0x7fffffffLL ? (int64_t)pos + reach : 0x7fffffffLL;
+}
 
 // One wave walks the n CIGAR words at c from the state (ts, qs): lo = the smallest strand coordinate among the states at reference
 // coordinate xlo (the first op that holds xlo within [p, p + its reference length]), hi = the largest among those at xhi (the last
@@ -158,7 +163,111 @@ static __device__ __forceinline__ int32_t draft_sig_bound(const telr_ins_sig *__
     }
     return lo;
 }
+// the signatures [s0, s1) within `reach` of call c: a contiguous run of the sorted array
+static __device__ __forceinline__ void d_sig_window(const telr_ins_sig *__restrict__ sigs, int32_t ns, const telr_ins_call &c, int32_t reach, int32_t *s0, int32_t *s1)
+{
+    int64_t lo, hi;
+    d_reach(c.pos, reach, &lo, &hi);
+    const uint64_t t = (uint64_t)(uint32_t)c.tid << 32;
+    *s0 = draft_sig_bound<false>(sigs, ns, t | (uint64_t)lo); *s1 = draft_sig_bound<true>(sigs, ns, t | (uint64_t)hi);
+}
 
+// One lane per signature: one whose kind is a bit of `kinds` (bit k = kind k) takes a lower and an upper bound in the calls' (tid, pos)
+// keys -- the calls within `reach` of it are a contiguous run of the ascending keys: cnt of them from first (nullable) on; others 0.
+__global__ void __launch_bounds__(256) k_cut_span(const telr_ins_sig *__restrict__ sigs, int32_t ns, const uint64_t *__restrict__ ckeys, int32_t ncall, int32_t reach,
+                                                  uint32_t kinds, int32_t *__restrict__ first, int32_t *__restrict__ cnt)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= ns) return;
+    const telr_ins_sig s = sigs[j];
+    int32_t f = 0, c = 0;
+    if ((uint32_t)s.kind < 32u && ((kinds >> s.kind) & 1u)) {
+        int64_t lo, hi;
+        d_reach(s.pos, reach, &lo, &hi);
+        d_span(ckeys, ncall, s.tid, lo, hi, &f, &c);
+    }
+    if (first) first[j] = f;
+    cnt[j] = c;
+}
+
+// The input of telr_draft_contigs and telr_bridge_contigs -- a result, a call list, its signature array, the read set -- refused or
+// brought to the device, in one set of context buffers (cut_*): a context that drafts and then bridges holds it once.  Every entry
+// synchronises its stream before it returns, so the next call may overwrite them.
+struct CutInput {
+    telr_ctx *ctx; const char *who; const telr_result *r; const telr_ins_call *calls; const int64_t *read_off; const int32_t *reads; const telr_ins_sig *sigs;
+    std::vector<uint64_t> ckeys; std::vector<CutRec> recs; int32_t nc = 0, ns = 0;      // check(): the calls' keys, a record per record of the result, the counts
+    int64_t P = 0;                                                                // span(): the (signature, call) pairs; off = the scan of cnt
+    telr_ins_sig *d_sig = nullptr; telr_ins_call *d_calls = nullptr; int32_t *d_first = nullptr, *d_cnt = nullptr; int64_t *d_off = nullptr;
+    uint32_t *d_cig = nullptr; CutRec *d_rec = nullptr; int64_t *d_roff = nullptr; int32_t *d_reads = nullptr;      // prepare_pairs()
+
+    // The host part, in the order a caller can observe: null arguments, the stage's own options (opt_fault: what the entry found wrong
+    // with them, or null), the count limits, the calls, the records, the signatures (record_checks.h).  `who` opens every message.
+    int check(telr_ctx *ctx_, const char *who_, const telr_result *r_, bool have_out, int32_t n_targets, int64_t n_calls, const telr_ins_call *calls_,
+              const int64_t *read_off_, const int32_t *reads_, int64_t n_sig, const telr_ins_sig *sigs_, const telr_seqset *read_set, const char *opt_fault)
+    {
+        ctx = ctx_; who = who_; r = r_; calls = calls_; read_off = read_off_; reads = reads_; sigs = sigs_;
+        auto bad = [&](const std::string &why) { ctx->err = std::string(who) + ": " + why; return TELR_E_ARG; };
+        auto many = [&](const char *what) { ctx->err = std::string(who) + ": too many " + what; return TELR_E_RANGE; };
+        if (!r || !have_out || !read_set) return bad("null result, read set or output");
+        if (n_targets <= 0) return bad("n_targets must be positive");
+        if (n_calls < 0 || (n_calls > 0 && (!calls || !read_off))) return bad("null calls or read offsets");
+        if (n_sig < 0 || (n_sig > 0 && !sigs)) return bad("null signatures");
+        if (opt_fault) return bad(opt_fault);
+        const size_t n = r->alns.size();
+        if (n >= 0x7ffffff0u) return many("records");
+        if (n_calls >= 0x7ffffff0LL) return many("calls");
+        if (n_sig >= 0x7ffffff0LL) return many("signatures");
+        std::string why;
+        ckeys.resize((size_t)n_calls);
+        if (!call_list_check(n_calls, calls, read_off, reads, n_targets, read_set->n, ckeys.data(), nullptr, &why)) return bad(why);
+        recs.resize(n);
+        for (size_t i = 0; i < n; ++i)
+            if (!cut_rec_check(r->alns[i], i, n_targets, r->ncig, read_set->n, read_set->len.data(), &recs[i], &why)) return bad(why);
+        if (!sig_list_check(n_sig, sigs, r->alns.data(), n, n_targets, read_set->n, &why)) return bad(why);
+        nc = (int32_t)n_calls; ns = (int32_t)n_sig;
+        return TELR_OK;
+    }
+    // signatures, calls and keys uploaded, k_cut_span (first is kept when want_first), the 64-bit scan, P and its limit; no calls or no
+    // signatures: no pairs, and nothing is touched
+    int span(int32_t reach, uint32_t kinds, bool want_first)
+    {
+        if (nc <= 0 || ns <= 0) return TELR_OK;
+        hipStream_t st = ctx->stream;
+        result_wait(r);
+        uint64_t *d_ckeys; int64_t *d_tot;
+        TRY(ctx_buf_t(ctx, "cut_sig", (size_t)ns, &d_sig));
+        TRY(ctx_buf_t(ctx, "cut_calls", (size_t)nc, &d_calls));
+        TRY(ctx_buf_t(ctx, "cut_ckeys", (size_t)nc, &d_ckeys));
+        if (want_first) TRY(ctx_buf_t(ctx, "cut_first", (size_t)ns, &d_first));
+        TRY(ctx_buf_t(ctx, "cut_cnt", (size_t)ns + 1, &d_cnt));
+        TRY(ctx_buf_t(ctx, "cut_off", (size_t)ns + 1, &d_off));
+        TRY(ctx_buf_t(ctx, "cut_tot", 4, &d_tot));
+        HIPCHK(hipMemcpyAsync(d_sig, sigs, (size_t)ns * sizeof(telr_ins_sig), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_calls, calls, (size_t)nc * sizeof(telr_ins_call), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_ckeys, ckeys.data(), (size_t)nc * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_cut_span, grid256((int64_t)ns), dim3(256), 0, st, d_sig, ns, d_ckeys, nc, reach, kinds, d_first, d_cnt);
+        HIPCHK(hipGetLastError());
+        TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt, ns, d_off, d_tot, 0, nullptr, nullptr)));
+        HIPCHK(hipMemcpyAsync(&P, d_tot, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (P >= 0x7ffffff0LL) { ctx->err = std::string(who) + ": too many (signature, call) pairs"; return TELR_E_RANGE; }
+        return TELR_OK;
+    }
+    // P > 0: the CIGAR words (the result's own copy or an upload), the records, read_off and reads on the device; not waited for
+    int prepare_pairs()
+    {
+        hipStream_t st = ctx->stream;
+        TRY(result_dev_cigars(ctx, r, "cut_cig", true, &d_cig, nullptr));
+        const int64_t nreads = read_off[nc];
+        TRY(ctx_buf_t(ctx, "cut_rec", recs.size(), &d_rec));
+        TRY(ctx_buf_t(ctx, "cut_roff", (size_t)nc + 1, &d_roff));
+        TRY(ctx_buf_t(ctx, "cut_reads", (size_t)nreads, &d_reads));
+        HIPCHK(hipMemcpyAsync(d_rec, recs.data(), recs.size() * sizeof(CutRec), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_roff, read_off, ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
+        if (nreads) HIPCHK(hipMemcpyAsync(d_reads, reads, (size_t)nreads * 4, hipMemcpyHostToDevice, st));
+        return TELR_OK;
+    }
+};
 
 // ---- stable permutation sort --------------------------------------------------------------------------------------------------------
 // LSD over a composite key, least significant group first: a permutation is carried from round to round, the keys of a round are

@@ -122,9 +122,9 @@ class Build:
     def call(self, pos, reads, tid=0):
         self.calls.append(call(tid, pos, 0, reads))
 
-    def done(self):
+    def done(self, sig_opt=SIG_OPT):
         alns, cig = pack(self.recs)
-        return alns, cig, iref.signatures(alns, cig, SIG_OPT), self.calls, self.reads
+        return alns, cig, iref.signatures(alns, cig, sig_opt), self.calls, self.reads
 
 
 def planted(rng, cL, cR, groups, k=K, n_at=()):
@@ -279,7 +279,25 @@ def bridge_cases():
     C.append(dict(name="want_all", data=data, opt=SMALL, want=None, expect=exp(votes=[12, 12, 12])))
     C.append(dict(name="want_mask", data=data, opt=SMALL, want=[1, 0, 1], expect=exp(votes=[12, 0, 12], sig_l=[0, -1, 4], n_left=[1, 1, 1], n_right=[1, 1, 1])))
     C.append(dict(name="want_none", data=data, opt=SMALL, want=[0, 0, 0], expect=exp(sig_l=[-1, -1, -1], n_left=[1, 1, 1])))
+    C.append(dict(name="sized_among_clips", data=sized_among_clips(), opt=SMALL, want=None,
+                  expect=exp(votes=12, sig_l=0, sig_r=2, qid_l=0, qid_r=1, n_left=1, n_right=1, n_voted=1)))
     return C
+
+
+def sized_among_clips():
+    """one call whose reach window holds a sized signature between two clips: a left read that ends two bases before the locus, a right
+    read that starts two bases behind it and a third read that spans it with an I of 60.  The bridge counts the two clips only, the
+    drafter (tests/draft_ref.py) the I only."""
+    b = Build(11)
+    U, V = planted(np.random.default_rng(12), 700, 700, [(100, 12, 300)])
+    p = b.locus()
+    ql, qr = b.left(p - 2, U), b.right(p + 2, V)
+    qi = b.read(rand_seq(b.rng, 100), 0)
+    b.recs.append(rec(qi, 100, 0, 100, p - 20, p + 20, [(20, "M"), (60, "I"), (20, "M")]))
+    b.calls.append(call(0, p, 60, [ql, qr, qi]))
+    data = b.done(dict(min_clip=1, min_mapq=0, min_len=50))
+    assert [(s["kind"], s["pos"] - p) for s in data[2]] == [(2, -2), (0, 0), (2, 2)]
+    return data
 
 
 def mutate(rng, s, rate):

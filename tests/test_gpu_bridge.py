@@ -9,10 +9,14 @@ import pytest
 
 import bridge_cases as cases
 import bridge_ref as bref
+import draft_cases
+import draft_ref as dref
 import packed_np
+from inscall_cases import pack
 from telr_amd import locus_pipeline, telr, telr_assembly, telr_sv
-from telr_amd._abi import BridgeOpt, InsOpt, MF_KEEP_CIGARS, TELR_E_ARG, BRIDGE_DTYPE
+from telr_amd._abi import BridgeOpt, DraftOpt, InsOpt, MF_KEEP_CIGARS, TELR_E_ARG, BRIDGE_DTYPE
 from telr_amd._lib import TelrError
+from telr_amd.aligner import Engine
 from telr_amd.presets import preset
 
 pytestmark = pytest.mark.gpu
@@ -177,6 +181,67 @@ def test_same_bytes_on_two_runs(engine, ix):
     assert len(picks) == 5
     runs = [b"".join(engine_bridges(engine, ix, c["data"], c["opt"], c["want"]).tobytes() for c in picks) for _ in range(2)]
     assert runs[0] == runs[1]
+
+
+def engine_drafts(engine, ix, data, opt):
+    """-> (draft records, lengths, 2-bit words, mask words of the output set) of Index.draft_contigs on a bridge-style data tuple"""
+    alns, cig, sigs, calls, reads = data
+    qs = engine.seqset(reads)
+    r = ix.result_from_arrays(alns, cig)
+    try:
+        d, s = ix.draft_contigs(r, cases.as_ic(calls, sigs), qs, DraftOpt.default(**opt))
+        out = (d, s.len.copy()) + words(s)
+        s.free()
+        return out
+    finally:
+        ix.free_raw(r); qs.free()
+
+
+def test_sized_and_clip_signatures_in_one_window(engine, ix):
+    """one call, a sized signature between two clips: the one span kernel counts the clips for the bridge and the sized one for the
+    drafter, and only the kind mask keeps them apart -- either step equals its own definition"""
+    c = next(c for c in BRIDGE if c["name"] == "sized_among_clips")
+    alns, cig, sigs, calls, reads = c["data"]
+    assert [s["kind"] for s in sigs] == [2, 0, 2] and len(calls) == 1
+    want, _ = bref.bridges(alns, cig, calls, sigs, reads, c["opt"])
+    assert want[0]["sig_l"] == 0 and want[0]["sig_r"] == 2 and want[0]["n_left"] == 1 and want[0]["n_right"] == 1
+    assert_equal_to_ref(engine_bridges(engine, ix, c["data"], c["opt"]), want)
+    wd, wseq = dref.drafts(alns, cig, calls, sigs, reads, draft_cases.SMALL)
+    assert wd[0]["sig"] == 1 and wd[0]["n_candidates"] == 1 and wd[0]["qid"] == 2 and len(wseq) == 1
+    d, lens, w2, wn = engine_drafts(engine, ix, c["data"], draft_cases.SMALL)
+    for f in dref.DRAFT_FIELDS:
+        np.testing.assert_array_equal(d[f], np.array([x[f] for x in wd], np.int64), err_msg=f)
+    e_len, e2, en = packed_np.pack(wseq)
+    np.testing.assert_array_equal(lens, e_len); np.testing.assert_array_equal(w2, e2); np.testing.assert_array_equal(wn, en)
+
+
+def test_draft_and_bridge_share_their_input_buffers(engine, ix):
+    """telr_draft_contigs and telr_bridge_contigs keep their input in the same context buffers.  On ONE engine: the drafter on two records
+    and one call, the bridge on its hand case of the most records, the drafter on 70 records (more than a wave), the bridge on its hand
+    case of the fewest, the first drafter call again -- inputs grow and shrink through the same buffers, and both kind masks go through
+    the one span kernel back to back.  Every result equals, byte for byte, that of the same call on a fresh engine."""
+    recs = [draft_cases.ins_rec(0, 1000, 60), draft_cases.ins_rec(1, 1003, 62)]      # the input of test_gpu_draft.py::test_argument_errors
+    alns, cig = pack(recs)
+    two = (alns, cig, draft_cases.sigs_of(alns, cig), [draft_cases.call(0, 1000, 60, [0, 1])], draft_cases.random_reads(recs))
+    recs, calls = draft_cases.many_candidates()
+    alns, cig = pack(recs)
+    many = (alns, cig, draft_cases.sigs_of(alns, cig), calls, draft_cases.random_reads(recs, calls))
+    big = max(BRIDGE, key=lambda c: len(c["data"][0]))
+    small = min(BRIDGE, key=lambda c: len(c["data"][0]))
+    assert len(big["data"][0]) >= 14 and len(small["data"][0]) == 2 and len(many[0]) == 70
+    draft = lambda e, i, data: b"".join(np.ascontiguousarray(x).tobytes() for x in engine_drafts(e, i, data, draft_cases.SMALL))
+    bridge = lambda e, i, c: engine_bridges(e, i, c["data"], c["opt"], c["want"]).tobytes()
+    steps = [(draft, two), (bridge, big), (draft, many), (bridge, small), (draft, two)]
+    got = [f(engine, ix, x) for f, x in steps]
+    assert got[0] == got[4] and len(got[0]) > 0 and len(got[2]) > 0
+    io, _ = preset("map-ont")
+    for k, (f, x) in enumerate(steps[:4]):
+        fresh = Engine(0)
+        fix = fresh.index(["ACGT" * 64, "TTGCA" * 64], io)
+        try:
+            assert f(fresh, fix, x) == got[k], "step %d" % k
+        finally:
+            fix.free(); fresh.close()
 
 
 def test_zero_calls_and_zero_signatures(engine, ix):

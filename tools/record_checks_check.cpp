@@ -3,7 +3,8 @@
 // which a sanitizer does not see into):
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o tools/record_checks_check tools/record_checks_check.cpp && tools/record_checks_check
 // Every refusal with its full text, the edges of the CIGAR range (the C ABI cannot produce that one on a device: telr_result_from_arrays
-// refuses it first), the order of a record's faults, and the keys and supports a passing call list leaves.  Exit status 0 and
+// refuses it first), the order of a record's faults, the keys and supports a passing call list leaves, the strand coordinates of a
+// forward and a reverse record, and the record of a read set (CutRec) field by field with its two refusals.  Exit status 0 and
 // "record_checks: N checks ok" when every one is the expected one.
 #include <cstdio>
 #include <cstring>
@@ -120,6 +121,56 @@ int main()
     expect("the index is the caller's", rec_why(a, 2147483648u), "record 2147483648: tid outside n_targets");
     expect("the index 0", rec_why(a, 0), "record 0: tid outside n_targets");
 
+    // ---- the strand coordinates: forward as stored, mirrored in the read on TELR_F_REV
+    {
+        auto strand = [](int qs, int qe, int qlen, int flags) { telr_aln x = good(); x.qs = qs; x.qe = qe; x.qlen = qlen; x.flags = flags; return strand_coords(x); };
+        StrandCoords s = strand(10, 990, 1000, 0);
+        expect("forward rev", s.rev, 0); expect("forward qs", s.qs, 10); expect("forward qe", s.qe, 990);
+        s = strand(10, 970, 1000, TELR_F_REV);
+        expect("reverse rev", s.rev, 1); expect("reverse qs = qlen - qe", s.qs, 30); expect("reverse qe = qlen - qs", s.qe, 990);
+        s = strand(0, 1000, 1000, 0);
+        expect("forward, qs == 0", s.qs, 0); expect("forward, qe == qlen", s.qe, 1000);
+        s = strand(0, 400, 1000, TELR_F_REV);
+        expect("reverse, qs == 0: qe' == qlen", s.qe, 1000); expect("reverse, qs == 0: qs'", s.qs, 600);
+        s = strand(400, 1000, 1000, TELR_F_REV);
+        expect("reverse, qe == qlen: qs' == 0", s.qs, 0); expect("reverse, qe == qlen: qe'", s.qe, 600);
+        s = strand(10, 970, 1000, TELR_F_REV | TELR_F_SECONDARY);
+        expect("other flags do not count", s.rev, 1); expect("... qs", s.qs, 30);
+        s = strand(10, 970, 1000, TELR_F_SECONDARY);
+        expect("secondary alone is forward", s.rev, 0); expect("... qs", s.qs, 10);
+    }
+    // ---- a record against a read set (telr_draft_contigs, telr_bridge_contigs): 5 reads, read 4 of 1000 bases
+    {
+        const std::vector<int32_t> lens = {7, 7, 7, 7, 1000};            // exactly n_reads: a load past them is the sanitizer's to find
+        auto cut = [&](const telr_aln &x, CutRec *e, int32_t n_reads = 5) {
+            std::string why = "untouched";
+            return cut_rec_check(x, 7, 3, 100, n_reads, lens.data(), e, &why) ? std::string("") : why; };
+        static_assert(sizeof(CutRec) == 40, "the device layout");
+        for (int rev = 0; rev < 2; ++rev) {
+            a = good(); a.qs = 10; a.qe = 970; a.flags = rev ? TELR_F_REV : 0;
+            CutRec e; memset(&e, 0xff, sizeof(e));
+            expect("a passing record of the set", cut(a, &e), "");
+            expect("ts", e.ts, 500); expect("te", e.te, 1500); expect("qs", e.qs, rev ? 30 : 10); expect("qe", e.qe, rev ? 990 : 970);
+            expect("qlen", e.qlen, 1000); expect("rev", e.rev, rev); expect("n_cigar", e.n_cigar, 60); expect("pad", e.pad, 0);
+            expect("cigar_off", (long long)e.cigar_off, 40);
+        }
+        CutRec e;
+        a = good(); a.qid = 5;
+        expect("qid = n_reads", cut(a, &e), "record 7: qid outside the read set");
+        a = good();
+        expect("qid = n_reads - 1", cut(a, &e), "");
+        expect("an empty read set", cut(a, &e, 0), "record 7: qid outside the read set");
+        a = good(); a.qlen = 1001;
+        expect("qlen one more than the read", cut(a, &e), "record 7: qlen is not the length of its read in the read set");
+        a = good(); a.qid = 3;
+        expect("the length of another read", cut(a, &e), "record 7: qlen is not the length of its read in the read set");
+        a = good(); a.qid = 5; a.qlen = 1001;
+        expect("two faults: the read id before the length (which is not loaded)", cut(a, &e), "record 7: qid outside the read set");
+        a = good(); a.qid = 5; a.n_cigar = 61;
+        expect("two faults: the record's own before the read set's", cut(a, &e), "record 7: CIGAR range outside the result's array");
+        a = good(); a.qid = -1;
+        expect("a negative qid is the record's fault", cut(a, &e), "record 7: coordinates");
+    }
     // ---- the call-list check
     {
         Calls L;
