@@ -563,6 +563,40 @@ const int64_t *telr_ins_calls_read_off(const telr_ins_calls *c);      /* count +
 const int32_t *telr_ins_calls_reads(const telr_ins_calls *c);
 void telr_ins_calls_free(telr_ins_calls *c);
 
+/* ---- the supporters of insertion sites the CALLER names (opt-in): another sample's calls, a cohort's merged list, a
+ *      truth set.  telr_call_insertions can only discover clusters and threshold them; this entry assigns the same signatures to given
+ *      positions and returns one call per site whatever its support, in the shape telr_genotype_insertions takes.  An OWN definition
+ *      like 5.10 and 5.11: NOT Sniffles' --genotype-vcf, and its agreement with Sniffles is not pinned.
+ * Signatures:  exactly those of telr_call_insertions under opt: same eligibility, same three kinds, and the same complete sort key
+ *              (tid, pos, rec, kind, len, mate).  min_support, min_sized and cluster_dist of opt are not read.
+ * Sites:       sites[n_sites], strictly ascending by (tid, pos); len = the expected insertion length, 0 = unknown.
+ * Assignment:  a signature s is NEAR site c iff s.tid == c.tid and |s.pos - c.pos| <= reach.  A signature goes to the nearest site it
+ *              is near; on equal distance to the site with the smaller index; a signature near no site is dropped.  (Because sites are
+ *              strictly ascending, the nearest site is one of the two around the signature's key.)
+ * Length test: only for sized signatures (kinds 0 and 1), and only when len_pct > 0 and the assigned site has len > 0: the signature
+ *              is dropped iff 100 * |s.len - c.len| > len_pct * c.len, in 64-bit integer arithmetic.  A dropped signature is not offered
+ *              to another site.  Clips are never length-tested.
+ * Output:      a telr_ins_calls with ONE CALL PER SITE, IN SITE ORDER, whatever its support: tid and pos are the site's; support =
+ *              the distinct qids of its kept signatures; n_sized = the distinct qids among the kept sized signatures; rep = the sized
+ *              signature holding the lower median in the order (len, qid, rec, mate), len = that signature's len (without a sized
+ *              signature rep = -1 and len = 0); the read list = the ascending distinct qids (a site with no kept signature has an
+ *              empty list).  The signature array of the result holds ONLY THE KEPT signatures, in their sorted order; rep indexes it.
+ *              Calls strictly ascending, each with a supporter list: what telr_genotype_insertions takes, unchanged.  (It returns
+ *              gt = 2 for alt = ref = 0, since 0 >= 0; the layers above print such a site as ./. with AF nan.)
+ * TELR_E_ARG (text in telr_last_error): everything telr_call_insertions refuses in a record or in the options this entry reads
+ *              (a negative min_len, min_mapq, min_clip or max_ref_gap), sites not strictly ascending, a site's tid outside
+ *              [0, n_targets), a negative pos or len, reach < 0, len_pct outside 0..100, a non-zero reserved field, n_sites < 0, a null
+ *              sites with n_sites > 0.  TELR_E_RANGE: 2^31 - 16 sites or more.  n_sites == 0: an empty result, nothing is launched;
+ *              no eligible record (or no signature): n_sites empty calls.  Everything is checked on the host before a kernel runs.
+ *              The output is the same on every run.  opt / sopt NULL = the defaults. */
+typedef struct telr_ins_site { int32_t tid, pos, len; } telr_ins_site;   /* len: expected insertion length, 0 = unknown */
+typedef struct telr_site_opt { int32_t reach;    /* 50 */
+                               int32_t len_pct;  /* 0: no length test */
+                               int32_t reserved[2]; } telr_site_opt;
+void telr_site_opt_default(telr_site_opt *o);
+int  telr_call_at_sites(telr_ctx *ctx, const telr_result *r, int32_t n_targets, const telr_ins_opt *opt,
+                        const telr_ins_site *sites, int64_t n_sites, const telr_site_opt *sopt, telr_ins_calls **out);
+
 /* ---- genotypes of those calls: reference reads, AF and GT (opt-in).  In the reference the three values come
  *      from Sniffles (`%AF`, `%GT`, `%DR`, src/telr/TELR_sv.py:161).  An OWN definition like the caller's, NOT Sniffles' genotyper;
  *      its agreement with Sniffles is unpinned.

@@ -49,6 +49,24 @@ class InsOpt(C.Structure):
         return o
 
 
+class SiteOpt(C.Structure):
+    """telr_site_opt: the options of telr_call_at_sites (defaults: SiteOpt.default())"""
+    _fields_ = [(n, C.c_int32) for n in ("reach", "len_pct", "reserved0", "reserved1")]
+
+    @classmethod
+    def default(cls, **kw):
+        o = cls(50, 0, 0, 0)
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("SiteOpt has no field %r" % k)
+            setattr(o, k, int(v))
+        return o
+
+
+class InsSite(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tid", "pos", "len")]
+
+
 class InsSig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("tid", "pos", "len", "qid", "kind", "rec", "mate", "seg_start", "seg_len")]
 
@@ -163,6 +181,8 @@ assert ALN_DTYPE.itemsize == C.sizeof(Aln) == 88, (ALN_DTYPE.itemsize, C.sizeof(
 INS_SIG_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsSig._fields_])
 INS_CALL_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsCall._fields_])
 assert INS_SIG_DTYPE.itemsize == C.sizeof(InsSig) == 36 and INS_CALL_DTYPE.itemsize == C.sizeof(InsCall) == 24
+INS_SITE_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsSite._fields_])
+assert INS_SITE_DTYPE.itemsize == C.sizeof(InsSite) == 12 and C.sizeof(SiteOpt) == 16
 GENO_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsGt._fields_])
 assert GENO_DTYPE.itemsize == C.sizeof(InsGt) == 16 and C.sizeof(GenoOpt) == 32
 DRAFT_DTYPE = _np.dtype([(n, _np.int32) for n, _ in Draft._fields_])

@@ -6,7 +6,7 @@ boundary (TELR_alignment.py:69-82 and the five other sites listed in include/tel
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._abi import IdxOpt, MapOpt, Counters, InsOpt, GenoOpt, DraftOpt, BridgeOpt, RefTeOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, DRAFT_DTYPE, BRIDGE_DTYPE, TILE_DTYPE, \
+from ._abi import IdxOpt, MapOpt, Counters, InsOpt, SiteOpt, GenoOpt, DraftOpt, BridgeOpt, RefTeOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, DRAFT_DTYPE, BRIDGE_DTYPE, TILE_DTYPE, \
     TE_FEAT_DTYPE, TELR_E_ARG, TELR_E_RANGE, MF_PER_TARGET, MF_KEEP_CIGARS, N_STAGES, N_DPCLS, STITCH_CHAIN_COLUMNS, ALIGN_CHAIN_COLUMNS, ALIGN_PROB_COLUMNS
 from .fasta import concat
 
@@ -943,6 +943,25 @@ class Index:
         rc = self.eng.L.telr_call_insertions(self.eng.h, r, self.targets.n, C.byref(o), C.byref(h))
         if rc != 0:
             raise _lib.TelrError("telr_call_insertions: %s [%s]" % (self.eng.L.telr_strerror(rc).decode(), self.eng.L.telr_last_error(self.eng.h).decode()), rc)
+        return self._ins_calls(h)
+
+    def call_at_sites(self, r, sites, opt=None, site_opt=None):
+        """the supporters of the insertion sites the caller names, on raw result r (telr_call_at_sites; include/telr_hip.h has the
+        definition, which is not Sniffles' forced genotyping): sites an (n, 3) int32 array or a list of (tid, pos, len) triples,
+        strictly ascending by (tid, pos), len = the expected insertion length or 0; opt an _abi.InsOpt, site_opt an _abi.SiteOpt
+        (None: the defaults) -> InsCalls with one call per site in site order, whatever its support, and only the kept signatures:
+        what genotype_insertions takes"""
+        o = InsOpt.default() if opt is None else opt
+        so = SiteOpt.default() if site_opt is None else site_opt
+        s = np.ascontiguousarray(np.asarray(sites, dtype=np.int32).reshape(-1, 3))
+        h = C.c_void_p()
+        rc = self.eng.L.telr_call_at_sites(self.eng.h, r, self.targets.n, C.byref(o), s.ctypes.data if len(s) else None, len(s), C.byref(so), C.byref(h))
+        if rc != 0:
+            raise _lib.TelrError("telr_call_at_sites: %s [%s]" % (self.eng.L.telr_strerror(rc).decode(), self.eng.L.telr_last_error(self.eng.h).decode()), rc)
+        return self._ins_calls(h)
+
+    def _ins_calls(self, h):
+        """a telr_ins_calls handle copied into an InsCalls, and freed"""
         try:
             L = self.eng.L
             nc, ns = int(L.telr_ins_calls_count(h)), int(L.telr_ins_calls_sig_count(h))
@@ -1065,7 +1084,7 @@ class Index:
 class PartIndex(Index):
     """An index over a target set of any total size: one Index per part (Engine.part_plan), the reads mapped against every part in turn
     and the per-part results merged on the device (telr_merge_parts; include/telr_hip.h has the definition).  `targets` is the full
-    resident set and the merged result carries global target ids, so call_insertions, genotype_insertions, draft_contigs,
+    resident set and the merged result carries global target ids, so call_insertions, call_at_sites, genotype_insertions, draft_contigs,
     bridge_contigs, depth_medians, result_arrays, write_bam_device and the text writers work as on an Index.  Not for a multi-part index: qtarget /
     MF_PER_TARGET, write_bam_slice, consensus, the debug taps.  All part indexes are resident together, and during a map the part
     results and the merged one live side by side."""

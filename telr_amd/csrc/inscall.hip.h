@@ -13,6 +13,8 @@
 //   clusters       head flags + scan; the distinct reads of a cluster from a sort by (cluster, read, unsized); its representative
 //                  from a sort by (cluster, unsized, len, read, rec, mate); counts are differences of scanned flags at the cluster's
 //                  bounds; calls and their read lists are compacted by two more scans.
+// The entry is three parts: InsFront (refusals, eligible records, signatures, the sort), the clusters, ins_collect (distinct reads,
+// representatives, calls).  telr_call_at_sites (sitecall.hip.h) shares the first and the last and puts the caller's sites in the middle.
 #pragma once
 
 struct InsRec {                 // an eligible record; qs / qe on the record's own strand
@@ -154,10 +156,12 @@ __global__ void __launch_bounds__(256) k_ins_cluster(const int32_t *__restrict__
     const int32_t ok = sup >= min_support && nsz >= min_sized ? 1 : 0;
     cflag[c] = ok; qcnt[c] = ok ? sup : 0;
 }
+// AT_SITES (telr_call_at_sites): cluster c is the caller's site c, which gives tid and pos; its run of signatures may be empty
+template <bool AT_SITES>
 __global__ void __launch_bounds__(256) k_ins_calls(const telr_ins_sig *__restrict__ sig, const int32_t *__restrict__ cstart, int32_t nc, const int32_t *__restrict__ dx,
                                                    const int32_t *__restrict__ sdx, const int32_t *__restrict__ sx, const uint32_t *__restrict__ perm_rep,
                                                    const int32_t *__restrict__ cflag, const int32_t *__restrict__ cx, const int64_t *__restrict__ qx,
-                                                   telr_ins_call *__restrict__ calls, int64_t *__restrict__ read_off)
+                                                   const telr_ins_site *__restrict__ sites, telr_ins_call *__restrict__ calls, int64_t *__restrict__ read_off)
 {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c > nc) return;
@@ -165,7 +169,8 @@ __global__ void __launch_bounds__(256) k_ins_calls(const telr_ins_sig *__restric
     if (!cflag[c]) return;
     const int32_t lo = cstart[c], hi = cstart[c + 1], ns = sx[hi] - sx[lo];
     telr_ins_call k;
-    k.tid = sig[lo].tid; k.pos = sig[lo + (hi - lo - 1) / 2].pos;
+    if (AT_SITES) { k.tid = sites[c].tid; k.pos = sites[c].pos; }
+    else { k.tid = sig[lo].tid; k.pos = sig[lo + (hi - lo - 1) / 2].pos; }
     k.support = dx[hi] - dx[lo]; k.n_sized = sdx[hi] - sdx[lo];
     k.rep = ns > 0 ? (int32_t)perm_rep[lo + (ns - 1) / 2] : -1;          // the sized signatures of the cluster come first in the representative sort
     k.len = ns > 0 ? sig[k.rep].len : 0;
@@ -195,110 +200,120 @@ extern "C" const int64_t *telr_ins_calls_read_off(const telr_ins_calls *c) { ret
 extern "C" const int32_t *telr_ins_calls_reads(const telr_ins_calls *c) { return c ? c->reads.data() : nullptr; }
 extern "C" void telr_ins_calls_free(telr_ins_calls *c) { delete c; }
 
-extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t n_targets, const telr_ins_opt *opt, telr_ins_calls **out)
+// The front half of the two entries on a result's signatures (telr_call_insertions here, telr_call_at_sites in sitecall.hip.h), stated
+// once: check() refuses on the host or lists the eligible records; signatures() counts, writes and sorts them on the device.
+struct InsFront {
+    telr_ctx *ctx; std::string who; const telr_result *r; telr_ins_opt O;
+    std::vector<InsRec> er; size_t n = 0; int32_t n_targets = 0, max_qid = 0;      // check(): the eligible records, grouped by read
+    int64_t N = 0; telr_ins_sig *d_sig = nullptr; int64_t *d_tot = nullptr;       // signatures(): N of them at d_sig in key order; d_tot: 4 words of scan totals
+    PermSort S; int rb = 0, qb = 0;                                                // the sort's buffers (ins_*), the bits of a record number + 1 / of a read number
+
+    int bad(const std::string &why) { ctx->err = who + ": " + why; return TELR_E_ARG; }
+    // null arguments, n_targets, the options (clusters: also those that only the clustering of telr_call_insertions reads), the record
+    // count, every record -- in this order
+    int check(telr_ctx *ctx_, const char *who_, const telr_result *r_, bool have_out, int32_t n_targets_, const telr_ins_opt *opt, bool clusters)
+    {
+        ctx = ctx_; who = who_; r = r_; n_targets = n_targets_;
+        if (!r || !have_out) return bad("null result or output");
+        if (n_targets <= 0) return bad("n_targets must be positive");
+        if (opt) O = *opt; else telr_ins_opt_default(&O);
+        if (O.min_len < 0 || O.min_mapq < 0 || O.min_clip < 0 || O.max_ref_gap < 0) return bad("negative option");
+        if (clusters) {
+            if (O.cluster_dist < 0 || O.min_support < 0 || O.min_sized < 0) return bad("negative option");
+            if (O.min_sized > O.min_support) return bad("min_sized > min_support");
+        }
+        n = r->alns.size();
+        if (n >= 0x7ffffff0u) { ctx->err = who + ": too many records"; return TELR_E_RANGE; }
+        // the eligible records, grouped by read (a mapped result is in read order already)
+        bool in_order = true;
+        std::string why;
+        for (size_t i = 0; i < n; ++i) {
+            const telr_aln &a = r->alns[i];
+            if (!record_check(a, i, n_targets, r->ncig, &why)) return bad(why);
+            if ((a.flags & TELR_F_SECONDARY) || a.mapq < O.min_mapq) continue;
+            InsRec e;
+            const StrandCoords s = strand_coords(a);
+            e.qid = a.qid; e.tid = a.tid; e.ts = a.ts; e.te = a.te; e.qlen = a.qlen; e.rev = s.rev; e.qs = s.qs; e.qe = s.qe;
+            e.n_cigar = a.n_cigar; e.rec = (int32_t)i; e.g0 = e.g1 = 0; e.cigar_off = a.cigar_off;
+            if (!er.empty() && er.back().qid > e.qid) in_order = false;
+            max_qid = std::max(max_qid, a.qid);
+            er.push_back(e);
+        }
+        if (!in_order) std::stable_sort(er.begin(), er.end(), [](const InsRec &x, const InsRec &y) { return x.qid < y.qid; });
+        const size_t ne = er.size();
+        for (size_t i = 0; i < ne; ) {
+            size_t j = i + 1;
+            while (j < ne && er[j].qid == er[i].qid) ++j;
+            for (size_t k = i; k < j; ++k) { er[k].g0 = (int32_t)i; er[k].g1 = (int32_t)j; }
+            i = j;
+        }
+        return TELR_OK;
+    }
+    // at least one eligible record: N and, when N > 0, the sorted signatures.  The stream is idle at N == 0, busy with the sort otherwise.
+    int signatures()
+    {
+        const size_t ne = er.size();
+        HIPCHK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        result_wait(r);
+        uint32_t *d_cig;
+        TRY(result_dev_cigars(ctx, r, "ins_cig", true, &d_cig, nullptr));
+        InsRec *d_rec; int32_t *d_cnt0, *d_cnt1; int64_t *d_off0, *d_off1;
+        TRY(ctx_buf_t(ctx, "ins_rec", ne, &d_rec));
+        TRY(ctx_buf_t(ctx, "ins_cnt0", ne + 1, &d_cnt0));
+        TRY(ctx_buf_t(ctx, "ins_cnt1", ne + 1, &d_cnt1));
+        TRY(ctx_buf_t(ctx, "ins_off0", ne + 1, &d_off0));
+        TRY(ctx_buf_t(ctx, "ins_off1", ne + 1, &d_off1));
+        TRY(ctx_buf_t(ctx, "ins_tot", 4, &d_tot));
+        HIPCHK(hipMemcpyAsync(d_rec, er.data(), ne * sizeof(InsRec), hipMemcpyHostToDevice, st));
+        const dim3 gw((unsigned)((ne + 3) / 4)), gl = grid256((int64_t)ne);
+        hipLaunchKernelGGL((k_ins_cigar<false>), gw, dim3(256), 0, st, d_rec, (int32_t)ne, d_cig, O.min_len, d_cnt0, (const int64_t*)nullptr, (telr_ins_sig*)nullptr);
+        hipLaunchKernelGGL((k_ins_query<false>), gl, dim3(256), 0, st, d_rec, (int32_t)ne, O.min_len, O.min_clip, O.max_ref_gap, d_cnt1, (const int64_t*)nullptr, (telr_ins_sig*)nullptr);
+        HIPCHK(hipGetLastError());
+        TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt0, (int32_t)ne, d_off0, d_tot, 0, nullptr, nullptr)));
+        TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt1, (int32_t)ne, d_off1, d_tot + 1, 0, nullptr, nullptr)));
+        int64_t tot[2];
+        HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        N = tot[0] + tot[1];
+        if (N == 0) return TELR_OK;
+        if (N >= 0x7ffffff0LL) { ctx->err = who + ": too many signatures"; return TELR_E_RANGE; }
+        telr_ins_sig *d_raw;
+        TRY(ctx_buf_t(ctx, "ins_raw", (size_t)N, &d_raw));
+        TRY(ctx_buf_t(ctx, "ins_sig", (size_t)N, &d_sig));
+        hipLaunchKernelGGL((k_ins_cigar<true>), gw, dim3(256), 0, st, d_rec, (int32_t)ne, d_cig, O.min_len, d_cnt0, d_off0, d_raw);
+        hipLaunchKernelGGL((k_ins_query<true>), gl, dim3(256), 0, st, d_rec, (int32_t)ne, O.min_len, O.min_clip, O.max_ref_gap, d_cnt1, d_off1, d_raw + tot[0]);
+        HIPCHK(hipGetLastError());
+        // sort by (tid, pos, rec, kind, len, mate): least significant group first
+        TRY(S.alloc(ctx, "ins_", (size_t)N));
+        rb = bits_of((uint64_t)n); qb = bits_of((uint64_t)max_qid);
+        const int tb = bits_of((uint64_t)n_targets - 1);
+        perm_iota(ctx, S, N);
+        TRY(perm_sort_round(ctx, S, d_raw, N, InsKeyKLM{rb}, 33 + rb));
+        TRY(perm_sort_round(ctx, S, d_raw, N, InsKeyREC{}, rb));
+        TRY(perm_sort_round(ctx, S, d_raw, N, InsKeyTP{}, 32 + tb));
+        perm_gather(ctx, S, d_raw, N, d_sig);
+        return TELR_OK;
+    }
+};
+
+// The back half of both: N > 0 signatures at d_sig in key order, in nc > 0 clusters -- cid[i] the cluster of signature i (non-decreasing),
+// cstart[c] its first signature (cstart[nc] = N; a run may be empty), sx the exclusive scan of the sized flags.  The distinct reads and
+// the representative of every cluster, then the calls: those of the clusters with enough support, or with d_sites (the caller's sites,
+// one per cluster) one per cluster.  Signatures, calls and read lists are copied into C; the stream is idle on return.
+static int ins_collect(InsFront &F, const telr_ins_sig *d_sig, int64_t N, const int32_t *d_cid, const int32_t *d_cstart, int32_t nc, const int32_t *d_sx,
+                       int32_t min_support, int32_t min_sized, const telr_ins_site *d_sites, telr_ins_calls *C)
 {
-    (void)hipGetLastError();
-    if (!ctx) return TELR_E_ARG;
-    auto bad = [&](const std::string &why) { ctx->err = "telr_call_insertions: " + why; return TELR_E_ARG; };
-    if (!r || !out) return bad("null result or output");
-    if (n_targets <= 0) return bad("n_targets must be positive");
-    telr_ins_opt O;
-    if (opt) O = *opt; else telr_ins_opt_default(&O);
-    if (O.min_len < 0 || O.min_mapq < 0 || O.min_clip < 0 || O.max_ref_gap < 0 || O.cluster_dist < 0 || O.min_support < 0 || O.min_sized < 0)
-        return bad("negative option");
-    if (O.min_sized > O.min_support) return bad("min_sized > min_support");
-    const size_t n = r->alns.size();
-    if (n >= 0x7ffffff0u) { ctx->err = "telr_call_insertions: too many records"; return TELR_E_RANGE; }
-    // the eligible records, grouped by read (a mapped result is in read order already)
-    std::vector<InsRec> er;
-    int32_t max_qid = 0; bool in_order = true;
-    std::string why;
-    for (size_t i = 0; i < n; ++i) {
-        const telr_aln &a = r->alns[i];
-        if (!record_check(a, i, n_targets, r->ncig, &why)) return bad(why);
-        if ((a.flags & TELR_F_SECONDARY) || a.mapq < O.min_mapq) continue;
-        InsRec e;
-        const StrandCoords s = strand_coords(a);
-        e.qid = a.qid; e.tid = a.tid; e.ts = a.ts; e.te = a.te; e.qlen = a.qlen; e.rev = s.rev; e.qs = s.qs; e.qe = s.qe;
-        e.n_cigar = a.n_cigar; e.rec = (int32_t)i; e.g0 = e.g1 = 0; e.cigar_off = a.cigar_off;
-        if (!er.empty() && er.back().qid > e.qid) in_order = false;
-        max_qid = std::max(max_qid, a.qid);
-        er.push_back(e);
-    }
-    if (!in_order) std::stable_sort(er.begin(), er.end(), [](const InsRec &x, const InsRec &y) { return x.qid < y.qid; });
-    const size_t ne = er.size();
-    for (size_t i = 0; i < ne; ) {
-        size_t j = i + 1;
-        while (j < ne && er[j].qid == er[i].qid) ++j;
-        for (size_t k = i; k < j; ++k) { er[k].g0 = (int32_t)i; er[k].g1 = (int32_t)j; }
-        i = j;
-    }
-    telr_ins_calls *C = new telr_ins_calls();
-    C->read_off.assign(1, 0);
-    std::unique_ptr<telr_ins_calls> guard(C);
-    if (ne == 0) { *out = guard.release(); return TELR_OK; }
-    HIPCHK(hipSetDevice(ctx->device));
+    telr_ctx *ctx = F.ctx;
     hipStream_t st = ctx->stream;
-    result_wait(r);
-    uint32_t *d_cig;
-    TRY(result_dev_cigars(ctx, r, "ins_cig", true, &d_cig, nullptr));
-    InsRec *d_rec; int32_t *d_cnt0, *d_cnt1; int64_t *d_off0, *d_off1, *d_tot;
-    TRY(ctx_buf_t(ctx, "ins_rec", ne, &d_rec));
-    TRY(ctx_buf_t(ctx, "ins_cnt0", ne + 1, &d_cnt0));
-    TRY(ctx_buf_t(ctx, "ins_cnt1", ne + 1, &d_cnt1));
-    TRY(ctx_buf_t(ctx, "ins_off0", ne + 1, &d_off0));
-    TRY(ctx_buf_t(ctx, "ins_off1", ne + 1, &d_off1));
-    TRY(ctx_buf_t(ctx, "ins_tot", 4, &d_tot));
-    HIPCHK(hipMemcpyAsync(d_rec, er.data(), ne * sizeof(InsRec), hipMemcpyHostToDevice, st));
-    const dim3 gw((unsigned)((ne + 3) / 4)), gl = grid256((int64_t)ne);
-    hipLaunchKernelGGL((k_ins_cigar<false>), gw, dim3(256), 0, st, d_rec, (int32_t)ne, d_cig, O.min_len, d_cnt0, (const int64_t*)nullptr, (telr_ins_sig*)nullptr);
-    hipLaunchKernelGGL((k_ins_query<false>), gl, dim3(256), 0, st, d_rec, (int32_t)ne, O.min_len, O.min_clip, O.max_ref_gap, d_cnt1, (const int64_t*)nullptr, (telr_ins_sig*)nullptr);
-    HIPCHK(hipGetLastError());
-    TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt0, (int32_t)ne, d_off0, d_tot, 0, nullptr, nullptr)));
-    TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt1, (int32_t)ne, d_off1, d_tot + 1, 0, nullptr, nullptr)));
-    int64_t tot[2];
-    HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const int64_t N = tot[0] + tot[1];
-    if (N == 0) { *out = guard.release(); return TELR_OK; }
-    if (N >= 0x7ffffff0LL) { ctx->err = "telr_call_insertions: too many signatures"; return TELR_E_RANGE; }
-    telr_ins_sig *d_raw, *d_sig;
-    TRY(ctx_buf_t(ctx, "ins_raw", (size_t)N, &d_raw));
-    TRY(ctx_buf_t(ctx, "ins_sig", (size_t)N, &d_sig));
-    hipLaunchKernelGGL((k_ins_cigar<true>), gw, dim3(256), 0, st, d_rec, (int32_t)ne, d_cig, O.min_len, d_cnt0, d_off0, d_raw);
-    hipLaunchKernelGGL((k_ins_query<true>), gl, dim3(256), 0, st, d_rec, (int32_t)ne, O.min_len, O.min_clip, O.max_ref_gap, d_cnt1, d_off1, d_raw + tot[0]);
-    HIPCHK(hipGetLastError());
-    // sort by (tid, pos, rec, kind, len, mate): least significant group first
-    PermSort S;
-    TRY(S.alloc(ctx, "ins_", (size_t)N));
-    const int rb = bits_of((uint64_t)n), qb = bits_of((uint64_t)max_qid), tb = bits_of((uint64_t)n_targets - 1);
+    PermSort &S = F.S;
+    const int rb = F.rb, qb = F.qb, cb = bits_of((uint64_t)nc - 1);
     const dim3 gN = grid256(N), gN1 = grid256(N + 1);
-    perm_iota(ctx, S, N);
-    TRY(perm_sort_round(ctx, S, d_raw, N, InsKeyKLM{rb}, 33 + rb));
-    TRY(perm_sort_round(ctx, S, d_raw, N, InsKeyREC{}, rb));
-    TRY(perm_sort_round(ctx, S, d_raw, N, InsKeyTP{}, 32 + tb));
-    perm_gather(ctx, S, d_raw, N, d_sig);
-    // clusters
-    int32_t *d_head, *d_hx, *d_sized, *d_sx, *d_cid, *d_cstart, *d_dflag, *d_sdflag, *d_dx, *d_sdx;
-    TRY(ctx_buf_t(ctx, "ins_head", (size_t)N + 1, &d_head));
-    TRY(ctx_buf_t(ctx, "ins_hx", (size_t)N + 1, &d_hx));
-    TRY(ctx_buf_t(ctx, "ins_sized", (size_t)N + 1, &d_sized));
-    TRY(ctx_buf_t(ctx, "ins_sx", (size_t)N + 1, &d_sx));
-    TRY(ctx_buf_t(ctx, "ins_cid", (size_t)N + 1, &d_cid));
-    TRY(ctx_buf_t(ctx, "ins_cstart", (size_t)N + 1, &d_cstart));
+    int32_t *d_dflag, *d_sdflag, *d_dx, *d_sdx;
     TRY(ctx_buf_t(ctx, "ins_dflag", (size_t)N + 1, &d_dflag));
     TRY(ctx_buf_t(ctx, "ins_sdflag", (size_t)N + 1, &d_sdflag));
     TRY(ctx_buf_t(ctx, "ins_dx", (size_t)N + 1, &d_dx));
     TRY(ctx_buf_t(ctx, "ins_sdx", (size_t)N + 1, &d_sdx));
-    hipLaunchKernelGGL(k_ins_heads, gN1, dim3(256), 0, st, d_sig, N, O.cluster_dist, d_head, d_sized);
-    HIPCHK(hipGetLastError());
-    TRY((dev_qscan<int32_t, int32_t>(ctx, d_head, (int32_t)N, d_hx, nullptr, 0, nullptr, nullptr)));
-    TRY((dev_qscan<int32_t, int32_t>(ctx, d_sized, (int32_t)N, d_sx, nullptr, 0, nullptr, nullptr)));
-    hipLaunchKernelGGL(k_ins_cid, gN1, dim3(256), 0, st, d_head, d_hx, N, d_cid, d_cstart);
-    int32_t nc = 0;
-    HIPCHK(hipMemcpyAsync(&nc, d_hx + N, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const int cb = bits_of((uint64_t)nc - 1);
     // the distinct reads of every cluster
     perm_iota(ctx, S, N);
     TRY(perm_sort_round(ctx, S, d_sig, N, InsKeyCQU{d_cid, qb}, cb + qb + 1));
@@ -315,16 +330,17 @@ extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t
     TRY(perm_sort_round(ctx, S, d_sig, N, InsKeyLQ{qb}, 31 + qb));
     TRY(perm_sort_round(ctx, S, d_sig, N, InsKeyCU{d_cid}, cb + 1));
     // calls
-    int32_t *d_cflag, *d_qcnt, *d_cx; int64_t *d_qx;
+    int32_t *d_cflag, *d_qcnt, *d_cx; int64_t *d_qx, *d_tot = F.d_tot;
     TRY(ctx_buf_t(ctx, "ins_cflag", (size_t)nc + 1, &d_cflag));
     TRY(ctx_buf_t(ctx, "ins_qcnt", (size_t)nc + 1, &d_qcnt));
     TRY(ctx_buf_t(ctx, "ins_cx", (size_t)nc + 1, &d_cx));
     TRY(ctx_buf_t(ctx, "ins_qx", (size_t)nc + 1, &d_qx));
     const dim3 gC1 = grid256((int64_t)nc + 1);
-    hipLaunchKernelGGL(k_ins_cluster, gC1, dim3(256), 0, st, d_cstart, nc, d_dx, d_sdx, O.min_support, O.min_sized, d_cflag, d_qcnt);
+    hipLaunchKernelGGL(k_ins_cluster, gC1, dim3(256), 0, st, d_cstart, nc, d_dx, d_sdx, min_support, min_sized, d_cflag, d_qcnt);
     HIPCHK(hipGetLastError());
     TRY((dev_qscan<int32_t, int32_t>(ctx, d_cflag, nc, d_cx, d_tot, 0, nullptr, nullptr)));
     TRY((dev_qscan<int32_t, int64_t>(ctx, d_qcnt, nc, d_qx, d_tot + 1, 0, nullptr, nullptr)));
+    int64_t tot[2];
     HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     const int64_t ncall = tot[0], nread = tot[1];
@@ -332,7 +348,8 @@ extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t
     TRY(ctx_buf_t(ctx, "ins_calls", (size_t)ncall, &d_calls));
     TRY(ctx_buf_t(ctx, "ins_roff", (size_t)ncall + 1, &d_roff));
     TRY(ctx_buf_t(ctx, "ins_reads", (size_t)nread, &d_reads));
-    hipLaunchKernelGGL(k_ins_calls, gC1, dim3(256), 0, st, d_sig, d_cstart, nc, d_dx, d_sdx, d_sx, S.perm, d_cflag, d_cx, d_qx, d_calls, d_roff);
+    if (d_sites) hipLaunchKernelGGL((k_ins_calls<true>), gC1, dim3(256), 0, st, d_sig, d_cstart, nc, d_dx, d_sdx, d_sx, S.perm, d_cflag, d_cx, d_qx, d_sites, d_calls, d_roff);
+    else hipLaunchKernelGGL((k_ins_calls<false>), gC1, dim3(256), 0, st, d_sig, d_cstart, nc, d_dx, d_sdx, d_sx, S.perm, d_cflag, d_cx, d_qx, d_sites, d_calls, d_roff);
     hipLaunchKernelGGL(k_ins_reads, gN, dim3(256), 0, st, d_sig, d_cid, d_permd, N, d_dflag, d_dx, d_cstart, d_cflag, d_qx, d_reads);
     HIPCHK(hipGetLastError());
     C->sigs.resize((size_t)N); C->calls.resize((size_t)ncall); C->read_off.resize((size_t)ncall + 1); C->reads.resize((size_t)nread);
@@ -341,6 +358,42 @@ extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t
     HIPCHK(hipMemcpyAsync(C->read_off.data(), d_roff, ((size_t)ncall + 1) * 8, hipMemcpyDeviceToHost, st));
     if (nread) HIPCHK(hipMemcpyAsync(C->reads.data(), d_reads, (size_t)nread * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return TELR_OK;
+}
+
+extern "C" int telr_call_insertions(telr_ctx *ctx, const telr_result *r, int32_t n_targets, const telr_ins_opt *opt, telr_ins_calls **out)
+{
+    (void)hipGetLastError();
+    if (!ctx) return TELR_E_ARG;
+    InsFront F;
+    TRY(F.check(ctx, "telr_call_insertions", r, out != nullptr, n_targets, opt, true));
+    telr_ins_calls *C = new telr_ins_calls();
+    C->read_off.assign(1, 0);
+    std::unique_ptr<telr_ins_calls> guard(C);
+    if (F.er.empty()) { *out = guard.release(); return TELR_OK; }
+    TRY(F.signatures());
+    const int64_t N = F.N;
+    if (N == 0) { *out = guard.release(); return TELR_OK; }
+    hipStream_t st = ctx->stream;
+    // clusters
+    int32_t *d_head, *d_hx, *d_sized, *d_sx, *d_cid, *d_cstart;
+    TRY(ctx_buf_t(ctx, "ins_head", (size_t)N + 1, &d_head));
+    TRY(ctx_buf_t(ctx, "ins_hx", (size_t)N + 1, &d_hx));
+    TRY(ctx_buf_t(ctx, "ins_sized", (size_t)N + 1, &d_sized));
+    TRY(ctx_buf_t(ctx, "ins_sx", (size_t)N + 1, &d_sx));
+    TRY(ctx_buf_t(ctx, "ins_cid", (size_t)N + 1, &d_cid));
+    TRY(ctx_buf_t(ctx, "ins_cstart", (size_t)N + 1, &d_cstart));
+    const dim3 gN1 = grid256(N + 1);
+    hipLaunchKernelGGL(k_ins_heads, gN1, dim3(256), 0, st, F.d_sig, N, F.O.cluster_dist, d_head, d_sized);
+    HIPCHK(hipGetLastError());
+    TRY((dev_qscan<int32_t, int32_t>(ctx, d_head, (int32_t)N, d_hx, nullptr, 0, nullptr, nullptr)));
+    TRY((dev_qscan<int32_t, int32_t>(ctx, d_sized, (int32_t)N, d_sx, nullptr, 0, nullptr, nullptr)));
+    hipLaunchKernelGGL(k_ins_cid, gN1, dim3(256), 0, st, d_head, d_hx, N, d_cid, d_cstart);
+    int32_t nc = 0;
+    HIPCHK(hipMemcpyAsync(&nc, d_hx + N, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(ins_collect(F, F.d_sig, N, d_cid, d_cstart, nc, d_sx, F.O.min_support, F.O.min_sized, nullptr, C));
     *out = guard.release();
     return TELR_OK;
 }
+

@@ -2,7 +2,7 @@
 // helpers, the wave and search inlines of the span / pair kernels, the funnel shifts of the piece cutters, what the drafter and the bridge
 // share (the one-coordinate CIGAR walk, the reach clamp, the signature window, the span kernel, their input: CutInput), and the stable permutation sort over radix.hip.h.  Included by telr_engine.hip once telr_result is
 // defined (telr_depth_medians is a caller), so before every feature header (inscall, genotype, draft, bridge, refte, bam_in, seq_extract,
-// part_merge, pileup, bam_dev): none of them takes a name from a sibling.  The host-side record and call-list checks of the call stages are record_checks.h.
+// part_merge, pileup, bam_dev): none of them takes a name from a sibling, but for sitecall, the second entry on inscall's signatures.  The host-side record and call-list checks of the call stages are record_checks.h.
 #pragma once
 #include "record_checks.h"
 

@@ -3335,6 +3335,7 @@ extern "C" int telr_seqset_attach_qual(telr_ctx *ctx, telr_seqset *s, const char
 #include "pileup.hip.h"
 #include "poa.hip.h"
 #include "inscall.hip.h"
+#include "sitecall.hip.h"           // the second entry on inscall.hip.h's signatures: it takes InsFront and ins_collect from there
 #include "genotype.hip.h"
 #include "draft.hip.h"
 #include "bridge.hip.h"

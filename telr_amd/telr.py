@@ -23,6 +23,14 @@ here; the flow is that of its `main` (src/telr/telr.py:22-189) with this project
                                clips alone is a call; a call without a draft gets a bridge of two reads joined at one shared k-mer
                                (Index.bridge_contigs + SeqSet.join; not an assembler); its row's sv_length and ins_seq become the
                                bridge's ins_len and ALT.  Without the option nothing changes.
+    `--sites FILE`             a mode of its own: genotype the insertion sites of FILE -- another sample's `telr.vcf`, a cohort's
+                               merged list, a truth set; a VCF as this command writes it or a TSV chrom, pos0[, len[, id]] -- on THIS sample.
+                               Reference, stage-1 index and the reads or BAM route as above, then telr_sv.genotype_sites (Index.call_at_sites
+                               + Index.genotype_insertions; not Sniffles' forced genotyping), then <sample>.telr.sites.tsv with one line
+                               per site, `0/0` and `./.` included, and for a VCF input <sample>.telr.sites.vcf.  `--site_reach N` (50): a
+                               signature supports the nearest site within N bases; `--site_len_pct N` (0: off): a sized signature whose
+                               length differs from the site's by more than N percent is dropped.  No discovery, draft, asm10 index or
+                               loci stage runs; `--polish`, `--bridge` and `--ref_te` are reported once as having no effect.
     asm10 index                Engine.index over the same resident reference
     a reference above 2^31     `--index_part_bases N`: the reference is cut into parts of at most N bases of padded extent, each
                                with an index of its own (Engine.index_parts); the reads are mapped against every part and the records merged
@@ -41,7 +49,8 @@ Different from the reference on purpose: every value it prints a message for end
 four of its messages: -p below 1, a negative --af_flank_offset or --af_te_offset, --af_te_interval below 1); a reads file of any
 extension other than `.bam` is read as reads (a `.gz` on the device, see above; one it refuses, and every plain file, by the readers).  Not built: the ALT pre-screen, merge_rows on the
 caller's rows, the RepeatMasker route for families, the N-rank path, gzip on the BAM route, a bridge of more than two reads (an
-element longer than two reads' clips together stays without a contig).  On a multi-part reference: the occurrence
+element longer than two reads' clips together stays without a contig); for `--sites`: no cohort merge of several samples' VCFs (the list
+comes merged), no draft or liftover for the listed sites, no N-rank path.  On a multi-part reference: the occurrence
 cut-off of the seeding is per part, as with minimap2 -I (secondaries the unsplit index would not report), all parts are resident together,
 and `--ref_te engine` maps the tiles to the library, not to the reference, so it runs as it is.
 """
@@ -53,6 +62,9 @@ import time
 
 INERT = "--assembler, --polisher, --different_contig_name and --minimap2_family have no effect here: this project has one drafting " \
         "step (a supporting read's piece, polished on the device) and annotates families by alignment only"
+
+
+SITES_INERT = ("--polish", "--bridge", "--ref_te")          # options of the stages that a --sites run does not have
 
 
 def _say(msg):
@@ -107,11 +119,17 @@ def get_args(argv=None):
                      "0: chunks of the engine's own size (default = 0)")
     own.add_argument("--bridge", action="store_true", help="also call insertions that no single read spans (clusters of clipped reads alone) and draft them "
                      "as a bridge of two reads joined at one shared k-mer (not an assembler)")
+    own.add_argument("--sites", type=str, help="genotype the insertion sites of FILE on this sample instead of discovering calls: a VCF as this command writes it, "
+                     "or a TSV with the columns chrom, pos0[, len[, id]]; writes <sample>.telr.sites.tsv (and .sites.vcf for a VCF) with one line per site, "
+                     "0/0 and ./. included (not Sniffles' forced genotyping)")
+    own.add_argument("--site_reach", type=int, default=50, help="with --sites: a signature supports the nearest site within N bases (default = 50)")
+    own.add_argument("--site_len_pct", type=int, default=0, help="with --sites: drop a sized signature whose length differs from the site's by more than N percent; "
+                     "0: no length test (default = 0)")
     own.add_argument("--sample", type=str, help="sample name (default: the reads file's name without its extension)")
     p._action_groups.append(opt)
     a = p.parse_args(argv)
 
-    for path in (a.reads, a.reference, a.library) + (() if a.ref_te in ("none", "engine") else (a.ref_te,)):
+    for path in (a.reads, a.reference, a.library) + (() if a.ref_te in ("none", "engine") else (a.ref_te,)) + (() if a.sites is None else (a.sites,)):
         try:
             open(path, "r").close()
         except Exception as e:
@@ -163,14 +181,19 @@ def get_args(argv=None):
         _exit("Please provide a valid BAM chunk size in MiB (0 or a positive integer), exiting...")
     if a.reads_chunk_mb < 0:
         _exit("Please provide a valid reads chunk size in MiB (0 or a positive integer), exiting...")
+    if a.site_reach < 0:
+        _exit("Please provide a valid site reach (0 or a positive integer), exiting...")
+    if not 0 <= a.site_len_pct <= 100:
+        _exit("Please provide a valid site length tolerance in percent (0 to 100), exiting...")
     if (a.chain_skip or a.seed_rescue or a.mm2_mapq) and a.aligner != "minimap2":
         _exit("--chain_skip, --seed_rescue and --mm2_mapq are options of the minimap2 aligner, exiting...")
     a.out = os.path.abspath("." if a.out is None else a.out)
     os.makedirs(a.out, exist_ok=True)
     if a.sample is None:
         a.sample = os.path.splitext(os.path.basename(a.reads))[0]
-    a.inert_given = [o for o in ("--assembler", "--polisher", "--different_contig_name", "--minimap2_family")
-                     if any(x == o or x.startswith(o + "=") for x in (sys.argv[1:] if argv is None else argv))]
+    given = lambda names: [o for o in names if any(x == o or x.startswith(o + "=") for x in (sys.argv[1:] if argv is None else argv))]
+    a.inert_given = given(("--assembler", "--polisher", "--different_contig_name", "--minimap2_family"))
+    a.sites_inert_given = given(SITES_INERT) if a.sites is not None else []
     return a
 
 
@@ -264,6 +287,13 @@ def call_stage(ix, r, tnames, qnames, read_set, sample, bridge=False):
     return rows, ix.call_insertions(r, opt)
 
 
+def sites_stage(ix, r, tnames, qnames, listed, args):
+    """--sites: the listed sites genotyped on this sample's result -> the dicts of telr_sv.genotype_sites, one per site"""
+    from . import telr_sv
+    from ._abi import SiteOpt
+    return telr_sv.genotype_sites(ix, r, tnames, qnames, listed["sites"], site_opt=SiteOpt.default(reach=args.site_reach, len_pct=args.site_len_pct))
+
+
 def draft_stage(ix, r, ic, rows, read_set, chrom_ids, bridge=False):
     from . import telr_assembly
     if not bridge:
@@ -297,7 +327,8 @@ EMPTY_RESULT = {"annotation": [], "liftover": [], "summary": {}, "af": {}}
 def run(args, engine=None):
     """One run of the pipeline with the Namespace of `get_args` -> dict(final = the rows of `<sample>.telr.json`, files = {name: path},
     counts = {reads, records, calls, calls_without_draft, loci_annotated, loci_lifted, loci_written; with --bridge also calls_bridged},
-    seconds = {stage: wall time}).
+    seconds = {stage: wall time}).  With args.sites: final = [], sites = the dicts of telr_sv.genotype_sites, files gains sites_tsv (and
+    sites_vcf), counts gains sites and sites_supported, and the stages are inputs, index, reads, sites, outputs.
     engine: an aligner.Engine to run on (default: a new one on args.device, closed at the end).  Engine errors are raised as TelrError;
     nothing falls back to another path."""
     from . import fasta, locus_pipeline, telr_sv
@@ -319,6 +350,10 @@ def run(args, engine=None):
 
     if getattr(args, "inert_given", None):
         _say("[telr] " + INERT)
+    sites_path = getattr(args, "sites", None)
+    if sites_path is not None and getattr(args, "sites_inert_given", None):
+        _say("[telr] %s %s no effect with --sites: the run genotypes the listed sites and has no discovery, draft or loci stage"
+             % (", ".join(args.sites_inert_given), "has" if len(args.sites_inert_given) == 1 else "have"))
     own_engine = engine is None
     eng = make_engine(args.device) if own_engine else engine
     release = None
@@ -334,7 +369,10 @@ def run(args, engine=None):
             os.symlink(os.path.abspath(args.reference), ref_copy)
         by_name = dict(zip(tnames, tseqs))
         chrom_ids = {n: i for i, n in enumerate(tnames)}
-        done("inputs", "%d reference sequences, %d library sequences" % (len(tnames), len(lib_names)))
+        listed = None
+        if sites_path is not None:                  # refused before anything is mapped
+            listed = telr_sv.read_sites(sites_path, chrom_ids, {n: len(q) for n, q in zip(tnames, tseqs)}, report=lambda m: _say("[telr] " + m))
+        done("inputs", "%d reference sequences, %d library sequences" % (len(tnames), len(lib_names)) + ("" if listed is None else ", %d sites" % len(listed["sites"])))
         # 2. the stage-1 index
         io, _ = preset(aligner_preset(args)[0])
         ix, n_parts = index_stage(eng, tseqs, io, args.index_part_bases)
@@ -350,6 +388,19 @@ def run(args, engine=None):
         counts["reads"] = len(qnames)
         counts["records"] = int(eng.L.telr_result_count(r))
         done("reads", "%d reads, %d records (%s)" % (counts["reads"], counts["records"], route))
+        if listed is not None:
+            # --sites: the listed sites genotyped, then the outputs; no discovery, draft, asm10 index or loci stage
+            site_rows = sites_stage(ix, r, tnames, qnames, listed, args)
+            counts["sites"] = len(site_rows)
+            counts["sites_supported"] = sum(1 for x in site_rows if x["support"] > 0)
+            done("sites", "%d sites genotyped, %d with a supporting read" % (counts["sites"], counts["sites_supported"]))
+            files["sites_tsv"] = os.path.join(args.out, sample + ".telr.sites.tsv")
+            telr_sv.write_sites_tsv(site_rows, listed["ids"], files["sites_tsv"])
+            if listed["vcf"]:
+                files["sites_vcf"] = os.path.join(args.out, sample + ".telr.sites.vcf")
+                telr_sv.write_sites_vcf(site_rows, listed, sample, files["sites_vcf"])
+            done("outputs", "%d sites written to %s" % (len(site_rows), files["sites_tsv"]))
+            return dict(final=[], files=files, counts=counts, seconds=seconds, sites=site_rows)
         # 4. the calls, genotyped
         bridge = bool(getattr(args, "bridge", False))
         rows, ic = call_stage(ix, r, tnames, qnames, read_set, sample, bridge) if bridge else call_stage(ix, r, tnames, qnames, read_set, sample)
@@ -425,6 +476,9 @@ def main(argv=None):
     except Exception as e:                          # TelrError carries the engine's text; nothing is retried another way
         _say("telr: %s: %s" % (type(e).__name__, e))
         return 1
+    if "sites" in out["counts"]:
+        _say("[telr] finished in %.2f s: %d sites genotyped" % (time.time() - t0, out["counts"]["sites"]))
+        return 0
     _say("[telr] finished in %.2f s: %d insertions" % (time.time() - t0, out["counts"]["loci_written"]))
     return 0
 

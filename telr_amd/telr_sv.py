@@ -8,7 +8,9 @@ alignment path and not provided; its opt-in counterpart is `call_insertions`: th
 (`telr_call_insertions`, a definition of its own, not Sniffles') run on the stage-1 result, returning rows of this table.  `filter_vcf` keeps the reference's table arithmetic and takes the TE intervals of the
 ALT sequences from a `screen`: `gff_screen` reads a RepeatMasker `.out.gff` (the reference's source, :256-295),
 `engine_screen` (opt-in: it changes which loci pass) maps the TE library onto the ALT sequences
-with the HIP engine instead.
+with the HIP engine instead.  `genotype_sites` answers the other question of a cohort study: for a site list that came from
+somewhere else (`read_sites`: a VCF of this project or a TSV), what does THIS sample show there -- supporters, reference reads and a
+genotype per site, `0/0` and `./.` included (`telr_call_at_sites`; not Sniffles' forced genotyping).
 
 The 14 columns are addressed by index by every later stage; COLUMNS names them.
 
@@ -84,6 +86,114 @@ def call_insertions(index, result, tnames, qnames, reads, opt=None, sample="telr
                      "%s.INS.%d" % (sample, k), seq.decode(), names, "PASS", genotype_text, ref_count, str(int(c["support"]))] +
                     ([NO_TE_PROP] if te_prop_column else []))
     return rows
+
+
+SITE_FIELDS = ("chrom", "pos", "site_len", "len", "support", "n_sized", "ref", "ambig", "gt_text", "af_text", "reads")
+
+
+def site_texts(alt, ref, gt):
+    """(gt_text, af_text) of a site: ./. and nan when no read speaks for either allele (the genotyper's gt is 2 there, since 0 >= 0),
+    else the genotyper's 0/0, 0/1 or 1/1 and "%.6f" % (alt / (alt + ref))"""
+    if alt + ref == 0:
+        return NO_GENOTYPE, NO_AF
+    return GENOTYPES[int(gt)], "%.6f" % (alt / (alt + ref))
+
+
+def genotype_sites(index, result, tnames, qnames, sites, opt=None, site_opt=None, geno_opt=None):
+    """Genotype insertion sites that came from somewhere else -- another sample's calls, a cohort's list, a truth set -- on this sample's
+    stage-1 result: `Index.call_at_sites` (telr_call_at_sites) gathers the supporters of every site, the existing
+    `Index.genotype_insertions` counts the reference and ambiguous reads.  An own definition, NOT Sniffles' forced genotyping
+    (--genotype-vcf); its agreement with Sniffles is not pinned.
+    sites: an (n, 3) int32 array or a list of (tid, pos, len) triples, strictly ascending by (tid, pos), len = the expected insertion
+    length or 0 (`read_sites` gives them); opt / site_opt / geno_opt: an `_abi.InsOpt` / `SiteOpt` / `GenoOpt` (None = defaults).
+    -> one dict per site, in site order (SITE_FIELDS): chrom, pos, site_len, len (the lower median length of the kept sized signatures,
+    0 without one), support and n_sized (distinct reads), ref and ambig (distinct reads), gt_text (./. when support + ref == 0, else
+    0/0, 0/1, 1/1), af_text ("%.6f" % (support / (support + ref)) or nan), reads (the supporters' names, ascending by read id)."""
+    import numpy as np
+    s = np.asarray(sites, dtype=np.int32).reshape(-1, 3)
+    ic = index.call_at_sites(result, s, opt, site_opt)
+    gt = index.genotype_insertions(result, ic, geno_opt).gt
+    out = []
+    for k, c in enumerate(ic.calls):
+        alt, ref = int(c["support"]), int(gt[k]["ref"])
+        gt_text, af_text = site_texts(alt, ref, gt[k]["gt"])
+        out.append(dict(chrom=tnames[int(c["tid"])], pos=int(c["pos"]), site_len=int(s[k][2]), len=int(c["len"]), support=alt, n_sized=int(c["n_sized"]),
+                        ref=ref, ambig=int(gt[k]["ambig"]), gt_text=gt_text, af_text=af_text, reads=[qnames[q] for q in ic.reads_of(k).tolist()]))
+    return out
+
+
+def read_sites(path, chrom_ids, chrom_lens=None, report=None):
+    """A site list for `genotype_sites` from a VCF as `telr_output.write_vcf` writes it (a first line `##fileformat=VCF...`), or from a plain
+    TSV with the columns chrom, pos0[, len[, id]] (lines starting with # and blank lines are skipped).
+    From a VCF: CHROM, the site position POS - 1, ID, and len(ALT) as the expected length when ALT is made of letters, else 0.
+    chrom_ids: {chromosome name: target id}; chrom_lens: {name: length} (None: the end is not checked).
+    -> dict(sites = [(tid, pos, len), ...] sorted by (tid, pos), ids = their ids ("" without one), vcf = is it a VCF, header = the VCF's
+    header lines, lines = the VCF's data lines split into columns, in site order, duplicates = the lines dropped).
+    A duplicate (chrom, pos) keeps the first line; all of them are reported in one message (report: a callable taking the text; default
+    stderr).  An unknown chromosome, a position that is negative or past the chromosome's end, a negative length or a line that does not
+    parse raise ValueError with the line's number."""
+    import sys
+    with open(path, "r") as fh:
+        text = fh.read().splitlines()
+    vcf = bool(text) and text[0].startswith("##fileformat=VCF")
+    header, found = [], []
+    for no, line in enumerate(text, 1):
+        if not line.strip():
+            continue
+        if line.startswith("#"):
+            if vcf:
+                header.append(line)
+            continue
+        f = line.split("\t")
+        where = "%s line %d: " % (path, no)
+        try:
+            if vcf:
+                if len(f) < 8:
+                    raise ValueError("a VCF line has at least 8 columns")
+                chrom, pos, ln, sid = f[0], int(f[1]) - 1, len(f[4]) if f[4].isalpha() else 0, f[2]
+            else:
+                if len(f) < 2:
+                    raise ValueError("a site line has the columns chrom, pos0[, len[, id]]")
+                chrom, pos, ln, sid = f[0], int(f[1]), int(f[2]) if len(f) > 2 and f[2] != "" else 0, f[3] if len(f) > 3 else ""
+        except ValueError as e:
+            raise ValueError(where + str(e))
+        if chrom not in chrom_ids:
+            raise ValueError(where + "chromosome %r is not in the reference" % chrom)
+        if pos < 0 or (chrom_lens is not None and pos > chrom_lens[chrom]):
+            raise ValueError(where + "position %d is negative or past the end of %s" % (pos, chrom))
+        if ln < 0:
+            raise ValueError(where + "negative length")
+        found.append(((chrom_ids[chrom], pos), ln, sid, f))
+    found.sort(key=lambda x: x[0])          # stable: the first line of a position stays first
+    kept = [x for k, x in enumerate(found) if k == 0 or x[0] != found[k - 1][0]]
+    dup = len(found) - len(kept)
+    if dup:
+        (report or (lambda m: sys.stderr.write(m + "\n")))("%s: %d line%s repeat%s the (chrom, pos) of an earlier line; the first line of a position is kept"
+                                                          % (path, dup, "" if dup == 1 else "s", "s" if dup == 1 else ""))
+    return dict(sites=[(k[0], k[1], ln) for k, ln, _, _ in kept], ids=[sid for _, _, sid, _ in kept], vcf=vcf, header=header,
+                lines=[f for _, _, _, f in kept] if vcf else [], duplicates=dup)
+
+
+def write_sites_tsv(rows, ids, path):
+    """the dicts of `genotype_sites` -> `<sample>.telr.sites.tsv`: a header line, then one line per site: id, SITE_FIELDS (reads joined by commas, `.` for none)"""
+    with open(path, "w") as fh:
+        fh.write("#id\t" + "\t".join(SITE_FIELDS) + "\n")
+        for sid, r in zip(ids, rows):
+            fh.write("\t".join([sid or "."] + [str(r[k]) for k in SITE_FIELDS[:-1]] + [",".join(r["reads"]) or "."]) + "\n")
+
+
+def write_sites_vcf(rows, listed, sample, path):
+    """the input VCF (`listed`: what `read_sites` returned) with this run's genotypes -> `<sample>.telr.sites.vcf`: the header as it was with
+    the sample's name in the #CHROM line, the eight fixed columns of every kept input line as they were, FORMAT GT:DR:DV and the sample
+    column GT : reference reads : supporting reads.  (This column follows its FORMAT string; `<sample>.telr.vcf` keeps the reference's
+    swapped order, telr_output.py.)"""
+    with open(path, "w") as fh:
+        for line in listed["header"]:
+            if line.startswith("#CHROM"):
+                line = "\t".join(line.split("\t")[:9] + [sample]) if line.count("\t") >= 8 else line + "\tFORMAT\t" + sample
+            fh.write(line + "\n")
+        for f, r in zip(listed["lines"], rows):
+            fh.write("\t".join(f[:8] + ["GT:DR:DV", "%s:%d:%d" % (r["gt_text"], r["ref"], r["support"])]) + "\n")
 
 
 def sv_info(rows):

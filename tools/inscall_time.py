@@ -2,8 +2,10 @@
 make it smaller), once with the result's resident CIGAR copy (TELR_MF_KEEP_CIGARS) and once with the CIGAR array uploaded, and the
 plain-Python restatement (tests/inscall_ref.py) on a sample of the reads, scaled to the whole set; then Index.genotype_insertions
 (telr_genotype_insertions) on the calls of that result, the same two ways, and Index.draft_contigs (telr_draft_contigs) on the same calls.  Writes profiles/inscall_time.json.
+Then Index.call_at_sites (telr_call_at_sites) on the positions of the run's own calls, on the resident copy, next to the
+call_insertions time of the same run: profiles/sitecall_time.json.
 
-    python tools/inscall_time.py [--coverage 30] [--genome-scale 1.0] [--repeat 5] [--sample-reads 2000] [--out profiles/inscall_time.json]
+    python tools/inscall_time.py [--coverage 30] [--genome-scale 1.0] [--repeat 5] [--sample-reads 2000] [--out profiles/inscall_time.json] [--sites-out profiles/sitecall_time.json]
 """
 import argparse
 import json
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--sample-reads", type=int, default=2000)
     ap.add_argument("--min-support", type=int, default=10)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "inscall_time.json"))
+    ap.add_argument("--sites-out", default=os.path.join(ROOT, "profiles", "sitecall_time.json"))
     a = ap.parse_args()
     import numpy as np
     import bench
@@ -69,10 +72,21 @@ def main():
             s.free()
         return out, ts[1:]
 
+    def timed_sites(r, ic):
+        """the run's own calls as sites: (tid, pos, the call's length)"""
+        sites = np.ascontiguousarray(np.stack([ic.calls["tid"], ic.calls["pos"], ic.calls["len"]], axis=1), dtype=np.int32)
+        ts = []
+        for _ in range(a.repeat + 1):
+            t0 = time.perf_counter()
+            sc = ix.call_at_sites(r, sites, opt)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return sc, ts[1:]
+
     mk = mo.copy(); mk.flags |= MF_KEEP_CIGARS
     r = ix.map_raw(qs, mk)
     res = ix.result_arrays(r)
     ic_res, ms_res = timed(r)
+    sc_res, sms_res = timed_sites(r, ic_res)
     ig_res, gms_res = timed_geno(r, ic_res)
     (dr_res, dr_bases), dms_res = timed_draft(r, ic_res)
     ix.free_raw(r)
@@ -113,6 +127,23 @@ def main():
                   "(validation, uploads, kernels, the genotypes and read lists copied back) and of Index.draft_contigs (validation, uploads, kernels, the draft "
                   "records copied back, the set left on the device), %d repeats after one untimed call each" % a.repeat,
     }
+    # (a site's support need not be its call's: a single-linkage cluster may reach farther than `reach` from its median position)
+    assert len(sc_res.calls) == len(ic_res.calls)
+    sites_out = {k: out[k] for k in ("workload", "device", "preset", "options", "reads", "records", "cigar_words", "signatures", "calls")}
+    sites_out.update({
+        "sites": int(len(sc_res.calls)), "site_options": {"reach": 50, "len_pct": 0}, "kept_signatures": int(len(sc_res.sigs)),
+        "sites_with_support": int((sc_res.calls["support"] > 0).sum()),
+        "sites_whose_support_is_the_calls": int((sc_res.calls["support"] == ic_res.calls["support"]).sum()),
+        "call_insertions_ms_resident_cigars": out["call_insertions_ms_resident_cigars"],
+        "call_at_sites_ms_resident_cigars": {"min": min(sms_res), "median": float(np.median(sms_res)), "all": sms_res},
+        "timing": "wall clock of Index.call_at_sites on the positions of the run's own calls (validation, record and site upload, kernels, the kept "
+                  "signatures and calls copied back), %d repeats after one untimed call, next to Index.call_insertions of the same run" % a.repeat,
+    })
+    os.makedirs(os.path.dirname(a.sites_out), exist_ok=True)
+    with open(a.sites_out, "w") as fh:
+        json.dump(sites_out, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps({k: sites_out[k] for k in ("sites", "kept_signatures", "sites_with_support", "call_insertions_ms_resident_cigars", "call_at_sites_ms_resident_cigars")}))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)
