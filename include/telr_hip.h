@@ -813,7 +813,8 @@ void telr_te_feats_free(telr_te_feats *f);
  *      context's scratch until telr_release_scratch).  telr_bam_load_chunked has no such limit.
  * counters: members, records, mapped, kept, reads, orphans, len_mismatch, no_cigar, no_eof.  The set and the result belong to the
  *      handle (telr_bam_in_free frees them) until detached; after that they are the caller's (telr_seqset_free / telr_result_free)
- *      and the handle's accessors stay valid while they live.  Not read: .bai, CRAM, SAM, the header text beyond its length.
+ *      and the handle's accessors stay valid while they live.  Not read: CRAM, SAM, .csi, the header text beyond its length (the
+ *      .bai is read by telr_bam_load_regions alone, below).
  * Chunked (telr_bam_load_chunked): the same result -- names, targets, counters, records, CIGAR words, the set's words and qualities,
  *      byte for byte -- for every accepted file and every chunk_bytes >= 1, with transient device memory that depends on the chunk and
  *      not on the file.  The file stays mapped on the host.  It is cut into chunks (telr_bam_chunk_plan: a chunk is a run of whole
@@ -866,6 +867,55 @@ int  telr_bam_in_ascii(const telr_bam_in *in, char *buf, int64_t *off);
  * chunk upload and inflate overlap with the others, so total is not the sum of the rest.  telr_bam_load is the load of one chunk: its
  * upload, inflate and chain used to be host wall clock, each ending in a synchronisation, and are device times between events now */
 int  telr_bam_in_phase_ms(const telr_bam_in *in, float *out /* [8] */);
+
+/* ---- only the regions asked for, through the .bai (opt-in).  `samtools view file.bam chr:beg-end` as a load: only the
+ *      BGZF members that the index names are uploaded and inflated; their records are chained, filtered by true overlap and parsed on
+ *      the device.  tests/bam_region_ref.py states the definition in plain Python.
+ * Regions:  (tid, beg, end), 0-based, half-open; any order, overlapping or touching.  The host clips end to the target's length (and to
+ *      2^29, the reach of a .bai), sorts them and merges them into disjoint ascending regions per target.  TELR_E_ARG before anything is
+ *      read beyond the header: a tid outside the header's targets, beg < 0, end <= beg after clipping, a non-zero reserved field,
+ *      n_regions < 0, a null pointer with n_regions > 0.  Zero regions: the header's targets, no read, no record; nothing beyond the
+ *      header is inflated and the index is not opened.
+ * Selection:  a record is selected iff it is mapped (flag & 4 == 0, refID >= 0) and its reference span [pos, pos + max(1, M + D))
+ *      overlaps a region on tid == refID: pos < end and pos + span > beg.  M and D are those of the CIGAR rules above, the CG:B,I array in
+ *      force where they say so.  Unmapped records are never selected, placed ones included.
+ * Result:   what telr_bam_load gives for a BAM that holds this file's header and exactly the selected records in file order -- targets,
+ *      names, lengths, the set's words, mask words and qualities, records, CIGAR words and the counters records .. no_cigar, byte for
+ *      byte, for every file that the whole-file load accepts.  members counts the members inflated for the intervals; no_eof is the
+ *      file's.  A CONSEQUENCE: a read whose sequence-bearing record (neither 0x100 nor 0x800) lies outside the regions has no read here,
+ *      and its selected records are orphans, exactly as after `samtools view` of the region.  Nothing repairs that.
+ * Index:    <bam>.bai, or the path given; SAM specification 5.2: magic, n_ref, per reference the bins with their chunks and the 16-kb
+ *      linear index, the optional n_no_coor; pseudo-bin 37450 is skipped.  Per merged region: the chunks of all bins of reg2bins(beg,
+ *      end); a chunk whose end is at or below the linear index's entry for beg >> 14 is dropped (an entry of 0 is unset and drops
+ *      nothing, and so does a window behind the last entry); an empty chunk (beg >= end) is dropped.  All regions' chunks are sorted by
+ *      start, and two become one INTERVAL when the next starts in, or before, the member in which the current one ends (coffset(next.beg)
+ *      <= coffset(cur.end)): no member belongs to two intervals and none is inflated twice.  An interval [vbeg, vend) is the members from
+ *      coffset(vbeg) to coffset(vend), the last one only when uoffset(vend) > 0; they are hopped from coffset(vbeg), not from the file's
+ *      start.  Its records start at uoffset(vbeg) in the first member and their chain must end exactly at uoffset(vend) in the last: a
+ *      chain that runs past that point or stops before it, a record with block_size < 32, an offset beyond its member's ISIZE, or members
+ *      that do not meet coffset(vend) are TELR_E_ARG, "the index does not match the file at virtual offset V".
+ *      TELR_E_IO: the .bai cannot be read.  TELR_E_ARG: wrong magic; n_ref is not the header's; a count or a chunk runs past the index's
+ *      end; a coffset at or beyond the BAM's size; a coffset that does not start with the BGZF magic.  A stale index that passes these
+ *      checks and chains cannot be told from a fresh one.
+ * Records:  every record walked inside an interval is checked as in telr_bam_load, selected or not (the bins over-select: more is walked
+ *      than kept).  File-order numbers are unknown here: texts say "record at virtual offset V" and "block at file offset P".
+ * Header:   read in a step of its own: the members from file offset 0, as few as hold it.  A member that also opens the first interval is
+ *      inflated a second time there -- the only exception to "no member twice", counted apart (region_info[3]).
+ * Chunks:   the intervals' members in file order are cut by telr_bam_chunk_plan as in telr_bam_load_chunked (chunk_bytes as there;
+ *      TELR_BAM_CHUNK_FIT decides on the intervals' bytes); an interval may span chunks (the carry goes on) and a chunk may hold many
+ *      intervals.  telr_bam_in_chunk_info and telr_bam_in_phase_ms keep their meaning (host hop: the index plan and the intervals' hops).
+ * telr_bam_in_region_info: merged regions, intervals, members inflated for the intervals, header members, records walked, records
+ *      selected; all 0 after the other two loads.  telr_bam_in_region_bytes: file bytes uploaded for the intervals, both passes.
+ * telr_bai_plan: host only, no device needed: the intervals of `regions` (not clipped to target lengths: it has none) over an index of
+ *      n_ref references, vbeg[i] / vend[i] for i < min(*n_intervals, cap).  TELR_E_RANGE: more intervals than cap (the first cap are
+ *      written and *n_intervals is exact: call again).  telr_bai_plan_error: the reason of the calling thread's last refusal. */
+typedef struct telr_region { int32_t tid, beg, end, reserved; } telr_region;
+int  telr_bam_load_regions(telr_ctx *ctx, const char *bam_path, const char *bai_path /* NULL: bam_path + ".bai" */, int32_t keep_qual, int64_t chunk_bytes,
+                           int64_t n_regions, const telr_region *regions, telr_bam_in **out);
+int  telr_bam_in_region_info(const telr_bam_in *in, int64_t *out /* [6] */);
+int64_t telr_bam_in_region_bytes(const telr_bam_in *in);
+int  telr_bai_plan(const char *bai_path, int32_t n_ref, int64_t n_regions, const telr_region *regions, uint64_t *vbeg, uint64_t *vend, int64_t cap, int64_t *n_intervals);
+const char *telr_bai_plan_error(void);
 
 /* ---- a FASTA / FASTQ file -- plain, gzip or BGZF -- as a read set, parsed and packed on the device (opt-in).  The
  *      text is never held as host text: it goes to the device in chunks (inflated there for BGZF, by one host thread running zlib for

@@ -25,6 +25,7 @@ EXPORTS = [
     "telr_bam_load", "telr_bam_in_free", "telr_bam_in_target_count", "telr_bam_in_target_names", "telr_bam_in_target_lens", "telr_bam_in_read_count",
     "telr_bam_in_read_names", "telr_bam_in_read_lens", "telr_bam_in_seqset", "telr_bam_in_result", "telr_bam_in_detach_seqset", "telr_bam_in_detach_result",
     "telr_bam_in_counters", "telr_bam_in_ascii", "telr_bam_in_phase_ms", "telr_bam_load_chunked", "telr_bam_chunk_plan", "telr_bam_in_chunk_info",
+    "telr_bam_load_regions", "telr_bam_in_region_info", "telr_bam_in_region_bytes", "telr_bai_plan", "telr_bai_plan_error",
     "telr_seqset_extract", "telr_seqset_pieces", "telr_seqset_join",
     "telr_bridge_opt_default", "telr_bridge_contigs", "telr_bridges_count", "telr_bridges_data", "telr_bridge_contigs_free",
     "telr_reads_load", "telr_reads_in_free", "telr_reads_in_count", "telr_reads_in_names", "telr_reads_in_lens", "telr_reads_in_seqset", "telr_reads_in_detach_seqset",
@@ -133,6 +134,11 @@ def lib():
     L.telr_bam_load_chunked.restype = C.c_int; L.telr_bam_load_chunked.argtypes = [vp, cp, i32, i64, C.POINTER(vp)]
     L.telr_bam_chunk_plan.restype = C.c_int; L.telr_bam_chunk_plan.argtypes = [i64, vp, i64, vp, i64, C.POINTER(i64)]
     L.telr_bam_in_chunk_info.restype = C.c_int; L.telr_bam_in_chunk_info.argtypes = [vp, vp]
+    L.telr_bam_load_regions.restype = C.c_int; L.telr_bam_load_regions.argtypes = [vp, cp, cp, i32, i64, i64, vp, C.POINTER(vp)]
+    L.telr_bam_in_region_info.restype = C.c_int; L.telr_bam_in_region_info.argtypes = [vp, vp]
+    L.telr_bam_in_region_bytes.restype = i64; L.telr_bam_in_region_bytes.argtypes = [vp]
+    L.telr_bai_plan.restype = C.c_int; L.telr_bai_plan.argtypes = [cp, i32, i64, vp, vp, vp, i64, C.POINTER(i64)]
+    L.telr_bai_plan_error.restype = cp; L.telr_bai_plan_error.argtypes = []
     L.telr_reads_load.restype = C.c_int; L.telr_reads_load.argtypes = [vp, cp, i32, i64, C.POINTER(vp)]
     L.telr_reads_in_free.restype = None; L.telr_reads_in_free.argtypes = [vp]
     L.telr_reads_in_count.restype = i32; L.telr_reads_in_count.argtypes = [vp]

@@ -125,13 +125,41 @@ class Engine:
             raise _lib.TelrError("telr_bam_chunk_plan: %s" % L.telr_strerror(rc).decode(), rc)
         return first[:int(n.value)]
 
-    def load_bam(self, path, keep_qual=False, chunk_bytes=None):
+    @staticmethod
+    def _regions(regions):
+        """(tid, beg, end[, reserved]) tuples -> the telr_region array"""
+        a = np.zeros((len(regions), 4), np.int32)
+        for i, r in enumerate(regions):
+            a[i, :len(r)] = [int(x) for x in r]
+        return a
+
+    @staticmethod
+    def bai_plan(bai, n_ref, regions):
+        """-> (vbeg, vend) (uint64): the intervals of virtual offsets that the index file `bai` names for `regions`, a list of
+        (tid, beg, end) -- sorted and merged, but not clipped to target lengths (telr_bai_plan; include/telr_hip.h has the definition;
+        no device needed)"""
+        L = _lib.lib()
+        reg = Engine._regions(regions)
+        n = C.c_int64(0)
+        rc = L.telr_bai_plan(str(bai).encode(), int(n_ref), len(reg), reg.ctypes.data, None, None, 0, C.byref(n))
+        vb, ve = np.zeros(max(int(n.value), 1), np.uint64), np.zeros(max(int(n.value), 1), np.uint64)
+        if rc == -4:          # TELR_E_RANGE: the count is exact, call again
+            rc = L.telr_bai_plan(str(bai).encode(), int(n_ref), len(reg), reg.ctypes.data, vb.ctypes.data, ve.ctypes.data, len(vb), C.byref(n))
+        if rc != 0:
+            raise _lib.TelrError("telr_bai_plan: %s [%s]" % (L.telr_strerror(rc).decode(), L.telr_bai_plan_error().decode()), rc)
+        return vb[:int(n.value)], ve[:int(n.value)]
+
+    def load_bam(self, path, keep_qual=False, chunk_bytes=None, regions=None, bai=None):
         """a BAM file as stage-1 input, inflated and parsed on the device (telr_bam_load; include/telr_hip.h has the definition)
         -> BamInput.  keep_qual: attach the reads' base qualities to the read set when every sequence-bearing record has them.
         chunk_bytes: None = the whole file at once (it must fit into device memory next to its inflated stream); n > 0 = in chunks of
         at most n inflated bytes, 0 = in chunks of the engine's own size (telr_bam_load_chunked: a file of any size, the same result);
-        BAM_CHUNK_FIT = the whole file when it fits into half the free device memory, else as 0"""
-        return BamInput(self, path, keep_qual, chunk_bytes)
+        BAM_CHUNK_FIT = the whole file when it fits into half the free device memory, else as 0.
+        regions: a list of (tid, beg, end), 0-based and half-open: only the records that overlap one of them are loaded, and only the
+        BGZF members that the index `bai` (None: path + ".bai") names for them are inflated (telr_bam_load_regions; chunk_bytes None
+        stands for BAM_CHUNK_FIT there).  A read whose sequence-bearing record lies outside the regions is no read of the result, and
+        its records inside are orphans.  None: the whole file, as ever"""
+        return BamInput(self, path, keep_qual, chunk_bytes, regions, bai)
 
     def load_reads(self, path, keep_qual=False, chunk_bytes=0):
         """a FASTA / FASTQ file -- plain, gzip or BGZF, decided by content -- as a resident read set, parsed and packed on the device
@@ -571,16 +599,23 @@ class BamInput:
     sequence-bearing record), read_set (a SeqSet resident on the device, qualities attached when kept), result (a raw result handle with
     its CIGARs resident: Index.call_insertions, genotype_insertions, draft_contigs, write_bam_device, result_arrays, ...), counters
     (dict: members, records, mapped, kept, reads, orphans, len_mismatch, no_cigar, no_eof), phase_ms (dict) and chunk_info (dict: chunks,
-    passes, largest_buffer, largest_carry; all 0 after a whole-file load)"""
+    passes, largest_buffer, largest_carry; all 0 after a whole-file load), region_info (dict: regions (merged), intervals, members
+    (inflated for the intervals), header_members, walked, selected; all 0 unless `regions` was given) and region_bytes (file bytes
+    that a region load uploaded)"""
     COUNTERS = ("members", "records", "mapped", "kept", "reads", "orphans", "len_mismatch", "no_cigar", "no_eof")
     PHASES = ("host_hop", "upload", "inflate", "chain", "parse", "names_host", "sequences", "total")
     CHUNK_INFO = ("chunks", "passes", "largest_buffer", "largest_carry")
+    REGION_INFO = ("regions", "intervals", "members", "header_members", "walked", "selected")
 
-    def __init__(self, eng, path, keep_qual=False, chunk_bytes=None):
+    def __init__(self, eng, path, keep_qual=False, chunk_bytes=None, regions=None, bai=None):
         L = eng.L
         self.eng = eng
         h = C.c_void_p()
-        if chunk_bytes is None:
+        if regions is not None:
+            reg = Engine._regions(regions)
+            rc = L.telr_bam_load_regions(eng.h, str(path).encode(), None if bai is None else str(bai).encode(), 1 if keep_qual else 0,
+                                         BAM_CHUNK_FIT if chunk_bytes is None else int(chunk_bytes), len(reg), reg.ctypes.data, C.byref(h))
+        elif chunk_bytes is None:
             rc = L.telr_bam_load(eng.h, str(path).encode(), 1 if keep_qual else 0, C.byref(h))
         else:
             rc = L.telr_bam_load_chunked(eng.h, str(path).encode(), 1 if keep_qual else 0, int(chunk_bytes), C.byref(h))
@@ -590,6 +625,10 @@ class BamInput:
         ci = np.zeros(len(self.CHUNK_INFO), np.int64)
         L.telr_bam_in_chunk_info(h, ci.ctypes.data)
         self.chunk_info = dict(zip(self.CHUNK_INFO, (int(x) for x in ci)))
+        ri = np.zeros(len(self.REGION_INFO), np.int64)
+        L.telr_bam_in_region_info(h, ri.ctypes.data)
+        self.region_info = dict(zip(self.REGION_INFO, (int(x) for x in ri)))
+        self.region_bytes = int(L.telr_bam_in_region_bytes(h))
         nt, nq = int(L.telr_bam_in_target_count(h)), int(L.telr_bam_in_read_count(h))
         self.tnames = [x.decode("latin-1") for x in _cstrs(L.telr_bam_in_target_names(h), nt)]
         self.tlens = _np_from(L.telr_bam_in_target_lens(h), nt, np.int32)

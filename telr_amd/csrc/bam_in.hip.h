@@ -445,6 +445,8 @@ struct telr_bam_in {
     int64_t counters[9] = {0};
     float phase_ms[BIN_NPHASE] = {0};
     int64_t chunk_info[4] = {0};       // telr_bam_load_chunked: chunks, passes, largest chunk buffer, largest carry (telr_bam_load leaves them 0)
+    int64_t region_info[6] = {0};      // telr_bam_load_regions: merged regions, intervals, their members, header members, records walked, selected
+    int64_t region_bytes = 0;          // ... and the file bytes it uploaded, both passes
 };
 struct BamInClock {
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
@@ -470,46 +472,57 @@ struct BamInHop {
     int64_t total = 0, no_eof = 0;                              // sum of ISIZE; 1 without the EOF marker
     float ms = 0;
 };
-static int bam_in_hop(telr_ctx *ctx, const char *what, const char *path, BamInHop &H)
+// one member's header at file offset p of the mapped file: nullptr and M, bsize (the member's whole length), or why it is none
+static const char *bgzf_member_at(const uint8_t *d, size_t size, size_t p, BgzfMember &M, size_t &bsize)
 {
-    BamInClock clk;
+    if (p + 12 > size) return "truncated member";
+    if (d[p] != 0x1f || d[p + 1] != 0x8b || d[p + 2] != 8 || d[p + 3] != 4) return "not a BGZF member (wrong magic, or bytes after the last member)";
+    const size_t xlen = (size_t)d[p + 10] | (size_t)d[p + 11] << 8;
+    if (p + 12 + xlen > size) return "truncated member";
+    size_t q = p + 12; bsize = 0;
+    while (q + 4 <= p + 12 + xlen) {
+        const size_t slen = (size_t)d[q + 2] | (size_t)d[q + 3] << 8;
+        if (d[q] == 'B' && d[q + 1] == 'C' && slen == 2 && q + 6 <= p + 12 + xlen) { bsize = ((size_t)d[q + 4] | (size_t)d[q + 5] << 8) + 1; break; }
+        q += 4 + slen;
+    }
+    if (!bsize) return "no BC subfield";
+    if (bsize < 12 + xlen + 8) return "BSIZE smaller than the member's own fields";
+    if (p + bsize > size) return "truncated member";
+    const uint8_t *t = d + p + bsize - 8;
+    M.off = (int64_t)(p + 12 + xlen); M.clen = (uint32_t)(bsize - 12 - xlen - 8); M.pad = 0;
+    M.crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+    M.isize = (uint32_t)t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+    if (M.isize > 65536u) return "ISIZE above 65,536";
+    return nullptr;
+}
+// the file, mapped; H.no_eof
+static int bam_in_open(telr_ctx *ctx, const char *what, const char *path, BamInHop &H)
+{
     BamInFile &F = H.F;
     F.fd = open(path, O_RDONLY);
     struct stat sb;
     if (F.fd < 0 || fstat(F.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { ctx->err = std::string(what) + ": cannot open " + path; return TELR_E_IO; }
     F.n = (size_t)sb.st_size;
     if (F.n) { void *m = mmap(nullptr, F.n, PROT_READ, MAP_PRIVATE, F.fd, 0); if (m == MAP_FAILED) { F.n = 0; ctx->err = std::string(what) + ": cannot map " + path; return TELR_E_IO; } F.p = (const uint8_t*)m; }
-    const uint8_t *d = F.p; const size_t size = F.n;
+    H.no_eof = (F.n >= 28 && !memcmp(F.p + F.n - 28, BGZF_EOF28, 28)) ? 0 : 1;
+    return TELR_OK;
+}
+static int bam_in_hop(telr_ctx *ctx, const char *what, const char *path, BamInHop &H)
+{
+    BamInClock clk;
+    TRY(bam_in_open(ctx, what, path, H));
+    const uint8_t *d = H.F.p; const size_t size = H.F.n;
     // hop the member headers
     std::vector<BgzfMember> &mem = H.mem; std::vector<int32_t> &isz = H.isz;
     size_t p = 0;
     while (p < size) {
-        const size_t k = mem.size();
-        auto bad = [&](const char *why) { ctx->err = std::string(what) + ": block " + std::to_string(k) + ": " + why; return TELR_E_ARG; };
-        if (p + 12 > size) return bad("truncated member");
-        if (d[p] != 0x1f || d[p + 1] != 0x8b || d[p + 2] != 8 || d[p + 3] != 4) return bad("not a BGZF member (wrong magic, or bytes after the last member)");
-        const size_t xlen = (size_t)d[p + 10] | (size_t)d[p + 11] << 8;
-        if (p + 12 + xlen > size) return bad("truncated member");
-        size_t q = p + 12, bsize = 0;
-        while (q + 4 <= p + 12 + xlen) {
-            const size_t slen = (size_t)d[q + 2] | (size_t)d[q + 3] << 8;
-            if (d[q] == 'B' && d[q + 1] == 'C' && slen == 2 && q + 6 <= p + 12 + xlen) { bsize = ((size_t)d[q + 4] | (size_t)d[q + 5] << 8) + 1; break; }
-            q += 4 + slen;
-        }
-        if (!bsize) return bad("no BC subfield");
-        if (bsize < 12 + xlen + 8) return bad("BSIZE smaller than the member's own fields");
-        if (p + bsize > size) return bad("truncated member");
-        const uint8_t *t = d + p + bsize - 8;
-        BgzfMember M; M.off = (int64_t)(p + 12 + xlen); M.clen = (uint32_t)(bsize - 12 - xlen - 8); M.pad = 0;
-        M.crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
-        M.isize = (uint32_t)t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
-        if (M.isize > 65536u) return bad("ISIZE above 65,536");
+        BgzfMember M; size_t bsize = 0;
+        if (const char *why = bgzf_member_at(d, size, p, M, bsize)) { ctx->err = std::string(what) + ": block " + std::to_string(mem.size()) + ": " + why; return TELR_E_ARG; }
         mem.push_back(M); isz.push_back((int32_t)M.isize);
         p += bsize;
     }
     const size_t nm = mem.size();
     if (nm >= 0x7ffffff0u) { ctx->err = std::string(what) + ": too many BGZF members"; return TELR_E_RANGE; }
-    H.no_eof = (size >= 28 && !memcmp(d + size - 28, BGZF_EOF28, 28)) ? 0 : 1;
     H.total = 0;
     for (size_t k = 0; k < nm; ++k) H.total += mem[k].isize;
     H.ms = clk.lap();

@@ -188,6 +188,111 @@ static int bamc_carry(BamChunked &C, int64_t k, const uint8_t *src, int64_t len,
     return TELR_OK;
 }
 
+// What a load does behind pass 1, whichever way its chunks came about: the host decides on all records (P.recs: those of the file, or the
+// selected ones of a region load), the result's arrays and the set are made, and pass 2 writes the kept records' words and the reads' bases
+// where they stay.  issue(k) / wait(k): chunk k uploaded and inflated again into its slot (more than one chunk only); who(r): how an error
+// text names record r.  The handle takes the set and the result
+struct BamPass1 {
+    std::vector<BamRec> recs; std::vector<int64_t> noff = std::vector<int64_t>(1, 0); std::vector<char> names;
+    std::vector<int64_t> rec0, carry_in, cut;      // per chunk: its first record, the carry it started with, where its walk ended
+    int64_t max_carry = 0;
+};
+template <class Issue, class Wait, class Who>
+static int bam_load_pass2(telr_ctx *ctx, telr_bam_in *B, BamChunked &C, BamPass1 &P1, int32_t keep_qual, BamInClock &clk, Issue issue, Wait wait, Who who, int64_t *passes)
+{
+    std::vector<BamRec> &recs = P1.recs; std::vector<int64_t> &noff = P1.noff, &rec0 = P1.rec0, &carry_in = P1.carry_in, &cut = P1.cut; std::vector<char> &names = P1.names;
+    const int64_t nch = C.nch, max_carry = P1.max_carry;
+    hipStream_t st = C.s_main;
+    // ---- host: names -> read numbers; which records are kept, and where
+    clk.lap();
+    names.push_back(0);
+    BamInDecided D;
+    TRY(bam_in_decide(ctx, B, recs, names, noff, D));
+    const int32_t nq = (int32_t)D.reads.size();
+    const size_t nk = D.kept_rec.size();
+    std::unique_ptr<telr_result> R(std::move(D.R));
+    std::vector<int32_t> kept_at(recs.size(), -1);             // record -> its place among the kept ones: pass 2 meets them in file order
+    for (size_t i = 0; i < nk; ++i) kept_at[(size_t)D.kept_rec[i]] = (int32_t)i;
+    B->phase_ms[BIN_NAMES_HOST] = clk.lap();
+    // ---- the result's arrays and the set, final from the start
+    TRY(bam_in_result_arrays(ctx, R.get(), D.ncig));
+    telr_seqset *S = new telr_seqset();
+    S->ctx = ctx; S->n = nq; S->len = D.rlen;
+    TRY(seqset_alloc(ctx, S, "telr_bam_load", true, st));          // (frees S on failure)
+    std::unique_ptr<telr_seqset, void (*)(telr_seqset*)> Sg(S, telr_seqset_free);
+    const bool with_qual = nq && keep_qual && !D.any_ff;
+    if (with_qual) {
+        HIPCHK(hipMalloc(&S->d_qual, (size_t)S->padded_bases + 64));
+        HIPCHK(hipMemsetAsync(S->d_qual + S->padded_bases, 0, 64, st));
+    }
+    // ---- pass 2: the kept records' words and the reads' bases go where they stay.  More than one chunk: each is uploaded and inflated
+    // again.  One chunk: slot 0 holds it where pass 1 left it (carry_in[0] == 0) and "bamin_recs" holds its records' fields
+    *passes = 1;
+    if (nq || nk) {
+        *passes = 2;
+        const bool again = nch > 1;
+        // (keep 0: a room that grew would drop the members behind it.  One chunk has no carry, max_carry is 0 and its room stays)
+        for (int i = 0; i < C.nslot; ++i) TRY(bamc_room(C, C.slot[i], (size_t)max_carry, 0));
+        std::vector<int32_t> h_idx, h_over; std::vector<int64_t> h_off;
+        int32_t q = 0;
+        if (again) TRY(issue(0));
+        for (int64_t k = 0; k < nch; ++k) {
+            if (again) TRY(wait(k));
+            BamChunkSlot &s = C.at(k);
+            const uint8_t *buf = s.d_buf + s.room - carry_in[(size_t)k];
+            const int64_t r0 = rec0[(size_t)k], r1 = rec0[(size_t)k + 1];
+            h_idx.clear(); h_off.clear();
+            for (int64_t r = r0; r < r1; ++r) if (kept_at[(size_t)r] >= 0) { h_idx.push_back((int32_t)(r - r0)); h_off.push_back(D.kept_off[(size_t)kept_at[(size_t)r]]); }
+            if (!h_idx.empty()) {
+                const size_t n = h_idx.size();
+                BamRec *d_recs; int32_t *d_krec; int64_t *d_koff;
+                TRY(ctx_buf_t(ctx, "bamin_recs", (size_t)(r1 - r0), &d_recs));
+                TRY(ctx_buf_t(ctx, "bamin_krec", n, &d_krec));
+                TRY(ctx_buf_t(ctx, "bamin_koff", n, &d_koff));
+                if (again) HIPCHK(hipMemcpyAsync(d_recs, recs.data() + r0, (size_t)(r1 - r0) * sizeof(BamRec), hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(d_krec, h_idx.data(), n * 4, hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(d_koff, h_off.data(), n * 8, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(k_bam_cig, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, buf, d_recs, d_krec, d_koff, (int64_t)n, R->d_cig);
+                HIPCHK(hipGetLastError());
+            }
+            const int32_t q0 = q;
+            while (q < nq && D.first_rec[(size_t)q] < r1) ++q;
+            const int32_t nqk = q - q0;
+            int32_t *d_over = nullptr;
+            if (nqk) {
+                BamRead *d_reads;
+                TRY(ctx_buf_t(ctx, "bamin_reads", (size_t)nqk, &d_reads));
+                HIPCHK(hipMemcpyAsync(d_reads, D.reads.data() + q0, (size_t)nqk * sizeof(BamRead), hipMemcpyHostToDevice, st));
+                const int64_t b0 = S->boff[(size_t)q0], b1 = S->boff[(size_t)q];
+                hipLaunchKernelGGL(k_bam_seq, grid256((b1 - b0) / 16), dim3(256), 0, st, buf, d_reads, S->d_boff + q0, nqk, b0 / 16, b1 / 16, S->d_seq2, S->d_nmask);
+                HIPCHK(hipGetLastError());
+                if (with_qual) {
+                    TRY(ctx_buf_t(ctx, "bamin_over", (size_t)nqk, &d_over));
+                    HIPCHK(hipMemsetAsync(d_over, 0, (size_t)nqk * 4, st));
+                    hipLaunchKernelGGL(k_bam_qual, grid256((b1 - b0) / 4), dim3(256), 0, st, buf, d_reads, S->d_boff + q0, nqk, b0 / 4, b1 / 4, (uint32_t*)S->d_qual, d_over);
+                    HIPCHK(hipGetLastError());
+                    h_over.resize((size_t)nqk);
+                    HIPCHK(hipMemcpyAsync(h_over.data(), d_over, (size_t)nqk * 4, hipMemcpyDeviceToHost, st));
+                }
+            }
+            if (k + 1 < nch) TRY(issue(k + 1));
+            HIPCHK(hipStreamSynchronize(st));
+            if (d_over)          // (reads are numbered in file order of their records: the first one found is the lowest record)
+                for (int32_t j = 0; j < nqk; ++j) if (h_over[(size_t)j]) {
+                    ctx->err = "telr_bam_load: record " + who(D.first_rec[(size_t)(q0 + j)]) + ": a base quality above 93"; return TELR_E_ARG;
+                }
+            if (k + 1 < nch) TRY(bamc_carry(C, k, buf + cut[(size_t)k], carry_in[(size_t)k + 1], (size_t)C.payload(k + 1)));
+        }
+        if (D.ncig) HIPCHK(hipMemcpyAsync(R->cig, R->d_cig, (size_t)D.ncig * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    R->twin_n = R->ncig; R->twin_off = false;
+    B->phase_ms[BIN_SEQ] = clk.lap();
+    B->phase_ms[BIN_UPLOAD] = C.ms_upload; B->phase_ms[BIN_INFLATE] = C.ms_inflate;
+    bam_in_finish(B, Sg.release(), R.release());
+    return TELR_OK;
+}
+
 // the load.  chunk_bytes BAMC_WHOLE: the whole file as one chunk in one slot.  report: the handle's chunk_info is filled
 static int bam_load(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual, int64_t chunk_bytes, bool report, telr_bam_in **out)
 {
@@ -202,10 +307,11 @@ static int bam_load(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual, int64_t
     hipStream_t st = C.s_main;
     const int64_t nch = C.nch, nrun = std::max<int64_t>(nch, 1);      // (a file without members: one empty chunk, for the header's error)
     // ---- pass 1: every chunk's records and names
-    std::vector<BamRec> recs; std::vector<int64_t> noff(1, 0), noff_k; std::vector<char> names;
-    std::vector<int64_t> rec0((size_t)nrun + 1, 0), carry_in((size_t)nrun + 1, 0), cut((size_t)nrun, 0);
+    BamPass1 P1;
+    std::vector<BamRec> &recs = P1.recs; std::vector<int64_t> &noff = P1.noff, &rec0 = P1.rec0, &carry_in = P1.carry_in, &cut = P1.cut, noff_k; std::vector<char> &names = P1.names;
+    rec0.assign((size_t)nrun + 1, 0); carry_in.assign((size_t)nrun + 1, 0); cut.assign((size_t)nrun, 0);
     bool hdr = false;
-    int64_t carry = 0, max_carry = 0;
+    int64_t carry = 0, &max_carry = P1.max_carry;
     int32_t n_ref = 0;
     float ms_parse = 0;
     if (nch) TRY(bamc_issue(C, 0));
@@ -286,95 +392,11 @@ static int bam_load(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual, int64_t
         if (!last) TRY(bamc_carry(C, k, buf + p_end, carry, (size_t)C.payload(k + 1)));
     }
     B->phase_ms[BIN_CHAIN] = C.ms_chain; B->phase_ms[BIN_PARSE] = ms_parse;
-    // ---- host: names -> read numbers; which records are kept, and where
-    clk.lap();
-    names.push_back(0);
-    BamInDecided D;
-    TRY(bam_in_decide(ctx, B.get(), recs, names, noff, D));
-    const int32_t nq = (int32_t)D.reads.size();
-    const size_t nk = D.kept_rec.size();
-    std::unique_ptr<telr_result> R(std::move(D.R));
-    std::vector<int32_t> kept_at(recs.size(), -1);             // record -> its place among the kept ones: pass 2 meets them in file order
-    for (size_t i = 0; i < nk; ++i) kept_at[(size_t)D.kept_rec[i]] = (int32_t)i;
-    B->phase_ms[BIN_NAMES_HOST] = clk.lap();
-    // ---- the result's arrays and the set, final from the start
-    TRY(bam_in_result_arrays(ctx, R.get(), D.ncig));
-    telr_seqset *S = new telr_seqset();
-    S->ctx = ctx; S->n = nq; S->len = D.rlen;
-    TRY(seqset_alloc(ctx, S, "telr_bam_load", true, st));          // (frees S on failure)
-    std::unique_ptr<telr_seqset, void (*)(telr_seqset*)> Sg(S, telr_seqset_free);
-    const bool with_qual = nq && keep_qual && !D.any_ff;
-    if (with_qual) {
-        HIPCHK(hipMalloc(&S->d_qual, (size_t)S->padded_bases + 64));
-        HIPCHK(hipMemsetAsync(S->d_qual + S->padded_bases, 0, 64, st));
-    }
-    // ---- pass 2: the kept records' words and the reads' bases go where they stay.  More than one chunk: each is uploaded and inflated
-    // again.  One chunk: slot 0 holds it where pass 1 left it (carry_in[0] == 0) and "bamin_recs" holds its records' fields
     int64_t passes = 1;
-    if (nq || nk) {
-        passes = 2;
-        const bool again = nch > 1;
-        // (keep 0: a room that grew would drop the members behind it.  One chunk has no carry, max_carry is 0 and its room stays)
-        for (int i = 0; i < C.nslot; ++i) TRY(bamc_room(C, C.slot[i], (size_t)max_carry, 0));
-        std::vector<int32_t> h_idx, h_over; std::vector<int64_t> h_off;
-        int32_t q = 0;
-        if (again) TRY(bamc_issue(C, 0));
-        for (int64_t k = 0; k < nch; ++k) {
-            if (again) TRY(bamc_wait(C, k));
-            BamChunkSlot &s = C.at(k);
-            const uint8_t *buf = s.d_buf + s.room - carry_in[(size_t)k];
-            const int64_t r0 = rec0[(size_t)k], r1 = rec0[(size_t)k + 1];
-            h_idx.clear(); h_off.clear();
-            for (int64_t r = r0; r < r1; ++r) if (kept_at[(size_t)r] >= 0) { h_idx.push_back((int32_t)(r - r0)); h_off.push_back(D.kept_off[(size_t)kept_at[(size_t)r]]); }
-            if (!h_idx.empty()) {
-                const size_t n = h_idx.size();
-                BamRec *d_recs; int32_t *d_krec; int64_t *d_koff;
-                TRY(ctx_buf_t(ctx, "bamin_recs", (size_t)(r1 - r0), &d_recs));
-                TRY(ctx_buf_t(ctx, "bamin_krec", n, &d_krec));
-                TRY(ctx_buf_t(ctx, "bamin_koff", n, &d_koff));
-                if (again) HIPCHK(hipMemcpyAsync(d_recs, recs.data() + r0, (size_t)(r1 - r0) * sizeof(BamRec), hipMemcpyHostToDevice, st));
-                HIPCHK(hipMemcpyAsync(d_krec, h_idx.data(), n * 4, hipMemcpyHostToDevice, st));
-                HIPCHK(hipMemcpyAsync(d_koff, h_off.data(), n * 8, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_bam_cig, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, buf, d_recs, d_krec, d_koff, (int64_t)n, R->d_cig);
-                HIPCHK(hipGetLastError());
-            }
-            const int32_t q0 = q;
-            while (q < nq && D.first_rec[(size_t)q] < r1) ++q;
-            const int32_t nqk = q - q0;
-            int32_t *d_over = nullptr;
-            if (nqk) {
-                BamRead *d_reads;
-                TRY(ctx_buf_t(ctx, "bamin_reads", (size_t)nqk, &d_reads));
-                HIPCHK(hipMemcpyAsync(d_reads, D.reads.data() + q0, (size_t)nqk * sizeof(BamRead), hipMemcpyHostToDevice, st));
-                const int64_t b0 = S->boff[(size_t)q0], b1 = S->boff[(size_t)q];
-                hipLaunchKernelGGL(k_bam_seq, grid256((b1 - b0) / 16), dim3(256), 0, st, buf, d_reads, S->d_boff + q0, nqk, b0 / 16, b1 / 16, S->d_seq2, S->d_nmask);
-                HIPCHK(hipGetLastError());
-                if (with_qual) {
-                    TRY(ctx_buf_t(ctx, "bamin_over", (size_t)nqk, &d_over));
-                    HIPCHK(hipMemsetAsync(d_over, 0, (size_t)nqk * 4, st));
-                    hipLaunchKernelGGL(k_bam_qual, grid256((b1 - b0) / 4), dim3(256), 0, st, buf, d_reads, S->d_boff + q0, nqk, b0 / 4, b1 / 4, (uint32_t*)S->d_qual, d_over);
-                    HIPCHK(hipGetLastError());
-                    h_over.resize((size_t)nqk);
-                    HIPCHK(hipMemcpyAsync(h_over.data(), d_over, (size_t)nqk * 4, hipMemcpyDeviceToHost, st));
-                }
-            }
-            if (k + 1 < nch) TRY(bamc_issue(C, k + 1));
-            HIPCHK(hipStreamSynchronize(st));
-            if (d_over)          // (reads are numbered in file order of their records: the first one found is the lowest record)
-                for (int32_t j = 0; j < nqk; ++j) if (h_over[(size_t)j]) {
-                    ctx->err = "telr_bam_load: record " + std::to_string(D.first_rec[(size_t)(q0 + j)]) + ": a base quality above 93"; return TELR_E_ARG;
-                }
-            if (k + 1 < nch) TRY(bamc_carry(C, k, buf + cut[(size_t)k], carry_in[(size_t)k + 1], (size_t)C.payload(k + 1)));
-        }
-        if (D.ncig) HIPCHK(hipMemcpyAsync(R->cig, R->d_cig, (size_t)D.ncig * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    R->twin_n = R->ncig; R->twin_off = false;
-    B->phase_ms[BIN_SEQ] = clk.lap();
-    B->phase_ms[BIN_UPLOAD] = C.ms_upload; B->phase_ms[BIN_INFLATE] = C.ms_inflate;
+    TRY(bam_load_pass2(ctx, B.get(), C, P1, keep_qual, clk, [&](int64_t k) { return bamc_issue(C, k); }, [&](int64_t k) { return bamc_wait(C, k); },
+                       [](int64_t r) { return std::to_string(r); }, &passes));
     B->phase_ms[BIN_TOTAL] = wall.lap() + H.ms;
     if (report) { B->chunk_info[0] = nch; B->chunk_info[1] = passes; B->chunk_info[2] = (int64_t)C.max_alloc; B->chunk_info[3] = max_carry; }
-    bam_in_finish(B.get(), Sg.release(), R.release());
     *out = B.release();
     return TELR_OK;
 }

@@ -3342,6 +3342,7 @@ extern "C" int telr_seqset_attach_qual(telr_ctx *ctx, telr_seqset *s, const char
 #include "refte.hip.h"
 #include "bam_in.hip.h"
 #include "bam_in_chunked.hip.h"
+#include "bam_in_regions.hip.h"
 #include "reads_in.hip.h"
 #include "seq_extract.hip.h"
 #include "part_merge.hip.h"

@@ -17,6 +17,15 @@ here; the flow is that of its `main` (src/telr/telr.py:22-189) with this project
                                inflated bytes (a file of any size); 0 (the default): the whole file at once when it and
                                its inflated stream fit into half the free device memory, else in chunks of the engine's own size --
                                one hop of the member headers decides and is handed on.  The outputs do not depend on the choice.
+    `--region SPEC[,SPEC...]`  on the BAM route, any number of times: only the records that overlap the regions are loaded, and
+                               only the BGZF members that <bam>.bai names for them are uploaded and inflated (Engine.load_bam(regions=...)).
+                               SPEC as samtools takes it -- `chr`, `chr:beg-end` (1-based, inclusive), `chr:beg` -- resolved against the
+                               reference's names, which check_targets ties to the BAM's header.  Discovery, drafts and loci (or `--sites`)
+                               then run on what was loaded.  `--region sites` with `--sites FILE`: one region [pos - m, pos + m) per listed
+                               site, m = site_reach + the caller's max_ref_gap + 1 (site_region_margin).  As after `samtools view` of the
+                               regions, a read whose primary record lies outside them is no read of the run and its records inside are
+                               orphans; nothing repairs that.  A missing or unfit .bai ends the run with the engine's text and status 1:
+                               nothing falls back to the whole file.  On the reads route the option is reported once as having no effect.
     calls                      telr_sv.call_insertions(..., reads=<the resident set>, genotype=True)      (not Sniffles)
     drafts                     telr_assembly.draft_loci(..., reads=<the resident set>)                     (not wtdbg2 / flye)
     `--bridge`                 insertions that no single read spans: the caller runs with min_sized = 0, so a cluster of
@@ -62,6 +71,9 @@ import time
 
 INERT = "--assembler, --polisher, --different_contig_name and --minimap2_family have no effect here: this project has one drafting " \
         "step (a supporting read's piece, polished on the device) and annotates families by alignment only"
+
+
+REGION_INERT = "--region has no effect on the reads route: it selects the records of a BAM of mapped reads through its .bai; reads are mapped as a whole"
 
 
 SITES_INERT = ("--polish", "--bridge", "--ref_te")          # options of the stages that a --sites run does not have
@@ -125,6 +137,9 @@ def get_args(argv=None):
     own.add_argument("--site_reach", type=int, default=50, help="with --sites: a signature supports the nearest site within N bases (default = 50)")
     own.add_argument("--site_len_pct", type=int, default=0, help="with --sites: drop a sized signature whose length differs from the site's by more than N percent; "
                      "0: no length test (default = 0)")
+    own.add_argument("--region", action="append", metavar="SPEC[,SPEC...]", help="on the BAM route: load only the records that overlap these regions, through "
+                     "<bam>.bai (samtools-style: chr, chr:beg-end 1-based and inclusive, chr:beg to the target's end); may be given more than once.  'sites' "
+                     "together with --sites: one region around every listed site.  A read whose primary record lies outside the regions is not loaded")
     own.add_argument("--sample", type=str, help="sample name (default: the reads file's name without its extension)")
     p._action_groups.append(opt)
     a = p.parse_args(argv)
@@ -185,6 +200,8 @@ def get_args(argv=None):
         _exit("Please provide a valid site reach (0 or a positive integer), exiting...")
     if not 0 <= a.site_len_pct <= 100:
         _exit("Please provide a valid site length tolerance in percent (0 to 100), exiting...")
+    if a.region and a.sites is None and any(s == "sites" for text in a.region for s in text.split(",")):
+        _exit("--region sites needs the site list of --sites, exiting...")
     if (a.chain_skip or a.seed_rescue or a.mm2_mapq) and a.aligner != "minimap2":
         _exit("--chain_skip, --seed_rescue and --mm2_mapq are options of the minimap2 aligner, exiting...")
     a.out = os.path.abspath("." if a.out is None else a.out)
@@ -278,6 +295,39 @@ def load_bam(eng, ix, args, tnames, tlens):
     return bi.qnames, bi.read_set, bi.result, lambda: (bi.free(), bi.read_set.free())
 
 
+def site_region_margin(args):
+    """`--region sites`: the margin m of the region [pos - m, pos + m) around a listed site (DESIGN.md 5.20 derives it): a signature is
+    kept at a site within site_reach of it and lies inside its record's span, ends included; the mate of a split signature starts
+    within the caller's max_ref_gap of that; a record that the genotyper counts spans the site itself.  So m = site_reach + max_ref_gap
+    + 1 is the smallest m for which every such record overlaps the region"""
+    from ._abi import InsOpt
+    return args.site_reach + InsOpt.default().max_ref_gap + 1
+
+
+def bam_regions(args, tnames, tlens, listed):
+    """the `--region` texts -> [(tid, beg, end)]; `sites`: one region per listed site"""
+    from .telr_alignment import parse_regions, split_region_specs
+    specs = [s for text in args.region for s in split_region_specs(text)]
+    out = parse_regions([s for s in specs if s != "sites"], tnames, tlens)
+    if "sites" in specs:
+        m = site_region_margin(args)
+        out += [(tid, max(0, pos - m), min(pos + m, int(tlens[tid]))) for tid, pos, _ in listed["sites"]]
+    return out
+
+
+def load_bam_regions(eng, ix, args, tnames, tlens, regions):
+    """the BAM route with `--region`: only what overlaps the regions is loaded, through the file's .bai -> the four of load_bam and
+    BamInput.region_info"""
+    from .aligner import BAM_CHUNK_FIT
+    bi = eng.load_bam(args.reads, keep_qual=args.keep_qual, chunk_bytes=args.bam_chunk_mb << 20 if args.bam_chunk_mb > 0 else BAM_CHUNK_FIT, regions=regions)
+    try:
+        bi.check_targets(tnames, tlens)
+    except BaseException:
+        bi.free()
+        raise
+    return bi.qnames, bi.read_set, bi.result, lambda: (bi.free(), bi.read_set.free()), bi.region_info
+
+
 def call_stage(ix, r, tnames, qnames, read_set, sample, bridge=False):
     """bridge: the caller's min_sized = 0 -- a cluster of clips alone is a call (rep = -1, len = 0, ins_seq "N")"""
     from . import telr_sv
@@ -326,7 +376,8 @@ EMPTY_RESULT = {"annotation": [], "liftover": [], "summary": {}, "af": {}}
 
 def run(args, engine=None):
     """One run of the pipeline with the Namespace of `get_args` -> dict(final = the rows of `<sample>.telr.json`, files = {name: path},
-    counts = {reads, records, calls, calls_without_draft, loci_annotated, loci_lifted, loci_written; with --bridge also calls_bridged},
+    counts = {reads, records, calls, calls_without_draft, loci_annotated, loci_lifted, loci_written; with --bridge also calls_bridged; with
+    --region on the BAM route also the six of BamInput.region_info: regions, intervals, members, header_members, walked, selected},
     seconds = {stage: wall time}).  With args.sites: final = [], sites = the dicts of telr_sv.genotype_sites, files gains sites_tsv (and
     sites_vcf), counts gains sites and sites_supported, and the stages are inputs, index, reads, sites, outputs.
     engine: an aligner.Engine to run on (default: a new one on args.device, closed at the end).  Engine errors are raised as TelrError;
@@ -378,10 +429,19 @@ def run(args, engine=None):
         ix, n_parts = index_stage(eng, tseqs, io, args.index_part_bases)
         done("index", "stage-1 index (%s), %d part%s" % (aligner_preset(args)[0], n_parts, "" if n_parts == 1 else "s"))
         # 3. the reads: mapped here, or taken from the BAM
-        if is_bam(args.reads):
+        region = getattr(args, "region", None)
+        if is_bam(args.reads) and region:
+            tlens = [len(s) for s in tseqs]
+            qnames, read_set, r, release, info = load_bam_regions(eng, ix, args, tnames, tlens, bam_regions(args, tnames, tlens, listed))
+            counts.update(info)
+            route = "BAM input, %d regions: %d of its BGZF members inflated, %d of %d records walked selected" % (
+                info["regions"], info["members"] + info["header_members"], info["selected"], info["walked"])
+        elif is_bam(args.reads):
             qnames, read_set, r, release = load_bam(eng, ix, args, tnames, [len(s) for s in tseqs])
             route = "BAM input"
         else:
+            if region:
+                _say("[telr] " + REGION_INERT)
             files["bam"] = os.path.join(inter, sample + "_sort.bam")
             qnames, read_set, r, release = load_reads(eng, ix, args, tnames, files["bam"])
             route = "mapped, sorted BAM written"

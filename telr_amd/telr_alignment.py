@@ -40,15 +40,72 @@ def wait_release():
 atexit.register(wait_release)
 
 
-def bam_input(bam, out, sample_name, engine=None, index=None, keep_qual=False, chunk_bytes=None):
+def split_region_specs(text):
+    """`SPEC[,SPEC...]` -> [SPEC]: a comma separates two specs unless it groups digits -- the piece behind it is three digits, alone or
+    followed by `-` and digits, and the spec before it holds a colon (`chr2L:32,000-34,000` is one spec; a target whose whole name is
+    three digits goes into an option of its own)"""
+    import re
+    out = []
+    for piece in text.split(","):
+        if out and ":" in out[-1] and re.fullmatch(r"\d{3}(-\d+)?", piece):
+            out[-1] += "," + piece
+        elif piece:
+            out.append(piece)
+    return out
+
+
+def parse_regions(specs, tnames, tlens):
+    """samtools-style region texts -> [(tid, beg, end)], 0-based and half-open.  `chr` is the whole target, `chr:beg-end` is 1-based and
+    inclusive, `chr:beg` runs to the target's end; digit-group commas are allowed in the numbers.  A text that is a target's name as it
+    stands, colon and all, is that target.  ValueError with the text of the spec: an unknown name, a bad number, beg below 1 or
+    behind the target's end, end below beg.  An end behind the target's end is clipped to it."""
+    names = [n.decode() if isinstance(n, bytes) else str(n) for n in tnames]
+    tid_of = {}
+    for i, n in enumerate(names):
+        tid_of.setdefault(n, i)
+    out = []
+    for spec in specs:
+        spec = str(spec)
+
+        def bad(why):
+            return ValueError("region %r: %s" % (spec, why))
+        if spec in tid_of:
+            tid = tid_of[spec]
+            out.append((tid, 0, int(tlens[tid])))
+            continue
+        name, colon, span = spec.rpartition(":")
+        if not colon or name not in tid_of:
+            raise bad("no target of that name")
+        tid = tid_of[name]
+        tlen = int(tlens[tid])
+        lo, dash, hi = span.partition("-")
+
+        def number(t):
+            t = t.replace(",", "")
+            if not t.isdigit() or not t.isascii():
+                raise bad("%r is no position" % t)
+            return int(t)
+        beg = number(lo)
+        end = number(hi) if dash else tlen
+        if beg < 1 or beg > tlen or end < beg:
+            raise bad("positions %d to %d are no stretch of a target of %d bases" % (beg, end, tlen))
+        out.append((tid, beg - 1, min(end, tlen)))
+    return out
+
+
+def bam_input(bam, out, sample_name, engine=None, index=None, keep_qual=False, chunk_bytes=None, regions=None, bai=None):
     """The `.bam` branch of parse_input (TELR_input.py:300-305, 329-361): the alignment is skipped and the reads come out of the BAM.
     The file is loaded on the device (Engine.load_bam); <out>/<sample_name>.telr.fasta is written as bam2fasta writes it (first
     record of a name wins) and the BamInput is returned: its read_set and result are what alignment() + a re-read of the BAM would
     have left on the device.  index: an Index whose targets the file's references must equal (names, lengths, order; ValueError).
     A coordinate-sorted file needs no sort_index_bam; another order is accepted as it is.  chunk_bytes: as Engine.load_bam takes it
-    (None: the whole file at once; 0 or n: in chunks, a file of any size)."""
+    (None: the whole file at once; 0 or n: in chunks, a file of any size).  regions: a list of (tid, beg, end) (parse_regions): only
+    what overlaps them is loaded, through the index `bai` (None: bam + ".bai"); None: the whole file."""
     eng = engine or (index.eng if index is not None else Engine(0))
-    bi = eng.load_bam(bam, keep_qual=keep_qual, chunk_bytes=chunk_bytes)
+    if regions is None:
+        bi = eng.load_bam(bam, keep_qual=keep_qual, chunk_bytes=chunk_bytes)
+    else:
+        bi = eng.load_bam(bam, keep_qual=keep_qual, chunk_bytes=chunk_bytes, regions=regions, bai=bai)
     if index is not None:
         names = getattr(index, "tnames", None)
         if names is not None:
