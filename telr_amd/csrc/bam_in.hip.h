@@ -575,15 +575,16 @@ extern "C" void telr_bam_in_free(telr_bam_in *in)
 }
 
 // ---- what the host decides from the records' fields and names (the whole file's records, in file order) ----
-// the first of recs[0 .. n) that breaks a rule; its number in the text is base + its index
-static int bam_in_rec_fault(telr_ctx *ctx, const BamRec *recs, int64_t n, int64_t base)
+// the first of recs[0 .. n) that breaks a rule; recs[k] is the load's record base + k, and who(base + k) is how the text names it
+template <class Who>
+static int bam_in_rec_fault(telr_ctx *ctx, const BamRec *recs, int64_t n, int64_t base, Who who)
 {
     for (int64_t k = 0; k < n; ++k) {
         const int s = recs[k].status;
         if (s == BREC_OK) continue;
         static const char *const why[] = { "", "fields run past the record", "malformed tags", "refID or pos outside the header's references",
                                            "a clip inside the CIGAR", "CIGAR op code above 8", "CIGAR lengths beyond the record's coordinate bits" };
-        ctx->err = "telr_bam_load: record " + std::to_string(base + k) + ": " + why[s >= 1 && s <= 6 ? s : 0];
+        ctx->err = "telr_bam_load: record " + who(base + k) + ": " + why[s >= 1 && s <= 6 ? s : 0];
         return s == BREC_RANGE ? TELR_E_RANGE : TELR_E_ARG;
     }
     return TELR_OK;

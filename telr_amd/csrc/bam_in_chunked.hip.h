@@ -1,7 +1,9 @@
 // bam_in_chunked.hip.h -- bam_load: the one load behind telr_bam_load and telr_bam_load_chunked, its chunk slots, and
 // the entry points.  The file is cut into chunks of whole BGZF members (bam_chunk_plan.h); every chunk is uploaded, inflated and parsed
 // in turn, so that the transient device memory depends on the chunk and not on the file.  telr_bam_load is the plan of one chunk: one
-// slot, the file next to its inflated stream.  The kernels are those of bam_in.hip.h.
+// slot, the file next to its inflated stream.  The kernels are those of bam_in.hip.h.  The region load (bam_in_regions.hip.h) and the
+// reads load (reads_in.hip.h) run the same slots, setup, issue and wait; the region load also the same tail of pass 1 (bam_load_fetch)
+// and the same back half (bam_load_pass2).
 //
 // Two passes.  Which records are kept and where their words and bases go depends on the whole file (a supplementary record may come
 // any number of chunks before its primary, the first name wins across chunks, orphans and len_mismatch need the primary's length):
@@ -19,6 +21,13 @@
 // chunk's kernels see  buf = slot + room - carry,  carry + members bytes long.  A carry longer than the room (a record or a header
 // longer than a chunk grows it over several chunks) makes the slot grow; that is no error.  Offsets into `buf` are the same in both
 // passes: same carry, same members.
+//
+// A chunk's file bytes.  The members of a list need not be neighbours in the file: a region load (bam_in_regions.hip.h) runs these slots
+// over the members of its intervals and says which are neighbours (BamChunked::run_of).  A chunk is uploaded run after run, packed one
+// behind the other in the slot's file buffer, and its member table points into the packed bytes; a whole file is the case of one run per
+// chunk.  bamc_setup sizes the file buffer by the same sum over runs that bamc_issue uploads, plus the padding that the inflate kernel's
+// staged reads need behind the last byte.  A block that fails to inflate is named by bamc_wait: by its number in the file or, for a list
+// that is not the file's, by its file offset (BamChunked::coff).
 //
 // Overlap.  Two slots (one chunk: one).  Chunk k + 1 is uploaded and inflated on a second stream while chunk k is chained and parsed on
 // the context's stream; the host waits for chunk k's results at the end of every chunk (it needs them), which also orders the slots' reuse.
@@ -52,6 +61,10 @@ struct BamChunked {
     hipEvent_t ec0 = nullptr, ec1 = nullptr;      // around a chunk's record chain
     float ms_upload = 0, ms_inflate = 0, ms_chain = 0;
     const char *what = "telr_bam_load";      // opens a failed block's error text (telr_reads_load runs the same slots: reads_in.hip.h)
+    // a member list that is not one stretch of the file (a region load's; null: all of H.mem are file neighbours):
+    const int32_t *run_of = nullptr;     // [members] two neighbours of the list are neighbours in the file iff their entries are equal
+    const int64_t *coff = nullptr;       // [members] file offsets: a failed block is named by its, not by its number in the list
+    int64_t uploaded = 0;                // file bytes that bamc_issue has sent up so far
     BamChunked(telr_ctx *c, const BamInHop &h) : ctx(c), H(h), s_main(c->stream), s_io(c->side[0]) {}
     ~BamChunked()
     {
@@ -112,22 +125,39 @@ static int bamc_slots(BamChunked &C, int nslot, bool members)
     return TELR_OK;
 }
 
-// the chunk plan and its slots: two, or one where the plan has at most one chunk and the caller asks for no more (min_slots 1)
+// members [m, m1) of a chunk: one behind the last member of the run of file neighbours that starts at m
+static int64_t bamc_run_end(const BamChunked &C, int64_t m, int64_t m1)
+{
+    if (!C.run_of) return m1;
+    int64_t e = m + 1;
+    while (e < m1 && C.run_of[(size_t)e] == C.run_of[(size_t)m]) ++e;
+    return e;
+}
+// the file bytes of the run [m, e)
+static size_t bamc_run_bytes(const BamChunked &C, int64_t m, int64_t e)
+{
+    const BgzfMember &a = C.H.mem[(size_t)m], &b = C.H.mem[(size_t)e - 1];
+    return (size_t)(b.off + b.clen - a.off);
+}
+
+// the chunk plan and its slots: two, or one where the plan has at most one chunk and the caller asks for no more (min_slots 1).  A chunk's
+// file bytes are those of its runs, which lie packed in the slot; one run: from its first member to the end of its last
 static int bamc_setup(BamChunked &C, int64_t chunk_bytes, int min_slots)
 {
     telr_ctx *ctx = C.ctx;
-    const std::vector<BgzfMember> &mem = C.H.mem;
-    const int64_t nm = (int64_t)mem.size();
+    const int64_t nm = (int64_t)C.H.mem.size();
     int64_t nch = 0;
     int rc = bam_chunk_plan(nm, C.H.isz.data(), chunk_bytes, nullptr, 0, &nch);
-    if (rc != TELR_OK && rc != TELR_E_RANGE) { ctx->err = "telr_bam_load_chunked: chunk plan"; return rc; }
+    if (rc != TELR_OK && rc != TELR_E_RANGE) { ctx->err = std::string(C.what) + ": chunk plan"; return rc; }
     C.first.assign((size_t)nch + 1, nm);
     if (nch) TRY(bam_chunk_plan(nm, C.H.isz.data(), chunk_bytes, C.first.data(), nch, &nch));
     C.nch = nch;
     for (int64_t k = 0; k < nch; ++k) {
         const int64_t m0 = C.first[(size_t)k], m1 = C.first[(size_t)k + 1];
+        size_t cb = 0;
+        for (int64_t m = m0, e; m < m1; m = e) { e = bamc_run_end(C, m, m1); cb += bamc_run_bytes(C, m, e); }
         C.max_payload = std::max(C.max_payload, (size_t)C.payload(k));
-        C.max_cbytes = std::max(C.max_cbytes, (size_t)(mem[(size_t)m1 - 1].off + mem[(size_t)m1 - 1].clen - mem[(size_t)m0].off));
+        C.max_cbytes = std::max(C.max_cbytes, cb);
         C.max_members = std::max(C.max_members, (size_t)(m1 - m0));
     }
     TRY(bamc_slots(C, (int)std::max<int64_t>(std::min<int64_t>(nch, 2), min_slots), true));
@@ -138,20 +168,30 @@ static int bamc_setup(BamChunked &C, int64_t chunk_bytes, int min_slots)
     return TELR_OK;
 }
 
-// chunk k: its slice of the file and its member table (offsets relative to the slice) go up, its members are inflated behind the slot's room
+// chunk k: its file bytes go up run after run, packed one behind the other, with its member table (offsets relative to the packed bytes);
+// its members are inflated behind the slot's room
 static int bamc_issue(BamChunked &C, int64_t k)
 {
     telr_ctx *ctx = C.ctx;
     BamChunkSlot &s = C.at(k);
     const std::vector<BgzfMember> &mem = C.H.mem;
     const int64_t m0 = C.first[(size_t)k], m1 = C.first[(size_t)k + 1], n = m1 - m0;
-    const int64_t f0 = mem[(size_t)m0].off, f1 = mem[(size_t)m1 - 1].off + mem[(size_t)m1 - 1].clen;
     s.h_mem.assign(mem.begin() + m0, mem.begin() + m1); s.h_ooff.resize((size_t)n); s.h_status.resize((size_t)n);
+    size_t cb = 0;
     int64_t o = 0;
-    for (int64_t j = 0; j < n; ++j) { s.h_mem[(size_t)j].off -= f0; s.h_ooff[(size_t)j] = o; o += s.h_mem[(size_t)j].isize; }
-    const size_t cb = (size_t)(f1 - f0);
+    for (int64_t m = m0, e; m < m1; m = e) {
+        e = bamc_run_end(C, m, m1);
+        const int64_t f0 = mem[(size_t)m].off;
+        for (int64_t j = m - m0; j < e - m0; ++j) { s.h_mem[(size_t)j].off += (int64_t)cb - f0; s.h_ooff[(size_t)j] = o; o += s.h_mem[(size_t)j].isize; }
+        cb += bamc_run_bytes(C, m, e);
+    }
+    C.uploaded += (int64_t)cb;
     HIPCHK(hipEventRecord(s.e0, C.s_io));
-    if (cb) HIPCHK(hipMemcpyAsync(s.d_file, C.H.F.p + f0, cb, hipMemcpyHostToDevice, C.s_io));
+    for (int64_t m = m0, e; m < m1; m = e) {          // (a run's place among the packed bytes is its first member's)
+        e = bamc_run_end(C, m, m1);
+        const size_t len = bamc_run_bytes(C, m, e);
+        if (len) HIPCHK(hipMemcpyAsync(s.d_file + s.h_mem[(size_t)(m - m0)].off, C.H.F.p + mem[(size_t)m].off, len, hipMemcpyHostToDevice, C.s_io));
+    }
     HIPCHK(hipMemsetAsync(s.d_file + cb, 0, ((cb + 3) & ~(size_t)3) - cb + BGZF_INCH + 16, C.s_io));
     HIPCHK(hipMemcpyAsync(s.d_mem, s.h_mem.data(), (size_t)n * sizeof(BgzfMember), hipMemcpyHostToDevice, C.s_io));
     HIPCHK(hipMemcpyAsync(s.d_ooff, s.h_ooff.data(), (size_t)n * 8, hipMemcpyHostToDevice, C.s_io));
@@ -163,7 +203,8 @@ static int bamc_issue(BamChunked &C, int64_t k)
     HIPCHK(hipEventRecord(s.e2, C.s_io));
     return TELR_OK;
 }
-// chunk k is inflated; the lowest block that failed is the error (its number is the file's)
+// chunk k is inflated; the lowest block that failed is the error.  It is named by its number in the member list, which for a whole file is
+// its number in the file; a load whose list is not the file's (C.coff) names it by its file offset
 static int bamc_wait(BamChunked &C, int64_t k)
 {
     telr_ctx *ctx = C.ctx;
@@ -173,7 +214,11 @@ static int bamc_wait(BamChunked &C, int64_t k)
     HIPCHK(hipEventElapsedTime(&a, s.e0, s.e1)); HIPCHK(hipEventElapsedTime(&b, s.e1, s.e2));
     C.ms_upload += a; C.ms_inflate += b;
     for (size_t j = 0; j < s.h_status.size(); ++j)
-        if (s.h_status[j] != INFL_OK) { ctx->err = std::string(C.what) + ": block " + std::to_string(C.first[(size_t)k] + (int64_t)j) + ": " + infl_text(s.h_status[j]); return TELR_E_ARG; }
+        if (s.h_status[j] != INFL_OK) {
+            const int64_t m = C.first[(size_t)k] + (int64_t)j;
+            ctx->err = std::string(C.what) + ": block " + (C.coff ? "at file offset " + std::to_string(C.coff[(size_t)m]) : std::to_string(m)) + ": " + infl_text(s.h_status[j]);
+            return TELR_E_ARG;
+        }
     return TELR_OK;
 }
 // the `len` bytes at src (chunk k's buffer) become chunk k + 1's carry: the end of its slot's room.  keep: the bytes of chunk k + 1 that
@@ -188,17 +233,66 @@ static int bamc_carry(BamChunked &C, int64_t k, const uint8_t *src, int64_t len,
     return TELR_OK;
 }
 
-// What a load does behind pass 1, whichever way its chunks came about: the host decides on all records (P.recs: those of the file, or the
-// selected ones of a region load), the result's arrays and the set are made, and pass 2 writes the kept records' words and the reads' bases
-// where they stay.  issue(k) / wait(k): chunk k uploaded and inflated again into its slot (more than one chunk only); who(r): how an error
-// text names record r.  The handle takes the set and the result
+// all of H.mem as one chunk, inflated in slot 0: *d_out = its inflated stream (the header step of a region load, the test tap)
+static int bamc_inflate_whole(BamChunked &C, const uint8_t **d_out)
+{
+    TRY(bamc_setup(C, BAMC_WHOLE, 1));
+    if (C.nch) { TRY(bamc_issue(C, 0)); TRY(bamc_wait(C, 0)); }
+    *d_out = C.slot[0].d_buf + C.slot[0].room;
+    return TELR_OK;
+}
+
+// chunk_bytes <= 0 becomes a size: free device memory / BAMC_AUTO_DIV, clamped; or, for TELR_BAM_CHUNK_FIT and a load whose file bytes and
+// inflated stream (fit_bytes together) stay below half the free memory, one chunk
+static int bamc_auto_chunk(telr_ctx *ctx, int64_t fit_bytes, int64_t *chunk_bytes)
+{
+    if (*chunk_bytes > 0) return TELR_OK;
+    int64_t fr = 0;
+    TRY(telr_device_mem(ctx, &fr, nullptr));
+    if (*chunk_bytes == TELR_BAM_CHUNK_FIT && fit_bytes < fr / 2) *chunk_bytes = BAMC_WHOLE;
+    else *chunk_bytes = std::min<int64_t>(std::max<int64_t>(fr / BAMC_AUTO_DIV, BAMC_AUTO_MIN), BAMC_AUTO_MAX);
+    return TELR_OK;
+}
+
+// what pass 1 leaves for the host: the records of the file, or the selected ones of a region load.  who(r), in the functions below: how an
+// error text names record r of them
 struct BamPass1 {
     std::vector<BamRec> recs; std::vector<int64_t> noff = std::vector<int64_t>(1, 0); std::vector<char> names;
     std::vector<int64_t> rec0, carry_in, cut;      // per chunk: its first record, the carry it started with, where its walk ended
     int64_t max_carry = 0;
+    std::vector<int64_t> noff_k;      // (bam_load_fetch's landing place for one chunk's name offsets)
 };
-template <class Issue, class Wait, class Who>
-static int bam_load_pass2(telr_ctx *ctx, telr_bam_in *B, BamChunked &C, BamPass1 &P1, int32_t keep_qual, BamInClock &clk, Issue issue, Wait wait, Who who, int64_t *passes)
+// The tail of pass 1 for one chunk, whichever way its n records came about: their fields, offsets in `buf` and name lengths are on the
+// device (k_bam_rec's own, or the gathered ones of a region load).  The name lengths are scanned and k_bam_names writes the names; fields,
+// name offsets and names come to the host behind what P1 holds; the lowest record that broke a rule is the error, named by who(its number)
+template <class Who>
+static int bam_load_fetch(telr_ctx *ctx, const uint8_t *buf, const BamRec *d_recs, const int64_t *d_offs, const int32_t *d_nlen, int64_t n, BamPass1 &P1, Who who)
+{
+    hipStream_t st = ctx->stream;
+    int64_t *d_noff, *d_ntot, ntot = 0; uint8_t *d_names;
+    TRY(ctx_buf_t(ctx, "bamin_noff", (size_t)n + 2, &d_noff));
+    TRY(ctx_buf_t(ctx, "bamin_ntot", 2, &d_ntot));
+    TRY((dev_qscan<int32_t, int64_t>(ctx, d_nlen, (int32_t)n, d_noff, d_ntot, 0, nullptr, nullptr)));
+    HIPCHK(hipMemcpyAsync(&ntot, d_ntot, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(ctx_buf_t(ctx, "bamin_names", (size_t)ntot + 1, &d_names));
+    hipLaunchKernelGGL(k_bam_names, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, buf, d_offs, n, d_nlen, d_noff, d_names);
+    HIPCHK(hipGetLastError());
+    const size_t nb = P1.names.size();
+    const int64_t base = (int64_t)P1.recs.size();
+    P1.recs.resize((size_t)(base + n)); P1.noff_k.resize((size_t)n + 1); P1.names.resize(nb + (size_t)ntot);
+    HIPCHK(hipMemcpyAsync(P1.recs.data() + base, d_recs, (size_t)n * sizeof(BamRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(P1.noff_k.data(), d_noff, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (ntot) HIPCHK(hipMemcpyAsync(P1.names.data() + nb, d_names, (size_t)ntot, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int64_t i = 1; i <= n; ++i) P1.noff.push_back((int64_t)nb + P1.noff_k[(size_t)i]);
+    return bam_in_rec_fault(ctx, P1.recs.data() + base, n, base, who);
+}
+// What a load does behind pass 1, whichever way its chunks came about: the host decides on all records (P1.recs), the result's arrays and
+// the set are made, and pass 2 writes the kept records' words and the reads' bases where they stay; with more than one chunk, each is
+// uploaded and inflated again into its slot.  The handle takes the set and the result
+template <class Who>
+static int bam_load_pass2(telr_ctx *ctx, telr_bam_in *B, BamChunked &C, BamPass1 &P1, int32_t keep_qual, BamInClock &clk, Who who, int64_t *passes)
 {
     std::vector<BamRec> &recs = P1.recs; std::vector<int64_t> &noff = P1.noff, &rec0 = P1.rec0, &carry_in = P1.carry_in, &cut = P1.cut; std::vector<char> &names = P1.names;
     const int64_t nch = C.nch, max_carry = P1.max_carry;
@@ -235,9 +329,9 @@ static int bam_load_pass2(telr_ctx *ctx, telr_bam_in *B, BamChunked &C, BamPass1
         for (int i = 0; i < C.nslot; ++i) TRY(bamc_room(C, C.slot[i], (size_t)max_carry, 0));
         std::vector<int32_t> h_idx, h_over; std::vector<int64_t> h_off;
         int32_t q = 0;
-        if (again) TRY(issue(0));
+        if (again) TRY(bamc_issue(C, 0));
         for (int64_t k = 0; k < nch; ++k) {
-            if (again) TRY(wait(k));
+            if (again) TRY(bamc_wait(C, k));
             BamChunkSlot &s = C.at(k);
             const uint8_t *buf = s.d_buf + s.room - carry_in[(size_t)k];
             const int64_t r0 = rec0[(size_t)k], r1 = rec0[(size_t)k + 1];
@@ -275,7 +369,7 @@ static int bam_load_pass2(telr_ctx *ctx, telr_bam_in *B, BamChunked &C, BamPass1
                     HIPCHK(hipMemcpyAsync(h_over.data(), d_over, (size_t)nqk * 4, hipMemcpyDeviceToHost, st));
                 }
             }
-            if (k + 1 < nch) TRY(issue(k + 1));
+            if (k + 1 < nch) TRY(bamc_issue(C, k + 1));
             HIPCHK(hipStreamSynchronize(st));
             if (d_over)          // (reads are numbered in file order of their records: the first one found is the lowest record)
                 for (int32_t j = 0; j < nqk; ++j) if (h_over[(size_t)j]) {
@@ -308,8 +402,9 @@ static int bam_load(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual, int64_t
     const int64_t nch = C.nch, nrun = std::max<int64_t>(nch, 1);      // (a file without members: one empty chunk, for the header's error)
     // ---- pass 1: every chunk's records and names
     BamPass1 P1;
-    std::vector<BamRec> &recs = P1.recs; std::vector<int64_t> &noff = P1.noff, &rec0 = P1.rec0, &carry_in = P1.carry_in, &cut = P1.cut, noff_k; std::vector<char> &names = P1.names;
+    std::vector<int64_t> &rec0 = P1.rec0, &carry_in = P1.carry_in, &cut = P1.cut;
     rec0.assign((size_t)nrun + 1, 0); carry_in.assign((size_t)nrun + 1, 0); cut.assign((size_t)nrun, 0);
+    const auto who = [](int64_t r) { return std::to_string(r); };      // a record is named by its number in the file
     bool hdr = false;
     int64_t carry = 0, &max_carry = P1.max_carry;
     int32_t n_ref = 0;
@@ -361,28 +456,12 @@ static int bam_load(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual, int64_t
             if (res[1] == 3 || base + res[0] >= 0x7ffffff0LL) { ctx->err = "telr_bam_load: too many records"; return TELR_E_RANGE; }
             nrec_k = res[0]; p_end = res[2];
             if (nrec_k) {
-                BamRec *d_recs; int32_t *d_nlen; int64_t *d_noff, *d_ntot; uint8_t *d_names; int64_t ntot = 0;
+                BamRec *d_recs; int32_t *d_nlen;
                 TRY(ctx_buf_t(ctx, "bamin_recs", (size_t)nrec_k, &d_recs));
                 TRY(ctx_buf_t(ctx, "bamin_nlen", (size_t)nrec_k + 1, &d_nlen));
-                TRY(ctx_buf_t(ctx, "bamin_noff", (size_t)nrec_k + 2, &d_noff));
-                TRY(ctx_buf_t(ctx, "bamin_ntot", 2, &d_ntot));
-                const dim3 grid((unsigned)((nrec_k + 3) / 4));
-                hipLaunchKernelGGL(k_bam_rec, grid, dim3(256), 0, st, buf, d_offs, nrec_k, n_ref, d_recs, d_nlen);
+                hipLaunchKernelGGL(k_bam_rec, dim3((unsigned)((nrec_k + 3) / 4)), dim3(256), 0, st, buf, d_offs, nrec_k, n_ref, d_recs, d_nlen);
                 HIPCHK(hipGetLastError());
-                TRY((dev_qscan<int32_t, int64_t>(ctx, d_nlen, (int32_t)nrec_k, d_noff, d_ntot, 0, nullptr, nullptr)));
-                HIPCHK(hipMemcpyAsync(&ntot, d_ntot, 8, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                TRY(ctx_buf_t(ctx, "bamin_names", (size_t)ntot + 1, &d_names));
-                hipLaunchKernelGGL(k_bam_names, grid, dim3(256), 0, st, buf, d_offs, nrec_k, d_nlen, d_noff, d_names);
-                HIPCHK(hipGetLastError());
-                const size_t nb = names.size();
-                recs.resize((size_t)(base + nrec_k)); noff_k.resize((size_t)nrec_k + 1); names.resize(nb + (size_t)ntot);
-                HIPCHK(hipMemcpyAsync(recs.data() + base, d_recs, (size_t)nrec_k * sizeof(BamRec), hipMemcpyDeviceToHost, st));
-                HIPCHK(hipMemcpyAsync(noff_k.data(), d_noff, ((size_t)nrec_k + 1) * 8, hipMemcpyDeviceToHost, st));
-                if (ntot) HIPCHK(hipMemcpyAsync(names.data() + nb, d_names, (size_t)ntot, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                for (int64_t i = 1; i <= nrec_k; ++i) noff.push_back((int64_t)nb + noff_k[(size_t)i]);
-                TRY(bam_in_rec_fault(ctx, recs.data() + base, nrec_k, base));
+                TRY(bam_load_fetch(ctx, buf, d_recs, d_offs, d_nlen, nrec_k, P1, who));
             }
             ms_parse += clk.lap();
         }
@@ -393,8 +472,7 @@ static int bam_load(telr_ctx *ctx, const BamInHop &H, int32_t keep_qual, int64_t
     }
     B->phase_ms[BIN_CHAIN] = C.ms_chain; B->phase_ms[BIN_PARSE] = ms_parse;
     int64_t passes = 1;
-    TRY(bam_load_pass2(ctx, B.get(), C, P1, keep_qual, clk, [&](int64_t k) { return bamc_issue(C, k); }, [&](int64_t k) { return bamc_wait(C, k); },
-                       [](int64_t r) { return std::to_string(r); }, &passes));
+    TRY(bam_load_pass2(ctx, B.get(), C, P1, keep_qual, clk, who, &passes));
     B->phase_ms[BIN_TOTAL] = wall.lap() + H.ms;
     if (report) { B->chunk_info[0] = nch; B->chunk_info[1] = passes; B->chunk_info[2] = (int64_t)C.max_alloc; B->chunk_info[3] = max_carry; }
     *out = B.release();
@@ -424,13 +502,9 @@ extern "C" int telr_bam_load_chunked(telr_ctx *ctx, const char *path, int32_t ke
     if (chunk_bytes < TELR_BAM_CHUNK_FIT) { ctx->err = "telr_bam_load_chunked: chunk_bytes below TELR_BAM_CHUNK_FIT"; return TELR_E_ARG; }
     BamInHop H;
     TRY(bam_in_hop(ctx, "telr_bam_load", path, H));
-    if (chunk_bytes <= 0) {
-        int64_t fr = 0;
-        TRY(telr_device_mem(ctx, &fr, nullptr));
-        if (chunk_bytes == TELR_BAM_CHUNK_FIT && (int64_t)H.F.n + H.total < fr / 2) return bam_load(ctx, H, keep_qual, BAMC_WHOLE, false, out);
-        chunk_bytes = std::min<int64_t>(std::max<int64_t>(fr / BAMC_AUTO_DIV, BAMC_AUTO_MIN), BAMC_AUTO_MAX);
-    }
-    return bam_load(ctx, H, keep_qual, chunk_bytes, true, out);
+    const bool fit = chunk_bytes == TELR_BAM_CHUNK_FIT;
+    TRY(bamc_auto_chunk(ctx, (int64_t)H.F.n + H.total, &chunk_bytes));
+    return bam_load(ctx, H, keep_qual, chunk_bytes, !(fit && chunk_bytes == BAMC_WHOLE), out);          // (a file that fits: telr_bam_load, which reports no chunks)
 }
 
 // test tap: the inflated stream of a BGZF file (any payload) -> out[0 .. cap); *n = its length (nothing is copied when it exceeds cap)
@@ -443,9 +517,9 @@ extern "C" int telr_debug_bgzf_inflate(telr_ctx *ctx, const char *path, uint8_t 
     HIPCHK(hipSetDevice(ctx->device));
     BamChunked C(ctx, H);
     C.what = "telr_debug_bgzf_inflate";
-    TRY(bamc_setup(C, BAMC_WHOLE, 1));
-    if (C.nch) { TRY(bamc_issue(C, 0)); TRY(bamc_wait(C, 0)); }
+    const uint8_t *d = nullptr;
+    TRY(bamc_inflate_whole(C, &d));
     *n = H.total;
-    if (H.total && H.total <= cap && out) HIPCHK(hipMemcpy(out, C.slot[0].d_buf + C.slot[0].room, (size_t)H.total, hipMemcpyDeviceToHost));
+    if (H.total && H.total <= cap && out) HIPCHK(hipMemcpy(out, d, (size_t)H.total, hipMemcpyDeviceToHost));
     return TELR_OK;
 }

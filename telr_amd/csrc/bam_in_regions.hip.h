@@ -5,14 +5,15 @@
 //   host      bai_plan.h: regions -> merged regions; the index -> intervals [vbeg, vend) of virtual offsets, no member in two of them
 //   device    the header, in a step of its own: the members from file offset 0 until bam_in_header is satisfied (k_bgzf_inflate)
 //   host      the member list: hopped from every interval's coffset (never from the file's start); telr_bam_chunk_plan cuts it into chunks
-//   per chunk (the slots, the carry and the overlap of bam_in_chunked.hip.h; the members of a chunk lie packed in the slot's file buffer,
-//             run after run, because they are not neighbours in the file):
+//   per chunk (bamc_setup / bamc_issue / bamc_wait of bam_in_chunked.hip.h with their slots, carry and overlap: this load tells them which
+//             members are file neighbours (BamChunked::run_of = the member's interval), so a chunk's file bytes go up run after run and lie
+//             packed in the slot, and gives them the members' file offsets (BamChunked::coff) to name a block that fails to inflate):
 //     k_bgzf_inflate
 //     k_bam_chain_seg     one lane per segment: count pass, dev_qscan, emit pass -> the offsets of every record walked
 //     k_bam_rec           every walked record is parsed and checked, selected or not (the bins over-select)
 //     k_bam_region_keep   one lane per walked record: lower bound in the merged regions' keys, the overlap test -> keep flag
 //     dev_qscan + k_bam_gather   dense BamRec, offsets and name lengths of the selected records
-//     k_bam_names, the copy to the host
+//     bam_load_fetch (bam_in_chunked.hip.h): k_bam_names, the copy to the host, the lowest record that broke a rule
 //   host      bam_load_pass2 (bam_in_chunked.hip.h): bam_in_decide on the selected records; pass 2 (k_bam_cig, k_bam_seq, k_bam_qual) finds
 //             them again by the same offsets
 //
@@ -103,9 +104,9 @@ static int bamr_header(telr_ctx *ctx, BamInHop &H, telr_bam_in *B, int64_t *n_me
         std::vector<uint8_t> h((size_t)total + 1);
         {
             BamChunked C(ctx, H);
-            TRY(bamc_setup(C, BAMC_WHOLE, 1));
-            if (C.nch) { TRY(bamc_issue(C, 0)); TRY(bamc_wait(C, 0)); }
-            if (total) HIPCHK(hipMemcpy(h.data(), C.slot[0].d_buf + C.slot[0].room, (size_t)total, hipMemcpyDeviceToHost));
+            const uint8_t *d_h = nullptr;
+            TRY(bamc_inflate_whole(C, &d_h));
+            if (total) HIPCHK(hipMemcpy(h.data(), d_h, (size_t)total, hipMemcpyDeviceToHost));
         }
         int64_t from = 0, want = 0;
         const int rc = bam_in_header(ctx, h.data(), total, all ? total : INT64_MAX / 2, B, &from, &want);
@@ -174,99 +175,6 @@ static uint64_t bamr_voff(const BamRegPlan &P, int64_t g, int64_t m0, int64_t m1
     return (uint64_t)P.coff[(size_t)m] << 16 | (uint64_t)std::min<int64_t>(std::max<int64_t>(g - P.ucum[(size_t)m], 0), 0xffff);
 }
 
-// chunk k's members as runs of neighbours in the file: (first member, one behind the last); a run ends where the interval does
-static void bamr_runs(const BamChunked &C, const BamRegPlan &P, int64_t k, std::vector<std::pair<int64_t, int64_t>> &runs)
-{
-    runs.clear();
-    const int64_t m0 = C.first[(size_t)k], m1 = C.first[(size_t)k + 1];
-    for (int64_t m = m0; m < m1; ++m) {
-        if (m == m0 || P.iv_of[(size_t)m] != P.iv_of[(size_t)m - 1]) runs.emplace_back(m, m + 1);
-        else runs.back().second = m + 1;
-    }
-}
-static size_t bamr_run_bytes(const BamInHop &H, const std::pair<int64_t, int64_t> &r)
-{
-    const BgzfMember &a = H.mem[(size_t)r.first], &b = H.mem[(size_t)r.second - 1];
-    return (size_t)(b.off + b.clen - a.off);
-}
-
-// bamc_setup for a member list that is not contiguous in the file: the chunk plan, the slots sized by the packed runs
-static int bamr_setup(BamChunked &C, const BamRegPlan &P, int64_t chunk_bytes)
-{
-    telr_ctx *ctx = C.ctx;
-    const int64_t nm = (int64_t)C.H.mem.size();
-    int64_t nch = 0;
-    int rc = bam_chunk_plan(nm, C.H.isz.data(), chunk_bytes, nullptr, 0, &nch);
-    if (rc != TELR_OK && rc != TELR_E_RANGE) { ctx->err = "telr_bam_load_regions: chunk plan"; return rc; }
-    C.first.assign((size_t)nch + 1, nm);
-    if (nch) TRY(bam_chunk_plan(nm, C.H.isz.data(), chunk_bytes, C.first.data(), nch, &nch));
-    C.nch = nch;
-    std::vector<std::pair<int64_t, int64_t>> runs;
-    for (int64_t k = 0; k < nch; ++k) {
-        size_t cb = 0;
-        bamr_runs(C, P, k, runs);
-        for (const auto &r : runs) cb += bamr_run_bytes(C.H, r);
-        C.max_payload = std::max(C.max_payload, (size_t)C.payload(k));
-        C.max_cbytes = std::max(C.max_cbytes, cb);
-        C.max_members = std::max(C.max_members, (size_t)(C.first[(size_t)k + 1] - C.first[(size_t)k]));
-    }
-    TRY(bamc_slots(C, (int)std::max<int64_t>(std::min<int64_t>(nch, 2), 1), true));
-    HIPCHK(hipEventCreate(&C.ec0)); HIPCHK(hipEventCreate(&C.ec1));
-    TRY(ctx_buf_t(ctx, "bamin_crctabs", 1, &C.d_tabs));
-    { static CrcTabs T; static bool made = false; if (!made) { crc_tabs_make(T); made = true; } HIPCHK(hipMemcpyAsync(C.d_tabs, &T, sizeof(T), hipMemcpyHostToDevice, C.s_main)); }
-    HIPCHK(hipStreamSynchronize(C.s_main));
-    return TELR_OK;
-}
-
-// bamc_issue for such a chunk: its runs go up one behind the other, the member table points into the packed bytes
-static int bamr_issue(BamChunked &C, const BamRegPlan &P, int64_t k, int64_t *uploaded)
-{
-    telr_ctx *ctx = C.ctx;
-    BamChunkSlot &s = C.at(k);
-    const std::vector<BgzfMember> &mem = C.H.mem;
-    const int64_t m0 = C.first[(size_t)k], m1 = C.first[(size_t)k + 1], n = m1 - m0;
-    std::vector<std::pair<int64_t, int64_t>> runs;
-    bamr_runs(C, P, k, runs);
-    s.h_mem.assign(mem.begin() + m0, mem.begin() + m1); s.h_ooff.resize((size_t)n); s.h_status.resize((size_t)n);
-    HIPCHK(hipEventRecord(s.e0, C.s_io));
-    size_t cb = 0;
-    for (const auto &r : runs) {
-        const int64_t f0 = mem[(size_t)r.first].off;
-        const size_t len = bamr_run_bytes(C.H, r);
-        for (int64_t m = r.first; m < r.second; ++m) s.h_mem[(size_t)(m - m0)].off = (int64_t)cb + (mem[(size_t)m].off - f0);
-        if (len) HIPCHK(hipMemcpyAsync(s.d_file + cb, C.H.F.p + f0, len, hipMemcpyHostToDevice, C.s_io));
-        cb += len;
-    }
-    if (uploaded) *uploaded += (int64_t)cb;
-    int64_t o = 0;
-    for (int64_t j = 0; j < n; ++j) { s.h_ooff[(size_t)j] = o; o += s.h_mem[(size_t)j].isize; }
-    HIPCHK(hipMemsetAsync(s.d_file + cb, 0, ((cb + 3) & ~(size_t)3) - cb + BGZF_INCH + 16, C.s_io));
-    HIPCHK(hipMemcpyAsync(s.d_mem, s.h_mem.data(), (size_t)n * sizeof(BgzfMember), hipMemcpyHostToDevice, C.s_io));
-    HIPCHK(hipMemcpyAsync(s.d_ooff, s.h_ooff.data(), (size_t)n * 8, hipMemcpyHostToDevice, C.s_io));
-    HIPCHK(hipMemsetAsync(s.d_buf + s.room + o, 0, 64, C.s_io));
-    HIPCHK(hipEventRecord(s.e1, C.s_io));
-    hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)n), dim3(64), 0, C.s_io, s.d_file, s.d_mem, s.d_ooff, C.d_tabs, s.d_buf + s.room, s.d_status);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s.h_status.data(), s.d_status, (size_t)n * 4, hipMemcpyDeviceToHost, C.s_io));
-    HIPCHK(hipEventRecord(s.e2, C.s_io));
-    return TELR_OK;
-}
-// bamc_wait, the failed block named by its file offset
-static int bamr_wait(BamChunked &C, const BamRegPlan &P, int64_t k)
-{
-    telr_ctx *ctx = C.ctx;
-    BamChunkSlot &s = C.at(k);
-    HIPCHK(hipEventSynchronize(s.e2));
-    float a = 0, b = 0;
-    HIPCHK(hipEventElapsedTime(&a, s.e0, s.e1)); HIPCHK(hipEventElapsedTime(&b, s.e1, s.e2));
-    C.ms_upload += a; C.ms_inflate += b;
-    for (size_t j = 0; j < s.h_status.size(); ++j)
-        if (s.h_status[j] != INFL_OK) {
-            ctx->err = "telr_bam_load: block at file offset " + std::to_string(P.coff[(size_t)C.first[(size_t)k] + j]) + ": " + infl_text(s.h_status[j]); return TELR_E_ARG;
-        }
-    return TELR_OK;
-}
-
 // chunk k's segments in the offsets of its buffer (carry + members)
 static void bamr_segments(const BamChunked &C, const BamRegPlan &P, int64_t k, int64_t carry, std::vector<BamSeg> &seg, std::vector<int32_t> &seg_iv)
 {
@@ -320,14 +228,10 @@ static int bam_load_regions(telr_ctx *ctx, const char *path, const char *bai_pat
     B->phase_ms[BIN_HOP] = H.ms;
     const int64_t nm = (int64_t)H.mem.size();
     B->counters[0] = nm;
-    if (chunk_bytes <= 0) {
-        int64_t fr = 0;
-        TRY(telr_device_mem(ctx, &fr, nullptr));
-        if (chunk_bytes == TELR_BAM_CHUNK_FIT && P.packed + H.total < fr / 2) chunk_bytes = BAMC_WHOLE;
-        else chunk_bytes = std::min<int64_t>(std::max<int64_t>(fr / BAMC_AUTO_DIV, BAMC_AUTO_MIN), BAMC_AUTO_MAX);
-    }
+    TRY(bamc_auto_chunk(ctx, P.packed + H.total, &chunk_bytes));
     BamChunked C(ctx, H);
-    TRY(bamr_setup(C, P, chunk_bytes));
+    C.run_of = P.iv_of.data(); C.coff = P.coff.data();          // a run ends where the interval does; a failed block is named by its file offset
+    TRY(bamc_setup(C, chunk_bytes, 1));
     hipStream_t st = C.s_main;
     const int64_t nch = C.nch;
     // the merged regions' keys
@@ -344,16 +248,17 @@ static int bam_load_regions(telr_ctx *ctx, const char *path, const char *bai_pat
     }
     // ---- pass 1: every chunk's segments, its walked records, the selected ones' fields and names
     BamPass1 P1;
-    std::vector<BamRec> &recs = P1.recs; std::vector<int64_t> &noff = P1.noff, &rec0 = P1.rec0, &carry_in = P1.carry_in, &cut = P1.cut, noff_k, offs_k;
-    std::vector<char> &names = P1.names; std::vector<uint64_t> voff;
+    std::vector<int64_t> &rec0 = P1.rec0, &carry_in = P1.carry_in, &cut = P1.cut, offs_k;
+    std::vector<uint64_t> voff;          // [selected] file-order numbers are unknown here: a record is named by its virtual offset
+    const auto who = [&](int64_t r) { return "at virtual offset " + std::to_string(voff[(size_t)r]); };
     rec0.assign((size_t)nch + 1, 0); carry_in.assign((size_t)nch + 1, 0); cut.assign((size_t)nch, 0);
     std::vector<BamSeg> seg; std::vector<int32_t> seg_iv, h_stat; std::vector<int64_t> h_endp;
-    int64_t carry = 0, &max_carry = P1.max_carry, n_walked = 0, uploaded = 0;
+    int64_t carry = 0, &max_carry = P1.max_carry, n_walked = 0;
     float ms_parse = 0;
-    if (nch) TRY(bamr_issue(C, P, 0, &uploaded));
+    if (nch) TRY(bamc_issue(C, 0));
     for (int64_t k = 0; k < nch; ++k) {
         const bool last = k + 1 >= nch;
-        TRY(bamr_wait(C, P, k));
+        TRY(bamc_wait(C, k));
         BamChunkSlot &s = C.at(k);
         const int64_t m0 = C.first[(size_t)k], buflen = carry + C.payload(k), g0 = P.ucum[(size_t)m0] - carry;      // g0: the buffer's first byte in the member list's stream
         uint8_t *buf = s.d_buf + s.room - carry;
@@ -374,7 +279,7 @@ static int bam_load_regions(telr_ctx *ctx, const char *path, const char *bai_pat
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(C.ec1, st));
         TRY((dev_qscan<int32_t, int64_t>(ctx, d_cnt, nseg, d_base, d_tot, 0, nullptr, nullptr)));
-        if (!last) TRY(bamr_issue(C, P, k + 1, &uploaded));          // (the host is busy with the upload while the segments walk)
+        if (!last) TRY(bamc_issue(C, k + 1));         // (the host is busy with the upload while the segments walk)
         h_stat.resize((size_t)nseg); h_endp.resize((size_t)nseg);
         int64_t nwalk = 0;
         HIPCHK(hipMemcpyAsync(h_stat.data(), d_stat, (size_t)nseg * 4, hipMemcpyDeviceToHost, st));
@@ -414,37 +319,18 @@ static int bam_load_regions(telr_ctx *ctx, const char *path, const char *bai_pat
             HIPCHK(hipMemcpyAsync(&nsel, d_tot + 1, 8, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             if (nsel) {
-                BamRec *d_recs; int32_t *d_nlen; int64_t *d_offs, *d_noff, *d_ntot; uint8_t *d_names; int64_t ntot = 0;
+                BamRec *d_recs; int32_t *d_nlen; int64_t *d_offs;
                 TRY(ctx_buf_t(ctx, "bamin_recs", (size_t)nsel, &d_recs));
                 TRY(ctx_buf_t(ctx, "bamin_offs", (size_t)nsel + 1, &d_offs));
                 TRY(ctx_buf_t(ctx, "bamin_nlen", (size_t)nsel + 1, &d_nlen));
-                TRY(ctx_buf_t(ctx, "bamin_noff", (size_t)nsel + 2, &d_noff));
-                TRY(ctx_buf_t(ctx, "bamin_ntot", 2, &d_ntot));
                 hipLaunchKernelGGL(k_bam_gather, grid256(nwalk), dim3(256), 0, st, d_wrecs, d_woffs, d_wnlen, nwalk, d_keep, d_kat, d_recs, d_offs, d_nlen);
                 HIPCHK(hipGetLastError());
-                TRY((dev_qscan<int32_t, int64_t>(ctx, d_nlen, (int32_t)nsel, d_noff, d_ntot, 0, nullptr, nullptr)));
-                HIPCHK(hipMemcpyAsync(&ntot, d_ntot, 8, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                TRY(ctx_buf_t(ctx, "bamin_names", (size_t)ntot + 1, &d_names));
-                hipLaunchKernelGGL(k_bam_names, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, st, buf, d_offs, nsel, d_nlen, d_noff, d_names);
-                HIPCHK(hipGetLastError());
-                const size_t nb = names.size();
-                const int64_t base = rec0[(size_t)k];
-                recs.resize((size_t)(base + nsel)); noff_k.resize((size_t)nsel + 1); offs_k.resize((size_t)nsel); names.resize(nb + (size_t)ntot);
-                HIPCHK(hipMemcpyAsync(recs.data() + base, d_recs, (size_t)nsel * sizeof(BamRec), hipMemcpyDeviceToHost, st));
-                HIPCHK(hipMemcpyAsync(noff_k.data(), d_noff, ((size_t)nsel + 1) * 8, hipMemcpyDeviceToHost, st));
+                // the selected records' virtual offsets first: a record that broke a rule -- it is selected too -- is named by its
+                offs_k.resize((size_t)nsel);
                 HIPCHK(hipMemcpyAsync(offs_k.data(), d_offs, (size_t)nsel * 8, hipMemcpyDeviceToHost, st));
-                if (ntot) HIPCHK(hipMemcpyAsync(names.data() + nb, d_names, (size_t)ntot, hipMemcpyDeviceToHost, st));
                 HIPCHK(hipStreamSynchronize(st));
-                for (int64_t i = 1; i <= nsel; ++i) noff.push_back((int64_t)nb + noff_k[(size_t)i]);
                 for (int64_t i = 0; i < nsel; ++i) voff.push_back(bamr_voff(P, g0 + offs_k[(size_t)i], 0, nm));
-                // a record that broke a rule, selected or not: the lowest one, named by its virtual offset
-                for (int64_t i = 0; i < nsel; ++i) if (recs[(size_t)(base + i)].status != BREC_OK) {
-                    const int frc = bam_in_rec_fault(ctx, &recs[(size_t)(base + i)], 1, 0);          // its code, and its reason behind "record 0"
-                    const std::string t = ctx->err;
-                    ctx->err = "telr_bam_load: record at virtual offset " + std::to_string(voff[(size_t)(base + i)]) + t.substr(t.find("record 0") + 8);
-                    return frc;
-                }
+                TRY(bam_load_fetch(ctx, buf, d_recs, d_offs, d_nlen, nsel, P1, who));
             }
         }
         ms_parse += clk.lap();
@@ -457,13 +343,12 @@ static int bam_load_regions(telr_ctx *ctx, const char *path, const char *bai_pat
     // ---- the host decides on the selected records -- they are the file now -- and pass 2 finds them again by the same offsets: same carry,
     // same members.  One chunk: slot 0 holds it where pass 1 left it and "bamin_recs" holds its selected records' fields
     int64_t passes = 1;
-    TRY(bam_load_pass2(ctx, B.get(), C, P1, keep_qual, clk, [&](int64_t k) { return bamr_issue(C, P, k, &uploaded); }, [&](int64_t k) { return bamr_wait(C, P, k); },
-                       [&](int64_t r) { return "at virtual offset " + std::to_string(voff[(size_t)r]); }, &passes));
+    TRY(bam_load_pass2(ctx, B.get(), C, P1, keep_qual, clk, who, &passes));
     B->phase_ms[BIN_TOTAL] = wall.lap();
     B->chunk_info[0] = nch; B->chunk_info[1] = passes; B->chunk_info[2] = (int64_t)C.max_alloc; B->chunk_info[3] = max_carry;
     B->region_info[0] = nreg; B->region_info[1] = (int64_t)P.vbeg.size(); B->region_info[2] = nm; B->region_info[3] = n_hdr;
-    B->region_info[4] = n_walked; B->region_info[5] = (int64_t)recs.size();
-    B->region_bytes = uploaded;
+    B->region_info[4] = n_walked; B->region_info[5] = (int64_t)P1.recs.size();
+    B->region_bytes = C.uploaded;          // both passes; the header step had slots of its own
     *out = B.release();
     return TELR_OK;
 }

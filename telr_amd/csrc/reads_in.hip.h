@@ -615,11 +615,7 @@ extern "C" int telr_reads_load(telr_ctx *ctx, const char *path, int32_t keep_qua
     if (n >= 2 && p[0] == 0x1f && p[1] == 0x8b) container = rc == TELR_OK && n >= 3 && p[2] == 8 ? RIN_BGZF : RIN_GZIP;
     else if (n && p[0] != '@' && p[0] != '>') { ctx->err = "telr_reads_load: neither gzip nor BGZF, and the file opens with neither '@' nor '>'"; return TELR_E_ARG; }
     ctx->err.clear();
-    if (chunk_bytes == 0) {
-        int64_t fr = 0;
-        TRY(telr_device_mem(ctx, &fr, nullptr));
-        chunk_bytes = std::min<int64_t>(std::max<int64_t>(fr / BAMC_AUTO_DIV, BAMC_AUTO_MIN), BAMC_AUTO_MAX);
-    }
+    TRY(bamc_auto_chunk(ctx, 0, &chunk_bytes));          // (0 is the only value it acts on here: there is no "fits" for a reads file)
     return reads_load(ctx, H, container, keep_qual, chunk_bytes, out);
 }
 extern "C" int32_t telr_reads_in_count(const telr_reads_in *in) { return in ? (int32_t)in->qnames.size() : 0; }

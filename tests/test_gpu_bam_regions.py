@@ -216,6 +216,72 @@ def test_a_fault_in_a_walked_record_is_named_by_its_virtual_offset(engine, tmp_p
     assert e.value.code == R.E_ARG and "record at virtual offset %d: CIGAR op code above 8" % want in str(e.value), str(e.value)
 
 
+IN_W30, IN_W100 = [(0, 30 * 16384, 31 * 16384)], [(0, 100 * 16384, 101 * 16384)]
+BOTH_CHUNKINGS = (1, 1 << 40)          # every member a chunk; one chunk
+
+
+def region_members(F, regions):
+    """the members that a load of `regions` inflates for its intervals: their numbers in the file"""
+    merged = G.merge_regions(regions, G.TLENS)
+    return [m for a, b in G.interval_members(F["data"], G.plan(F["bai"], len(G.TLENS), merged)) for m in range(a, b)]
+
+
+@pytest.fixture(scope="module")
+def crc_damaged(tmp_path_factory):
+    """the `per_record` file with one bit flipped in the CRC-32 field of the first member of w30's interval: the file's length, every
+    member's frame and the index stay valid.  -> (path, the member's number in the file, its file offset)"""
+    F = G.layout("per_record")
+    k = region_members(F, IN_W30)[0]
+    off, n, _, _ = R.hop(F["data"])[k]
+    data = bytearray(F["data"])
+    data[off + n] ^= 0x10
+    assert G.member_table(bytes(data)) == G.member_table(F["data"]) and k >= G.header_members(F["data"], F["raw"])
+    p = tmp_path_factory.mktemp("bam_regions_crc") / "crc.bam"
+    p.write_bytes(bytes(data))
+    open(str(p) + ".bai", "wb").write(F["bai"])
+    return str(p), k, G.member_table(F["data"])[k][0]
+
+
+@pytest.mark.parametrize("chunk_bytes", BOTH_CHUNKINGS)
+def test_a_failed_member_of_a_region_load_is_named_by_its_file_offset(engine, files, crc_damaged, chunk_bytes):
+    path, k, coff = crc_damaged
+    good = BY_NAME["w16_left"]
+    engine.release_scratch()
+    free0 = engine.mem_info()[0]
+    with pytest.raises(TelrError) as e:
+        engine.load_bam(path, regions=IN_W30, chunk_bytes=chunk_bytes)
+    assert e.value.code == R.E_ARG and "block at file offset %d: CRC-32 mismatch" % coff in str(e.value), str(e.value)
+    engine.release_scratch()                                      # nothing is left allocated beyond the context's scratch
+    assert engine.mem_info()[0] == free0, (free0, engine.mem_info()[0])
+    bi = load(engine, files, good)                                # the engine is as good as before
+    loaded_equals(engine, bi, definition(good))
+    bi.free()
+
+
+@pytest.mark.parametrize("chunk_bytes", BOTH_CHUNKINGS)
+def test_a_damaged_member_that_no_interval_names_is_never_inflated(engine, crc_damaged, chunk_bytes):
+    """the same file, a region elsewhere: the load is the definition's of the undamaged file"""
+    path, k, _ = crc_damaged
+    F = G.layout("per_record")
+    assert k not in range(G.header_members(F["data"], F["raw"])) and k not in region_members(F, IN_W100)
+    L = G.load(F["data"], F["bai"], IN_W100)
+    assert L.region_info["selected"] == 1
+    bi = engine.load_bam(path, regions=IN_W100, chunk_bytes=chunk_bytes)
+    loaded_equals(engine, bi, L)
+    info = bi.region_info
+    bi.free()
+    assert info == L.region_info
+
+
+@pytest.mark.parametrize("chunk_bytes", BOTH_CHUNKINGS)
+def test_the_whole_file_load_names_the_same_member_by_its_number(engine, crc_damaged, chunk_bytes):
+    """both namings come out of the one wait"""
+    path, k, _ = crc_damaged
+    with pytest.raises(TelrError) as e:
+        engine.load_bam(path, chunk_bytes=chunk_bytes)
+    assert e.value.code == R.E_ARG and "block %d: CRC-32 mismatch" % k in str(e.value), str(e.value)
+
+
 # ---- 3. the other two loads ----------------------------------------------------------------------------------------------------------
 def test_whole_file_and_chunked_loads_are_untouched(engine, files):
     def both():
