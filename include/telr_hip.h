@@ -515,7 +515,18 @@ void telr_consensus_free(telr_consensus *c);
  * to the left; callers pass the positions they want counted) compute the
  * per-base depth of the result's primary+supplementary records (secondary
  * skipped, deletions not counted) and return the median as samtools+python
- * `statistics.median` would (mean of the two middle values for even counts). */
+ * `statistics.median` would (mean of the two middle values for even counts).
+ * A depth above 8,000 counts as 8,000; an interval is clamped to the target, an
+ * empty one (start past the last base, end before the start) gives NaN.
+ * Refused with TELR_E_ARG, before anything is launched, with the reason in
+ * telr_last_error ("telr_depth_medians: ..."): a negative target_len; an interval
+ * whose tid is no target; any record (secondary ones included) with a tid that is
+ * no target, with qid / qlen / qs < 0, qe outside [qs, qlen], ts < 0 or te < ts, or
+ * with a CIGAR range outside the result's array; a record that is not secondary
+ * with te > target_len[tid].  A record whose te is inside its target but whose
+ * CIGAR (M and D lengths from ts on) runs past the target's end is found on the
+ * device: TELR_E_ARG, "record's CIGAR leaves its target".  median_out is written
+ * only when the call returns TELR_OK. */
 int  telr_depth_medians(telr_ctx *ctx, const telr_result *r, int32_t n_targets,
                         const int32_t *target_len, int32_t n_iv, const int32_t *iv_tid,
                         const int32_t *iv_start, const int32_t *iv_end, double *median_out);

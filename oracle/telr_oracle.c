@@ -1520,8 +1520,8 @@ void tor_depth_medians(const telr_aln *alns, int64_t n_aln, const uint32_t *ciga
         /* -aa prints every position of the region that exists on the target */
         if (s < 0) s = 0;
         if (e > L - 1) e = L - 1;
+        if (e < s) { out[v] = NAN; continue; }       /* (before the subtraction: s = INT32_MAX with e = INT32_MIN does not fit) */
         int32_t n = e - s + 1;
-        if (n <= 0) { out[v] = NAN; continue; }
         int32_t *a = (int32_t*)malloc(4 * n);
         for (int32_t x = 0; x < n; ++x) { a[x] = depth[tid] ? depth[tid][s + x] : 0; if (a[x] > DEPTH_CAP) a[x] = DEPTH_CAP; }
         qsort(a, n, 4, cmp_u32);

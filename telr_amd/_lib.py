@@ -218,6 +218,8 @@ def lib():
     L.telr_debug_align.restype = C.c_int
     L.telr_debug_align.argtypes = [vp, vp, vp, C.POINTER(MapOpt), i32, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i32), vp]
     L.telr_debug_chain.restype = C.c_int; L.telr_debug_chain.argtypes = [vp, i32, vp, vp, C.POINTER(MapOpt), vp, vp]
+    L.telr_debug_radix_sort.restype = C.c_int; L.telr_debug_radix_sort.argtypes = [vp, i32, vp, vp, i64, i32, vp, vp]
+    L.telr_debug_qscan.restype = C.c_int; L.telr_debug_qscan.argtypes = [vp, i32, i32, vp, i32, vp, vp, i64, vp, vp]
     L.telr_debug_backtrack.restype = C.c_int
     L.telr_debug_backtrack.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(MapOpt), vp, vp, vp, vp, vp, vp, vp, i64, vp]
     _lib = L

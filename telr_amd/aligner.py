@@ -81,7 +81,7 @@ class Engine:
     def _chk(self, rc, what):
         if rc != 0:
             raise _lib.TelrError("%s: %s [%s]" % (what, self.L.telr_strerror(rc).decode(),
-                                                  self.L.telr_last_error(self.h).decode()))
+                                                  self.L.telr_last_error(self.h).decode()), rc)
 
     def device_name(self):
         b = C.create_string_buffer(256)
@@ -326,6 +326,34 @@ class Engine:
         self._chk(self.L.telr_debug_chain(self.h, len(O) - 1, K.ctypes.data, O.ctypes.data, C.byref(mo), f.ctypes.data, p.ctypes.data),
                   "telr_debug_chain")
         return f, p
+
+    def debug_radix_sort(self, keys, nbits, vals=None):
+        """the LSD radix sort of the index build and the call stages (radix_sort_passes) on host arrays -- test tap.  keys: uint64 with
+        vals (uint32), or uint32 without; sorted stably by the low 8 * ceil(nbits / 8) bits.  -> (keys, vals or None)"""
+        K = np.ascontiguousarray(keys)
+        if K.dtype not in (np.uint64, np.uint32):
+            raise ValueError("keys must be uint64 or uint32")
+        V = None if vals is None else np.ascontiguousarray(vals, dtype=np.uint32)
+        if V is not None and len(V) != len(K):
+            raise ValueError("one value per key")
+        ok = np.zeros_like(K); ov = None if V is None else np.zeros_like(V)
+        self._chk(self.L.telr_debug_radix_sort(self.h, K.itemsize, K.ctypes.data, None if V is None else V.ctypes.data, len(K), nbits,
+                                               ok.ctypes.data, None if ov is None else ov.ctypes.data), "telr_debug_radix_sort")
+        return ok, ov
+
+    def debug_qscan(self, cnt, out_dtype, cap=0, want_tot=True, want_n_over=False, want_list=False, n_over_in=0):
+        """the tiled exclusive scan (dev_qscan) on host counts -- test tap.  cnt: int32 or int64; out_dtype np.int32 or np.int64 (int32
+        -> int32 / int64, int64 -> int64).  n_over_in: what the counter of over-cap counts holds on entry.
+        -> dict: out (n + 1), tot64 (or None), n_over (or None), over_list (the reported indices in arrival order, or None)"""
+        A = np.ascontiguousarray(cnt)
+        if A.dtype not in (np.int32, np.int64):
+            raise ValueError("cnt must be int32 or int64")
+        out = np.full(len(A) + 1, -1, out_dtype)
+        tot = C.c_int64(-1); nov = C.c_int32(n_over_in); lst = np.full(max(len(A), 1), -1, np.int32)
+        self._chk(self.L.telr_debug_qscan(self.h, A.itemsize, out.itemsize, A.ctypes.data, len(A), out.ctypes.data, C.byref(tot) if want_tot else None, cap,
+                                          C.byref(nov) if want_n_over else None, lst.ctypes.data if want_list else None), "telr_debug_qscan")
+        return dict(out=out, tot64=int(tot.value) if want_tot else None, n_over=int(nov.value) if want_n_over else None,
+                    over_list=lst[:max(0, min(int(nov.value), len(A)))].copy() if want_list else None)
 
     def debug_backtrack(self, keys, q_aoff, f, p, qlen, goff, tlen, mo):
         """peaks and back-tracking, pass-1 chain selection and DP segmenting of map() on anchor lists with their chaining scores -- test

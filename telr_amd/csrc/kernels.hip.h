@@ -4486,18 +4486,24 @@ __global__ void k_stitch_write(int32_t np, const StitchProb *__restrict__ sp, co
 // ---------------------------------------------------------------------------------------
 // 6. depth medians (samtools depth -aa -r | statistics.median)
 struct DepthRec { int32_t tid, ts, n_cigar, pad; int64_t cigar_off; };
+// A target's slice of `diff` is tlen + 1 words (the last takes the -1 of a record that ends on the target's last base).  The host has
+// checked tid, ts >= 0, te <= tlen and the CIGAR range, but not that the CIGAR's reference length is te - ts (a resident CIGAR array has
+// no host copy to walk): an M or D run that would leave [0, tlen] raises *bad and ends the record's walk before it touches anything.
 __global__ void k_depth_diff(const DepthRec *__restrict__ recs, int32_t nrec, const uint32_t *__restrict__ cig,
-                             const int64_t *__restrict__ toff, int32_t *__restrict__ diff)
+                             const int64_t *__restrict__ toff, const int32_t *__restrict__ tlen, int32_t *__restrict__ diff, int32_t *__restrict__ bad)
 {
     int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nrec) return;
     const DepthRec R = recs[r];
     int32_t *d = diff + toff[R.tid];
-    int t = R.ts;
+    const int64_t L = tlen[R.tid];
+    int64_t t = R.ts;
     for (int z = 0; z < R.n_cigar; ++z) {
         uint32_t c = cig[R.cigar_off + z]; int op = c & 0xf, l = c >> 4;
-        if (op == 0) { atomicAdd(&d[t], 1); atomicAdd(&d[t + l], -1); t += l; }
-        else if (op == 2) t += l;
+        if (op != 0 && op != 2) continue;
+        if (t < 0 || t + l > L) { atomicOr(bad, 1); return; }
+        if (op == 0) { atomicAdd(&d[t], 1); atomicAdd(&d[t + l], -1); }
+        t += l;
     }
 }
 #define DEPTH_CAP 8000
@@ -4512,7 +4518,7 @@ __global__ void __launch_bounds__(256) k_depth_median(const int32_t *__restrict_
     int s = iv_s[v], e = iv_e[v];
     if (s < 0) s = 0;
     if (e > L - 1) e = L - 1;
-    const int n = e - s + 1;
+    const int n = e < s ? 0 : e - s + 1;       // (an s far above an e far below 0 would wrap the difference into a positive count)
     for (int x = threadIdx.x; x <= DEPTH_CAP; x += blockDim.x) hist[x] = 0;
     __syncthreads();
     const int32_t *d = depth + toff[tid];

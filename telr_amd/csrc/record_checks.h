@@ -1,5 +1,5 @@
 // record_checks.h — what the call stages (telr_call_insertions, telr_genotype_insertions, telr_draft_contigs, telr_bridge_contigs;
-// DESIGN.md 5.10 - 5.12, 5.18) refuse in a result's records, in a call list and in a signature array, stated once, with a record's strand
+// DESIGN.md 5.10 - 5.12, 5.18) and telr_depth_medians refuse in a result's records, in a call list and in a signature array, stated once, with a record's strand
 // coordinates (strand_coords) and the record that the two stages which cut reads at reference coordinates upload (CutRec).  These checks are
 // all that stands between a caller's arrays and the kernels that index with them.  Plain C++: no HIP call and no type of the engine's own, so they are pinned on a CPU and run under the
 // sanitizers from a stand-alone program (tools/record_checks_check.cpp).  The reason comes back in a std::string; the entry's name in
@@ -24,6 +24,15 @@ static inline bool record_check(const telr_aln &a, size_t i, int32_t n_targets, 
     else if (a.n_cigar < 0 || a.cigar_off < 0 || (uint64_t)a.cigar_off + (uint64_t)a.n_cigar > ncig) what = "CIGAR range outside the result's array";
     if (what) *why = "record " + std::to_string(i) + ": " + what;
     return !what;
+}
+
+// Record i as telr_depth_medians takes it, against targets of lengths target_len (none negative): record_check, then -- unless the
+// record is secondary, which the depth does not count -- its end inside its target.  True, or false with "record i: <what>" in *why.
+static inline bool depth_rec_check(const telr_aln &a, size_t i, int32_t n_targets, const int32_t *target_len, uint64_t ncig, std::string *why)
+{
+    if (!record_check(a, i, n_targets, ncig, why)) return false;
+    if (!(a.flags & TELR_F_SECONDARY) && a.te > target_len[a.tid]) { *why = "record " + std::to_string(i) + ": te beyond its target's end"; return false; }
+    return true;
 }
 
 // A record on its own strand: the query interval as stored on a forward record, mirrored in the read on TELR_F_REV.

@@ -2819,6 +2819,72 @@ extern "C" int telr_debug_chain(telr_ctx *ctx, int32_t nq, const uint64_t *keys,
     HIPCHK(hipStreamSynchronize(st));
     return TELR_OK;
 }
+// The LSD radix sort (radix.hip.h: radix_sort_passes) on a caller's keys (test tap: its tile, pass-count and stability edges without an
+// index build or a call stage around it).  key_bytes 8 with vals = <uint64_t, true>, what perm_sort_round and the index build run;
+// key_bytes 4 without vals = <uint32_t, false>, the index build's sort of the occurrence counts.  Out: the n keys (and values) from
+// whichever buffer pair the sort names as holding the result.
+extern "C" int telr_debug_radix_sort(telr_ctx *ctx, int32_t key_bytes, const void *keys, const uint32_t *vals, int64_t n, int32_t nbits, void *out_keys, uint32_t *out_vals)
+{
+    (void)hipGetLastError();
+    if (!ctx) return TELR_E_ARG;
+    auto bad = [&](const char *why) { ctx->err = std::string("telr_debug_radix_sort: ") + why; return TELR_E_ARG; };
+    if (key_bytes != 8 && key_bytes != 4) return bad("key_bytes must be 8 (with values) or 4 (without)");
+    const bool wide = key_bytes == 8;
+    if (nbits < 0 || nbits > 8 * key_bytes) return bad("nbits outside the key");
+    if (n < 0 || n >= 0x7ffffff0LL) return bad("n outside [0, 2^31)");
+    if (!wide && (vals || out_vals)) return bad("32-bit keys carry no values");
+    if (n == 0) return TELR_OK;
+    if (!keys || !out_keys || (wide && (!vals || !out_vals))) return bad("null array");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    void *d_k, *d_tk; uint32_t *d_v = nullptr, *d_tv = nullptr, *d_hist;
+    const size_t kb = (size_t)n * key_bytes;
+    TRY(ctx_buf(ctx, "dbg_rs_keys", kb, &d_k));
+    TRY(ctx_buf(ctx, "dbg_rs_tkeys", kb, &d_tk));
+    if (wide) { TRY(ctx_buf_t(ctx, "dbg_rs_vals", (size_t)n, &d_v)); TRY(ctx_buf_t(ctx, "dbg_rs_tvals", (size_t)n, &d_tv)); }
+    TRY(ctx_buf_t(ctx, "dbg_rs_hist", rs_hist_words((size_t)n), &d_hist));
+    HIPCHK(hipMemcpyAsync(d_k, keys, kb, hipMemcpyHostToDevice, st));
+    if (wide) HIPCHK(hipMemcpyAsync(d_v, vals, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    const int where = wide ? radix_sort_passes<uint64_t, true>((uint64_t*)d_k, d_v, (uint64_t*)d_tk, d_tv, n, nbits, d_hist, st)
+                           : radix_sort_passes<uint32_t, false>((uint32_t*)d_k, nullptr, (uint32_t*)d_tk, nullptr, n, nbits, d_hist, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_keys, where ? d_tk : d_k, kb, hipMemcpyDeviceToHost, st));
+    if (wide) HIPCHK(hipMemcpyAsync(out_vals, where ? d_tv : d_v, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return TELR_OK;
+}
+// The tiled exclusive scan (dev_qscan) on a caller's counts (test tap: its tile edges, the int32 wrap beside the exact total and the
+// over-cap list without a pipeline around it).  (in_bytes, out_bytes) = (4, 4), (4, 8) or (8, 8): the combinations the engine runs.
+// out holds n + 1 elements.  tot64, n_over and over_list (n slots; only with n_over) are optional; what *tot64 and *n_over hold on
+// entry goes to the device first, so that a stale value shows; over_list comes back in the first *n_over slots, in arrival order.
+extern "C" int telr_debug_qscan(telr_ctx *ctx, int32_t in_bytes, int32_t out_bytes, const void *cnt, int32_t n, void *out, int64_t *tot64, int64_t cap,
+                                int32_t *n_over, int32_t *over_list)
+{
+    (void)hipGetLastError();
+    if (!ctx) return TELR_E_ARG;
+    auto bad = [&](const char *why) { ctx->err = std::string("telr_debug_qscan: ") + why; return TELR_E_ARG; };
+    if (!((in_bytes == 4 && (out_bytes == 4 || out_bytes == 8)) || (in_bytes == 8 && out_bytes == 8))) return bad("(in_bytes, out_bytes) must be (4, 4), (4, 8) or (8, 8)");
+    if (n < 0 || !out || (n > 0 && !cnt)) return bad("null array or negative n");
+    if (over_list && !n_over) return bad("over_list without n_over");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    void *d_cnt, *d_out; int64_t *d_tot = nullptr; int32_t *d_nover = nullptr, *d_over = nullptr;
+    TRY(ctx_buf(ctx, "dbg_qs_cnt", (size_t)n * in_bytes, &d_cnt));
+    TRY(ctx_buf(ctx, "dbg_qs_out", ((size_t)n + 1) * out_bytes, &d_out));
+    if (tot64) { TRY(ctx_buf_t(ctx, "dbg_qs_tot", 1, &d_tot)); HIPCHK(hipMemcpyAsync(d_tot, tot64, 8, hipMemcpyHostToDevice, st)); }
+    if (n_over) { TRY(ctx_buf_t(ctx, "dbg_qs_nover", 1, &d_nover)); HIPCHK(hipMemcpyAsync(d_nover, n_over, 4, hipMemcpyHostToDevice, st)); }
+    if (over_list) TRY(ctx_buf_t(ctx, "dbg_qs_over", (size_t)n, &d_over));
+    if (n) HIPCHK(hipMemcpyAsync(d_cnt, cnt, (size_t)n * in_bytes, hipMemcpyHostToDevice, st));
+    if (in_bytes == 8) TRY((dev_qscan<int64_t, int64_t>(ctx, (const int64_t*)d_cnt, n, (int64_t*)d_out, d_tot, cap, d_nover, d_over)));
+    else if (out_bytes == 8) TRY((dev_qscan<int32_t, int64_t>(ctx, (const int32_t*)d_cnt, n, (int64_t*)d_out, d_tot, cap, d_nover, d_over)));
+    else TRY((dev_qscan<int32_t, int32_t>(ctx, (const int32_t*)d_cnt, n, (int32_t*)d_out, d_tot, cap, d_nover, d_over)));
+    HIPCHK(hipMemcpyAsync(out, d_out, ((size_t)n + 1) * out_bytes, hipMemcpyDeviceToHost, st));
+    if (tot64) HIPCHK(hipMemcpyAsync(tot64, d_tot, 8, hipMemcpyDeviceToHost, st));
+    if (n_over) HIPCHK(hipMemcpyAsync(n_over, d_nover, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (over_list && *n_over > 0) HIPCHK(hipMemcpy(over_list, d_over, (size_t)(*n_over < n ? *n_over : n) * 4, hipMemcpyDeviceToHost));
+    return TELR_OK;
+}
 // The three stages of telr_map between the chaining scores and the banded DP -- peaks and back-tracking (backtrack_dispatch), pass-1
 // chain selection (select1_dispatch), DP segmenting (segments_dispatch) -- on a caller's anchor lists with their f and p (test tap:
 // the edges of those kernels without an index or sequences).  In: nq queries, query q's sorted anchors at keys[q_aoff[q] ..
@@ -3194,28 +3260,38 @@ extern "C" int telr_debug_align(telr_ctx *ctx, const telr_seqset *qs, const telr
 }
 
 // ---------------------------------------------------------------------------------------
-// depth medians
+// depth medians.  Everything a kernel indexes with is checked first: the host refuses, with a reason, what the call stages refuse in a
+// record (record_checks.h: depth_rec_check -- tid, coordinates, CIGAR range, te inside the target), a negative target length and an
+// interval on no target; k_depth_diff holds the CIGAR walk itself inside the target's slice and flags a record whose CIGAR would leave it.
 extern "C" int telr_depth_medians(telr_ctx *ctx, const telr_result *r, int32_t n_targets, const int32_t *target_len, int32_t n_iv,
                                   const int32_t *iv_tid, const int32_t *iv_start, const int32_t *iv_end, double *median_out)
 {
     (void)hipGetLastError();          // a failed allocation of an EARLIER call leaves its error with the thread: not this call's
-    if (!ctx || !r || n_targets <= 0 || !target_len || n_iv < 0 || (n_iv && (!iv_tid || !iv_start || !iv_end || !median_out))) return TELR_E_ARG;
+    if (!ctx) return TELR_E_ARG;
+    auto bad = [&](const std::string &why) { ctx->err = "telr_depth_medians: " + why; return TELR_E_ARG; };
+    if (!r || n_targets <= 0 || !target_len || n_iv < 0 || (n_iv && (!iv_tid || !iv_start || !iv_end || !median_out))) return bad("null or negative argument");
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     std::vector<int64_t> toff(n_targets + 1, 0);
-    for (int i = 0; i < n_targets; ++i) toff[i + 1] = toff[i] + target_len[i] + 1;
-    for (int i = 0; i < n_iv; ++i) if (iv_tid[i] < 0 || iv_tid[i] >= n_targets) return TELR_E_ARG;
+    for (int i = 0; i < n_targets; ++i) {
+        if (target_len[i] < 0) return bad("target " + std::to_string(i) + ": negative length");
+        toff[i + 1] = toff[i] + target_len[i] + 1;
+    }
+    for (int i = 0; i < n_iv; ++i) if (iv_tid[i] < 0 || iv_tid[i] >= n_targets) return bad("interval " + std::to_string(i) + ": tid outside n_targets");
     std::vector<DepthRec> recs;
-    for (const telr_aln &a : r->alns) {
+    std::string why;
+    for (size_t i = 0; i < r->alns.size(); ++i) {
+        const telr_aln &a = r->alns[i];
+        if (!depth_rec_check(a, i, n_targets, target_len, r->ncig, &why)) return bad(why);
         if (a.flags & TELR_F_SECONDARY) continue;
-        if (a.tid < 0 || a.tid >= n_targets) return TELR_E_ARG;
         DepthRec d; d.tid = a.tid; d.ts = a.ts; d.n_cigar = a.n_cigar; d.pad = 0; d.cigar_off = a.cigar_off; recs.push_back(d);
     }
-    int32_t *d_diff, *d_tlen, *d_ivt, *d_ivs, *d_ive; int64_t *d_toff; DepthRec *d_recs; uint32_t *d_cig; double *d_out;
+    int32_t *d_diff, *d_tlen, *d_ivt, *d_ivs, *d_ive, *d_bad; int64_t *d_toff; DepthRec *d_recs; uint32_t *d_cig; double *d_out;
     TRY(ctx_buf_t(ctx, "dm_diff", (size_t)toff[n_targets] + 1, &d_diff));
     TRY(ctx_buf_t(ctx, "dm_toff", (size_t)n_targets + 1, &d_toff));
     TRY(ctx_buf_t(ctx, "dm_tlen", (size_t)n_targets, &d_tlen));
     TRY(ctx_buf_t(ctx, "dm_recs", recs.size(), &d_recs));
+    TRY(ctx_buf_t(ctx, "dm_bad", 1, &d_bad));
     result_wait(r);
     TRY(result_dev_cigars(ctx, r, "dm_cig", true, &d_cig, nullptr));
     TRY(ctx_buf_t(ctx, "dm_ivt", (size_t)n_iv, &d_ivt));
@@ -3223,6 +3299,7 @@ extern "C" int telr_depth_medians(telr_ctx *ctx, const telr_result *r, int32_t n
     TRY(ctx_buf_t(ctx, "dm_ive", (size_t)n_iv, &d_ive));
     TRY(ctx_buf_t(ctx, "dm_out", (size_t)n_iv, &d_out));
     HIPCHK(hipMemsetAsync(d_diff, 0, ((size_t)toff[n_targets] + 1) * 4, st));
+    HIPCHK(hipMemsetAsync(d_bad, 0, 4, st));
     HIPCHK(hipMemcpyAsync(d_toff, toff.data(), (size_t)(n_targets + 1) * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_tlen, target_len, (size_t)n_targets * 4, hipMemcpyHostToDevice, st));
     if (!recs.empty()) HIPCHK(hipMemcpyAsync(d_recs, recs.data(), recs.size() * sizeof(DepthRec), hipMemcpyHostToDevice, st));
@@ -3231,14 +3308,21 @@ extern "C" int telr_depth_medians(telr_ctx *ctx, const telr_result *r, int32_t n
         HIPCHK(hipMemcpyAsync(d_ivs, iv_start, (size_t)n_iv * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_ive, iv_end, (size_t)n_iv * 4, hipMemcpyHostToDevice, st));
     }
-    if (!recs.empty()) hipLaunchKernelGGL(k_depth_diff, dim3(((int)recs.size() + 63) / 64), dim3(64), 0, st, d_recs, (int32_t)recs.size(), d_cig, d_toff, d_diff);
+    if (!recs.empty()) hipLaunchKernelGGL(k_depth_diff, dim3(((int)recs.size() + 63) / 64), dim3(64), 0, st, d_recs, (int32_t)recs.size(), d_cig, d_toff, d_tlen, d_diff, d_bad);
     TRY(dev_inclusive_scan_i32(ctx, d_diff, (size_t)toff[n_targets]));
+    // the medians come back into a buffer of the call's own: the caller's array is filled only once the flag is known to be down.  (A
+    // flagged record has skipped whole M runs, never half of one: every depth the median kernel reads is still a count >= 0.)
+    std::vector<double> h_out((size_t)n_iv);
+    int32_t h_bad = 0;
     if (n_iv) {
         hipLaunchKernelGGL(k_depth_median, dim3(n_iv), dim3(256), 0, st, d_diff, d_toff, d_tlen, n_iv, d_ivt, d_ivs, d_ive, d_out);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(median_out, d_out, (size_t)n_iv * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_out.data(), d_out, (size_t)n_iv * 8, hipMemcpyDeviceToHost, st));
     }
+    HIPCHK(hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    if (h_bad) return bad("record's CIGAR leaves its target");
+    if (n_iv) memcpy(median_out, h_out.data(), (size_t)n_iv * 8);
     return TELR_OK;
 }
 

@@ -1,5 +1,5 @@
 // telr_amd/csrc/record_checks.h alone -- the record, call-list and signature refusals of telr_call_insertions, telr_genotype_insertions,
-// telr_draft_contigs and telr_bridge_contigs -- as a program of its own for a sanitizer build (the Python tests load the engine library,
+// telr_draft_contigs and telr_bridge_contigs, and the record refusals of telr_depth_medians -- as a program of its own for a sanitizer build (the Python tests load the engine library,
 // which a sanitizer does not see into):
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o tools/record_checks_check tools/record_checks_check.cpp && tools/record_checks_check
 // Every refusal with its full text, the edges of the CIGAR range (the C ABI cannot produce that one on a device: telr_result_from_arrays
@@ -121,6 +121,39 @@ int main()
     expect("the index is the caller's", rec_why(a, 2147483648u), "record 2147483648: tid outside n_targets");
     expect("the index 0", rec_why(a, 0), "record 0: tid outside n_targets");
 
+    // ---- a record as telr_depth_medians takes it: record_check, then te inside its target unless the record is secondary
+    {
+        const std::vector<int32_t> tlens = {10, 20, 1500};                 // exactly n_targets: a load past them is the sanitizer's to find
+        auto depth = [&](const telr_aln &x) {
+            std::string why = "untouched";
+            const bool ok = depth_rec_check(x, 7, 3, tlens.data(), 100, &why);
+            if (ok) { expect("a passing depth record leaves the reason alone", why, "untouched"); return std::string(""); }
+            return why; };
+        a = good();                                                    // te = 1500 = the target's length
+        expect("depth: te = tlen", depth(a), "");
+        a = good(); a.te = 1501;
+        expect("depth: te = tlen + 1", depth(a), "record 7: te beyond its target's end");
+        a = good(); a.te = 1501; a.flags = TELR_F_SECONDARY;
+        expect("depth: a secondary record is not counted, its end not held to the target", depth(a), "");
+        a = good(); a.te = 1501; a.flags = TELR_F_SECONDARY | TELR_F_REV;
+        expect("depth: secondary among other flags", depth(a), "");
+        a = good(); a.te = 1501; a.flags = TELR_F_REV;
+        expect("depth: other flags do not excuse", depth(a), "record 7: te beyond its target's end");
+        a = good(); a.tid = 0; a.ts = 0; a.te = 11;
+        expect("depth: the length of the record's own target", depth(a), "record 7: te beyond its target's end");
+        a = good(); a.tid = 0; a.ts = 10; a.te = 10;
+        expect("depth: an empty record at the target's end", depth(a), "");
+        a = good(); a.tid = 3; a.te = 1 << 30;
+        expect("depth: tid first (no length is loaded for it)", depth(a), "record 7: tid outside n_targets");
+        a = good(); a.tid = -1;
+        expect("depth: tid -1", depth(a), "record 7: tid outside n_targets");
+        a = good(); a.ts = -1; a.te = 1501;
+        expect("depth: coordinates before the target's end", depth(a), "record 7: coordinates");
+        a = good(); a.n_cigar = 61; a.te = 1501;
+        expect("depth: the CIGAR range before the target's end", depth(a), "record 7: CIGAR range outside the result's array");
+        a = good(); a.ts = -1; a.flags = TELR_F_SECONDARY;
+        expect("depth: a secondary record is still held to record_check", depth(a), "record 7: coordinates");
+    }
     // ---- the strand coordinates: forward as stored, mirrored in the read on TELR_F_REV
     {
         auto strand = [](int qs, int qe, int qlen, int flags) { telr_aln x = good(); x.qs = qs; x.qe = qe; x.qlen = qlen; x.flags = flags; return strand_coords(x); };
