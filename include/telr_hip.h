@@ -608,6 +608,50 @@ void telr_site_opt_default(telr_site_opt *o);
 int  telr_call_at_sites(telr_ctx *ctx, const telr_result *r, int32_t n_targets, const telr_ins_opt *opt,
                         const telr_ins_site *sites, int64_t n_sites, const telr_site_opt *sopt, telr_ins_calls **out);
 
+/* ---- several samples' insertion calls merged into ONE site list (opt-in): the step between the per-sample calls of a
+ *      cohort and the list telr_call_at_sites takes.  An OWN definition like 5.10, 5.11 and 5.19: NOT bcftools merge, SURVIVOR or
+ *      Jasmine, and its agreement with them is not pinned.  It reads no sequence and needs no index.
+ * Input:       e[0 .. n) in any order: len = the insertion length, 0 = unknown; sample = the caller's sample number; group = a class
+ *              the caller chooses (a TE family number, or 0 for all): entries of different groups never merge.
+ * Order:       the complete key (tid, group, pos, sample, len, i) ascending, i = the input index: a total order.
+ * Clusters:    single linkage in that order: a new one where tid changes, group changes, or pos - previous pos > dist (64-bit).
+ * Site of a cluster of m members: tid, group = the cluster's; pos = the position of member (m - 1) / 2 in key order (the lower median);
+ *              pos_min / pos_max = its first / last member's positions; n_members = m; n_samples = its distinct sample values;
+ *              n_sized = the members with len > 0; len = the lower median of the sized members in the order (len, sample, i), 0 without
+ *              one; len_min / len_max = the smallest / largest sized length (0, 0 without one); rep = the input index of the sized
+ *              member holding that median, without a sized member the input index of member (m - 1) / 2.
+ * Filter:      sites with n_samples < min_samples are dropped before anything below.
+ * Final order: ascending by (tid, pos, n_samples descending, n_members descending, group).  A site is SHADOWED when the site before
+ *              it in this order has the same (tid, pos) (only possible across groups); its winner = the output index of the first site
+ *              of that (tid, pos) run, -1 for a site that is not shadowed.  The sites that are not shadowed are strictly ascending
+ *              by (tid, pos): what telr_call_at_sites takes.  A site that is not shadowed is CROWDED when the previous or the next
+ *              not-shadowed site is on its tid and at most dist away (64-bit); shadowed sites are skipped there and never crowded.
+ *              Both are reported, not repaired.  flags = (shadowed ? 1 : 0) | (crowded ? 2 : 0).
+ * Output:      all surviving sites in final order; the input indices of site k's members, in key order, at
+ *              members[member_off[k] .. member_off[k + 1]); its distinct sample numbers, ascending, at samples[sample_off[k] ..
+ *              sample_off[k + 1]).  The output is the same on every run.
+ * TELR_E_ARG (text "telr_merge_sites: ..." in telr_last_error), on the host before any launch, *out untouched: n < 0; null entries
+ *              with n > 0; a null out; dist < 0; min_samples < 1; a non-zero reserved field; a tid outside [0, n_targets); a negative
+ *              pos, len, sample or group.  TELR_E_RANGE: 2^31 - 16 entries or more.  n == 0, or nothing surviving the filter: an empty
+ *              result (nothing is launched at n == 0, nothing more once the filter's count is known).  opt NULL = the defaults. */
+typedef struct telr_cohort_entry { int32_t tid, pos, len, sample, group; } telr_cohort_entry;
+typedef struct telr_cohort_opt { int32_t dist;         /* 50 */
+                                 int32_t min_samples;  /* 1  */
+                                 int32_t reserved[2]; } telr_cohort_opt;
+typedef struct telr_cohort_site { int32_t tid, pos, len, group, n_samples, n_members, n_sized, len_min, len_max, pos_min, pos_max, rep, flags, winner; } telr_cohort_site;
+#define TELR_COHORT_SHADOWED 1
+#define TELR_COHORT_CROWDED  2
+typedef struct telr_cohort_sites telr_cohort_sites;
+void telr_cohort_opt_default(telr_cohort_opt *o);
+int  telr_merge_sites(telr_ctx *ctx, const telr_cohort_entry *e, int64_t n, int32_t n_targets, const telr_cohort_opt *opt, telr_cohort_sites **out);
+int64_t telr_cohort_sites_count(const telr_cohort_sites *s);
+const telr_cohort_site *telr_cohort_sites_sites(const telr_cohort_sites *s);
+const int64_t *telr_cohort_sites_member_off(const telr_cohort_sites *s);      /* count + 1 offsets into telr_cohort_sites_members */
+const int32_t *telr_cohort_sites_members(const telr_cohort_sites *s);
+const int64_t *telr_cohort_sites_sample_off(const telr_cohort_sites *s);      /* count + 1 offsets into telr_cohort_sites_samples */
+const int32_t *telr_cohort_sites_samples(const telr_cohort_sites *s);
+void telr_cohort_sites_free(telr_cohort_sites *s);
+
 /* ---- genotypes of those calls: reference reads, AF and GT (opt-in).  In the reference the three values come
  *      from Sniffles (`%AF`, `%GT`, `%DR`, src/telr/TELR_sv.py:161).  An OWN definition like the caller's, NOT Sniffles' genotyper;
  *      its agreement with Sniffles is unpinned.

@@ -67,6 +67,29 @@ class InsSite(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("tid", "pos", "len")]
 
 
+class CohortOpt(C.Structure):
+    """telr_cohort_opt: the options of telr_merge_sites (defaults: CohortOpt.default())"""
+    _fields_ = [(n, C.c_int32) for n in ("dist", "min_samples", "reserved0", "reserved1")]
+
+    @classmethod
+    def default(cls, **kw):
+        o = cls(50, 1, 0, 0)
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("CohortOpt has no field %r" % k)
+            setattr(o, k, int(v))
+        return o
+
+
+class CohortEntry(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tid", "pos", "len", "sample", "group")]
+
+
+class CohortSite(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tid", "pos", "len", "group", "n_samples", "n_members", "n_sized", "len_min", "len_max", "pos_min", "pos_max",
+                                         "rep", "flags", "winner")]
+
+
 class InsSig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("tid", "pos", "len", "qid", "kind", "rec", "mate", "seg_start", "seg_len")]
 
@@ -183,6 +206,10 @@ INS_CALL_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsCall._fields_])
 assert INS_SIG_DTYPE.itemsize == C.sizeof(InsSig) == 36 and INS_CALL_DTYPE.itemsize == C.sizeof(InsCall) == 24
 INS_SITE_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsSite._fields_])
 assert INS_SITE_DTYPE.itemsize == C.sizeof(InsSite) == 12 and C.sizeof(SiteOpt) == 16
+COHORT_ENTRY_DTYPE = _np.dtype([(n, _np.int32) for n, _ in CohortEntry._fields_])
+COHORT_SITE_DTYPE = _np.dtype([(n, _np.int32) for n, _ in CohortSite._fields_])
+assert COHORT_ENTRY_DTYPE.itemsize == C.sizeof(CohortEntry) == 20 and COHORT_SITE_DTYPE.itemsize == C.sizeof(CohortSite) == 56 and C.sizeof(CohortOpt) == 16
+COHORT_SHADOWED, COHORT_CROWDED = 1, 2          # TELR_COHORT_* (telr_cohort_site.flags)
 GENO_DTYPE = _np.dtype([(n, _np.int32) for n, _ in InsGt._fields_])
 assert GENO_DTYPE.itemsize == C.sizeof(InsGt) == 16 and C.sizeof(GenoOpt) == 32
 DRAFT_DTYPE = _np.dtype([(n, _np.int32) for n, _ in Draft._fields_])

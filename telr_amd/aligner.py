@@ -6,6 +6,7 @@ boundary (TELR_alignment.py:69-82 and the five other sites listed in include/tel
 import ctypes as C
 import numpy as np
 from . import _lib
+from ._abi import CohortOpt, COHORT_ENTRY_DTYPE, COHORT_SITE_DTYPE, COHORT_SHADOWED
 from ._abi import IdxOpt, MapOpt, Counters, InsOpt, SiteOpt, GenoOpt, DraftOpt, BridgeOpt, RefTeOpt, ALN_DTYPE, INS_SIG_DTYPE, INS_CALL_DTYPE, GENO_DTYPE, DRAFT_DTYPE, BRIDGE_DTYPE, TILE_DTYPE, \
     TE_FEAT_DTYPE, TELR_E_ARG, TELR_E_RANGE, MF_PER_TARGET, MF_KEEP_CIGARS, N_STAGES, N_DPCLS, STITCH_CHAIN_COLUMNS, ALIGN_CHAIN_COLUMNS, ALIGN_PROB_COLUMNS
 from .fasta import concat
@@ -107,6 +108,28 @@ class Engine:
         if rc != 0:
             raise _lib.TelrError("telr_part_plan: %s [%s]" % (L.telr_strerror(rc).decode(), L.telr_part_plan_error().decode()), rc)
         return part_of[:len(a)]
+
+    def merge_sites(self, entries, n_targets, opt=None):
+        """several samples' insertion calls merged into one site list on the device (telr_merge_sites; include/telr_hip.h has the
+        definition, which is not bcftools merge, SURVIVOR or Jasmine): entries a COHORT_ENTRY_DTYPE array or a list of
+        (tid, pos, len, sample, group) tuples in any order, opt an _abi.CohortOpt (None: the defaults) -> CohortSites.  No index is
+        needed: the merge reads no sequence."""
+        o = CohortOpt.default() if opt is None else opt
+        if isinstance(entries, np.ndarray) and entries.dtype == COHORT_ENTRY_DTYPE:
+            e = np.ascontiguousarray(entries)
+        else:
+            e = np.ascontiguousarray(np.asarray(entries, dtype=np.int32).reshape(-1, 5)).view(COHORT_ENTRY_DTYPE).reshape(-1)
+        h = C.c_void_p()
+        self._chk(self.L.telr_merge_sites(self.h, e.ctypes.data if len(e) else None, len(e), int(n_targets), C.byref(o), C.byref(h)), "telr_merge_sites")
+        try:
+            L = self.L
+            k = int(L.telr_cohort_sites_count(h))
+            member_off = _np_from(L.telr_cohort_sites_member_off(h), k + 1, np.int64)
+            sample_off = _np_from(L.telr_cohort_sites_sample_off(h), k + 1, np.int64)
+            return CohortSites(_np_from(L.telr_cohort_sites_sites(h), k, COHORT_SITE_DTYPE), member_off, _np_from(L.telr_cohort_sites_members(h), int(member_off[-1]), np.int32),
+                               sample_off, _np_from(L.telr_cohort_sites_samples(h), int(sample_off[-1]), np.int32))
+        finally:
+            self.L.telr_cohort_sites_free(h)
 
     def index_parts(self, targets, io, max_part_bases=0, like=None):
         """a multi-part index over targets of any total size -> PartIndex.  like: another PartIndex over the same
@@ -776,6 +799,26 @@ class InsCalls:
 
     def reads_of(self, i):
         return self.reads[self.read_off[i]:self.read_off[i + 1]]
+
+
+class CohortSites:
+    """what Engine.merge_sites returns: sites (COHORT_SITE_DTYPE, in final order, shadowed ones included), the input indices of site
+    k's members in key order at members[member_off[k]:member_off[k + 1]], its ascending distinct sample numbers at
+    samples[sample_off[k]:sample_off[k + 1]]"""
+    def __init__(self, sites, member_off, members, sample_off, samples):
+        self.sites, self.member_off, self.members, self.sample_off, self.samples = sites, member_off, members, sample_off, samples
+
+    def members_of(self, k):
+        return self.members[self.member_off[k]:self.member_off[k + 1]]
+
+    def samples_of(self, k):
+        return self.samples[self.sample_off[k]:self.sample_off[k + 1]]
+
+    def site_list(self):
+        """the sites that are not shadowed as an (n, 3) int32 array of (tid, pos, len), strictly ascending by (tid, pos): what
+        Index.call_at_sites takes"""
+        s = self.sites[(self.sites["flags"] & COHORT_SHADOWED) == 0]
+        return np.stack([s["tid"], s["pos"], s["len"]], axis=1).astype(np.int32).reshape(-1, 3)
 
 
 class InsGenotypes:

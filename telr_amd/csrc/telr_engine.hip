@@ -3420,6 +3420,7 @@ extern "C" int telr_seqset_attach_qual(telr_ctx *ctx, telr_seqset *s, const char
 #include "poa.hip.h"
 #include "inscall.hip.h"
 #include "sitecall.hip.h"           // the second entry on inscall.hip.h's signatures: it takes InsFront and ins_collect from there
+#include "cohort.hip.h"             // several samples' calls -> one site list for sitecall.hip.h; takes k_ins_cid from inscall.hip.h
 #include "genotype.hip.h"
 #include "draft.hip.h"
 #include "bridge.hip.h"

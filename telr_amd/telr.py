@@ -58,8 +58,8 @@ Different from the reference on purpose: every value it prints a message for end
 four of its messages: -p below 1, a negative --af_flank_offset or --af_te_offset, --af_te_interval below 1); a reads file of any
 extension other than `.bam` is read as reads (a `.gz` on the device, see above; one it refuses, and every plain file, by the readers).  Not built: the ALT pre-screen, merge_rows on the
 caller's rows, the RepeatMasker route for families, the N-rank path, gzip on the BAM route, a bridge of more than two reads (an
-element longer than two reads' clips together stays without a contig); for `--sites`: no cohort merge of several samples' VCFs (the list
-comes merged), no draft or liftover for the listed sites, no N-rank path.  On a multi-part reference: the occurrence
+element longer than two reads' clips together stays without a contig); for `--sites`: no draft or liftover for the listed sites, no
+N-rank path (several samples' VCFs are merged into the list by `python -m telr_amd.telr_cohort merge`).  On a multi-part reference: the occurrence
 cut-off of the seeding is per part, as with minimap2 -I (secondaries the unsplit index would not report), all parts are resident together,
 and `--ref_te engine` maps the tiles to the library, not to the reference, so it runs as it is.
 """

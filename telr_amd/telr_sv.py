@@ -10,7 +10,9 @@ ALT sequences from a `screen`: `gff_screen` reads a RepeatMasker `.out.gff` (the
 `engine_screen` (opt-in: it changes which loci pass) maps the TE library onto the ALT sequences
 with the HIP engine instead.  `genotype_sites` answers the other question of a cohort study: for a site list that came from
 somewhere else (`read_sites`: a VCF of this project or a TSV), what does THIS sample show there -- supporters, reference reads and a
-genotype per site, `0/0` and `./.` included (`telr_call_at_sites`; not Sniffles' forced genotyping).
+genotype per site, `0/0` and `./.` included (`telr_call_at_sites`; not Sniffles' forced genotyping).  The list itself
+can come from the cohort's own calls: `read_cohort` -> `merge_site_lists` (`telr_merge_sites`; not bcftools merge, SURVIVOR
+or Jasmine) -> `write_cohort_tsv` / `write_cohort_vcf`, and `join_sites_vcfs` puts the per-sample results into one multi-sample VCF.
 
 The 14 columns are addressed by index by every later stage; COLUMNS names them.
 
@@ -122,13 +124,13 @@ def genotype_sites(index, result, tnames, qnames, sites, opt=None, site_opt=None
     return out
 
 
-def read_sites(path, chrom_ids, chrom_lens=None, report=None):
+def read_sites(path, chrom_ids, chrom_lens=None, report=None, all_lines=False):
     """A site list for `genotype_sites` from a VCF as `telr_output.write_vcf` writes it (a first line `##fileformat=VCF...`), or from a plain
     TSV with the columns chrom, pos0[, len[, id]] (lines starting with # and blank lines are skipped).
     From a VCF: CHROM, the site position POS - 1, ID, and len(ALT) as the expected length when ALT is made of letters, else 0.
     chrom_ids: {chromosome name: target id}; chrom_lens: {name: length} (None: the end is not checked).
     -> dict(sites = [(tid, pos, len), ...] sorted by (tid, pos), ids = their ids ("" without one), vcf = is it a VCF, header = the VCF's
-    header lines, lines = the VCF's data lines split into columns, in site order, duplicates = the lines dropped).
+    header lines, lines = the VCF's data lines split into columns, in site order (all_lines: a TSV's too), duplicates = the lines dropped).
     A duplicate (chrom, pos) keeps the first line; all of them are reported in one message (report: a callable taking the text; default
     stderr).  An unknown chromosome, a position that is negative or past the chromosome's end, a negative length or a line that does not
     parse raise ValueError with the line's number."""
@@ -171,7 +173,159 @@ def read_sites(path, chrom_ids, chrom_lens=None, report=None):
         (report or (lambda m: sys.stderr.write(m + "\n")))("%s: %d line%s repeat%s the (chrom, pos) of an earlier line; the first line of a position is kept"
                                                           % (path, dup, "" if dup == 1 else "s", "s" if dup == 1 else ""))
     return dict(sites=[(k[0], k[1], ln) for k, ln, _, _ in kept], ids=[sid for _, _, sid, _ in kept], vcf=vcf, header=header,
-                lines=[f for _, _, _, f in kept] if vcf else [], duplicates=dup)
+                lines=[f for _, _, _, f in kept] if vcf or all_lines else [], duplicates=dup)
+
+
+# ---- a cohort: several samples' calls -> one site list ----------------------------------------------------------
+NO_FAMILY = "."
+COHORT_FIELDS = ("chrom", "pos", "len", "id", "family", "n_samples", "n_members", "n_sized", "len_min", "len_max", "pos_min", "pos_max", "crowded", "samples")
+
+
+def _sample_name(path):
+    import os
+    base = os.path.basename(path)
+    return base[:-len(".telr.vcf")] if base.endswith(".telr.vcf") else os.path.splitext(base)[0]
+
+
+def _family_of(fields, vcf):
+    if not vcf:
+        return fields[4] if len(fields) > 4 and fields[4] != "" else NO_FAMILY
+    for kv in fields[7].split(";"):
+        if kv.startswith("FAMILY="):
+            return kv[len("FAMILY="):] or NO_FAMILY
+    return NO_FAMILY
+
+
+def read_cohort(paths, chrom_ids, chrom_lens=None, by_family=True, report=None):
+    """The per-sample call files of a cohort -> the entries `merge_site_lists` takes.  Every file is read by `read_sites`, with its rules (a
+    VCF of this project or a TSV; a repeated (chrom, pos) within one file keeps its first line); the family of a call is FAMILY= in INFO of a
+    VCF line, the optional fifth column of a TSV line, `.` without one.  The sample of file k is number k; its name is the file's base
+    name without `.telr.vcf` (else without its extension), and two files of one name are refused (ValueError).  by_family: the family
+    names, sorted, are numbered as the groups (calls of different families never merge -- by NAME: one family under two spellings is
+    two groups); else every call is in group 0.
+    -> dict(entries = a COHORT_ENTRY_DTYPE array in file order, samples = the sample names, families = the group's name by number (["*"]
+    without by_family), family = the family name of every entry, origin = (file number, line number in its `lines`) of every entry,
+    inputs = what read_sites returned per file, vcf = is every file a VCF, chroms = the chromosome name by id)."""
+    import numpy as np
+    from ._abi import COHORT_ENTRY_DTYPE
+    names = [_sample_name(p) for p in paths]
+    for k, n in enumerate(names):
+        if n in names[:k]:
+            raise ValueError("%s and %s are both sample %r: sample names come from the file names and must differ" % (paths[names.index(n)], paths[k], n))
+    inputs = [read_sites(p, chrom_ids, chrom_lens, report=report, all_lines=True) for p in paths]
+    family, origin, raw = [], [], []
+    for k, listed in enumerate(inputs):
+        for j, ((tid, pos, ln), f) in enumerate(zip(listed["sites"], listed["lines"])):
+            family.append(_family_of(f, listed["vcf"]))
+            origin.append((k, j))
+            raw.append((tid, pos, ln, k))
+    families = sorted(set(family)) if by_family else ["*"]
+    number = {n: g for g, n in enumerate(families)}
+    entries = np.zeros(len(raw), COHORT_ENTRY_DTYPE)
+    for i, (tid, pos, ln, k) in enumerate(raw):
+        entries[i] = (tid, pos, ln, k, number[family[i]] if by_family else 0)
+    chroms = [None] * len(chrom_ids)
+    for n, t in chrom_ids.items():
+        chroms[t] = n
+    return dict(entries=entries, samples=names, families=families, family=family, origin=origin, inputs=inputs, vcf=bool(inputs) and all(x["vcf"] for x in inputs), chroms=chroms)
+
+
+def merge_site_lists(engine, cohort, opt=None):
+    """the entries of `read_cohort` merged on the device (`Engine.merge_sites`, telr_merge_sites, DESIGN.md 5.21: an own definition, NOT
+    bcftools merge, SURVIVOR or Jasmine) -> one dict per site in final order, shadowed ones included and marked: COHORT_FIELDS (id =
+    chrom:pos0:family, samples = the names of its samples) plus group, rep (the entry that gives its length), members (its entries),
+    shadowed, winner (the row that shadows it, or -1)."""
+    res = engine.merge_sites(cohort["entries"], len(cohort["chroms"]), opt)
+    return cohort_rows(cohort, res.sites, res.members_of, res.samples_of)
+
+
+def cohort_rows(cohort, sites, members_of, samples_of):
+    """the rows of `merge_site_lists` from the merged sites (records with the fields of telr_cohort_site) and the two list accessors"""
+    from ._abi import COHORT_SHADOWED, COHORT_CROWDED
+    rows = []
+    for k, s in enumerate(sites):
+        chrom, fam = cohort["chroms"][int(s["tid"])], cohort["families"][int(s["group"])]
+        row = dict(chrom=chrom, pos=int(s["pos"]), len=int(s["len"]), id="%s:%d:%s" % (chrom, int(s["pos"]), fam), family=fam)
+        row.update({f: int(s[f]) for f in ("n_samples", "n_members", "n_sized", "len_min", "len_max", "pos_min", "pos_max", "group", "rep", "winner")})
+        row.update(crowded=bool(int(s["flags"]) & COHORT_CROWDED), shadowed=bool(int(s["flags"]) & COHORT_SHADOWED),
+                   samples=[cohort["samples"][int(q)] for q in samples_of(k)], members=[int(i) for i in members_of(k)])
+        rows.append(row)
+    return rows
+
+
+def write_cohort_tsv(rows, path):
+    """the rows of `merge_site_lists` -> `cohort.sites.tsv`: a header line, then one line per site with COHORT_FIELDS (crowded as 0 / 1, samples
+    joined by commas).  chrom, pos0, len, id come first, so `read_sites` reads the file as it stands (and `read_cohort`, the family being the
+    fifth column); a shadowed site is a comment line `#shadowed`, which `read_sites` skips: it reads exactly the sites that are not shadowed."""
+    with open(path, "w") as fh:
+        fh.write("#" + "\t".join(COHORT_FIELDS) + "\n")
+        for r in rows:
+            cells = [str(int(r[k])) if k == "crowded" else ",".join(r[k]) if k == "samples" else str(r[k]) for k in COHORT_FIELDS]
+            fh.write(("#shadowed\t" if r["shadowed"] else "") + "\t".join(cells) + "\n")
+
+
+COHORT_VCF_META = ('##INFO=<ID=NSAMP,Number=1,Type=Integer,Description="samples of the cohort with a call merged into this site">',
+                   '##INFO=<ID=SAMPLES,Number=.,Type=String,Description="their names">')
+
+
+def write_cohort_vcf(rows, cohort, path):
+    """the rows of `merge_site_lists` -> `cohort.sites.vcf`, only when every input was a VCF (ValueError otherwise): the first input's header
+    (with the two INFO lines of COHORT_VCF_META before its #CHROM line, which is cut to the eight fixed columns), then one line per site that is
+    not shadowed: the eight fixed columns of its `rep` entry's line with POS = pos + 1, ID = the site's id and `;NSAMP=..;SAMPLES=a,b`
+    appended to INFO.  `read_sites` reads it as a site list."""
+    if not cohort["vcf"]:
+        raise ValueError("write_cohort_vcf: every input must be a VCF")
+    with open(path, "w") as fh:
+        for line in cohort["inputs"][0]["header"]:
+            if line.startswith("#CHROM"):
+                fh.write("\n".join(COHORT_VCF_META) + "\n")
+                line = "\t".join(line.split("\t")[:8])
+            fh.write(line + "\n")
+        for r in rows:
+            if r["shadowed"]:
+                continue
+            k, j = cohort["origin"][r["rep"]]
+            f = list(cohort["inputs"][k]["lines"][j][:8])
+            f[1], f[2] = str(r["pos"] + 1), r["id"]
+            f[7] = (f[7] + ";" if f[7] not in ("", ".") else "") + "NSAMP=%d;SAMPLES=%s" % (r["n_samples"], ",".join(r["samples"]))
+            fh.write("\t".join(f) + "\n")
+
+
+def join_sites_vcfs(paths, out):
+    """the `<sample>.telr.sites.vcf` files of `--sites` runs on ONE site list -> one multi-sample VCF (host glue): the first file's header
+    with every file's sample name in the #CHROM line, FORMAT GT:DR:DV, one sample column per file in the order given.  The eight fixed
+    columns of every line must be equal across the files, and so must the number of lines; where they are not, ValueError names the file
+    and the line.  -> the number of sites written."""
+    if not paths:
+        raise ValueError("join_sites_vcfs: no input")
+    files = []
+    for p in paths:
+        with open(p, "r") as fh:
+            text = fh.read().splitlines()
+        head = [(no, l) for no, l in enumerate(text, 1) if l.startswith("#")]
+        data = [(no, l.split("\t")) for no, l in enumerate(text, 1) if l.strip() and not l.startswith("#")]
+        chrom = [l for _, l in head if l.startswith("#CHROM")]
+        if not chrom or len(chrom[0].split("\t")) != 10:
+            raise ValueError("%s: no #CHROM line with one sample column" % p)
+        for no, f in data:
+            if len(f) != 10 or f[8] != "GT:DR:DV":
+                raise ValueError("%s line %d: not a line of ten columns with FORMAT GT:DR:DV" % (p, no))
+        files.append(dict(path=p, head=[l for _, l in head], data=data, sample=chrom[0].split("\t")[9]))
+    first = files[0]
+    for x in files[1:]:
+        if len(x["data"]) != len(first["data"]):
+            raise ValueError("%s: %d sites, but %s has %d: the files must come from one site list" % (x["path"], len(x["data"]), first["path"], len(first["data"])))
+        for (no, f), (_, g) in zip(x["data"], first["data"]):
+            if f[:8] != g[:8]:
+                raise ValueError("%s line %d: the eight fixed columns differ from those of %s" % (x["path"], no, first["path"]))
+    with open(out, "w") as fh:
+        for line in first["head"]:
+            if line.startswith("#CHROM"):
+                line = "\t".join(line.split("\t")[:9] + [x["sample"] for x in files])
+            fh.write(line + "\n")
+        for k, (_, f) in enumerate(first["data"]):
+            fh.write("\t".join(f[:8] + ["GT:DR:DV"] + [x["data"][k][1][9] for x in files]) + "\n")
+    return len(first["data"])
 
 
 def write_sites_tsv(rows, ids, path):
